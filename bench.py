@@ -31,11 +31,11 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-# eight hardware queues instead of the HIP runtime's default four (before the runtime starts): the upload / download streams then
-# do not share a queue with a solve (gfbe_create sets the same default for callers that have not initialised HIP yet)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 import numpy as np  # noqa: E402
+
+DUMP_WINDOWS = 64            # windows of the timed batch --dump-outputs writes (<= 0.6 MB each: the prior's J0 is at most 246 x 246)
+DUMP_MAX_BYTES = 64 << 20
 
 
 def parse_args(argv=None):
@@ -75,7 +75,13 @@ def parse_args(argv=None):
     ap.add_argument("--launch-check", action="store_true",
                     help="only exercise the N-rank launch + rendezvous + the throughput aggregation (no GPU needed with GFBE_DIST_BACKEND=gloo)")
     ap.add_argument("--master-port", type=int, default=29511)
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (state, inverse depths, prior, summary of a fixed "
+                         "seeded sample of %d windows) as DIR/<name>.npy, float64" % DUMP_WINDOWS)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def relaunch_under_launcher(args):
@@ -188,6 +194,8 @@ def main():
 
     # ---- correctness of what was timed (cheap): every window converged to the same cost as window 0 of its kind
     res = batch.download()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, abi)
     final_costs = [r["summary"]["final_cost"] for r in res[: args.unique]]
     iters = [r["summary"]["iterations"] for r in res[: args.unique]]
     phase_ms = {"solve": res[0]["perf"]["ms_solve"], "marginalize": res[0]["perf"]["ms_marginalize"]}
@@ -327,6 +335,40 @@ def main():
         dist.destroy_process_group()
     if out is not None:
         print(json.dumps(out))
+
+
+def dump_outputs(out_dir, res, abi):
+    """--dump-outputs: what gfbe_batch_download returned for the last timed step, for DUMP_WINDOWS windows drawn with a fixed seed
+    (the same windows for the same --batch), one float64 array per field, stacked over the sampled windows. Fields whose length
+    differs between windows (inverse depths, prior, cost history) are padded with NaN."""
+    idx = np.sort(np.random.default_rng(0).choice(len(res), size=min(len(res), DUMP_WINDOWS), replace=False))
+    fields = {"window_index": [float(k) for k in idx]}
+
+    def put(name, v):
+        fields.setdefault(name, []).append(v)
+    for k in idx:
+        r = res[k]
+        for name, v in abi.flat_state(r["state"]).items():
+            put("state_" + name, v)
+        put("feature", r["feature"])
+        pr = r["prior"] or {"valid": 0, "n": 0}
+        for name in ("valid", "n", "block_id", "block_size", "block_idx", "x0", "J0", "r0"):
+            put("prior_" + name, pr.get(name, np.zeros((0, 0) if name == "J0" else 0)))
+        for name, v in r["summary"].items():
+            put("summary_" + name, v)
+    arrays = {}
+    for name, vals in fields.items():
+        vals = [np.asarray(v, dtype=np.float64) for v in vals]
+        a = np.full((len(vals),) + tuple(np.max([v.shape for v in vals], axis=0).astype(int)), np.nan)
+        for k, v in enumerate(vals):
+            a[(k,) + tuple(slice(0, d) for d in v.shape)] = v
+        arrays[name] = a
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def per_window_quotients(cpu, lat):

@@ -152,7 +152,6 @@ int main(int argc, char **argv) {
   if (argc < 3) { std::fprintf(stderr, "usage: %s stream.bin traj_out.bin\n", argv[0]); return 2; }
   Stream S;
   if (!read_stream(argv[1], S)) { std::fprintf(stderr, "cannot read %s\n", argv[1]); return 2; }
-  setenv("GPU_MAX_HW_QUEUES", "8", 0);   // before HIP initialises
   gfbe_options opt;
   gfbe_default_options(&opt);
   gfbe_ctx *ctx = nullptr;

@@ -122,9 +122,6 @@ class Backend(abi.CApi):
         _SO = so or globals()["_SO"]          # (so: another build of the library, e.g. DIAG_SO)
         if not os.path.exists(_SO):
             raise BackendError("HIP extension %s is missing: run __graft_entry__.build() (no CPU fallback)" % _SO)
-        # the solver drives up to eight streams: the HIP runtime's hardware-queue count is the CALLER's to set, before HIP
-        # initialises in this process; a value the embedding application already chose is left alone
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
         self.lib = abi.bind(C.CDLL(_SO), "gfbe_")
         self.opt = options or abi.default_options()
         self.ctx = C.c_void_p()
@@ -137,7 +134,7 @@ class Backend(abi.CApi):
             raise BackendError("gfbe_create(device=%d) failed with status %d (%s)" % (device, rc, self._err()))
         self.lib.gfbe_create_note.restype = C.c_char_p
         self.lib.gfbe_create_note.argtypes = [C.c_void_p]
-        self.create_note = (self.lib.gfbe_create_note(self.ctx) or b"").decode()   # (a remark, not an error: e.g. fewer than eight hardware queues configured)
+        self.create_note = (self.lib.gfbe_create_note(self.ctx) or b"").decode()   # (a remark, not an error: e.g. speculative_linearization switched off for a batch)
         self.head = self.ctx
         self.device = device
         for name in ("batch_upload", "batch_solve", "batch_download", "solve_batch", "profile_enable",

@@ -320,14 +320,9 @@ gfbe_status gfbe_create(gfbe_ctx **out, int device, const gfbe_options *opt) {
   c->device = device;
   *out = c;
   if (device < 0) return GFBE_OK;   // host-only context: bookkeeping entry points only
-  // A context drives up to eight streams (two parts x (main + dense-factor stream), upload, download, the caller's): with the
-  // HIP runtime's default of four hardware queues they share queues and an upload queues up behind a whole solve. The queue
-  // count is a process-wide setting read when the runtime initialises, so it belongs to the caller (the Python
-  // host layer and bench.py set GPU_MAX_HW_QUEUES=8 before they load HIP): the library only says so when it finds less.
-  {
-    const char *q = getenv("GPU_MAX_HW_QUEUES");
-    if (!q || atoi(q) < 8) c->note = "GPU_MAX_HW_QUEUES is unset or below 8 — uploads and downloads will share hardware queues with the solver streams (set it before HIP initialises)";
-  }
+  // A context drives up to eight streams (two parts x (main + dense-factor stream), upload, download, the caller's). They share
+  // the process's hardware queues, whose number is a process-wide runtime setting that belongs to the caller: the library
+  // neither reads nor sets it.
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n <= device) {
     c->err = "no HIP device " + std::to_string(device) + " visible (the HIP back end has no CPU fallback)";

@@ -349,12 +349,11 @@ int32_t gfbe_options_size(void);
 
 /* device < 0: host-only context (bookkeeping functions only; every compute entry point returns
  * GFBE_NO_DEVICE). device >= 0: HIP device ordinal; fails with GFBE_NO_DEVICE if absent.
- * The solver drives up to eight HIP streams (two solver lanes with a side stream each, upload, download, the caller's): set
- * GPU_MAX_HW_QUEUES=8 in the process environment before HIP initialises — the runtime's default of four makes uploads queue
- * behind solves. The library does not touch the environment; gfbe_create returns GFBE_OK and leaves a note in gfbe_create_note
- * (never in gfbe_last_error, which only ever holds the cause of a failing call) when the variable is unset or below 8.
- * (gfbe_batch_upload leaves a note there too when it had to switch speculative_linearization off for a batch whose second set of
- * outputs did not fit the device.) */
+ * The solver drives up to eight HIP streams (two solver lanes with a side stream each, upload, download, the caller's); they
+ * share the hardware queues the HIP runtime gives the process. The library does not touch the environment.
+ * gfbe_create_note holds remarks that are not errors (never in gfbe_last_error, which only ever holds the cause of a failing
+ * call): gfbe_batch_upload leaves one there when it had to switch speculative_linearization off for a batch whose second set of
+ * outputs did not fit the device. */
 gfbe_status gfbe_create(gfbe_ctx **ctx, int device, const gfbe_options *opt);
 /* Frees the context and the device memory it caches. Batches (gfbe_batch_free) and feature tables (gfbe_ftab_destroy) made with
  * the context must be released BEFORE it. The HIP streams the context created are kept in a process-wide pool for the next

@@ -3,7 +3,7 @@
 # its own rocprofv3 run; --pmc never with sys / hip / hsa traces), the bench line (reads the PMC summaries of THIS build), the
 # single-window kernel trace, the chain kernels' phase stamps and the three factorisations side by side, the speculative linearisation on
 # against off, the eigen square root of the prior, the GNSS window, the end-to-end loop under the tracer, the one-robot frame loop, the parity soaks.
-mkdir -p gpurun_out; R=$GRAFT_REPO_ROOT; export TMPDIR=/tmp; export GPU_MAX_HW_QUEUES=8
+R=$(cd "$(dirname "$0")/../.." && pwd); export TMPDIR=/tmp
 cd /tmp
 rm -rf /tmp/ks; rocprofv3 --kernel-trace --stats -d /tmp/ks -- python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-e2e --no-single --mixed 0 --no-other-configs > $R/gpurun_out/r5_bench_under_rocprof.json 2> /tmp/ks.err
 python $R/profiles/summarize_rocpd.py /tmp/ks/*/*_results.db $R/gpurun_out/r5_kernel_stats_b8192.txt | head -14

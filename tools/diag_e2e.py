@@ -6,7 +6,6 @@ _sys.path[:0] = [_r, _os.path.join(_r, "tests")]   # (measurement scripts: the p
 """End-to-end loop alone (host-fed, fresh inputs every batch) with host-side phase timers; run under rocprofv3 for the device side.
   B=512 DEPTH=3 STEPS=12 python tools/diag_e2e.py"""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", os.environ.get("HWQ", "8"))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from collections import deque

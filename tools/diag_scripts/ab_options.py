@@ -1,6 +1,5 @@
 #!/usr/bin/env python
 import os, sys, time, json
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 """Resident throughput of bench.py's default workload (8192 windows of 2000 landmarks, 8 unique) under several settings of gfbe_options on
 ONE box, with the per-kernel profile of one part (2048 windows, kernels one after the other) for each:

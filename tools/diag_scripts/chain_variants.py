@@ -7,7 +7,6 @@ _sys.path[:0] = [_r, _os.path.join(_r, "tests")]
 part — gfbe_options.solve_kernel = 2 (one-ended chain, k_solve_chain) / 3 (two-ended, k_solve_chain_tw) / 1 (monolithic) —, the
 single-window solve times (resident and host to host), and the throughput of a 4 x 2048 batch. GFBE_LIB selects a variant library."""
 import os, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 import numpy as np
 from _gfbe_import import gf

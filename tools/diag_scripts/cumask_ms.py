@@ -5,7 +5,6 @@ while not _os.path.exists(_os.path.join(_r, "_gfbe_import.py")):
 _sys.path[:0] = [_r, _os.path.join(_r, "tests")]   # (measurement scripts: the package root and the test helpers they share)
 """single-window latency on a CU-masked stream: does keeping a window's kernels on ONE XCD (one L2) shorten the dependent launches?"""
 import os, sys, time, ctypes
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
 import numpy as np, torch
 from _gfbe_import import gf
 abi, synth = gf.abi, gf.synth

@@ -4,7 +4,6 @@ while not _os.path.exists(_os.path.join(_r, "_gfbe_import.py")):
     _r = _os.path.dirname(_r)
 _sys.path[:0] = [_r, _os.path.join(_r, "tests")]   # (measurement scripts: the package root and the test helpers they share)
 import sys, os
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
 import torch, numpy as np
 from _gfbe_import import gf
 abi, synth = gf.abi, gf.synth

@@ -6,7 +6,6 @@ _sys.path[:0] = [_r, _os.path.join(_r, "tests")]
 """What batches solved SIDE BY SIDE would gain over batches solved one after the other (gfbe_batch_solve puts every batch of a context on
 the context's one stream): K contexts, a resident batch of B windows each, all enqueued before anything is waited for."""
 import os, time, numpy as np, torch
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 from _gfbe_import import gf
 abi, synth = gf.abi, gf.synth
 B = int(os.environ.get("B", "1024"))

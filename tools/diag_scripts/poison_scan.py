@@ -5,7 +5,6 @@ while not _os.path.exists(_os.path.join(_r, "_gfbe_import.py")):
 _sys.path[:0] = [_r, _os.path.join(_r, "tests")]   # (measurement scripts: the package root and the test helpers they share)
 """which not-cleared array of the slab is read before it is written? One array at a time filled with NaN patterns (GFBE_POISON_UNCLEARED=<name>)."""
 import os, sys
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
 import numpy as np, torch
 from _gfbe_import import gf
 import gnss_window_cases as gw

@@ -1,6 +1,5 @@
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
-export GPU_MAX_HW_QUEUES=8
 (timeout 900 python -m pytest tests -m gpu -x -q 2>&1 | tail -8) > gpurun_out/full_tests.log 2>&1
 (timeout 600 python bench.py 2> gpurun_out/full_bench.err | tail -1) > gpurun_out/full_bench.json
 tail -4 gpurun_out/full_tests.log

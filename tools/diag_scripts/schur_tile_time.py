@@ -5,7 +5,6 @@ while not _os.path.exists(_os.path.join(_r, "_gfbe_import.py")):
 _sys.path[:0] = [_r, _os.path.join(_r, "tests")]
 """k_schur under load: the stamps of workgroup (window 0, group 0) in a batch of B 2k-landmark windows, and the kernel's launch time."""
 import os
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 import numpy as np
 from _gfbe_import import gf

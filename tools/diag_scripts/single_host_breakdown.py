@@ -6,7 +6,6 @@ _sys.path[:0] = [_r, _os.path.join(_r, "tests")]
 """Where the host-to-host time of ONE window goes on the host's clock: the upload call (scan, pack, enqueue of the ingest / expand
 kernels), the solve call (enqueue of ~45 launches), the download call (wait + unpack) — against gfbe_solve_window as one call."""
 import os, time, numpy as np, torch
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 from _gfbe_import import gf
 abi, synth = gf.abi, gf.synth
 scn = synth.Scenario(seed=20250708 + 2, n_landmarks=int(os.environ.get("L", "2000")), use_wheel=True)

@@ -5,7 +5,6 @@ while not _os.path.exists(_os.path.join(_r, "_gfbe_import.py")):
 _sys.path[:0] = [_r, _os.path.join(_r, "tests")]
 """Resident throughput of 8192 windows by the number of parts the batch is solved in (gfbe_options.split_batch), one box."""
 import os, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 import numpy as np
 from _gfbe_import import gf

@@ -6,7 +6,6 @@ _sys.path[:0] = [_r, _os.path.join(_r, "tests")]   # (measurement scripts: the p
 """One resident 2k-landmark window solved repeatedly (the B = 1 latency path); run under rocprofv3 --kernel-trace for the per-kernel
 table (profiles/summarize_rocpd.py). Prints the wall time per solve."""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from _gfbe_import import gf
