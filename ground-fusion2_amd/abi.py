@@ -871,3 +871,77 @@ def gnss_eval(lib, prefix, ctx, obs, iono, pose, speed_bias, rcv_dt, rcv_ddt, ya
     if rc != OK:
         raise RuntimeError("%sgnss_eval failed with status %d" % (prefix, rc))
     return dict(r=r, J=J if want_J else None, r_dt_ddt=rc_, r_smooth=rs, cost=float(cost[0]))
+
+
+# ---------------------------------------------------------------------------------------------
+# Line landmarks (gfbe_line_eval / gfbe_line_refine)
+# ---------------------------------------------------------------------------------------------
+class LineWindow(C.Structure):
+    _fields_ = [("struct_size", c_i), ("n_lines", c_i), ("start_frame", PI), ("n_obs", PI), ("obs", PD),
+                ("is_triangulation", PU8), ("line_plucker", PD), ("pose", (c_d * 7) * NFRAMES), ("ex_cam", c_d * 7)]
+
+
+class LineWindowHolder:
+    """A gfbe_line_window over the numpy arrays of a line-window dict (keys: start_frame, n_obs, obs [sum n_obs][4],
+    is_triangulation, line_plucker [n][6], pose [11][7], ex_cam [7]); keeps the arrays alive."""
+
+    def __init__(self, lw):
+        self.sf, self.no = _i32(lw["start_frame"]), _i32(lw["n_obs"])
+        self.obs, self.tri = _f64(lw["obs"]).reshape(-1, 4), _u8(lw["is_triangulation"])
+        self.plk = _f64(lw["line_plucker"]).reshape(-1, 6)
+        n = len(self.sf)
+        assert len(self.no) == n and len(self.tri) == n and len(self.plk) == n and len(self.obs) == int(self.no.sum())
+        self.c = LineWindow()
+        self.c.struct_size, self.c.n_lines = C.sizeof(LineWindow), n
+        self.c.start_frame, self.c.n_obs, self.c.obs = _pi(self.sf), _pi(self.no), _pd(self.obs)
+        self.c.is_triangulation, self.c.line_plucker = self.tri.ctypes.data_as(PU8), _pd(self.plk)
+        pose = _f64(lw["pose"]).reshape(NFRAMES, 7)
+        for i in range(NFRAMES):
+            self.c.pose[i][:] = pose[i].tolist()
+        self.c.ex_cam[:] = _f64(lw["ex_cam"]).tolist()
+        self.n = n
+
+
+def line_eval(lib, prefix, ctx, pose, ex_cam, orth, obs, sqrt_info=400.0, robustify=True):
+    pose, orth, obs, ex = _f64(pose).reshape(-1, 7), _f64(orth).reshape(-1, 4), _f64(obs).reshape(-1, 4), _f64(ex_cam)
+    n = len(pose)
+    assert len(orth) == n and len(obs) == n
+    r, Jp, Je, Jo, cost = np.zeros((n, 2)), np.zeros((n, 2, 7)), np.zeros((n, 2, 7)), np.zeros((n, 2, 4)), np.zeros(1)
+    f = getattr(lib, prefix + "line_eval")
+    f.restype = c_i
+    f.argtypes = [C.c_void_p, c_i, PD, PD, PD, PD, c_d, c_i, PD, PD, PD, PD, PD]
+    rc = f(ctx, n, _pd(pose), _pd(ex), _pd(orth), _pd(obs), float(sqrt_info), int(bool(robustify)), _pd(r), _pd(Jp), _pd(Je), _pd(Jo), _pd(cost))
+    if rc != OK:
+        raise RuntimeError("%sline_eval failed with status %d" % (prefix, rc))
+    return dict(r=r, J_pose=Jp, J_ex=Je, J_orth=Jo, cost=float(cost[0]))
+
+
+def line_refine_raw(lib, prefix, ctx, holders, sqrt_info=400.0, cauchy_scale=1.0, max_num_iterations=8, plucker_out=None, keep_out=None,
+                    summary=None):
+    """gfbe_line_refine over prebuilt LineWindowHolders; returns (status, plucker_out, keep_out, summary array). The output buffers
+    may be passed in (a failed call must leave them untouched)."""
+    n_lines = sum(h.n for h in holders)
+    arr = (C.POINTER(LineWindow) * max(len(holders), 1))(*[C.pointer(h.c) for h in holders])
+    plk = np.zeros((n_lines, 6)) if plucker_out is None else plucker_out
+    keep = np.zeros(n_lines, np.uint8) if keep_out is None else keep_out
+    sums = (Summary * max(len(holders), 1))() if summary is None else summary
+    f = getattr(lib, prefix + "line_refine")
+    f.restype = c_i
+    f.argtypes = [C.c_void_p, c_i, C.POINTER(C.POINTER(LineWindow)), c_d, c_d, c_i, PD, PU8, C.POINTER(Summary)]
+    rc = f(ctx, len(holders), arr, float(sqrt_info), float(cauchy_scale), int(max_num_iterations), _pd(plk), keep.ctypes.data_as(PU8), sums)
+    return rc, plk, keep, sums
+
+
+def line_refine(lib, prefix, ctx, windows, sqrt_info=400.0, cauchy_scale=1.0, max_num_iterations=8):
+    """Batched onlyLineOpt + removeLineOutlier. windows: line-window dicts. Returns one dict per window: plucker [n][6], keep [n] (bool),
+    summary (summary_to_dict), and the call's status."""
+    holders = [w if isinstance(w, LineWindowHolder) else LineWindowHolder(w) for w in windows]
+    rc, plk, keep, sums = line_refine_raw(lib, prefix, ctx, holders, sqrt_info, cauchy_scale, max_num_iterations)
+    if rc not in (OK, NO_CONVERGENCE, NUMERICAL_FAILURE):
+        raise RuntimeError("%sline_refine failed with status %d" % (prefix, rc))
+    out, o = [], 0
+    for k, h in enumerate(holders):
+        out.append(dict(plucker=plk[o:o + h.n].copy(), keep=keep[o:o + h.n].astype(bool), summary=summary_to_dict(sums[k]),
+                        perf=summary_perf(sums[k]), status=rc))
+        o += h.n
+    return out

@@ -33,6 +33,7 @@ EXPORTS = [
     "gfbe_ftab_triangulate", "gfbe_ftab_check_outliers", "gfbe_ftab_size", "gfbe_ftab_download", "gfbe_slide_window_state",
     "gfbe_pg_eval", "gfbe_pg_solve", "gfbe_lio_linearize", "gfbe_batch_upload_tables", "gfbe_batch_feature_count",
     "gfbe_plane_eval", "gfbe_anchor_eval", "gfbe_orientation_subset_plus", "gfbe_gnss_eval",
+    "gfbe_line_eval", "gfbe_line_refine",
 ]
 
 
@@ -175,6 +176,22 @@ class Backend(abi.CApi):
 
     def set_stream(self, stream_ptr):
         self.check(self.lib.gfbe_set_stream(self.ctx, C.c_void_p(stream_ptr)), "set_stream")
+
+    # ---- line landmarks (gfbe_line_eval / gfbe_line_refine)
+    def line_eval(self, pose, ex_cam, orth, obs, sqrt_info=400.0, robustify=True):
+        """lineProjectionFactor at n (pose, line, observation) triples: r [n][2], J_pose / J_ex [n][2][7], J_orth [n][2][4], cost."""
+        try:
+            return abi.line_eval(self.lib, "gfbe_", self.ctx, pose, ex_cam, orth, obs, sqrt_info, robustify)
+        except RuntimeError as e:
+            raise BackendError("%s: %s" % (e, self._err()))
+
+    def line_refine(self, windows, sqrt_info=400.0, cauchy_scale=1.0, max_num_iterations=8):
+        """onlyLineOpt() + removeLineOutlier() of each line window (dicts as synth_line.LineScenario makes them, or
+        abi.LineWindowHolder): per window plucker [n][6] (ineligible lines unchanged), keep [n], summary."""
+        try:
+            return abi.line_refine(self.lib, "gfbe_", self.ctx, windows, sqrt_info, cauchy_scale, max_num_iterations)
+        except RuntimeError as e:
+            raise BackendError("%s: %s" % (e, self._err()))
 
     # ---- device-resident batch
     def batch_upload(self, snaps):

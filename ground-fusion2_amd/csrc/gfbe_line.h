@@ -1,0 +1,192 @@
+// gfbe_line.h — line landmarks: the orthonormal line representation, the line projection factor and the culling test, as
+// __host__ __device__ functions used by csrc/gfbe_line.hip (and compiled for the host by tests/line_host_shim.cpp).
+// Reference semantics:
+//   plk_to_orth / orth_to_plk / plk_to_pose / plk_from_pose   utility/line_geometry.cpp:56-113, 181-200
+//   lineProjectionFactor::Evaluate                            factor/line_projection_factor.cpp:18-231
+//   LineOrthParameterization::Plus                            factor/line_parameterization.cpp:10-95 (ComputeJacobian = I)
+//   ceres::CauchyLoss + the corrector of the residual block   (rho'' < 0: r and J scaled by sqrt(rho'))
+//   FeatureManager::removeLineOutlier / reprojection_error    estimator/feature_manager.cpp:1126-1150, 1372-1460
+// Plücker lines are [n(3) | v(3)] (moment, direction); orthonormal lines [theta(3) | phi]. Poses are [p(3) | q(x, y, z, w)].
+#pragma once
+#include "gfbe_math.h"
+
+namespace gfd {
+
+GF_HD vec3 lcross(const vec3 &a, const vec3 &b) {
+  return mk3(a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]);
+}
+GF_HD double lnorm3(const vec3 &a) { return sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); }
+
+// R(theta) = Rz(theta2) Ry(theta1) Rx(theta0), written out as the reference does (line_geometry.cpp:84-94)
+GF_HD mat3 line_theta_rot(double t0, double t1, double t2) {
+  const double s1 = sin(t0), c1 = cos(t0), s2 = sin(t1), c2 = cos(t1), s3 = sin(t2), c3 = cos(t2);
+  mat3 R;
+  R.m[0] = c2 * c3; R.m[1] = s1 * s2 * c3 - c1 * s3; R.m[2] = c1 * s2 * c3 + s1 * s3;
+  R.m[3] = c2 * s3; R.m[4] = s1 * s2 * s3 + c1 * c3; R.m[5] = c1 * s2 * s3 - s1 * c3;
+  R.m[6] = -s2;     R.m[7] = s1 * c2;                R.m[8] = c1 * c2;
+  return R;
+}
+
+// orth -> Plücker: n = cos(phi) u1, v = sin(phi) u2 (u1, u2 the first two columns of R(theta))
+GF_HD void line_orth_to_plk(const double *o, double *plk) {
+  const mat3 R = line_theta_rot(o[0], o[1], o[2]);
+  const double w1 = cos(o[3]), w2 = sin(o[3]);
+  for (int a = 0; a < 3; a++) { plk[a] = w1 * R(a, 0); plk[3 + a] = w2 * R(a, 1); }
+}
+
+// Plücker -> orth (any scale of the line; the result describes the normalised line)
+GF_HD void line_plk_to_orth(const double *plk, double *o) {
+  const vec3 n = ld3(plk), v = ld3(plk + 3);
+  const double nn = lnorm3(n), vn = lnorm3(v);
+  const vec3 u1 = mk3(n[0] / nn, n[1] / nn, n[2] / nn), u2 = mk3(v[0] / vn, v[1] / vn, v[2] / vn);
+  const vec3 u3 = lcross(u1, u2);
+  o[0] = atan2(u2[2], u3[2]);
+  o[1] = asin(-u1[2]);
+  o[2] = atan2(u1[1], u1[0]);
+  const double wn = sqrt(nn * nn + vn * vn);
+  o[3] = asin(vn / wn);
+}
+
+// plk_to_pose(plk, Rcw, tcw): the line expressed in the frame that (Rcw, tcw) maps into
+GF_HD void line_plk_to_pose(const double *plk, const mat3 &R, const vec3 &t, double *out) {
+  const vec3 Rv = mv(R, ld3(plk + 3));
+  const vec3 nc = add(mv(R, ld3(plk)), lcross(t, Rv));
+  for (int a = 0; a < 3; a++) { out[a] = nc[a]; out[3 + a] = Rv[a]; }
+}
+// plk_from_pose(plk, Rcw, tcw) = plk_to_pose(plk, Rcw^T, -Rcw^T tcw)
+GF_HD void line_plk_from_pose(const double *plk, const mat3 &R, const vec3 &t, double *out) {
+  line_plk_to_pose(plk, transp(R), neg(tmv(R, t)), out);
+}
+
+// LineOrthParameterization::Plus: R <- R Rx(d0) Ry(d1) Rz(d2), W <- W W(d3), back to (theta, phi)
+GF_HD void line_orth_plus(const double *x, const double *d, double *out) {
+  const mat3 R0 = line_theta_rot(x[0], x[1], x[2]);
+  const double cx = cos(d[0]), sx = sin(d[0]), cy = cos(d[1]), sy = sin(d[1]), cz = cos(d[2]), sz = sin(d[2]);
+  mat3 Rx, Ry, Rz;
+  Rx.m[0] = 1.0; Rx.m[1] = 0.0; Rx.m[2] = 0.0; Rx.m[3] = 0.0; Rx.m[4] = cx; Rx.m[5] = -sx; Rx.m[6] = 0.0; Rx.m[7] = sx; Rx.m[8] = cx;
+  Ry.m[0] = cy; Ry.m[1] = 0.0; Ry.m[2] = sy; Ry.m[3] = 0.0; Ry.m[4] = 1.0; Ry.m[5] = 0.0; Ry.m[6] = -sy; Ry.m[7] = 0.0; Ry.m[8] = cy;
+  Rz.m[0] = cz; Rz.m[1] = -sz; Rz.m[2] = 0.0; Rz.m[3] = sz; Rz.m[4] = cz; Rz.m[5] = 0.0; Rz.m[6] = 0.0; Rz.m[7] = 0.0; Rz.m[8] = 1.0;
+  const mat3 R = mul(mul(mul(R0, Rx), Ry), Rz);
+  const double w1 = cos(x[3]), w2 = sin(x[3]), c4 = cos(d[3]), s4 = sin(d[3]);
+  const double W10 = w2 * c4 + w1 * s4;      // (W dW)(1, 0)
+  out[0] = atan2(R(2, 1), R(2, 2));
+  out[1] = asin(-R(2, 0));
+  out[2] = atan2(R(1, 0), R(0, 0));
+  out[3] = asin(W10);
+}
+
+// ceres::CauchyLoss(a) and the corrector of a 2-row residual block: cost = 1/2 rho(s); r, J scaled by sqrt(rho') (rho'' < 0 always)
+GF_HD double line_cauchy(double s, double a, double *sqrt_rho1) {
+  const double b = a * a, c = 1.0 / b;
+  const double sum = 1.0 + s * c, inv = 1.0 / sum;
+  *sqrt_rho1 = sqrt(fmax(2.2250738585072014e-308, inv));
+  return 0.5 * (b * log(sum));
+}
+
+// lineProjectionFactor::Evaluate. Pose / extrinsic as rotation + translation (PoseRT-like), orth [4], obs [4] = the two endpoints on
+// the normalised image plane. r [2]; if JAC: Jp, Je [2][7] (tangent columns dp(3) dtheta(3), the 7th zero), Jo [2][4].
+struct LineRT { vec3 t; mat3 R; };
+GF_HD LineRT line_make_pose(const double *p7) { LineRT o; o.t = ld3(p7); o.R = qrot(ldq(p7 + 3)); return o; }
+
+template <bool JAC>
+GF_HD void line_factor(const LineRT &B, const LineRT &E, const double *orth, const double *obs, double sqrt_info, double *r, double *Jp,
+                       double *Je, double *Jo) {
+  double lw[6], lb[6], lc[6];
+  line_orth_to_plk(orth, lw);
+  line_plk_from_pose(lw, B.R, B.t, lb);
+  line_plk_from_pose(lb, E.R, E.t, lc);
+  const double l_norm = lc[0] * lc[0] + lc[1] * lc[1];
+  const double l_sqrt = sqrt(l_norm), l_tri = l_norm * l_sqrt;
+  const double e1 = obs[0] * lc[0] + obs[1] * lc[1] + lc[2];
+  const double e2 = obs[2] * lc[0] + obs[3] * lc[1] + lc[2];
+  r[0] = sqrt_info * (e1 / l_sqrt);
+  r[1] = sqrt_info * (e2 / l_sqrt);
+  if (!JAC) return;
+  // d e / d nc (2 x 3), sqrt_info applied; the direction part of line_c does not enter the residual
+  double jel[6] = {obs[0] / l_sqrt - lc[0] * e1 / l_tri, obs[1] / l_sqrt - lc[1] * e1 / l_tri, 1.0 / l_sqrt,
+                   obs[2] / l_sqrt - lc[0] * e2 / l_tri, obs[3] / l_sqrt - lc[1] * e2 / l_tri, 1.0 / l_sqrt};
+  for (int q = 0; q < 6; q++) jel[q] = sqrt_info * jel[q];
+  // J = jel * M for a 3 x 3 block M, into columns [c0, c0 + 3) of a row-major matrix with `ld` columns
+  auto put = [&](double *J, int ld, int c0, const mat3 &M) {
+    for (int i = 0; i < 2; i++)
+      for (int b = 0; b < 3; b++) J[i * ld + c0 + b] = jel[3 * i] * M(0, b) + jel[3 * i + 1] * M(1, b) + jel[3 * i + 2] * M(2, b);
+  };
+  if (Jp) {   // top rows of invTbc * dLb/d(pose): Rbc^T [Rwb^T [dw]x | [Rwb^T (nw + [dw]x twb)]x] - Rbc^T [tbc]x [0 | [Rwb^T dw]x]
+    const vec3 nw = ld3(lw), dw = ld3(lw + 3);
+    const mat3 Mt = tmul(E.R, tmul(B.R, hat(dw)));
+    const mat3 Mth = msub(tmul(E.R, hat(tmv(B.R, add(nw, lcross(dw, B.t))))), tmul(E.R, mul(hat(E.t), hat(tmv(B.R, dw)))));
+    put(Jp, 7, 0, Mt); put(Jp, 7, 3, Mth);
+    Jp[6] = 0.0; Jp[13] = 0.0;
+  }
+  if (Je) {
+    const vec3 nb = ld3(lb), db = ld3(lb + 3);
+    put(Je, 7, 0, tmul(E.R, hat(db))); put(Je, 7, 3, hat(tmv(E.R, add(nb, lcross(db, E.t)))));
+    Je[6] = 0.0; Je[13] = 0.0;
+  }
+  if (Jo) {   // jel * [Rwc^T, -Rwc^T [twc]x] * dLw/d(orth)
+    const mat3 Rwc = mul(B.R, E.R);
+    const vec3 twc = add(mv(B.R, E.t), B.t);
+    const vec3 nw = ld3(lw), vw = ld3(lw + 3);
+    const double nn = lnorm3(nw), vn = lnorm3(vw);
+    const vec3 u1 = mk3(nw[0] / nn, nw[1] / nn, nw[2] / nn), u2 = mk3(vw[0] / vn, vw[1] / vn, vw[2] / vn), u3 = lcross(u1, u2);
+    const double wn = sqrt(nn * nn + vn * vn), w0 = nn / wn, w1 = vn / wn;
+    // columns of dLw/d(orth): n part Ln, v part Lv (3 x 4 each)
+    vec3 Ln[4], Lv[4];
+    Ln[0] = mk3(0.0, 0.0, 0.0);  Lv[0] = scl(w1, u3);
+    Ln[1] = scl(-w0, u3);        Lv[1] = mk3(0.0, 0.0, 0.0);
+    Ln[2] = scl(w0, u2);         Lv[2] = scl(-w1, u1);
+    Ln[3] = scl(-w1, u1);        Lv[3] = scl(w0, u2);
+    const mat3 Tw = tmul(Rwc, hat(twc));      // Rwc^T [twc]x
+    for (int k = 0; k < 4; k++) {
+      const vec3 c = sub(tmv(Rwc, Ln[k]), mv(Tw, Lv[k]));
+      for (int i = 0; i < 2; i++) Jo[i * 4 + k] = jel[3 * i] * c[0] + jel[3 * i + 1] * c[1] + jel[3 * i + 2] * c[2];
+    }
+  }
+}
+
+// ---- removeLineOutlier (feature_manager.cpp:1372-1460)
+// pi_from_ppp(x1, x2, x3) with x1 = the camera centre (0): [(x1 - x3) x (x2 - x3) | -x3 . (x1 x x2)]
+GF_HD void line_plane_through_origin(const vec3 &x2, const vec3 &x3, double *pi) {
+  const vec3 z = mk3(0.0, 0.0, 0.0);
+  const vec3 c = lcross(sub(z, x3), sub(x2, x3));
+  pi[0] = c[0]; pi[1] = c[1]; pi[2] = c[2];
+  pi[3] = -dot3(x3, lcross(z, x2));
+}
+// The endpoint test on the start-frame Plücker line (camera frame) and its first observation: true = erase (an endpoint behind the
+// camera, or the two endpoints more than 10 apart). Endpoints e = Lc pi / (Lc pi)[3], Lc = [[n]x v; -v^T 0].
+GF_HD bool line_endpoints_bad(const double *plk_c, const double *obs0) {
+  const vec3 nc = ld3(plk_c), vc = ld3(plk_c + 3);
+  const vec3 p11 = mk3(obs0[0], obs0[1], 1.0), p21 = mk3(obs0[2], obs0[3], 1.0);
+  const vec3 l = lcross(p11, p21);
+  const double ln = sqrt(l[0] * l[0] + l[1] * l[1]), lx = l[0] / ln, ly = l[1] / ln;
+  const vec3 p12 = mk3(p11[0] + lx, p11[1] + ly, 1.0), p22 = mk3(p21[0] + lx, p21[1] + ly, 1.0);
+  double pi1[4], pi2[4], e1[4], e2[4];
+  line_plane_through_origin(p11, p12, pi1);
+  line_plane_through_origin(p21, p22, pi2);
+  const mat3 N = hat(nc);
+  for (int a = 0; a < 3; a++) {
+    e1[a] = N(a, 0) * pi1[0] + N(a, 1) * pi1[1] + N(a, 2) * pi1[2] + vc[a] * pi1[3];
+    e2[a] = N(a, 0) * pi2[0] + N(a, 1) * pi2[1] + N(a, 2) * pi2[2] + vc[a] * pi2[3];
+  }
+  e1[3] = -vc[0] * pi1[0] - vc[1] * pi1[1] - vc[2] * pi1[2] + 0.0 * pi1[3];
+  e2[3] = -vc[0] * pi2[0] - vc[1] * pi2[1] - vc[2] * pi2[2] + 0.0 * pi2[3];
+  const double d1 = e1[3], d2 = e2[3];
+  for (int a = 0; a < 4; a++) { e1[a] = e1[a] / d1; e2[a] = e2[a] / d2; }
+  if (e1[2] < 0 || e2[2] < 0) return true;
+  double s = 0.0;
+  for (int a = 0; a < 4; a++) s += (e1[a] - e2[a]) * (e1[a] - e2[a]);
+  return sqrt(s) > 10;
+}
+// FeatureManager::reprojection_error: mean distance of the two observed endpoints to the projected line (camera pose Rwc, twc)
+GF_HD double line_reprojection_error(const double *obs, const mat3 &Rwc, const vec3 &twc, const double *line_w) {
+  double lc[6];
+  line_plk_from_pose(line_w, Rwc, twc, lc);
+  const double sql = sqrt(lc[0] * lc[0] + lc[1] * lc[1]);
+  const double n0 = lc[0] / sql, n1 = lc[1] / sql, n2 = lc[2] / sql;
+  double err = 0.0;
+  err += fabs(n0 * obs[0] + n1 * obs[1] + n2);
+  err += fabs(n0 * obs[2] + n1 * obs[3] + n2);
+  return err / 2.0;
+}
+
+}  // namespace gfd

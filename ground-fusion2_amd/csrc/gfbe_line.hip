@@ -1,0 +1,456 @@
+// gfbe_line.hip — line landmarks on the device: stand-alone evaluation of the line projection factor, and the line-only refinement
+// that runs on every frame of a `use_line` deployment (estimator.cpp:1426-1438), as one batched call:
+//
+//   Estimator::onlyLineOpt                       estimator/estimator.cpp:4264-4332
+//   FeatureManager::getLineOrthVector / setLineOrth   estimator/feature_manager.cpp:1068-1125 (orth <-> Plücker on entry and exit)
+//   FeatureManager::removeLineOutlier            estimator/feature_manager.cpp:1372-1460 (with reprojection_error :1126-1150)
+//
+// Solver: ceres::Solve with Ceres 1.14's defaults as onlyLineOpt leaves them — Levenberg-Marquardt trust region, Jacobi scaling,
+// max_num_iterations = NUM_ITERATIONS — with every pose and the camera extrinsic constant and CauchyLoss(1.0) on each observation. The
+// LM conventions are those of the pose graph's restatement (gfbe_posegraph.hip, oracle/gfo_posegraph.cpp): Jacobi scaling fixed at
+// iteration 0, diagonal clamp(diag, 1e-6, 1e32) / radius (kept on a rejected step), initial radius 1e4, the radius / decrease-factor
+// update, min_relative_decrease 1e-3, function / gradient / parameter tolerances 1e-6 / 1e-10 / 1e-8; the gradient max-norm is
+// |x - Plus(x, -g)|_inf through the line Plus, as Ceres takes it. With the poses constant the normal equations are block-diagonal:
+// one 4 x 4 block per line.
+//
+// Shape: ONE WORKGROUP PER WINDOW runs the whole loop in one launch. Lines are spread over the threads (line t, t + 256, ...); each
+// line's linearisation (4 x 4 J^T J, J^T r), scaling, LM diagonal and parameters live in a per-line scratch row; the per-window sums
+// (cost, model cost change, |step|^2, |x|^2, gradient max-norm, the factorisation failure flag) go through a fixed-order reduction
+// (wave shuffle tree, then the waves in order through LDS). Every thread holds the loop's scalars and takes the same decisions from
+// the broadcast sums. No grid barrier, no atomics, nothing shared between windows: a window's outputs are bit-reproducible and do not
+// depend on the batch around it. FP64 vector ALU only (4 x 4 blocks leave the matrix cores nothing to do).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "gfbe_device.h"
+#include "gfbe_line.h"
+
+using namespace gfd;
+
+namespace {
+
+enum { LR_THREADS = 256, LR_WAVES = LR_THREADS / 64, LR_ROW = 40 };
+// per-line scratch row (LR_ROW doubles): x [0, 4), candidate [4, 8), H [8, 24), g [24, 28), Jacobi scale [28, 32), LM diagonal [32, 36)
+enum { LX = 0, LC = 4, LH = 8, LG = 24, LS = 28, LD = 32 };
+
+__global__ __launch_bounds__(256) void k_line_eval(int n, const double *pose, const double *ex, const double *orth, const double *obs,
+                                                   double sqrt_info, int robust, double *r, double *Jp, double *Je, double *Jo,
+                                                   double *cost_part) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const LineRT B = line_make_pose(pose + 7 * (size_t)k), E = line_make_pose(ex);
+  double res[2], jp[14], je[14], jo[8];
+  line_factor<true>(B, E, orth + 4 * (size_t)k, obs + 4 * (size_t)k, sqrt_info, res, jp, je, jo);
+  const double s = res[0] * res[0] + res[1] * res[1];
+  double c;
+  if (robust) {
+    double sr;
+    c = line_cauchy(s, 1.0, &sr);
+    res[0] *= sr; res[1] *= sr;
+    for (int q = 0; q < 14; q++) { jp[q] *= sr; je[q] *= sr; }
+    for (int q = 0; q < 8; q++) jo[q] *= sr;
+  } else {
+    c = 0.5 * s;
+  }
+  if (r) for (int q = 0; q < 2; q++) r[2 * (size_t)k + q] = res[q];
+  if (Jp) for (int q = 0; q < 14; q++) Jp[14 * (size_t)k + q] = jp[q];
+  if (Je) for (int q = 0; q < 14; q++) Je[14 * (size_t)k + q] = je[q];
+  if (Jo) for (int q = 0; q < 8; q++) Jo[8 * (size_t)k + q] = jo[q];
+  cost_part[k] = c;       // summed in factor order on the host
+}
+
+struct LineBatch {
+  const int *line_off;          // [n_windows + 1]
+  const int *obs_off;           // [n_lines + 1] (over the whole batch)
+  const int *start;             // [n_lines]
+  const unsigned char *tri;     // [n_lines]
+  const double *plk_in;         // [n_lines][6]
+  const double *obs;            // [n_obs][4]
+  const double *pose;           // [n_windows][11][7]
+  const double *ex;             // [n_windows][7]
+  double sqrt_info, cauchy;
+  int max_it;
+  double *row;                  // [n_lines][LR_ROW]
+  double *plk_out;              // [n_lines][6]
+  unsigned char *keep;          // [n_lines]
+  gfbe_summary *sum;            // [n_windows]
+};
+
+__device__ __forceinline__ bool line_eligible(const LineBatch &P, int l) {
+  return P.obs_off[l + 1] - P.obs_off[l] >= 5 && P.start[l] < GFBE_WINDOW_SIZE - 2 && P.tri[l];   // LINE_MIN_OBS, WINDOW_SIZE - 2
+}
+
+// cost of line l at x; with H, g: its Cauchy-corrected normal-equation block and gradient
+template <bool LIN>
+__device__ double line_lin(const LineBatch &P, int l, const double *x, const LineRT *Bs, const LineRT &Ex, double *H, double *g) {
+  double cost = 0.0;
+  if (LIN) { for (int q = 0; q < 16; q++) H[q] = 0.0; for (int q = 0; q < 4; q++) g[q] = 0.0; }
+  const int s = P.start[l], o0 = P.obs_off[l], o1 = P.obs_off[l + 1];
+  for (int o = o0; o < o1; o++) {
+    double r[2], Jo[8];
+    line_factor<LIN>(Bs[s + o - o0], Ex, x, P.obs + 4 * (size_t)o, P.sqrt_info, r, nullptr, nullptr, LIN ? Jo : nullptr);
+    double sr;
+    cost += line_cauchy(r[0] * r[0] + r[1] * r[1], P.cauchy, &sr);
+    if (LIN) {
+      r[0] *= sr; r[1] *= sr;
+      for (int q = 0; q < 8; q++) Jo[q] *= sr;
+      for (int a = 0; a < 4; a++) {
+        g[a] += Jo[a] * r[0] + Jo[4 + a] * r[1];
+        for (int b = 0; b < 4; b++) H[4 * a + b] += Jo[a] * Jo[b] + Jo[4 + a] * Jo[4 + b];
+      }
+    }
+  }
+  return cost;
+}
+
+// |x - Plus(x, -g)|_inf of one line
+__device__ double line_grad_norm(const double *x, const double *g) {
+  const double mg[4] = {-g[0], -g[1], -g[2], -g[3]};
+  double xp[4], m = 0.0;
+  line_orth_plus(x, mg, xp);
+  for (int a = 0; a < 4; a++) m = fmax(m, fabs(x[a] - xp[a]));
+  return m;
+}
+
+// Fixed-order reduction of four per-thread values over the workgroup: entry 0 by max when max0, the others by sum. Every thread gets
+// the results in out[4].
+__device__ void lr_reduce(double v0, double v1, double v2, double v3, bool max0, double (*sh)[LR_WAVES], double *out) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double a = __shfl_down(v0, o, 64), b = __shfl_down(v1, o, 64), c = __shfl_down(v2, o, 64), d = __shfl_down(v3, o, 64);
+    v0 = max0 ? fmax(v0, a) : v0 + a; v1 += b; v2 += c; v3 += d;
+  }
+  if ((t & 63) == 0) { sh[0][t >> 6] = v0; sh[1][t >> 6] = v1; sh[2][t >> 6] = v2; sh[3][t >> 6] = v3; }
+  __syncthreads();
+  if (t < 4) {
+    double v = 0.0;
+    for (int q = 0; q < LR_WAVES; q++) v = (max0 && t == 0) ? fmax(v, sh[t][q]) : v + sh[t][q];
+    out[t] = v;
+  }
+  __syncthreads();
+}
+
+// 4 x 4 SPD solve A y = b by Cholesky; false if a pivot is not positive (or not a number)
+__device__ bool chol4_solve(double *A, const double *b, double *y) {
+  double L[16];
+  for (int q = 0; q < 16; q++) L[q] = 0.0;
+  for (int j = 0; j < 4; j++) {
+    double d = A[5 * j];
+    for (int k = 0; k < j; k++) d -= L[4 * j + k] * L[4 * j + k];
+    if (!(d > 0.0)) return false;
+    const double ljj = sqrt(d);
+    L[5 * j] = ljj;
+    for (int i = j + 1; i < 4; i++) {
+      double s = A[4 * i + j];
+      for (int k = 0; k < j; k++) s -= L[4 * i + k] * L[4 * j + k];
+      L[4 * i + j] = s / ljj;
+    }
+  }
+  double z[4];
+  for (int i = 0; i < 4; i++) { double s = b[i]; for (int k = 0; k < i; k++) s -= L[4 * i + k] * z[k]; z[i] = s / L[5 * i]; }
+  for (int i = 3; i >= 0; i--) { double s = z[i]; for (int k = i + 1; k < 4; k++) s -= L[4 * k + i] * y[k]; y[i] = s / L[5 * i]; }
+  return true;
+}
+
+__global__ __launch_bounds__(LR_THREADS) void k_line_refine(LineBatch P) {
+  const int w = blockIdx.x, t = threadIdx.x;
+  __shared__ LineRT Bs[GFBE_NFRAMES], Cw[GFBE_NFRAMES];
+  __shared__ LineRT Ex;
+  __shared__ double sh[4][LR_WAVES];
+  __shared__ double red[4];
+  const int l0 = P.line_off[w], l1 = P.line_off[w + 1];
+  const uint64_t t_start = wall_clock64();
+  if (t < GFBE_NFRAMES) Bs[t] = line_make_pose(P.pose + (size_t)w * 77 + 7 * t);
+  if (t == GFBE_NFRAMES) Ex = line_make_pose(P.ex + (size_t)w * 7);
+  __syncthreads();
+  if (t < GFBE_NFRAMES) { Cw[t].R = mul(Bs[t].R, Ex.R); Cw[t].t = add(Bs[t].t, mv(Bs[t].R, Ex.t)); }   // Rwc = Rs ric, twc = Ps + Rs tic
+  // eligibility count
+  double ne = 0.0;
+  for (int l = l0 + t; l < l1; l += LR_THREADS) ne += line_eligible(P, l) ? 1.0 : 0.0;
+  lr_reduce(0.0, ne, 0.0, 0.0, false, sh, red);
+  const int n_elig = (int)red[1];
+  // the loop's scalars live in every thread (the same values everywhere); its per-iteration record in LDS, written by thread 0
+  __shared__ double hist[16];
+  __shared__ unsigned char acc[16];
+  int status = GFBE_OK, termination = 0, num_successful = 0;
+  auto record = [&](int i, int a, double v) { if (t == 0) { hist[i] = v; acc[i] = (unsigned char)a; } };
+  if (n_elig < 4) {      // `if (feature_index < 3) return;` — nothing solved, nothing written back, removeLineOutlier not called
+    for (int l = l0 + t; l < l1; l += LR_THREADS) {
+      for (int a = 0; a < 6; a++) P.plk_out[6 * (size_t)l + a] = P.plk_in[6 * (size_t)l + a];
+      P.keep[l] = 1;
+    }
+    if (t == 0) { gfbe_summary sm{}; sm.status = GFBE_OK; sm.termination = 5; P.sum[w] = sm; }
+    return;
+  }
+  // entry: para_LineFeature = plk_to_orth(plk_to_pose(line_plucker, Rwc, twc)) of the start frame; the first linearisation
+  double c = 0.0, x2 = 0.0, gm = 0.0;
+  for (int l = l0 + t; l < l1; l += LR_THREADS) {
+    if (!line_eligible(P, l)) continue;
+    double *row = P.row + (size_t)l * LR_ROW, lw[6];
+    const int s = P.start[l];
+    line_plk_to_pose(P.plk_in + 6 * (size_t)l, Cw[s].R, Cw[s].t, lw);
+    line_plk_to_orth(lw, row + LX);
+    c += line_lin<true>(P, l, row + LX, Bs, Ex, row + LH, row + LG);
+    for (int a = 0; a < 4; a++) { x2 += row[LX + a] * row[LX + a]; row[LS + a] = 1.0 / (1.0 + sqrt(row[LH + 5 * a])); }
+    gm = fmax(gm, line_grad_norm(row + LX, row + LG));
+  }
+  lr_reduce(gm, c, x2, 0.0, true, sh, red);
+  double cost = red[1], gmax = red[0], x_norm = sqrt(red[2]), radius = 1e4, decrease = 2.0;
+  const double initial_cost = cost;
+  if (t < 16) { hist[t] = 0.0; acc[t] = 0; }
+  __syncthreads();
+  record(0, 0, cost);
+  status = GFBE_NO_CONVERGENCE;
+  int it = 0, invalid = 0;
+  bool reuse = false;
+  while (true) {
+    if (it >= P.max_it) { termination = 0; break; }
+    if (gmax <= 1e-10) { termination = 3; status = GFBE_OK; break; }
+    if (radius < 1e-32) { termination = 4; break; }
+    it++;
+    // every line: scaled system, LM diagonal, 4 x 4 solve, model cost change, candidate
+    double fail = 0.0, mc = 0.0, st2 = 0.0, cx2 = 0.0;
+    for (int l = l0 + t; l < l1; l += LR_THREADS) {
+      if (!line_eligible(P, l)) continue;
+      double *row = P.row + (size_t)l * LR_ROW;
+      double Hs[16], A[16], rhs[4], y[4];
+      for (int a = 0; a < 4; a++) {
+        for (int b = 0; b < 4; b++) Hs[4 * a + b] = row[LH + 4 * a + b] * row[LS + a] * row[LS + b];
+        rhs[a] = -row[LS + a] * row[LG + a];
+      }
+      if (!reuse) for (int a = 0; a < 4; a++) row[LD + a] = fmin(fmax(Hs[5 * a], 1e-6), 1e32);
+      for (int q = 0; q < 16; q++) A[q] = Hs[q];
+      for (int a = 0; a < 4; a++) A[5 * a] += row[LD + a] / radius;
+      if (!chol4_solve(A, rhs, y)) { fail = 1.0; continue; }
+      double gy = 0.0, yHy = 0.0;
+      for (int a = 0; a < 4; a++) {
+        double s = 0.0;
+        for (int b = 0; b < 4; b++) s += Hs[4 * a + b] * y[b];
+        gy += -rhs[a] * y[a]; yHy += y[a] * s;
+      }
+      mc += -(gy + 0.5 * yHy);
+      double d[4];
+      for (int a = 0; a < 4; a++) d[a] = row[LS + a] * y[a];
+      line_orth_plus(row + LX, d, row + LC);
+      for (int a = 0; a < 4; a++) { const double df = row[LC + a] - row[LX + a]; st2 += df * df; cx2 += row[LC + a] * row[LC + a]; }
+    }
+    lr_reduce(fail, mc, st2, cx2, true, sh, red);
+    const double model_change = red[1], step2 = red[2], cand_x2 = red[3];
+    if (red[0] != 0.0 || !(model_change > 0.0)) {      // invalid step
+      record(it, 0, cost);
+      if (++invalid >= 5) { termination = 4; status = GFBE_NUMERICAL_FAILURE; break; }
+      radius /= decrease; decrease *= 2; reuse = true;
+      continue;
+    }
+    invalid = 0;
+    double cc = 0.0;
+    for (int l = l0 + t; l < l1; l += LR_THREADS)
+      if (line_eligible(P, l)) cc += line_lin<false>(P, l, P.row + (size_t)l * LR_ROW + LC, Bs, Ex, nullptr, nullptr);
+    lr_reduce(0.0, cc, 0.0, 0.0, false, sh, red);
+    const double cand_cost = red[1];
+    record(it, 0, cost);
+    if (sqrt(step2) <= 1e-8 * (x_norm + 1e-8)) { termination = 2; status = GFBE_OK; break; }
+    const double change = cost - cand_cost;
+    if (fabs(change) <= 1e-6 * cost) { termination = 1; status = GFBE_OK; break; }
+    const double rho = change / model_change;
+    if (rho > 1e-3) {
+      cost = cand_cost; x_norm = sqrt(cand_x2);
+      record(it, 1, cost); num_successful++;
+      radius = fmin(1e16, radius / fmax(1.0 / 3.0, 1.0 - pow(2.0 * rho - 1.0, 3.0)));
+      decrease = 2.0; reuse = false;
+      double g2 = 0.0;
+      for (int l = l0 + t; l < l1; l += LR_THREADS) {
+        if (!line_eligible(P, l)) continue;
+        double *row = P.row + (size_t)l * LR_ROW;
+        for (int a = 0; a < 4; a++) row[LX + a] = row[LC + a];
+        (void)line_lin<true>(P, l, row + LX, Bs, Ex, row + LH, row + LG);
+        g2 = fmax(g2, line_grad_norm(row + LX, row + LG));
+      }
+      lr_reduce(g2, 0.0, 0.0, 0.0, true, sh, red);
+      gmax = red[0];
+    } else {
+      record(it, 0, cost);
+      radius /= decrease; decrease *= 2; reuse = true;
+    }
+  }
+  // exit: setLineOrth (line_plucker = plk_from_pose(orth_to_plk(orth), Rwc, twc)), then removeLineOutlier on the written-back lines
+  for (int l = l0 + t; l < l1; l += LR_THREADS) {
+    double *out = P.plk_out + 6 * (size_t)l;
+    if (!line_eligible(P, l)) {
+      for (int a = 0; a < 6; a++) out[a] = P.plk_in[6 * (size_t)l + a];
+      P.keep[l] = 1;
+      continue;
+    }
+    const int s = P.start[l], o0 = P.obs_off[l], o1 = P.obs_off[l + 1];
+    double lw[6];
+    line_orth_to_plk(P.row + (size_t)l * LR_ROW + LX, lw);
+    line_plk_from_pose(lw, Cw[s].R, Cw[s].t, out);
+    unsigned char keep = 1;
+    if (line_endpoints_bad(out, P.obs + 4 * (size_t)o0)) {
+      keep = 0;
+    } else {
+      line_plk_to_pose(out, Cw[s].R, Cw[s].t, lw);
+      double allerr = 0.0;
+      for (int o = o0; o < o1; o++) {
+        const double err = line_reprojection_error(P.obs + 4 * (size_t)o, Cw[s + o - o0].R, Cw[s + o - o0].t, lw);
+        if (allerr < err) allerr = err;
+      }
+      if (allerr > 3.0 / 500.0) keep = 0;
+    }
+    P.keep[l] = keep;
+  }
+  if (t == 0) {
+    gfbe_summary sm{};
+    sm.status = status; sm.termination = termination; sm.num_successful = num_successful;
+    sm.iterations = it; sm.initial_cost = initial_cost; sm.final_cost = cost; sm.final_radius = radius;
+    for (int q = 0; q < 16; q++) { sm.cost_history[q] = hist[q]; sm.accepted[q] = acc[q]; }
+    sm.ms_solve = (double)(wall_clock64() - t_start) * 1e-5;      // (100 MHz device wall clock)
+    P.sum[w] = sm;
+  }
+}
+
+#define LN_CHECK(c, call)                                                                                      \
+  do {                                                                                                         \
+    hipError_t e_ = (call);                                                                                    \
+    if (e_ != hipSuccess) { ctx_set_error(c, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); st = GFBE_DEVICE_ERROR; goto done; } \
+  } while (0)
+
+}  // namespace
+
+extern "C" gfbe_status gfbe_line_eval(gfbe_ctx *c, int32_t n, const double *pose, const double *ex_cam, const double *orth, const double *obs,
+                                      double sqrt_info, int32_t robustify, double *r, double *J_pose, double *J_ex, double *J_orth,
+                                      double *cost) {
+  if (!c || n < 0 || (n > 0 && (!pose || !orth || !obs)) || !ex_cam) return GFBE_BAD_INPUT;
+  if (ctx_device(c) < 0) { ctx_set_error(c, "gfbe_line_eval: HIP device context required (no CPU fallback)"); return GFBE_NO_DEVICE; }
+  if (n == 0) { if (cost) *cost = 0.0; return GFBE_OK; }
+  hipStream_t s = ctx_stream(c);
+  gfbe_status st = GFBE_OK;
+  double *d = nullptr;
+  const size_t np = (size_t)7 * n, no = (size_t)4 * n, nr = (size_t)2 * n, nj = (size_t)14 * n, nk = (size_t)8 * n;
+  double *dpose, *dex, *dorth, *dobs, *dr, *djp, *dje, *djo, *dc;
+  std::vector<double> hc(n);
+  LN_CHECK(c, hipMalloc((void **)&d, sizeof(double) * (np + 7 + 2 * no + nr + 2 * nj + nk + n)));
+  dpose = d; dex = dpose + np; dorth = dex + 7; dobs = dorth + no; dr = dobs + no; djp = dr + nr; dje = djp + nj; djo = dje + nj; dc = djo + nk;
+  LN_CHECK(c, hipMemcpyAsync(dpose, pose, sizeof(double) * np, hipMemcpyHostToDevice, s));
+  LN_CHECK(c, hipMemcpyAsync(dex, ex_cam, sizeof(double) * 7, hipMemcpyHostToDevice, s));
+  LN_CHECK(c, hipMemcpyAsync(dorth, orth, sizeof(double) * no, hipMemcpyHostToDevice, s));
+  LN_CHECK(c, hipMemcpyAsync(dobs, obs, sizeof(double) * no, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_line_eval, dim3((n + 255) / 256), dim3(256), 0, s, n, dpose, dex, dorth, dobs, sqrt_info, robustify ? 1 : 0,
+                     r ? dr : nullptr, J_pose ? djp : nullptr, J_ex ? dje : nullptr, J_orth ? djo : nullptr, dc);
+  LN_CHECK(c, hipGetLastError());
+  LN_CHECK(c, hipMemcpyAsync(hc.data(), dc, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+  LN_CHECK(c, hipStreamSynchronize(s));
+  // (outputs are written only once the whole evaluation has succeeded)
+  if (r) LN_CHECK(c, hipMemcpy(r, dr, sizeof(double) * nr, hipMemcpyDeviceToHost));
+  if (J_pose) LN_CHECK(c, hipMemcpy(J_pose, djp, sizeof(double) * nj, hipMemcpyDeviceToHost));
+  if (J_ex) LN_CHECK(c, hipMemcpy(J_ex, dje, sizeof(double) * nj, hipMemcpyDeviceToHost));
+  if (J_orth) LN_CHECK(c, hipMemcpy(J_orth, djo, sizeof(double) * nk, hipMemcpyDeviceToHost));
+  if (cost) { double tot = 0.0; for (int k = 0; k < n; k++) tot += hc[k]; *cost = tot; }
+done:
+  if (d) (void)hipFree(d);
+  return st;
+}
+
+extern "C" gfbe_status gfbe_line_refine(gfbe_ctx *c, int32_t n_windows, const gfbe_line_window *const *win, double sqrt_info,
+                                        double cauchy_scale, int32_t max_num_iterations, double *plucker_out, uint8_t *keep_out,
+                                        gfbe_summary *summary) {
+  if (!c || n_windows < 0 || (n_windows > 0 && (!win || !summary)) || !(cauchy_scale > 0.0) || max_num_iterations < 0) return GFBE_BAD_INPUT;
+  // the windows: sizes, frames and pointers
+  std::vector<int> line_off(n_windows + 1, 0);
+  size_t n_obs_total = 0;
+  for (int w = 0; w < n_windows; w++) {
+    const gfbe_line_window *L = win[w];
+    if (!L || L->struct_size != (int32_t)sizeof(gfbe_line_window)) { ctx_set_error(c, "gfbe_line_refine: gfbe_line_window ABI mismatch"); return GFBE_BAD_INPUT; }
+    if (L->n_lines < 0 || (L->n_lines > 0 && (!L->start_frame || !L->n_obs || !L->is_triangulation || !L->line_plucker))) return GFBE_BAD_INPUT;
+    size_t no = 0;
+    for (int i = 0; i < L->n_lines; i++) {
+      const int s = L->start_frame[i], k = L->n_obs[i];
+      if (s < 0 || k < 0 || s + k > GFBE_NFRAMES) { ctx_set_error(c, "gfbe_line_refine: a line's observations run past the window"); return GFBE_BAD_INPUT; }
+      no += (size_t)k;
+    }
+    if (no > 0 && !L->obs) return GFBE_BAD_INPUT;
+    if ((size_t)line_off[w] + (size_t)L->n_lines > (size_t)INT32_MAX / 64 || n_obs_total + no > (size_t)INT32_MAX / 8) return GFBE_BAD_INPUT;
+    line_off[w + 1] = line_off[w] + L->n_lines;
+    n_obs_total += no;
+  }
+  const int n_lines = n_windows ? line_off[n_windows] : 0;
+  if (n_lines > 0 && (!plucker_out || !keep_out)) return GFBE_BAD_INPUT;
+  if (ctx_device(c) < 0) { ctx_set_error(c, "gfbe_line_refine: HIP device context required (no CPU fallback)"); return GFBE_NO_DEVICE; }
+  if (n_windows == 0) return GFBE_OK;
+  // pack: ints (line_off, obs_off, start), then doubles (plucker, obs, poses, extrinsics), then the triangulation flags
+  std::vector<int> ints((size_t)n_windows + 1 + 2 * (size_t)n_lines + 1);
+  int *h_line_off = ints.data(), *h_obs_off = h_line_off + n_windows + 1, *h_start = h_obs_off + n_lines + 1;
+  std::vector<double> dbl((size_t)6 * n_lines + 4 * n_obs_total + 84 * (size_t)n_windows);
+  double *h_plk = dbl.data(), *h_obs = h_plk + 6 * (size_t)n_lines, *h_pose = h_obs + 4 * n_obs_total, *h_ex = h_pose + 77 * (size_t)n_windows;
+  std::vector<unsigned char> h_tri(std::max(n_lines, 1));
+  {
+    size_t o = 0;
+    for (int w = 0; w < n_windows; w++) {
+      const gfbe_line_window *L = win[w];
+      h_line_off[w] = line_off[w];
+      std::memcpy(h_pose + 77 * (size_t)w, L->pose, sizeof(double) * 77);
+      std::memcpy(h_ex + 7 * (size_t)w, L->ex_cam, sizeof(double) * 7);
+      size_t lo = 0;
+      for (int i = 0; i < L->n_lines; i++) {
+        const int l = line_off[w] + i;
+        h_obs_off[l] = (int)o; h_start[l] = L->start_frame[i]; h_tri[l] = L->is_triangulation[i] ? 1 : 0;
+        std::memcpy(h_plk + 6 * (size_t)l, L->line_plucker + 6 * (size_t)i, sizeof(double) * 6);
+        if (L->n_obs[i] > 0) std::memcpy(h_obs + 4 * o, L->obs + 4 * lo, sizeof(double) * 4 * L->n_obs[i]);
+        o += L->n_obs[i]; lo += L->n_obs[i];
+      }
+    }
+    h_line_off[n_windows] = n_lines;
+    h_obs_off[n_lines] = (int)o;
+  }
+  hipStream_t s = ctx_stream(c);
+  gfbe_status st = GFBE_OK;
+  char *d = nullptr;
+  const size_t b_int = sizeof(int) * ints.size(), b_dbl = sizeof(double) * dbl.size(), b_row = sizeof(double) * LR_ROW * (size_t)n_lines,
+               b_out = sizeof(double) * 6 * (size_t)n_lines, b_sum = sizeof(gfbe_summary) * (size_t)n_windows, b_tri = h_tri.size();
+  auto up8 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  std::vector<double> h_out((size_t)6 * n_lines);
+  std::vector<unsigned char> h_keep(std::max(n_lines, 1));
+  std::vector<gfbe_summary> h_sum(n_windows);
+  LineBatch P;
+  LN_CHECK(c, hipMalloc((void **)&d, up8(b_int) + up8(b_dbl) + up8(b_row) + up8(b_out) + up8(b_sum) + up8(b_tri) + up8(b_tri)));
+  {
+    char *p = d;
+    int *d_int = (int *)p; p += up8(b_int);
+    double *d_dbl = (double *)p; p += up8(b_dbl);
+    P.row = (double *)p; p += up8(b_row);
+    P.plk_out = (double *)p; p += up8(b_out);
+    P.sum = (gfbe_summary *)p; p += up8(b_sum);
+    unsigned char *d_tri = (unsigned char *)p; p += up8(b_tri);
+    P.keep = (unsigned char *)p;
+    P.line_off = d_int; P.obs_off = d_int + (h_obs_off - h_line_off); P.start = d_int + (h_start - h_line_off);
+    P.plk_in = d_dbl; P.obs = d_dbl + (h_obs - h_plk); P.pose = d_dbl + (h_pose - h_plk); P.ex = d_dbl + (h_ex - h_plk);
+    P.tri = d_tri;
+    P.sqrt_info = sqrt_info; P.cauchy = cauchy_scale; P.max_it = std::min<int>(max_num_iterations, 15);
+    LN_CHECK(c, hipMemcpyAsync(d_int, ints.data(), b_int, hipMemcpyHostToDevice, s));
+    LN_CHECK(c, hipMemcpyAsync(d_dbl, dbl.data(), b_dbl, hipMemcpyHostToDevice, s));
+    LN_CHECK(c, hipMemcpyAsync(d_tri, h_tri.data(), b_tri, hipMemcpyHostToDevice, s));
+  }
+  hipLaunchKernelGGL(k_line_refine, dim3(n_windows), dim3(LR_THREADS), 0, s, P);
+  LN_CHECK(c, hipGetLastError());
+  if (n_lines) {
+    LN_CHECK(c, hipMemcpyAsync(h_out.data(), P.plk_out, b_out, hipMemcpyDeviceToHost, s));
+    LN_CHECK(c, hipMemcpyAsync(h_keep.data(), P.keep, (size_t)n_lines, hipMemcpyDeviceToHost, s));
+  }
+  LN_CHECK(c, hipMemcpyAsync(h_sum.data(), P.sum, b_sum, hipMemcpyDeviceToHost, s));
+  LN_CHECK(c, hipStreamSynchronize(s));
+  {
+    int worst = GFBE_OK;
+    for (int w = 0; w < n_windows; w++) worst = std::max(worst, (int)h_sum[w].status);
+    if (n_lines) { std::memcpy(plucker_out, h_out.data(), b_out); std::memcpy(keep_out, h_keep.data(), (size_t)n_lines); }
+    std::memcpy(summary, h_sum.data(), b_sum);
+    st = (gfbe_status)worst;
+  }
+done:
+  if (d) (void)hipFree(d);
+  return st;
+}

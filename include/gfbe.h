@@ -583,6 +583,52 @@ gfbe_status gfbe_gnss_eval(gfbe_ctx *ctx, int32_t n_obs, const gfbe_gnss_obs *ob
                            double ddt_weight, double *r_obs, double *J_obs, double *r_dt_ddt, double *r_smooth, double *cost);
 
 /* ------------------------------------------------------------------------------------------
+ * Line landmarks (use_line: 1). The line-only refinement every use_line frame runs before optimizationwithLine
+ * (estimator.cpp:1426-1438), on the device:
+ *   lineProjectionFactor::Evaluate           factor/line_projection_factor.cpp:18-231
+ *   LineOrthParameterization::Plus           factor/line_parameterization.cpp:10-95
+ *   Estimator::onlyLineOpt                   estimator.cpp:4264-4332 (poses and extrinsic constant, CauchyLoss(1.0), Ceres' default
+ *                                            Levenberg-Marquardt, max_num_iterations = NUM_ITERATIONS)
+ *   FeatureManager::getLineOrthVector / setLineOrth / removeLineOutlier   feature_manager.cpp:1068-1125, 1372-1460
+ * Plücker lines are [n(3) | v(3)], orthonormal lines [theta(3) | phi], poses [p(3) | q(x, y, z, w)].
+ * ------------------------------------------------------------------------------------------ */
+
+/* gfbe_line_eval: n independent factors; factor k sees pose[k], the shared camera extrinsic, the world line orth[k] and the observed
+ * endpoints obs[k] = [x1 y1 x2 y2] (normalised image plane). sqrt_info is FOCAL_LENGTH / 1.5 = 400 in the reference. robustify != 0
+ * applies CauchyLoss(1.0) and its corrector (r and J scaled by sqrt(rho')). Outputs (any may be NULL): r [n][2]; J_pose [n][2][7] and
+ * J_ex [n][2][7] (tangent columns dp(3) dtheta(3), the 7th zero, as the reference writes them); J_orth [n][2][4]; cost = sum of
+ * 1/2 rho(|r|^2) (1/2 |r|^2 without the loss). */
+gfbe_status gfbe_line_eval(gfbe_ctx *ctx, int32_t n, const double *pose /*[n][7]*/, const double *ex_cam /*[7]*/,
+                           const double *orth /*[n][4]*/, const double *obs /*[n][4]*/, double sqrt_info, int32_t robustify,
+                           double *r, double *J_pose, double *J_ex, double *J_orth, double *cost);
+
+/* What FeatureManager::linefeature holds for one window, in list order. Observation k of line i is in frame start_frame[i] + k
+ * (start_frame[i] + n_obs[i] <= GFBE_NFRAMES); the observations of all lines are packed in line order. */
+typedef struct gfbe_line_window {
+  int32_t struct_size;                /* sizeof(gfbe_line_window) as the caller was built (refused otherwise: GFBE_BAD_INPUT) */
+  int32_t n_lines;
+  const int32_t *start_frame;         /* [n_lines] */
+  const int32_t *n_obs;               /* [n_lines] linefeature_per_frame.size() */
+  const double *obs;                  /* [sum n_obs][4] lineobs */
+  const uint8_t *is_triangulation;    /* [n_lines] */
+  const double *line_plucker;         /* [n_lines][6] in the start frame's camera frame */
+  double pose[GFBE_NFRAMES][7];       /* Ps / Rs of the window */
+  double ex_cam[7];                   /* tic / ric */
+} gfbe_line_window;
+
+/* gfbe_line_refine: onlyLineOpt() followed by removeLineOutlier(Ps, tic, ric), for n_windows independent windows in one launch.
+ * Eligible lines (n_obs >= LINE_MIN_OBS = 5, start_frame < GFBE_WINDOW_SIZE - 2, is_triangulation) are refined and written back through
+ * setLineOrth; every other line comes back bit-identical. With fewer than 4 eligible lines nothing is solved, every line comes back
+ * bit-identical and none is culled (estimator.cpp:4318-4321). plucker_out [sum n_lines][6] and keep_out [sum n_lines] are concatenated
+ * in window order; keep_out[i] = 0: the reference erases line i. sqrt_info: 400 in the reference; cauchy_scale: 1.0;
+ * max_num_iterations: NUM_ITERATIONS (8 in every shipped yaml; at most 15 are run). summary [n_windows] as gfbe_pg_solve fills it
+ * (ms_solve: the window's time in the kernel); iterations = 0 and termination = 5 when the < 4 exit was taken.
+ * Return value: the worst summary status. GFBE_BAD_INPUT / GFBE_NO_DEVICE / GFBE_DEVICE_ERROR: no output has been touched. */
+gfbe_status gfbe_line_refine(gfbe_ctx *ctx, int32_t n_windows, const gfbe_line_window *const *win, double sqrt_info,
+                             double cauchy_scale, int32_t max_num_iterations, double *plucker_out, uint8_t *keep_out,
+                             gfbe_summary *summary);
+
+/* ------------------------------------------------------------------------------------------
  * a4/a5/a7/a9/a10  Factor evaluation on the device, block-CSR output (parity / inspection API).
  * Each evaluates residuals and TANGENT-space Jacobian blocks at the window's current state,
  * exactly what ceres::CostFunction::Evaluate + the manifold lift produce:
