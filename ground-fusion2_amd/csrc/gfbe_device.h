@@ -20,25 +20,16 @@
                                 // (round 5; until then five workgroups per tile: 4 -> 5 measured 1.244 -> 1.227 ms, 10: 1.316), workgroups in k_vis_split
 #endif
 
-// Small batches (< 32 windows, no landmark sharding): launches of one iteration merged on a single window's latency path. Bit 0:
-// k_schur + k_visblock_small in one launch; bit 1: k_step and the dense half of k_candidate by the workgroup of k_lm_step that
-// finishes last, the landmark half of k_candidate by k_lin_small<1>'s tile workgroups; bit 2: k_accept by the workgroup of
-// k_lin_small<1> that finishes last; bit 3: the marginalisation's linearisation (k_vis_split<2> + k_dense) in one launch, its pair sums
-// and its Schur partial in another. Same code, same order of every sum: the results do not change by a bit.
-#ifndef GFBE_FUSE_SMALL
-#define GFBE_FUSE_SMALL 15
-#endif
-
 // GFBE_DIAG = 1: the diagnostics build (libgfbe_diag.so; backend.build_native(diag=True)). Only that build reads the environment
 // hooks of the measurement / test scripts (GFBE_POISON_UNCLEARED, GFBE_VIS_FULL, GFBE_DEBUG_UPLOAD) and accepts the kernel
-// time-stamp / ablation macros (GFBE_ABLATE, GFBE_*_STAMP). The shipped library has none of them: no environment variable can
+// time-stamp macros (GFBE_*_STAMP). The shipped library has none of them: no environment variable can
 // change what it computes or writes.
 #ifndef GFBE_DIAG
 #define GFBE_DIAG 0
 #endif
-#if !GFBE_DIAG && (defined(GFBE_ABLATE) || defined(GFBE_KVIS_STAMP) || defined(GFBE_LIN_STAMP) || defined(GFBE_CHOL_STAMP) || \
+#if !GFBE_DIAG && (defined(GFBE_KVIS_STAMP) || defined(GFBE_LIN_STAMP) || defined(GFBE_CHOL_STAMP) || \
                    defined(GFBE_CHAIN_STAMP) || defined(GFBE_BIG_STAMP) || defined(GFBE_LDLT_STAMP))
-#error "kernel time stamps / ablations are diagnostics: build with -DGFBE_DIAG=1"
+#error "kernel time stamps are diagnostics: build with -DGFBE_DIAG=1"
 #endif
 
 namespace gfd {
@@ -296,7 +287,7 @@ struct BatchDev {
   double *tile_cost;          // [B][max_tiles]   visual cost partials (current linearisation)
   double *vis_contrib;        // [B][max_tiles][MAXOBS][16][64] small batches: per-step contributions to Hll, gl, hC, cost (k_lin_small)
   int *tile_cnt;              // [B][max_tiles]   arrival counter of the tile's LIN_SMALL_KS workgroups in k_vis_split (zero between launches)
-  int *win_cnt;               // [B][2]           arrival counters of a window's k_lm_step / k_lin_small<1> workgroups (GFBE_FUSE_SMALL; zero between launches)
+  int *win_cnt;               // [B][2]           arrival counters of a window's k_lm_step / k_lin_small<1> workgroups (gfbe_host.cpp: small_fuse; zero between launches)
   double *tile_cand;          // [B][max_tiles][4] candidate: cost, |x-xc|^2, |xc|^2, pad
   double *tile_gram;          // [B][max_tiles][8] landmark parts of G2 N2 gy vHv vHy yHy gradmax
   double *dense_cand;         // [B][4] dense-factor candidate cost, |x-xc|^2, |xc|^2

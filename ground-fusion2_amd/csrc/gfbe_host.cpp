@@ -6,9 +6,6 @@
 // Reference being replaced: Estimator::optimization()
 //   Ground-Fusion++/vins_estimator/src/estimator/estimator.cpp:2951-3698
 #include "gfbe_device.h"
-#ifndef GFBE_CLEAR_LM
-#define GFBE_CLEAR_LM 0
-#endif
 #include <algorithm>
 #include <atomic>
 #include <condition_variable>
@@ -873,12 +870,11 @@ static gfbe_status upload_one(gfbe_ctx *c, int32_t B, const gfbe_window *const *
   d.nu = (any_gnss || gnss_dims) ? (int)ND : (int)NC;       // a batch without GNSS blocks never touches the last 59 tangent dims
   d.solve_big = d.nu > NC;                                  // (decided per batch: k_solve / k_solve_chain hold the 187 core dims only)
   if (diag_getenv("GFBE_VIS_FULL")) d.vis_full = 1;   // (diagnostics build only: force the 20-column panel)
-  // speculative linearisation (gfbe_options.speculative_linearization): batches whose candidate costs are all formed by the visual /
-  // dense-factor / LiDAR / GNSS launches (no all-reduce hook) get a second set of the linearisation's outputs
-  // (round 6: also with an all-reduce hook — the landmark-sharded solve: the candidate's pass linearises its own tiles, the ranks' candidate
-  //  costs travel as before; one evaluation pass less per iteration there too. The number of collectives per iteration stays: DESIGN.md section 7)
-  d.spec = (c->opt.speculative_linearization && max_tiles > 0 &&
-            (B >= DENSE_SPLIT_MIN_B || (GFBE_FUSE_SMALL & 2) || c->allreduce)) ? 1 : 0;
+  // speculative linearisation (gfbe_options.speculative_linearization): every batch with landmarks gets a second set of the
+  // linearisation's outputs (round 6: also with an all-reduce hook — the landmark-sharded solve: the candidate's pass linearises its own
+  // tiles, the ranks' candidate costs travel as before; one evaluation pass less per iteration there too. The number of collectives per
+  // iteration stays: DESIGN.md section 7)
+  d.spec = (c->opt.speculative_linearization && max_tiles > 0) ? 1 : 0;
   // k_linschur (gfbe_options.merge_lin_schur): throughput batches on the 7 x 7 panel, every tile on this rank
   d.linschur = (c->opt.merge_lin_schur && B >= DENSE_SPLIT_MIN_B && !d.vis_full && !c->allreduce && max_tiles > 0) ? 1 : 0;
   const size_t TL = tot_lm;
@@ -927,9 +923,6 @@ static gfbe_status upload_one(gfbe_ctx *c, int32_t B, const gfbe_window *const *
     const size_t up_end = b->dry ? b->slab_bytes : b->slab_off;
     // -- arrays the kernels expect zeroed at the start (rows past a track's length, partials of absent factors, ...)
     if (tabs) { AL(lm_info, TL); AL(lm_abi, TL); AL(lm_pts, (size_t)6 * TL); AL(lam0, TL); d.fobs = nullptr; d.fvel = nullptr; }
-#if GFBE_CLEAR_LM      // (diagnostics: the landmark rows back in the cleared region)
-    AL(lm_obs, (size_t)MAXOBS * 5 * TL); AL(lm_rec, (size_t)MAXOBS * TL); AL(lm_hP, (size_t)MAXOBS * 6 * TL);
-#endif
     AL(lio_part, (size_t)B * LIOW_WGS * LIOW_PART);
     AL(raw_imu, (size_t)MAX_IMU * (15 + 450) * 4 * ((B + 3) / 4)); AL(raw_wheel, (size_t)MAX_WHEEL * (6 + 132) * 4 * ((B + 3) / 4));   // [factor][window / 4][value][window % 4]
     AL(zero, 16); AL(vis_H, (size_t)B * NV * (NV + 1));
@@ -966,10 +959,8 @@ static gfbe_status upload_one(gfbe_ctx *c, int32_t B, const gfbe_window *const *
     const size_t zero_end = b->dry ? b->slab_bytes : b->slab_off;
     // -- written before they are read: no clearing (block-CSR records only exist for the inspection API)
     AL(prior_J0, (size_t)B * ND * ND);     // (the n x n prior block arrives by copy; nothing reads past it)
-#if !GFBE_CLEAR_LM
     AL(lm_obs, (size_t)MAXOBS * 5 * TL); AL(lm_rec, (size_t)MAXOBS * TL);   // (k_expand / k_ftab_pack write the rows of a track; the evaluation uses a row only below the track's length: 0.9 of the 2.8 MB per window that used to be cleared)
     AL(lm_hP, (size_t)MAXOBS * 6 * TL);    // (k_vis writes the rows below a track's length, k_schur masks the others per landmark: 1.0 MB per window)
-#endif
     AL(vis_part, (size_t)B * std::max(max_tiles, 1) * MAXOBS * VP_STRIDE);   // (a tile's steps below its longest track are written by k_vis, the others never read)
     // (the second set: the solve's linearisation only — its 7 x 7 partials take VPY_STRIDE doubles per step when no window frees the extrinsic / td)
     if (d.spec) { AL(lm_hP2, (size_t)MAXOBS * 6 * TL); AL(vis_part2, (size_t)B * std::max(max_tiles, 1) * MAXOBS * (d.vis_full ? (size_t)VP_STRIDE : (size_t)VPY_STRIDE)); }
@@ -1415,14 +1406,16 @@ static void run_allreduce(gfbe_ctx *c, double *ptr, int64_t n, hipStream_t s) {
   if (rc != 0 && c->allreduce_rc == 0) c->allreduce_rc = rc;
 }
 
-// GFBE_FUSE_SMALL (gfbe_device.h): which launches of an iteration are merged for this batch. Small batches on the latency path only:
-// not while profiling (per-kernel events), not with an all-reduce hook, not without landmarks (k_lm_step is not launched then).
-#ifndef GFBE_MARG_DENSE_ASIDE
-#define GFBE_MARG_DENSE_ASIDE 1      // the marginalisation's dense factors of a throughput batch on the side stream (0: in line, rounds 1-6)
-#endif
+// Which launches of an iteration are merged for this batch. Small batches (< 32 windows) on a single window's latency path only: not
+// while profiling (per-kernel events), not with an all-reduce hook, not without landmarks (k_lm_step is not launched then). Bit 0:
+// k_schur + k_visblock_small in one launch; bit 1: k_step and the dense half of k_candidate by the workgroup of k_lm_step that
+// finishes last, the landmark half of k_candidate by k_lin_small<1>'s tile workgroups; bit 2: k_accept by the workgroup of
+// k_lin_small<1> that finishes last; bit 3: the marginalisation's linearisation (k_vis_split<2> + k_dense) in one launch, its pair sums
+// and its Schur partial in another (nobody reads the bit: gfbe_marg.hip's launch_marginalize_partials tests the batch itself). Same
+// code, same order of every sum: the results do not change by a bit.
 static int small_fuse(const gfbe_ctx *c, const BatchDev &d) {
   if (c->profiling || d.B >= DENSE_SPLIT_MIN_B || !d.vis_Hs || d.sharded || d.max_tiles == 0) return 0;
-  int f = GFBE_FUSE_SMALL;
+  int f = 15;
   // (a LiDAR window's candidate cost — and a GNSS window's beyond the size k_lin_small takes itself — is a launch of its own between
   //  k_lin_small<1 / 3> and k_accept)
   if (d.tot_lio > 0 || (d.any_gnss && !lin_small_takes_gnss(d, 1))) f &= ~4;
@@ -1540,7 +1533,7 @@ static gfbe_status enqueue_solve(gfbe_ctx *c, gfbe_batch *b, const Lane &ln, int
       run_allreduce(c, d.pair_part, (int64_t)d.B * NF * VP_STRIDE, ln.s);
       run_allreduce(c, d.schur_part, (int64_t)d.B * d.schur_groups * SCHUR_STRIDE, ln.s);
       launch_marginalize_finish(d, margin_flag, ln.s);
-    } else if (GFBE_MARG_DENSE_ASIDE && margin_flag == GFBE_MARGIN_OLD && !c->profiling && ln.aux && d.B >= DENSE_SPLIT_MIN_B) {
+    } else if (margin_flag == GFBE_MARGIN_OLD && !c->profiling && ln.aux && d.B >= DENSE_SPLIT_MIN_B) {
       // (end of round 6) throughput batches: the frame-0 inertial / wheel / prior factors of the marginalisation set (k_dense<false>: a few
       // latency-bound workgroups per window, ~40 us per launch over 512 windows) on the side stream, beside k_vis<2> / k_pairsum / k_schur —
       // they read the re-anchored state and nothing of the visual kernels', k_marg reads them all: fork behind k_reanchor, join in front of k_marg

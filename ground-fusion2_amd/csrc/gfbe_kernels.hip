@@ -26,35 +26,17 @@
 
 namespace gfd {
 
-#ifndef GFBE_ABLATE
-#define GFBE_ABLATE 0   // timing ablations of k_vis (tools/diag_ablate.sh); 0 in every shipped build
-#endif
-#ifndef GFBE_KVIS_EARLY
-#define GFBE_KVIS_EARLY 1   // k_vis: the prefetched observation of the next step is waited for BEFORE this step's stores are issued
-#endif
-#ifndef GFBE_FUSE_CAND
-#define GFBE_FUSE_CAND 1   // throughput batches: the landmark half of k_candidate at the head of the cost pass (k_vis<1>)
-#endif
-#ifndef GFBE_PCS_ONE_ROUND
-#define GFBE_PCS_ONE_ROUND 1      // k_vis_chunk: the pair records of a wave's start frame in one round of loads (0: one dependent round trip per pair, rounds 4-6)
-#endif
 #ifndef GFBE_ASM_U
 #define GFBE_ASM_U 4       // k_visasm: entries of H a thread has in flight
 #endif
-#ifndef GFBE_ASM_TP
-#define GFBE_ASM_TP 29     // k_visasm (end of round 6; every output keeps its bits): 1 = the entries of H by asm_H_tp,
-                           // 4 = the descriptor tables requested before the visual block is gathered, 8 = the gradient's dense terms by gather_g_dense_tp
-                           // (k_assemble's as well), 16 = the gather of the visual block's partials (visblock_y); 0 = rounds 4-6
-#endif
-// which form runs: the build's choice — and, in the diagnostics build, the older form on request (BatchDev::asm_legacy, GFBE_ASM_LEGACY=1 at upload:
-// tests/test_gpu_uncleared.py compares H entry by entry and every output's bits between the two)
+// k_visasm's throughput-batch forms (every output keeps its bits): the entries of H by asm_H_tp, the descriptor tables requested before
+// the visual block is gathered, the gradient's dense terms by gather_g_dense_tp (k_assemble's as well), the gather of the visual block's
+// partials (visblock_y). The diagnostics build runs the older loops of rounds 4-6 on request (BatchDev::asm_legacy, GFBE_ASM_LEGACY=1
+// at upload: tests/test_gpu_uncleared.py compares H entry by entry and every output's bits between the two).
 #if GFBE_DIAG
-#define ASM_TP_ON(d, bit) (((GFBE_ASM_TP) & (bit)) && !(d).asm_legacy)
+#define ASM_TP_ON(d) (!(d).asm_legacy)
 #else
-#define ASM_TP_ON(d, bit) (((GFBE_ASM_TP) & (bit)) != 0)
-#endif
-#ifndef GFBE_DENSE_TP
-#define GFBE_DENSE_TP 1    // throughput batches: k_dense_tp (matrix-core whitening / J^T J, four windows per workgroup) instead of k_dense<false>
+#define ASM_TP_ON(d) true
 #endif
 #ifndef GFBE_KVIS_WAVES
 #define GFBE_KVIS_WAVES 3   // k_vis<0, false>: waves per SIMD the register allocation aims at (measured: 4 — 128 VGPRs, a 12-byte spill — 152 us per
@@ -420,31 +402,23 @@ __device__ __forceinline__ void vis_body(const BatchDev &d, int write_records, c
   {
     const double *src = d.pc + (((size_t)w * 3 + (MODE == 2 ? 2 : buf)) * NPAIR + sframe * NF) * PC_DOUBLES;
     // (WS: the records dealt over the workgroup's waves)
-#if GFBE_PCS_ONE_ROUND
-    // (end of round 6, as in k_vis_chunk: every record this wave stages is requested before the first is written — the loop below is a
-    //  dependent round trip per pair; a slot beyond the window's last frame re-reads a valid entry and writes nothing)
-    {
-      constexpr int JS = WS ? KS : 1, NJ = (NF - 1 + JS - 1) / JS, NR = (PCW + LM_TILE - 1) / LM_TILE;
-      double rec[NJ][NR];
+    // (as in k_vis_chunk: every record this wave stages is requested before the first is written, not one dependent round trip per
+    //  pair; a slot beyond the window's last frame re-reads a valid entry and writes nothing)
+    constexpr int JS = WS ? KS : 1, NJ = (NF - 1 + JS - 1) / JS, NR = (PCW + LM_TILE - 1) / LM_TILE;
+    double rec[NJ][NR];
 #pragma unroll
-      for (int jj = 0; jj < NJ; jj++)
+    for (int jj = 0; jj < NJ; jj++)
 #pragma unroll
-        for (int r = 0; r < NR; r++)
-          rec[jj][r] = src[(size_t)min(sframe + 1 + (WS ? kq : 0) + jj * JS, NF - 1) * PC_DOUBLES + min(lane + r * LM_TILE, PCW - 1)];
-      const double fcv = src[(size_t)sframe * PC_DOUBLES + min(lane, (int)FC_DOUBLES - 1)];
+      for (int r = 0; r < NR; r++)
+        rec[jj][r] = src[(size_t)min(sframe + 1 + (WS ? kq : 0) + jj * JS, NF - 1) * PC_DOUBLES + min(lane + r * LM_TILE, PCW - 1)];
+    const double fcv = src[(size_t)sframe * PC_DOUBLES + min(lane, (int)FC_DOUBLES - 1)];
 #pragma unroll
-      for (int jj = 0; jj < NJ; jj++) {
-        const int j = sframe + 1 + (WS ? kq : 0) + jj * JS;
+    for (int jj = 0; jj < NJ; jj++) {
+      const int j = sframe + 1 + (WS ? kq : 0) + jj * JS;
 #pragma unroll
-        for (int r = 0; r < NR; r++) if (j < NF && lane + r * LM_TILE < PCW) ((double *)&pcs[min(j, NF - 1)])[lane + r * LM_TILE] = rec[jj][r];
-      }
-      if (YM && (!WS || kq == 0) && lane < FC_DOUBLES) ((double *)&fcs)[lane] = fcv;
+      for (int r = 0; r < NR; r++) if (j < NF && lane + r * LM_TILE < PCW) ((double *)&pcs[min(j, NF - 1)])[lane + r * LM_TILE] = rec[jj][r];
     }
-#else
-    for (int j = sframe + 1 + (WS ? kq : 0); j < NF; j += (WS ? KS : 1))
-      for (int q = lane; q < PCW; q += LM_TILE) ((double *)&pcs[j])[q] = src[(size_t)j * PC_DOUBLES + q];     // (the whole record is 75 doubles: two rounds)
-    if (YM && (!WS || kq == 0) && lane < FC_DOUBLES) ((double *)&fcs)[lane] = src[(size_t)sframe * PC_DOUBLES + lane];
-#endif
+    if (YM && (!WS || kq == 0) && lane < FC_DOUBLES) ((double *)&fcs)[lane] = fcv;
   }
   __syncthreads();
   const double sq = d.opt.vis_sqrt_info, delta = d.opt.huber_delta;
@@ -557,10 +531,8 @@ __device__ __forceinline__ void vis_body(const BatchDev &d, int write_records, c
 #pragma unroll
         for (int q = 0; q < 7; q++) { xr[q] = 0.0; xr[8 + q] = 0.0; }
       }
-#if GFBE_KVIS_EARLY
 #pragma unroll
       for (int q = 0; q < 2; q++) asm volatile("" : "+v"(nob[q]));      // (see the 13-column path below)
-#endif
       if (k < m) {
 #pragma unroll
         for (int q = 0; q < 3; q++) d.lm_hP[((size_t)k * 6 + q) * TL + slot] = hp[q];
@@ -596,16 +568,9 @@ __device__ __forceinline__ void vis_body(const BatchDev &d, int write_records, c
     }
     if constexpr (!YM && MODE != 1) {
     if (k < m) {
-      if (GFBE_ABLATE == 4 && MODE == 0) {
-#pragma unroll
-        for (int q = 0; q < 12; q++) { Ji[q] = pjx + q; Jj[q] = pjy * q; if (FULL) Je[q] = vjx - q; }
-        Jl[0] = lam; Jl[1] = tdj; Jt[0] = vjy; Jt[1] = pix; r[0] = piy * 1e-3; r[1] = piz * 1e-3;
-      } else
-      {
-        const double ck = visual_lin<MODE != 1, FULL>(pcs[sframe + 1 + k], lam, td, pix, piy, piz, pjx, pjy, vix, viy, vjx, vjy, tdi, tdj,
-                                                      sq, delta, r, Ji, Jj, Je, Jl, Jt);
-        if (KS > 1) contrib[((size_t)k * VC_STRIDE + 15) * LM_TILE] = ck; else cost += ck;
-      }
+      const double ck = visual_lin<MODE != 1, FULL>(pcs[sframe + 1 + k], lam, td, pix, piy, piz, pjx, pjy, vix, viy, vjx, vjy, tdi, tdj,
+                                                    sq, delta, r, Ji, Jj, Je, Jl, Jt);
+      if (KS > 1) contrib[((size_t)k * VC_STRIDE + 15) * LM_TILE] = ck; else cost += ck;
       if (MODE != 1) {
         if (FULL && write_records) {   // inspection path (gfbe_eval_factors): block-CSR record r(2) | row0: Ji Jj Je Jl Jt | row1
           double *rb = d.rec + ((size_t)ds.rec_off + d.lm_rec[(size_t)k * TL + slot]) * REC;
@@ -649,21 +614,19 @@ __device__ __forceinline__ void vis_body(const BatchDev &d, int write_records, c
     }
     if (k < 5) KSTAMP(4 + 5 * k);
     if (MODE != 1) {
-#if GFBE_KVIS_EARLY
       // vmcnt counts loads and stores in one queue: if the next step's observation (loaded at the top of this step) were first
       // touched at the loop's back edge, the wave would sit there until this step's partial-sum stores have been acknowledged.
       // Touching it here — after the evaluation, before any store of this step, on a path every lane takes — costs nothing.
 #pragma unroll
       for (int q = 0; q < 5; q++) asm volatile("" : "+v"(nob[q]));
-#endif
-      if (k < m && (GFBE_ABLATE != 3 || hp[0] == 1.2345)) {   // the landmark's H_pl block of observing pose s + 1 + k
+      if (k < m) {   // the landmark's H_pl block of observing pose s + 1 + k
         // (lm_hP is not cleared at upload: rows from a track's length on hold whatever the memory held; k_schur masks them per
         //  landmark, nobody else reads past a track's length)
 #pragma unroll
         for (int q = 0; q < 6; q++) d.lm_hP[((size_t)k * 6 + q) * TL + slot] = hp[q];
       }
     }
-    if (MODE != 1 && GFBE_ABLATE != 1) {
+    if (MODE != 1) {
       // X^T X of the step's 128-row panel on the FP64 matrix cores (the J^T J / J^T r of this tile's factors of pose pair
       // (sframe, sframe+1+k)); J never leaves the CU. The panel goes through LDS 64 rows at a time (row h of every lane's
       // factor, h = 0, 1).
@@ -723,7 +686,6 @@ __device__ __forceinline__ void vis_body(const BatchDev &d, int write_records, c
       }
       if (k < 5) KSTAMP(7 + 5 * k);
       double *vo = d.vis_part + (((size_t)w * d.max_tiles + tile) * MAXOBS + k) * VP_STRIDE;
-      if (GFBE_ABLATE == 2 && acc0[0] != 1.2345) continue;
       if (FULL) {
 #pragma unroll
         for (int q = 0; q < 4; q++) vo[(lk + 4 * q) * 16 + lr] = acc0[q];
@@ -857,7 +819,7 @@ __global__ __launch_bounds__(LM_TILE, (MODE == 0 && !FULL) ? GFBE_KVIS_WAVES : 2
   // tile-major dispatch order (x = window): all windows' tile 0 (start frame 0, the longest tracks) first, the
   // short start-frame-7 tiles last — a longest-first schedule that shortens the tail of the launch
   // (the cost pass of a throughput batch, write_records = 1: the tile first forms the candidate inverse depths of its landmarks —
-  //  the landmark half of k_candidate, the same 64 lanes and the same sums (vis_body's head); k_candidate_dense has formed the candidate's
+  //  the landmark half of k_candidate, the same 64 lanes and the same sums (vis_body's head); k_step_candidate_dense has formed the candidate's
   //  dense blocks and pair constants before. A launch of its own walked a window's tiles four at a time: 115 us per 2048 windows.)
   vis_body<MODE, FULL, 1, SPEC>(d, (MODE == 1 || SPEC) ? 0 : write_records, blockIdx.x, blockIdx.y, 0, (MODE == 1 || SPEC) && write_records);
 }
@@ -873,9 +835,6 @@ __global__ __launch_bounds__(LM_TILE, (MODE == 0 && !FULL) ? GFBE_KVIS_WAVES : 2
 // Grid: (window, start frame x sub-chunk): blockIdx.y = s * nsub + sub takes the tiles [begin(s) + VIS_CHUNK sub, + VIS_CHUNK) of start
 // frame s (start frame 0 — the longest tracks — is dispatched first).
 // =============================================================================================
-#ifndef GFBE_VIS_CHUNK
-#define GFBE_VIS_CHUNK 1
-#endif
 #ifndef VIS_CHUNK
 #define VIS_CHUNK 4
 #endif
@@ -922,26 +881,19 @@ __global__ __launch_bounds__(LM_TILE, GFBE_KVIS_WAVES) void k_vis_chunk(BatchDev
   const double td = X[A_TD];
   {
     const double *src = d.pc + (((size_t)w * 3 + buf) * NPAIR + sframe * NF) * PC_DOUBLES;
-#if GFBE_PCS_ONE_ROUND
-    // (end of round 6) every record of the start frame's pairs requested before the first is written to LDS: the loop below compiles to
-    // load, s_waitcnt vmcnt(0), ds_write per pair — up to ten dependent round trips in front of a wave's first tile (its ISA; the prologue
-    // was a third of a wave's life, profiles/r6_kvis_ablation.txt). A pair beyond the window's last frame re-reads the last record and writes nothing.
+    // (end of round 6) every record of the start frame's pairs requested before the first is written to LDS: a loop that copies one
+    // pair at a time compiles to load, s_waitcnt vmcnt(0), ds_write per pair — up to ten dependent round trips in front of a wave's first
+    // tile (its ISA; the prologue was a third of a wave's life, profiles/r6_kvis_ablation.txt). A pair beyond the window's last frame
+    // re-reads the last record and writes nothing.
     static_assert(PCY_DOUBLES <= LM_TILE && FC_DOUBLES <= LM_TILE, "one lane per entry of a pair record");
-    {
-      const int ql = min(lane, (int)PCY_DOUBLES - 1);
-      double rec[NF - 1];
+    const int ql = min(lane, (int)PCY_DOUBLES - 1);
+    double rec[NF - 1];
 #pragma unroll
-      for (int jj = 0; jj < NF - 1; jj++) rec[jj] = src[(size_t)min(sframe + 1 + jj, NF - 1) * PC_DOUBLES + ql];
-      const double fcv = src[(size_t)sframe * PC_DOUBLES + min(lane, (int)FC_DOUBLES - 1)];
+    for (int jj = 0; jj < NF - 1; jj++) rec[jj] = src[(size_t)min(sframe + 1 + jj, NF - 1) * PC_DOUBLES + ql];
+    const double fcv = src[(size_t)sframe * PC_DOUBLES + min(lane, (int)FC_DOUBLES - 1)];
 #pragma unroll
-      for (int jj = 0; jj < NF - 1; jj++) if (sframe + 1 + jj < NF && lane < (int)PCY_DOUBLES) ((double *)&pcs[min(sframe + 1 + jj, NF - 1)])[lane] = rec[jj];
-      if (lane < (int)FC_DOUBLES) ((double *)&fcs)[lane] = fcv;
-    }
-#else
-    for (int j = sframe + 1; j < NF; j++)
-      for (int q = lane; q < (int)PCY_DOUBLES; q += LM_TILE) ((double *)&pcs[j])[q] = src[(size_t)j * PC_DOUBLES + q];
-    if (lane < (int)FC_DOUBLES) ((double *)&fcs)[lane] = src[(size_t)sframe * PC_DOUBLES + lane];
-#endif
+    for (int jj = 0; jj < NF - 1; jj++) if (sframe + 1 + jj < NF && lane < (int)PCY_DOUBLES) ((double *)&pcs[min(sframe + 1 + jj, NF - 1)])[lane] = rec[jj];
+    if (lane < (int)FC_DOUBLES) ((double *)&fcs)[lane] = fcv;
   }
   __syncthreads();
   for (int tile = t0; tile < t1; tile++) {
@@ -1010,10 +962,8 @@ __global__ __launch_bounds__(LM_TILE, GFBE_KVIS_WAVES) void k_vis_chunk(BatchDev
 #pragma unroll
         for (int q = 0; q < 7; q++) { xr[q] = 0.0; xr[8 + q] = 0.0; }
       }
-#if GFBE_KVIS_EARLY
 #pragma unroll
       for (int q = 0; q < 2; q++) asm volatile("" : "+v"(nob[q]));      // (the next step's observation is waited for BEFORE this step's stores are issued: vis_body)
-#endif
       if (k < m) {
 #pragma unroll
         for (int q = 0; q < 3; q++) d.lm_hP[((size_t)k * 6 + q) * TL + slot] = hp[q];
@@ -1198,7 +1148,6 @@ __device__ __forceinline__ size_t raw_of(int f, int w, int B, int raw_len) { ret
 // lanes of the wave are all busy. Output: raw residual + raw Jacobian non-zeros, window-minor
 // (raw_imu[f][q][B]: coalesced stores here, one 32-byte sector per value for the per-factor workgroup of k_dense).
 __global__ __launch_bounds__(64) void k_dense_raw(BatchDev d, int mode, int spec) {
-  GFBE_SMALL_KERNEL_PRIO();
   const int f = blockIdx.x, w = blockIdx.y * 64 + threadIdx.x;
   if (w >= d.B) return;
   const WinDesc &ds = d.desc[w];
@@ -1605,7 +1554,6 @@ enum { PRIOR_REGS = 32, PRIOR_LDS_N = 90 };      // 256 threads x 32 values >= 9
 static_assert(256 * PRIOR_REGS >= PRIOR_LDS_N * PRIOR_LDS_N, "k_prior_tp: a thread's share of J0");
 static_assert(ND <= 256, "k_prior_tp: one thread per row / column of the prior (n <= GFBE_DENSE_DIM) in a 256-thread workgroup");
 __global__ __launch_bounds__(256) void k_prior_tp(BatchDev d, int mode, int lds_n, int spec) {
-  GFBE_SMALL_KERNEL_PRIO();
   extern __shared__ __attribute__((aligned(16))) double psm[];      // dx[ND] | r[ND] | partial sums [4][ND] | J0 [lds_n x lds_n]
   __shared__ double red[16];
   const int w = blockIdx.x, t = threadIdx.x, wv = t >> 6, lane = t & 63;
@@ -1694,7 +1642,6 @@ __global__ __launch_bounds__(256) void k_prior_tp(BatchDev d, int mode, int lds_
 }
 
 __global__ __launch_bounds__(256) void k_dense_tp(BatchDev d, int mode, int spec) {
-  GFBE_SMALL_KERNEL_PRIO();
   __shared__ double sm[DTP_LDS];
   __shared__ int s_act[4];
   const int slot = blockIdx.x, w0 = blockIdx.y * 4;
@@ -1717,7 +1664,7 @@ struct AcceptLocal {
 template <class CT>
 __device__ __forceinline__ void accept_body(const BatchDev &d, const int w, const int lane, CT &c, WinCtl &cg, const int cslot = 1);
 __device__ __forceinline__ bool arrive_last(int *cnt, const int expected, const int lane);
-// fuse (MODE 1, GFBE_FUSE_SMALL): bit 1 — a tile workgroup first forms the candidate inverse depths of its tile (the landmark half of
+// fuse (MODE 1, gfbe_host.cpp: small_fuse): bit 1 — a tile workgroup first forms the candidate inverse depths of its tile (the landmark half of
 // k_candidate; the dense half ran at the tail of k_lm_step_fused); bit 2 — the workgroup of a window that finishes last goes on with
 // k_accept.
 // MODE 3 (BatchDev::spec, every iteration of the batch but the last): the candidate is LINEARISED — MODE 0's work at the candidate state,
@@ -1809,9 +1756,6 @@ __global__ __launch_bounds__(LIN_SMALL_THREADS, 1) void k_lin_small(BatchDev d0,
 //   marg :  w_l = 1 / Hll                                         (marginalization_factor.cpp:286-292)
 // =============================================================================================
 typedef double dbl4_t __attribute__((ext_vector_type(4)));
-#ifndef GFBE_SCHUR_COMPACT
-#define GFBE_SCHUR_COMPACT 1      // 0 (diagnostics build): the absolute column layout of rounds 1-3 in the solve's Schur panels as well
-#endif
 #ifndef HS_LD
 #define HS_LD 75   // LDS row stride of the landmark panel: odd (the 64 lanes that stage one column spread over 32 bank pairs, two-way instead of
                    // four-way) and just wide enough for the 74 columns in use — the matrix-core operand loads of the last 16-column block run
@@ -1857,7 +1801,7 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
   // blocks of [6 s, 6 (s + m0 + 1)) plus the block of column 73 (counted on the 2k-landmark windows of the bench: 219 instead of 326
   // tile pairs per window and linearisation). Pairs are numbered column-major — (I, J) at J (J + 1) / 2 + I — so the active ones of
   // any tile are a prefix dealt evenly over the four waves. The marginalisation pass keeps the absolute layout k_marg reads.
-  const bool compact = GFBE_SCHUR_COMPACT && !marg;
+  const bool compact = !marg;
   const int coff = compact ? 1 - 6 * s_first : 0;                     // column of dim a: a + coff
   const int I0 = compact ? 0 : (6 * s_first) / 16;
   // slot q of this wave owns the (4 q + wave)-th upper tile pair (I, J), I <= J — all wave-uniform
@@ -2070,9 +2014,6 @@ __global__ __launch_bounds__(256, GFBE_SCHUR_WGS) void k_schur(BatchDev d0, int 
 #ifndef GFBE_LINSCHUR_WGS
 #define GFBE_LINSCHUR_WGS 3
 #endif
-#ifndef GFBE_LINSCHUR_WRITE_D
-#define GFBE_LINSCHUR_WRITE_D 1
-#endif
 #define LS_XLD 17
 template <bool SPEC>
 __global__ __launch_bounds__(256, GFBE_LINSCHUR_WGS) void k_linschur(BatchDev d0, int head_in, int gate_mu) {
@@ -2220,10 +2161,8 @@ __global__ __launch_bounds__(256, GFBE_LINSCHUR_WGS) void k_linschur(BatchDev d0
 #pragma unroll
           for (int q = 0; q < 3; q++) { xr[q] = g0[q]; xr[3 + q] = y0[q]; xr[8 + q] = g1[q]; xr[11 + q] = y1[q]; }
           xr[6] = r[0]; xr[14] = r[1];
-          if (GFBE_LINSCHUR_WRITE_D) {
 #pragma unroll
-            for (int q = 0; q < 3; q++) d.lm_hP[((size_t)k * 6 + q) * TL + slot] = dk[u][q];
-          }
+          for (int q = 0; q < 3; q++) d.lm_hP[((size_t)k * 6 + q) * TL + slot] = dk[u][q];
         } else {
 #pragma unroll
           for (int q = 0; q < 7; q++) { xr[q] = 0.0; xr[8 + q] = 0.0; }
@@ -2344,7 +2283,7 @@ __global__ __launch_bounds__(256, GFBE_LINSCHUR_WGS) void k_linschur(BatchDev d0
 }
 
 // Small batches, marginalisation: the pair sums (0, j) and the Schur partial of start frame 0 both read what the linearisation of the
-// marginalisation set left and nothing of each other: one launch (GFBE_FUSE_SMALL bit 3).
+// marginalisation set left and nothing of each other: one launch (gfbe_host.cpp: small_fuse, bit 3).
 __global__ __launch_bounds__(VP_STRIDE) void k_pairsum_schur_marg(BatchDev d) {
   const int w = blockIdx.x, y = blockIdx.y;
   if (y < NF - 1) pairsum_body(d, 1, w, y);
@@ -2585,7 +2524,6 @@ __device__ __forceinline__ double gather_E11(const BatchDev &d, const double *Z,
   // gradient in column 0; entry (r, c), r <= c, of the panel product at tile pair (r >> 4, c >> 4) = slot J (J + 1) / 2 + I
   const double *sp = uniform_ptr(d.schur_part + (size_t)w * d.schur_groups * SCHUR_STRIDE);
   auto off_of = [&](int s) {
-    if (!GFBE_SCHUR_COMPACT) return schur_pair(a >> 4, b >> 4) * 256 + (a & 15) * 16 + (b & 15);      // (diagnostics: the absolute layout of rounds 1-3)
     const int ca = 1 + a - 6 * s, r = b == NV ? 0 : ca, cc = b == NV ? ca : 1 + b - 6 * s;
     const int I = r >> 4, J = cc >> 4;
     return (J * (J + 1) / 2 + I) * 256 + (r & 15) * 16 + (cc & 15);
@@ -2703,7 +2641,7 @@ __device__ __forceinline__ void visblock_y(const BatchDev &d, const WinDesc &ds,
       else { i = 0; int rem = pq; while (rem >= NF - 1 - i) { rem -= NF - 1 - i; i++; } k = rem; }
       const int t0 = s_tile_begin[i], t1 = s_tile_begin[i + 1];
       double sum = 0.0;
-      if (!ROW && staged_m && ASM_TP_ON(d, 16)) {
+      if (!ROW && staged_m && ASM_TP_ON(d)) {
         // (end of round 6, like asm_H_tp: the tiles' step counts read unconditionally at a clamped index — one wait for the four —, the
         //  partials loaded from the window's scalar base at a 32-bit offset, offset 0 for a tile that did not run the step, and the VALUE
         //  selected: the same sums in the same order)
@@ -3252,7 +3190,7 @@ __device__ __forceinline__ void asm_g(const BatchDev &d, const int w, const doub
   for (int a = gt; a < ND; a += gn) {
     double v = 0.0;
     if (tb.act[a]) {
-      if (ASM_TP_ON(d, 8)) v = dense_here ? gather_g_dense_tp(d, tb, w, a) : 0.0;
+      if (ASM_TP_ON(d)) v = dense_here ? gather_g_dense_tp(d, tb, w, a) : 0.0;
       else v = dense_here ? gather_g_dense(d, tb, Z, w, a) : 0.0;
       if (a < NV) {
         if (!vsplit) v += vis_w[a * V_LD + NV];
@@ -3285,7 +3223,7 @@ __device__ __forceinline__ void assemble_body(const BatchDev &d, const int w, co
   }
   ASTAMP(4);
   const AsmCommon cm = asm_common(d, w);
-  if (ASM_TP_ON(d, 1)) asm_H_tp<GFBE_ASM_U>(d, w, vis_w, tb, cm, gt, gn);      // (k_visasm: throughput batches, the visual block in the caller's LDS)
+  if (ASM_TP_ON(d)) asm_H_tp<GFBE_ASM_U>(d, w, vis_w, tb, cm, gt, gn);      // (k_visasm: throughput batches, the visual block in the caller's LDS)
   else asm_H<GFBE_ASM_U, false>(d, w, vis_w, tb, cm, gt, gn, nullptr);
   ASTAMP(5);
   asm_E(d, w, tb, cm, gt, gn);      // (E's entries the branch-free way — loop-free triangle decode, 2 / 3 / 6 entries in flight — measured: no gain, profiles/r6_late_experiments.txt)
@@ -3337,7 +3275,7 @@ __global__ __launch_bounds__(VB_GROUP, GFBE_VISASM_WAVES) void k_visasm(BatchDev
   __shared__ double V[NV * V_LD];
   __shared__ AsmTab tb;
   static_assert(VB_GROUP >= ND, "asm_stage_store: one table entry per thread");
-  if (ASM_TP_ON(d, 4)) {
+  if (ASM_TP_ON(d)) {
     const AsmStagePre pre = asm_stage_load(d, w);
     visblock_body<false, true, true>(d, w, 0, NF - 2, 0, V);
     asm_stage_store(tb, pre);
@@ -3639,7 +3577,6 @@ __device__ __forceinline__ void step_body(const BatchDev &d, const WinDesc &ds, 
   c.have_step = 1;
 }
 __global__ __launch_bounds__(64) void k_step(BatchDev d) {
-  GFBE_SMALL_KERNEL_PRIO();
   const int w = blockIdx.x;
   step_body(d, d.desc[w], d.ctl[w], d.ctl[w], w, threadIdx.x);
 }
@@ -3728,9 +3665,9 @@ __global__ __launch_bounds__(LM_TILE) void k_candidate(BatchDev d) {
 #ifndef CAND_THREADS
 #define CAND_THREADS 256   // (512 / 1024 measured: 36 / 49 us per launch over 512 windows against 41, throughput -1 % / -4 %)
 #endif
-// the dense half alone (throughput batches, GFBE_FUSE_CAND: the landmark half runs at the head of the cost pass, k_vis<1>)
+// The dense half alone. No launch reaches it: launch_step runs k_step_candidate_dense for the batches it was meant for. It stays
+// because deleting it changes the register allocation of k_lm_step_fused and k_step_candidate_dense.
 __global__ __launch_bounds__(LM_TILE) void k_candidate_dense(BatchDev d) {
-  GFBE_SMALL_KERNEL_PRIO();
   const int w = blockIdx.x;
   const WinDesc &ds = d.desc[w];
   const WinCtl &c = d.ctl[w];
@@ -3738,12 +3675,6 @@ __global__ __launch_bounds__(LM_TILE) void k_candidate_dense(BatchDev d) {
   __shared__ PoseRT sp_cand[NF + 1];
   candidate_dense(d, ds, c, w, threadIdx.x, sp_cand, true);
 }
-// ... and behind k_step in ONE launch (round 6): both are one wave per window of dependent scalar work, 8 + 25 us per 512 windows as two
-// launches. Lane 0's trust-region scalars reach the other lanes of its wave through a workgroup-scope fence; the
-// arithmetic is step_body's and candidate_dense's, operand for operand.
-#ifndef GFBE_FUSE_STEP_CAND
-#define GFBE_FUSE_STEP_CAND 1
-#endif
 __global__ __launch_bounds__(CAND_THREADS) void k_candidate_window(BatchDev d) {
   const int w = blockIdx.x;
   const WinDesc &ds = d.desc[w];
@@ -3756,7 +3687,7 @@ __global__ __launch_bounds__(CAND_THREADS) void k_candidate_window(BatchDev d) {
   candidate_dense(d, ds, c, w, t, sp_cand, wave == 0);
 }
 
-// Small batches (GFBE_FUSE_SMALL bit 1): k_lm_step whose last workgroup of a window to finish (an arrival counter per window; nobody
+// Small batches (gfbe_host.cpp: small_fuse, bit 1): k_lm_step whose last workgroup of a window to finish (an arrival counter per window; nobody
 // waits for anybody) goes on with k_step's scalar logic and the dense parameter blocks of k_candidate — two dependent launches
 // less per iteration on a single window's latency path. The landmark half of k_candidate runs at the head of k_lin_small<1>'s tile
 // workgroups. A window that re-uses its linearisation (or is done) has nothing to back-substitute: its workgroups only arrive.
@@ -3829,18 +3760,16 @@ __device__ __forceinline__ void block_candidate(const BatchDev &d, const int w, 
 #pragma unroll
   for (int k = 0; k < MAXS; k++) if (k < q.gs) Y[q.am + k] = Yl[k];
 }
-#ifndef GFBE_STEP_CAND_REGS
-#define GFBE_STEP_CAND_REGS 1      // k_step_candidate_dense on register copies, like the tail of k_lm_step_fused (0: step_body on WinCtl in memory + candidate_dense)
-#endif
+// Throughput batches with landmarks: k_step and the dense half of k_candidate in ONE launch (round 6; the landmark half runs at the head
+// of the cost pass, k_vis<1>): both are one wave per window of dependent scalar work, 8 + 25 us per 512 windows as two launches.
 __global__ __launch_bounds__(LM_TILE) void k_step_candidate_dense(BatchDev d) {
-  GFBE_SMALL_KERNEL_PRIO();
   const int w = blockIdx.x;
   const WinDesc &ds = d.desc[w];
-#if GFBE_STEP_CAND_REGS
-  // (end of round 6) The form above walks memory one dependent access at a time: step_body reads and writes the window's trust-region
-  // scalars in WinCtl field by field, candidate_dense's loop over a block's dims loads sp / vp / yp and stores the step entry per
-  // iteration (the store may alias the next loads: load, wait, store, nine times for a speed-bias block), re-reads the candidate it has
-  // just written for |dx|^2 and |x|^2, and the pair constants read it a third time: 28 us per launch over 512 windows. Here — the tail of
+  // (end of round 6) The first fused form — step_body on WinCtl, then candidate_dense — walked memory one dependent access at a time:
+  // step_body reads and writes the window's trust-region scalars in WinCtl field by field, candidate_dense's loop over a block's dims
+  // loads sp / vp / yp and stores the step entry per iteration (the store may alias the next loads: load, wait, store, nine times for a
+  // speed-bias block), re-reads the candidate it has just written for |dx|^2 and |x|^2, and the pair constants read it a third time:
+  // 28 us per launch over 512 windows. Here — the tail of
   // k_lm_step_fused, operand for operand: StepLocal, block_preload, block_candidate, pair_consts_from_staged — everything the wave needs
   // is requested at the start in one round, the scalars live in lane 0's registers, a lane's block in its own, the poses go to the pair
   // constants through LDS. Same operations in the same order.
@@ -3878,15 +3807,6 @@ __global__ __launch_bounds__(LM_TILE) void k_step_candidate_dense(BatchDev d) {
   if (t == GFBE_BLK_EX_CAM) sp_cand[NF] = make_pose(Yl0);
   __syncthreads();
   pair_consts_from_staged(d.pc + ((size_t)w * 3 + (1 - cur)) * NPAIR * PC_DOUBLES, sp_cand, t);
-#else
-  step_body(d, ds, d.ctl[w], d.ctl[w], w, threadIdx.x);
-  __threadfence_block();      // (one wave, one CU, one vector cache: workgroup scope — a device-scope fence writes the XCD's L2 back, measured -4 % end to end)
-  __builtin_amdgcn_wave_barrier();
-  const WinCtl &c = d.ctl[w];
-  if (c.done || !c.have_step) return;
-  __shared__ PoseRT sp_cand[NF + 1];
-  candidate_dense(d, ds, c, w, threadIdx.x, sp_cand, true);
-#endif
 }
 #ifndef GFBE_LMS_AHEAD
 #define GFBE_LMS_AHEAD 3      // k_lm_step_fused: rows of the observation steps in flight ahead of the one being multiplied (lm_step_tile)
@@ -4049,7 +3969,6 @@ __device__ __forceinline__ void accept_body(const BatchDev &d, const int w, cons
   c.have_step = 0;
 }
 __global__ __launch_bounds__(64) void k_accept(BatchDev d, int spec) {      // spec: after the candidate's linearisation (its costs, its set of outputs)
-  GFBE_SMALL_KERNEL_PRIO();
   const int w = blockIdx.x;
   if (spec) accept_body(lin_view(d, 1 - d.ctl[w].lb), w, threadIdx.x, d.ctl[w], d.ctl[w], 2);
   else accept_body(d, w, threadIdx.x, d.ctl[w], d.ctl[w], 1);
@@ -4262,16 +4181,16 @@ void launch_reset(const BatchDev &d, hipStream_t s) {
 void launch_vis(const BatchDev &d, int mode, hipStream_t s, int write_records, int spec) {
   if (d.max_tiles == 0) return;
   const dim3 g(d.B, d.max_tiles), b(LM_TILE);
-  if (GFBE_VIS_CHUNK && mode == 0 && !d.vis_full && !write_records && d.B >= DENSE_SPLIT_MIN_B && d.world == 1) {
+  if (mode == 0 && !d.vis_full && !write_records && d.B >= DENSE_SPLIT_MIN_B && d.world == 1) {
     // throughput batches on the 7 x 7 panel: a wave per (window, start frame, chunk of VIS_CHUNK tiles) — k_vis_chunk
     const int nsub = (d.max_sf_tiles + VIS_CHUNK - 1) / VIS_CHUNK;
     const dim3 gc(d.B, NF * nsub);
-    if (spec) hipLaunchKernelGGL(k_vis_chunk<true>, gc, b, 0, s, d, GFBE_FUSE_CAND ? 1 : 0, nsub);
+    if (spec) hipLaunchKernelGGL(k_vis_chunk<true>, gc, b, 0, s, d, 1, nsub);
     else hipLaunchKernelGGL(k_vis_chunk<false>, gc, b, 0, s, d, 0, nsub);
     return;
   }
   if (mode == 0 && spec) {      // (the candidate linearised; its tiles form the candidate inverse depths first, as the cost pass's do)
-    const int head = (d.B >= DENSE_SPLIT_MIN_B && GFBE_FUSE_CAND) ? 1 : 0;
+    const int head = d.B >= DENSE_SPLIT_MIN_B ? 1 : 0;
     if (d.vis_full) hipLaunchKernelGGL((k_vis<0, true, true>), g, b, 0, s, d, head);
     else hipLaunchKernelGGL((k_vis<0, false, true>), g, b, 0, s, d, head);
     return;
@@ -4279,7 +4198,7 @@ void launch_vis(const BatchDev &d, int mode, hipStream_t s, int write_records, i
   // (reduced panel: only when the camera extrinsic and td are constant in EVERY window of the batch and no records are asked for)
   if (mode == 0 && (d.vis_full || write_records)) hipLaunchKernelGGL((k_vis<0, true>), g, b, 0, s, d, write_records);
   else if (mode == 0) hipLaunchKernelGGL((k_vis<0, false>), g, b, 0, s, d, 0);
-  else if (mode == 1) hipLaunchKernelGGL((k_vis<1, true>), g, b, 0, s, d, (d.B >= DENSE_SPLIT_MIN_B && GFBE_FUSE_CAND) ? 1 : 0);   // (1: the tiles form their candidate inverse depths first)
+  else if (mode == 1) hipLaunchKernelGGL((k_vis<1, true>), g, b, 0, s, d, d.B >= DENSE_SPLIT_MIN_B ? 1 : 0);   // (1: the tiles form their candidate inverse depths first)
   else if (d.B < DENSE_SPLIT_MIN_B) hipLaunchKernelGGL((k_vis_split<2, true>), dim3(d.B, d.max_tiles * LIN_SMALL_KS), b, 0, s, d, write_records);
   else hipLaunchKernelGGL((k_vis<2, true>), g, b, 0, s, d, write_records);
 }
@@ -4324,7 +4243,7 @@ void launch_dense_factors(const BatchDev &d, int mode, int debug_out, hipStream_
     return;
   }
   if (mode != 3) hipLaunchKernelGGL(k_dense_raw, dim3(MAX_IMU + MAX_WHEEL, (d.B + 63) / 64), dim3(64), 0, s, d, mode, spec);
-  if (GFBE_DENSE_TP && mode <= 1 && !debug_out) {
+  if (mode <= 1 && !debug_out) {
     // the linearisation and the candidate cost of a throughput batch: factor slots of four windows per workgroup + the priors
     hipLaunchKernelGGL(k_dense_tp, dim3(DTP_PRIOR0, (d.B + 3) / 4), dim3(256), 0, s, d, mode, spec);
     const int lds_n = d.prior_n_max <= PRIOR_LDS_N ? d.prior_n_max : 0;
@@ -4342,8 +4261,8 @@ void launch_schur(const BatchDev &d, int marg, hipStream_t s, int with_visblock)
 void launch_linschur(const BatchDev &d, int spec, int gate_mu, hipStream_t s) {
   if (d.max_tiles == 0) return;
   const dim3 g(d.B, SCHUR_GROUPS), b(256);
-  const int head = GFBE_FUSE_CAND ? 1 : 0;      // (the candidate's pass: its tiles form the candidate inverse depths first, as the cost pass's do)
-  if (spec) hipLaunchKernelGGL(k_linschur<true>, g, b, 0, s, d, head, 0);
+  // (spec: the candidate's pass, its tiles form the candidate inverse depths first, as the cost pass's do)
+  if (spec) hipLaunchKernelGGL(k_linschur<true>, g, b, 0, s, d, 1, 0);
   else hipLaunchKernelGGL(k_linschur<false>, g, b, 0, s, d, 0, gate_mu);
 }
 void launch_xchg_gram(const BatchDev &d, hipStream_t s) { hipLaunchKernelGGL(k_xchg_gram, dim3(d.B), dim3(64), 0, s, d); }
@@ -4395,15 +4314,14 @@ void launch_lm_step(const BatchDev &d, hipStream_t s, int fuse) {
   if (fuse) hipLaunchKernelGGL(k_lm_step_fused, dim3(d.B, d.max_tiles), dim3(LM_TILE), 0, s, d);
   else hipLaunchKernelGGL(k_lm_step, dim3(d.B, d.max_tiles), dim3(LM_TILE), 0, s, d);
 }
-static bool step_candidate_fused(const BatchDev &d) { return GFBE_FUSE_STEP_CAND && LM_TILE == 64 && d.B >= DENSE_SPLIT_MIN_B && GFBE_FUSE_CAND && d.max_tiles > 0; }
+static bool step_candidate_fused(const BatchDev &d) { return LM_TILE == 64 && d.B >= DENSE_SPLIT_MIN_B && d.max_tiles > 0; }
 void launch_step(const BatchDev &d, hipStream_t s) {
   if (step_candidate_fused(d)) hipLaunchKernelGGL(k_step_candidate_dense, dim3(d.B), dim3(LM_TILE), 0, s, d);      // (launch_candidate has nothing left to do)
   else hipLaunchKernelGGL(k_step, dim3(d.B), dim3(64), 0, s, d);
 }
 void launch_candidate(const BatchDev &d, hipStream_t s) {
   if (step_candidate_fused(d)) return;
-  if (d.B >= DENSE_SPLIT_MIN_B && GFBE_FUSE_CAND && d.max_tiles > 0) hipLaunchKernelGGL(k_candidate_dense, dim3(d.B), dim3(LM_TILE), 0, s, d);
-  else if (d.B >= DENSE_SPLIT_MIN_B) hipLaunchKernelGGL(k_candidate_window, dim3(d.B), dim3(CAND_THREADS), 0, s, d);
+  if (d.B >= DENSE_SPLIT_MIN_B) hipLaunchKernelGGL(k_candidate_window, dim3(d.B), dim3(CAND_THREADS), 0, s, d);
   else hipLaunchKernelGGL(k_candidate, dim3(d.max_tiles + 1, d.B), dim3(LM_TILE), 0, s, d);
 }
 void launch_accept(const BatchDev &d, hipStream_t s, int spec) { hipLaunchKernelGGL(k_accept, dim3(d.B), dim3(64), 0, s, d, spec); }

@@ -605,9 +605,6 @@ __device__ void tridiag_dc(mlds_double *Q, mlds_double *Vt, const int n, const i
 #ifndef GFBE_EIG_DC
 #define GFBE_EIG_DC 1      // phase 3 of the eigen-decomposition of an in-LDS A': divide & conquer (0: the implicit QL iteration)
 #endif
-#ifndef GFBE_EIG_NOAPPLY
-#define GFBE_EIG_NOAPPLY 0      // (timing experiment: the scalar lane alone)
-#endif
 // park (round 6; LDS instantiation only): an n x n global scratch. When given, phase 3 is the divide & conquer above instead of the QL
 // iteration: Z (= Q of the tridiagonalisation) is parked there, tridiag_dc runs on the two LDS matrices, and the eigenvectors
 // Q_dc^T Z are written to `park` (row j = eigenvector j, row stride n) — return value 2; a non-finite eigenvalue falls back to the QL.
@@ -803,7 +800,7 @@ __device__ int tridiag_ql_eig(PD A, PD Z, int n, int ld, double *lam, PD wk, dou
     if (fin) break;
     nsweep++;
     if (t < 64) scalar_sweep(b ^ 1);
-    else if (!GFBE_EIG_NOAPPLY && t >= 64 && t - 64 < n) {
+    else if (t >= 64 && t - 64 < n) {
       // component k of the eigenvectors: rotations hi .. lo on the rows (i, i + 1) of Z, the rotated row i carried in a register
       const int k = t - 64;
       PD L = b ? pp : cs;
@@ -1662,7 +1659,7 @@ __global__ __launch_bounds__(64) void k_marg_ldlt_tp(BatchDev d) {
 // dense_elsewhere (throughput batches, end of round 6): the caller runs the frame-0 inertial / wheel / prior factors on its side stream, beside the
 // visual kernels of the marginalisation set, and joins in front of launch_marginalize_finish (gfbe_host.cpp: enqueue_solve)
 void launch_marginalize_partials(const BatchDev &d, hipStream_t s, bool dense_elsewhere) {
-  if ((GFBE_FUSE_SMALL & 8) && d.B < DENSE_SPLIT_MIN_B && d.vis_Hs && !d.sharded && d.max_tiles > 0) {   // (small batches: two launches instead of four)
+  if (d.B < DENSE_SPLIT_MIN_B && d.vis_Hs && !d.sharded && d.max_tiles > 0) {   // (small batches: two launches instead of four)
     launch_lin_small(d, 2, s);
     launch_pair_schur_marg(d, s);
     launch_gnss(d, 2, s);

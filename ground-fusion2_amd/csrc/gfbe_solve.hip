@@ -24,19 +24,8 @@ namespace gfd {
 #define BUILD_UNROLL 6
 #endif
 #define BRM_T t      // (every kernel of this file names its thread index t; only k_solve_chain's may differ from threadIdx.x)
-#ifndef GFBE_SOLVE_INLINE
-#define GFBE_SOLVE_INLINE 0
-#endif
-#if GFBE_SOLVE_INLINE
-#define GFBE_SOLVE_FN __forceinline__
-#else
-#define GFBE_SOLVE_FN __noinline__
-#endif
 #ifndef GFBE_CHOL_STAMP
 #define GFBE_CHOL_STAMP 0   // diagnostics: per-panel time stamps into the NEXT window's timing slots (single-window runs only)
-#endif
-#ifndef GFBE_SOLVE_ESYM
-#define GFBE_SOLVE_ESYM 1
 #endif
 #define TB 16                          // tile edge of the blocked Cholesky
 typedef double dbl4 __attribute__((ext_vector_type(4)));
@@ -159,6 +148,8 @@ __device__ __forceinline__ void chol_inv_step(double (&row)[TB], double (&u)[TB]
 #pragma unroll
   for (int c = 0; c <= K; c++) dpp_fmac<K>(u[c], m);
 }
+// (the kernels run the pipelined form of this step, chol_inv_tile16_p below; this plain form is what profiles/ubench/chol_tile_check2.hip
+//  checks it against, bit for bit)
 __device__ __forceinline__ bool chol_inv_tile16(lds_double *T, int lane, int zrow, lds_double *zout, double *stamp = nullptr) {
   double row[TB], u[TB];
   const int li = lane & 15;
@@ -197,9 +188,6 @@ __device__ __forceinline__ bool chol_inv_tile16(lds_double *T, int lane, int zro
 // four 16-lane rows like the passive columns of chain_block — row group g keeps the columns c with c mod 4 == g — which leaves
 // (15 - K) + ceil((K + 1) / 4) updates per pivot instead of 16; the groups' columns are gathered when the tile is stored.
 // Same operations on every entry as chol_inv_tile16, in the same order: bit-identical results (profiles/ubench/chol_tile_check2.hip).
-#ifndef GFBE_TILE_PIPELINED
-#define GFBE_TILE_PIPELINED 1
-#endif
 // One stage of the 1/sqrt chain (rsqrt_refined, the same operations): the value is pinned where the stage is placed in the
 // instruction stream — an empty volatile assembly statement keeps its place among the (volatile) updates around it.
 template <int S>
@@ -293,7 +281,7 @@ __device__ __forceinline__ bool chol_inv_tile16_p(lds_double *T, int lane, int z
 // (address-space-typed pointers: through generic ones every load here would be a FLAT instruction)
 typedef __attribute__((address_space(3))) short lds_short;
 typedef __attribute__((address_space(1))) double glb_double;
-__device__ GFBE_SOLVE_FN double solve_build_tiles(lds_double *smem, const lds_short *perm, const lds_double *ys, const glb_double *H, const glb_double *E,
+__device__ __noinline__ double solve_build_tiles(lds_double *smem, const lds_short *perm, const lds_double *ys, const glb_double *H, const glb_double *E,
                                                  const glb_double *eg, const glb_double *gsp, const glb_double *gDp, const glb_double *ggts, double mu,
                                                  int n, int ntile_all, int t) {
   double vsv = 0.0;      // v^T S v, summed over the tile entries as they are built (off-diagonal tiles stand for both triangles)
@@ -315,11 +303,7 @@ __device__ GFBE_SOLVE_FN double solve_build_tiles(lds_double *smem, const lds_sh
           const int a = perm[ia], b = perm[ib];
           aa[u] = a; bb[u] = b; kind[u] = 1;
           hv[u] = H[(size_t)max(a, b) * ND + min(a, b)];   // H holds its lower triangle
-#if GFBE_SOLVE_ESYM
           if (a < NV && b < NV) ev[u] = E[max(a, b) * NV + min(a, b)];   // (lower triangle, like H: the diagonal tiles come out exactly symmetric)
-#else
-          if (a < NV && b < NV) ev[u] = E[a * NV + b];
-#endif
         } else if (ia == n && ib < n) { bb[u] = perm[ib]; kind[u] = 2; }
         else if (ib == n && ia < n) { bb[u] = perm[ia]; kind[u] = 2; }
         else kind[u] = (ia == ib) ? (ia == n ? 4 : 3) : 5;
@@ -350,7 +334,7 @@ __device__ GFBE_SOLVE_FN double solve_build_tiles(lds_double *smem, const lds_sh
 // (VAR: an instance of its own for k_solve_chain_wide — an out-of-line function shared by kernels of different launch bounds is compiled to the
 //  most permissive of them, and the two-workgroups-per-CU kernels then exceed their register budget)
 template <int NWAVES, int VAR = 0>
-__device__ GFBE_SOLVE_FN void chol_factor_all(lds_double *smem, int nt, int n, int t, lds_double *zlast, lds_int *flag, double *stamp) {
+__device__ __noinline__ void chol_factor_all(lds_double *smem, int nt, int n, int t, lds_double *zlast, lds_int *flag, double *stamp) {
   const int lane = t & 63, wave = t >> 6;
 #define CF_STAMP(i) do { if (t == 0) stamp[i] = (double)wall_clock64(); } while (0)
   const int lr = lane & 15, lk = lane >> 4;
@@ -396,11 +380,7 @@ __device__ GFBE_SOLVE_FN void chol_factor_all(lds_double *smem, int nt, int n, i
       if (e == 0 && P + 1 < nt) {   // tile (P+1, P+1) is final now: factorise and invert it here (wave 0), ahead of the block barrier
         __threadfence_block();
         __builtin_amdgcn_wave_barrier();
-#if GFBE_TILE_PIPELINED
         if (!chol_inv_tile16_p(C, lane, P + 2 == nt ? n % TB : -1, zlast, P == 0 ? stamp : nullptr) && lane == 0) *flag = 1;
-#else
-        if (!chol_inv_tile16(C, lane, P + 2 == nt ? n % TB : -1, zlast, P == 0 ? stamp : nullptr) && lane == 0) *flag = 1;
-#endif
       }
     }
     if (P == 0) CF_STAMP(20);
@@ -679,28 +659,6 @@ __global__ __launch_bounds__(SOLVE_THREADS, SOLVE_WAVES_PER_EU) void k_solve(Bat
 // are identity rows of their block.
 // =============================================================================================
 #define S2_THREADS 256
-#ifndef GFBE_ROLE_INLINE
-#define GFBE_ROLE_INLINE 0
-#endif
-#ifndef GFBE_WIDE_PREFETCH2
-#define GFBE_WIDE_PREFETCH2 0      // k_solve_chain's wide rows: the rows of S two blocks ahead instead of one (measured: 86.9 against 84.4 us per 512
-                                   // windows — the pipeline does not wait for those loads)
-#endif
-#ifndef GFBE_SOLVE_WIDE
-#define GFBE_SOLVE_WIDE 1          // batches with GNSS dims on k_solve_chain_wide where they fit (0: k_solve_big for all of them, rounds 3-5)
-#endif
-#ifndef GFBE_CHAIN_PRIO
-#define GFBE_CHAIN_PRIO 0          // k_solve_chain: s_setprio 3 for wave 0 and GFBE_CHAIN_PRIO - 1 for the wide waves (0: the priorities are left alone)
-#endif
-#ifndef GFBE_CHAIN_SIMD_ROLES
-#define GFBE_CHAIN_SIMD_ROLES 0    // k_solve_chain's waves numbered by the SIMD they sit on (measured: the pipeline 33.3 -> 31.5 us beside a second
-                                   // workgroup, the dense Cholesky 15.8 -> 19.2: 89.6 against 85.0 us per 512 windows; tools/diag_scripts/hwid)
-#endif
-#if GFBE_ROLE_INLINE
-#define GFBE_ROLE_FN __forceinline__
-#else
-#define GFBE_ROLE_FN __noinline__
-#endif
 #define S2_WAVES (S2_THREADS >> 6)
 enum { CH_NB = 9, CH_NC = NF, CH_ROWS = CH_NB * CH_NC, CH_BLK = CH_NB * CH_NB, RING_ROWS = 12,
        S2_MAX_NT = 6, S2_MAX_TILES = S2_MAX_NT * (S2_MAX_NT + 1) / 2, GYT_LD = 104, GYT_COLS = TB * S2_MAX_NT,
@@ -869,7 +827,7 @@ template <int TW> struct ChainCfg {
   static constexpr int STEPS = TW ? NB0 + 1 : NB0 + 2;         // block barriers of the pipeline (chain | wide rows | classic: the dense update one more step behind)
 };
 template <int TW, int SEG, int VAR = 0>
-__device__ GFBE_ROLE_FN void chain_role(lds_double *Ach, lds_double *Cch, lds_double *Amid, lds_int *flag, int lane, double *rstamp) {
+__device__ __noinline__ void chain_role(lds_double *Ach, lds_double *Cch, lds_double *Amid, lds_int *flag, int lane, double *rstamp) {
   constexpr int NB = SEG == 0 ? ChainCfg<TW>::NB0 : ChainCfg<TW>::NB1;
   for (int s = 0; s < ChainCfg<TW>::STEPS; s++) {
     RSTAMP(lane == 0 && SEG == 0, 32 + s);
@@ -901,7 +859,7 @@ __device__ GFBE_ROLE_FN void chain_role(lds_double *Ach, lds_double *Cch, lds_do
 enum { CH_ZERO = 96 };     // doubles behind the chain blocks: a zero slot (first half: parked operand reads reach 36 doubles in) and a dump slot
 // MAXNT: tile columns of the dense part the instance holds (6: k_solve_chain; 9: k_solve_chain_wide) — NU column tiles of Yr and TPW dense tiles per wave
 template <int MAXNT>
-__device__ GFBE_ROLE_FN double wide_role(lds_double *tiles, lds_double *Ach, lds_double *Cch, lds_double *ring, lds_double *zslot, const lds_double *sS,
+__device__ __noinline__ double wide_role(lds_double *tiles, lds_double *Ach, lds_double *Cch, lds_double *ring, lds_double *zslot, const lds_double *sS,
                                          const lds_double *vS, const lds_double *rS, const lds_short *perm, const lds_int *s_lo, lds_double *zzc_out,
                                          const glb_double *H, glb_double *gYT, int n_, int nt_, int ring_ld_, int wv_, int lane, double *rstamp) {
   // (wave-uniform values in scalar registers: the compiler cannot see that they are uniform — they come from LDS / the thread
@@ -936,11 +894,11 @@ __device__ GFBE_ROLE_FN double wide_role(lds_double *tiles, lds_double *Ach, lds
     pY8[u] = (col_on && lk == 0) ? col + 8 : gYT + (size_t)(GYTC - 1) * GYT_LD + (CH_NC - 1) * CH_NB + 8;
     pR[u] = ring + lk * ring_ld + min(TB * c, ring_ld - TB) + lr;
   }
-  double yv[NU][3], rpre[NU][3], rnxt[NU][3], vsv = 0.0, zzc = 0.0;
+  double yv[NU][3], rpre[NU][3], vsv = 0.0, zzc = 0.0;
 #pragma unroll
   for (int u = 0; u < NU; u++)
 #pragma unroll
-    for (int kk = 0; kk < 3; kk++) { yv[u][kk] = 0.0; rpre[u][kk] = 0.0; rnxt[u][kk] = 0.0; }
+    for (int kk = 0; kk < 3; kk++) { yv[u][kk] = 0.0; rpre[u][kk] = 0.0; }
   // rows lk, lk + 4, lk + 8 of block k (the third only counts for lk == 0: the others read into the next block and are masked)
   // (row 8 + lk exists for lk == 0 only: the other lanes' third load lands in the next block or above the diagonal, on entries nobody
   //  writes — H is not cleared at upload — and is replaced by zero, not multiplied by it)
@@ -951,12 +909,6 @@ __device__ GFBE_ROLE_FN double wide_role(lds_double *tiles, lds_double *Ach, lds
   };
 #pragma unroll
   for (int u = 0; u < NU; u++) if (on[u]) load_R(u, rpre[u]);
-#if GFBE_WIDE_PREFETCH2
-  // (round 6) TWO blocks ahead: beside a second workgroup on the CU — and the batch's other parts' kernels — a load takes longer than a step
-  // of the pipeline (stamps, B = 1 / 256 / 512: the pipeline 19.6 / 24.8 / 33.3 us), so the rows requested one step ahead paced the steps
-#pragma unroll
-  for (int u = 0; u < NU; u++) if (on[u]) load_R(u, rnxt[u]);
-#endif
   // operand pointers into the chain blocks (block CH_NC - 1 first; per-lane stride, 0 for the lanes parked on the zero slot)
   //   a2[kk] = W_k[lr][4 kk + lk]        a1[kk] = -Yc_k+1[4 kk + lk][lr]      (G: W_kG[4 kk + lk][lr], Yc_kG[4 kk + lk][lr])
   const int sW01 = in01 ? CH_BLK : 0, sW2 = in2 ? CH_BLK : 0;
@@ -1020,14 +972,8 @@ __device__ GFBE_ROLE_FN double wide_role(lds_double *tiles, lds_double *Ach, lds
         double r[3];
 #pragma unroll
         for (int kk = 0; kk < 3; kk++) r[kk] = __builtin_fma(rpre[u][kk] * sk[kk], m1, mr * rk[kk]);
-#if GFBE_WIDE_PREFETCH2
-#pragma unroll
-        for (int kk = 0; kk < 3; kk++) rpre[u][kk] = rnxt[u][kk];
-        load_R(u, rnxt[u]);                                        // (block k - 2; the loads of the two steps after block 1 read valid, unused rows of H)
-#else
         load_R(u, rpre[u]);                                        // (block k - 1; in flight during this block's products. The loads of
                                                                    //  the step after block 0 read valid, unused rows of H)
-#endif
         if (!zero_tile) {
 #pragma unroll
           for (int kk = 0; kk < 3; kk++) vsv = __builtin_fma(r[kk] * vk[kk], vbj2[u], vsv);
@@ -1099,7 +1045,7 @@ __device__ GFBE_ROLE_FN double wide_role(lds_double *tiles, lds_double *Ach, lds
 // the matrix-core operand pattern (two rows x 16 consecutive doubles per half-wave) still only collides on two of its 64 banks.
 enum { YALL_ROWS = 104, YALL_LD = 81 };     // 99 rows of Yr | row 99: zeros (the 25th group of four) | rows 100..103: dump rows of the masked third store
 template <int SEG>
-__device__ GFBE_ROLE_FN double wide_role_tw(lds_double *Ach, lds_double *Cch, lds_double *Yall, lds_double *zslot, const lds_double *sS, const lds_double *vS,
+__device__ __noinline__ double wide_role_tw(lds_double *Ach, lds_double *Cch, lds_double *Yall, lds_double *zslot, const lds_double *sS, const lds_double *vS,
                                             const lds_double *rS, const lds_short *perm, lds_double *zzc_out, const glb_double *H, int n_, int nt_, int ld_,
                                             int wv_, int lane, double *rstamp) {
   constexpr int NB = SEG == 0 ? ChainCfg<1>::NB0 : ChainCfg<1>::NB1;
@@ -1132,11 +1078,11 @@ __device__ GFBE_ROLE_FN double wide_role_tw(lds_double *Ach, lds_double *Cch, ld
     pR8[u] = lk == 0 ? Yall + (KF * CH_NB + 8) * ld + cc : Yall + (100 + lk) * ld + cc;
   }
   const int sR = SG * CH_NB * ld, sR8 = lk == 0 ? SG * CH_NB * ld : 0;
-  double yv[2][3], rpre[2][3], rnxt[2][3], vsv = 0.0, zzc = 0.0;
+  double yv[2][3], rpre[2][3], vsv = 0.0, zzc = 0.0;
 #pragma unroll
   for (int u = 0; u < 2; u++)
 #pragma unroll
-    for (int kk = 0; kk < 3; kk++) { yv[u][kk] = 0.0; rpre[u][kk] = 0.0; rnxt[u][kk] = 0.0; }
+    for (int kk = 0; kk < 3; kk++) { yv[u][kk] = 0.0; rpre[u][kk] = 0.0; }
   // rows lk, lk + 4, lk + 8 of block k (row 8 + lk exists for lk == 0 only: the other lanes' third load lands in the next block or above
   // the diagonal, on entries nobody writes, and is replaced by zero, not multiplied by it)
   auto load_R = [&](int u, double (&r)[3]) {
@@ -1305,36 +1251,7 @@ __device__ __forceinline__ void solve_chain_body(const BatchDev &d, int retry_pa
   const int w = blockIdx.x;
   const WinDesc &ds = d.desc[w];
   WinCtl &c = d.ctl[w];
-#if GFBE_CHAIN_SIMD_ROLES
-  // (round 6) the waves numbered by the SIMD they sit on: wave 0 — the chain role and every serial section — of BOTH workgroups of a CU on
-  // SIMD 0, the wide waves pairwise on SIMDs 1..3. The dispatcher gives a workgroup one wave per SIMD and rotates the start, so that wave 0
-  // of one workgroup shares its SIMD with a wide wave of the other one — whose FP64 matrix-core instructions hold the FP64 vector pipe the
-  // chain's dependent instructions need (the pipeline: 19.6 us alone, 33.3 beside a second workgroup). Everything below uses the logical
-  // index t, the block sums included: the results do not depend on the placement. (Not one wave per SIMD: the physical numbering.)
-  int t_;
-  {
-    const int tp = threadIdx.x, wp = tp >> 6;
-    __shared__ int simd_of[S2_WAVES];
-    int lw = wp;
-    if (!TW) {
-      const int simd = (int)(__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4) & 3u);      // HW_REG_HW_ID, SIMD_ID = bits 5:4
-      if ((tp & 63) == 0) simd_of[wp] = simd;
-      __syncthreads();
-      int m = 0;
-      for (int q = 0; q < S2_WAVES; q++) m |= 1 << simd_of[q];
-      lw = (m == 15) ? simd : wp;
-    }
-    t_ = lw * 64 + (tp & 63);
-  }
-  const int t = t_, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
-#else
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
-#endif
-#if GFBE_CHAIN_PRIO
-  // (round 6) instruction-arbitration priority: the kernel is a chain of dependent instructions on single waves — wave 0 above all — that
-  // shares its SIMDs with the second workgroup of the CU and, in a split batch, with the streaming kernels of the other parts
-  if (!TW) { if (wave == 0) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(GFBE_CHAIN_PRIO - 1); }
-#endif
   const double *H = d.H + (size_t)w * ND * ND, *g = d.g + (size_t)w * ND;
   double *gsp = d.sp + (size_t)w * ND, *gDp = d.Dp + (size_t)w * ND, *ggts = d.gts + (size_t)w * ND;
   double *gvp = d.vp + (size_t)w * ND, *gyp = d.yp + (size_t)w * ND;
@@ -1983,11 +1900,7 @@ __device__ __noinline__ void big_factor(glb_double *S, int nt, int n, int lane, 
       for (int q = 0; q < 4; q++) Dgl[tsw(lk + 4 * q, lr)] = acc0[q];
       __threadfence_block();
       __builtin_amdgcn_wave_barrier();
-#if GFBE_TILE_PIPELINED
       if (!chol_inv_tile16_p(Dgl, lane, j == nt - 1 ? n % TB : -1, zlast) && lane == 0) *flag = 1;
-#else
-      if (!chol_inv_tile16(Dgl, lane, j == nt - 1 ? n % TB : -1, zlast) && lane == 0) *flag = 1;
-#endif
     }
     FSTAMP(10);
     __syncthreads();
@@ -2254,9 +2167,6 @@ static_assert(((NC + 1 + TB - 1) / TB) * (((NC + 1 + TB - 1) / TB) + 1) / 2 * TB
               + sizeof(short) * (NC + TB) + sizeof(double) * (16 + 2 * NC + TB + 2 + TB) + sizeof(int) * 6      // perm, red, ys, s_zz, s_vSv, zlast, flags
               + 128 /* alignment padding */ <= 160 * 1024, "k_solve: tiles + static LDS exceed a CU's 160 KB");
 static size_t solve_smem_bytes() { const int nt = (NC + 1 + TB - 1) / TB;   /* (k_solve never sees the GNSS dims: those batches take k_solve_big) */ return sizeof(double) * (size_t)(nt * (nt + 1) / 2) * TB * TB; }
-#ifndef GFBE_CHAIN_LDS_PAD
-#define GFBE_CHAIN_LDS_PAD 0       // (measurement) bytes of dynamic LDS k_solve_chain asks for beyond its layout: 24576 leaves ONE workgroup per CU
-#endif
 static size_t chain_smem_bytes(int ntile, bool tw = false) {     // tw: k_solve_chain_tw — every row of Yr instead of the two-block ring, and the middle block's second downdate
   return sizeof(double) * ((size_t)ntile * TB * TB + 2 * CH_NC * CH_BLK + CH_ZERO + (tw ? (size_t)YALL_ROWS * YALL_LD + CH_BLK : (size_t)2 * RING_ROWS * (ntile > S2_MAX_TILES ? (int)CHAIN_RING_LD_WIDE : chain_ring_ld(ntile))));
 }
@@ -2274,7 +2184,7 @@ int solve_chain_tiles(const unsigned char *act) {
 hipError_t kernels_init_device() {
   const hipError_t e = hipFuncSetAttribute((const void *)k_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)solve_smem_bytes());
   if (e != hipSuccess) return e;
-  const hipError_t e2 = hipFuncSetAttribute((const void *)k_solve_chain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(chain_smem_bytes(S2_MAX_TILES) + GFBE_CHAIN_LDS_PAD));
+  const hipError_t e2 = hipFuncSetAttribute((const void *)k_solve_chain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)chain_smem_bytes(S2_MAX_TILES));
   if (e2 != hipSuccess) return e2;
   const hipError_t e3 = hipFuncSetAttribute((const void *)k_solve_chain_tw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)chain_smem_bytes(15, true));
   if (e3 != hipSuccess) return e3;
@@ -2284,13 +2194,13 @@ hipError_t kernels_init_device() {
 }
 // a batch with GNSS dims takes the chain kernel when every window's dense part fits nine tile columns (column 143 of the transposed Yr rows
 // is the dump column: n + 1 <= 143) — else k_solve_big
-bool solve_chain_wide_fits(int n_dense_max) { return GFBE_SOLVE_WIDE && n_dense_max + 1 <= TB * S2_WIDE_NT - 1; }
+bool solve_chain_wide_fits(int n_dense_max) { return n_dense_max + 1 <= TB * S2_WIDE_NT - 1; }
 void launch_solve(const BatchDev &d, hipStream_t s, int retry_pass) {
   if (d.solve_big && d.solve_wide) hipLaunchKernelGGL(k_solve_chain_wide, dim3(d.B), dim3(S2_THREADS), chain_smem_bytes(S2_WIDE_TILES), s, d, retry_pass);
   else if (d.solve_big) hipLaunchKernelGGL(k_solve_big, dim3(d.B), dim3(BIG_THREADS), big_smem_bytes(), s, d, retry_pass);
   else if (d.solve_mono) hipLaunchKernelGGL(k_solve, dim3(d.B), dim3(SOLVE_THREADS), solve_smem_bytes(), s, d, retry_pass);
   else if (d.solve_tw) hipLaunchKernelGGL(k_solve_chain_tw, dim3(d.B), dim3(2 * S2_THREADS), chain_smem_bytes(d.solve_ntile, true), s, d, retry_pass);
-  else hipLaunchKernelGGL(k_solve_chain, dim3(d.B), dim3(S2_THREADS), chain_smem_bytes(d.solve_ntile) + GFBE_CHAIN_LDS_PAD, s, d, retry_pass);
+  else hipLaunchKernelGGL(k_solve_chain, dim3(d.B), dim3(S2_THREADS), chain_smem_bytes(d.solve_ntile), s, d, retry_pass);
 }
 void launch_rebuild_E_shard(const BatchDev &d, hipStream_t s) { hipLaunchKernelGGL(k_rebuild_E_shard, dim3(d.B), dim3(1024), 0, s, d); }
 

@@ -13,25 +13,19 @@ sys.path.insert(0, ROOT)
 VDIR = os.path.join(ROOT, "ground-fusion2_amd", "csrc", "variants")
 VARIANTS = {   # name -> (extra flags, fp-contract)
     "base": ([], "off"),
-    "eignoapply": (["-DGFBE_EIG_NOAPPLY=1"], "off"),
-    "schurabs": (["-DGFBE_SCHUR_COMPACT=0"], "off"),
     "kvis3": (["-DGFBE_KVIS_WAVES=3"], "off"),
-    "densetp0": (["-DGFBE_DENSE_TP=0"], "off"),
     "asmu6": (["-DGFBE_ASM_U=6"], "off"),
     "asmu8": (["-DGFBE_ASM_U=8"], "off"),
     "asmu2": (["-DGFBE_ASM_U=2"], "off"),
     "cand512": (["-DCAND_THREADS=512"], "off"),
     "cand1024": (["-DCAND_THREADS=1024"], "off"),
     "schur3": (["-DGFBE_SCHUR_WGS=3", "-DHS_LD=83"], "off"),
-    "noearly": (["-DGFBE_KVIS_EARLY=0"], "off"),
     "contract": ([], "fast"),
     "stamp": (["-DGFBE_KVIS_STAMP=1"], "off"),
-    "noesym": (["-DGFBE_SOLVE_ESYM=0"], "off"),
     "cholstamp": (["-DGFBE_CHOL_STAMP=1"], "off"),
     "chainstamp": (["-DGFBE_CHAIN_STAMP=1"], "off"),
     "bigstamp": (["-DGFBE_BIG_STAMP=1"], "off"),
     "ldltstamp": (["-DGFBE_LDLT_STAMP=1"], "off"),
-    "clearlm": (["-DGFBE_CLEAR_LM=1"], "off"),
     "linstamp": (["-DGFBE_LIN_STAMP=1"], "off"),
     "linstamp3": (["-DGFBE_LIN_STAMP=1", "-DGFBE_LIN_STAMP_MODE=3"], "off"),
     "linstamp3_512": (["-DGFBE_LIN_STAMP=1", "-DGFBE_LIN_STAMP_MODE=3", "-DGFBE_LIN_SMALL_THREADS=512"], "off"),
@@ -45,35 +39,20 @@ VARIANTS = {   # name -> (extra flags, fp-contract)
     "kvis2": (["-DGFBE_KVIS_WAVES=2"], "off"),
     "chunk8": (["-DVIS_CHUNK=8"], "off"),
     "chunk6": (["-DVIS_CHUNK=6"], "off"),
-    "nochunk": (["-DGFBE_VIS_CHUNK=0"], "off"),
     "marg256": (["-DGFBE_MARG_TP_THREADS=256"], "off"),
     "marg1024": (["-DGFBE_MARG_TP_THREADS=1024"], "off"),
     "vb256": (["-DVB_GROUP=256", "-DGFBE_VISASM_WAVES=2"], "off"),
     "vb384": (["-DVB_GROUP=384", "-DGFBE_VISASM_WAVES=3"], "off"),
     "noldlttp": (["-DGFBE_LDLT_TP=0"], "off"),
     "ldlttp2": (["-DGFBE_LDLT_TP=2"], "off"),
-    "pf2": (["-DGFBE_WIDE_PREFETCH2=1"], "off"),
-    "nosimdroles": (["-DGFBE_CHAIN_SIMD_ROLES=0"], "off"),
     "ql": (["-DGFBE_EIG_DC=0"], "off"),
     "lmsstamp": (["-DGFBE_LMS_STAMP=1"], "off"),
     "linstamp1": (["-DGFBE_LIN_STAMP=1", "-DGFBE_LIN_STAMP_MODE=1"], "off"),
     "lin512": (["-DGFBE_LIN_SMALL_THREADS=512"], "off"),
-    "chain1wg": (["-DGFBE_CHAIN_LDS_PAD=24576"], "off"),
-    "asmtp0": (["-DGFBE_ASM_TP=0"], "off"),
-    "asmtp1": (["-DGFBE_ASM_TP=1"], "off"),
-    "asmtp5": (["-DGFBE_ASM_TP=5"], "off"),
-    "asmtp13": (["-DGFBE_ASM_TP=13"], "off"),
-    "margaside0": (["-DGFBE_MARG_DENSE_ASIDE=0"], "off"),
-    "pcs0": (["-DGFBE_PCS_ONE_ROUND=0"], "off"),
-    "stepcand0": (["-DGFBE_STEP_CAND_REGS=0"], "off"),
     "lmsstamp0": (["-DGFBE_LMS_STAMP=1", "-DGFBE_LMS_AHEAD=0"], "off"),
     "lmsa0": (["-DGFBE_LMS_AHEAD=0"], "off"),
     "lin1024": (["-DGFBE_LIN_SMALL_THREADS=1024"], "off"),
     "lin512ks5": (["-DGFBE_LIN_SMALL_THREADS=512", "-DGFBE_LIN_SMALL_KS=5"], "off"),
-    "fuse0": (["-DGFBE_FUSE_SMALL=0"], "off"),
-    "fuse1": (["-DGFBE_FUSE_SMALL=1"], "off"),
-    "fuse3": (["-DGFBE_FUSE_SMALL=3"], "off"),
-    "fuse5": (["-DGFBE_FUSE_SMALL=5"], "off"),
     "ks5": (["-DGFBE_LIN_SMALL_KS=5"], "off"),
     "ks10": (["-DGFBE_LIN_SMALL_KS=10"], "off"),
     "ks4": (["-DGFBE_LIN_SMALL_KS=4"], "off"),
@@ -83,18 +62,7 @@ VARIANTS = {   # name -> (extra flags, fp-contract)
     "s512u10": (["-DSOLVE_THREADS=512", "-DSOLVE_WAVES_PER_EU=2", "-DBUILD_UNROLL=10"], "off"),
     "s512u13": (["-DSOLVE_THREADS=512", "-DSOLVE_WAVES_PER_EU=2", "-DBUILD_UNROLL=13"], "off"),
     "s768": (["-DSOLVE_THREADS=768", "-DSOLVE_WAVES_PER_EU=3", "-DBUILD_UNROLL=9"], "off"),
-    "s768i": (["-DSOLVE_THREADS=768", "-DSOLVE_WAVES_PER_EU=3", "-DBUILD_UNROLL=9", "-DGFBE_SOLVE_INLINE=1"], "off"),
     "s768u6": (["-DSOLVE_THREADS=768", "-DSOLVE_WAVES_PER_EU=3", "-DBUILD_UNROLL=6"], "off"),
-    "s512i": (["-DSOLVE_THREADS=512", "-DSOLVE_WAVES_PER_EU=2", "-DGFBE_SOLVE_INLINE=1"], "off"),
-    "cprio1": (["-DGFBE_CHAIN_PRIO=1"], "off"),
-    "cprio3": (["-DGFBE_CHAIN_PRIO=3"], "off"),
-    "sprio": (["-DGFBE_PRIO_SMALL=1"], "off"),
-    "allprio": (["-DGFBE_PRIO_SMALL=1", "-DGFBE_CHAIN_PRIO=3"], "off"),
-    "nostepcand": (["-DGFBE_FUSE_STEP_CAND=0"], "off"),
-    "abl1_nomfma": (["-DGFBE_ABLATE=1"], "off"),
-    "abl2_nopartstore": (["-DGFBE_ABLATE=2"], "off"),
-    "abl3_nohpstore": (["-DGFBE_ABLATE=3"], "off"),
-    "abl4_noeval": (["-DGFBE_ABLATE=4"], "off"),
 }
 
 def build(names):
