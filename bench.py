@@ -8,7 +8,12 @@ marginalisation. Workload = BASELINE.json configs[1]: 10-keyframe VI-wheel windo
 with a marginalisation prior (SURVEY.md section 8d generator), B independent windows per GPU resident in
 HBM (`value`: inputs already in HBM when the timed region starts).
 
-Next to `value` the JSON line carries `end_to_end`: the same workload with FRESH inputs every step —
+A plain run does only what `value` needs: set-up, warm-up, the timed steps, `--dump-outputs` if asked, the JSON line.
+Everything else it can measure runs with `--full` (about 90 s more): the roofline of the dominant kernel, `resident_1024`,
+`end_to_end`, `mixed_batch`, the single-window latencies, `cpu_baseline` with the accuracy against the oracle, `other_configs`
+and the like-for-like speed-ups.
+
+With `--full` the JSON line carries `end_to_end`: the same workload with FRESH inputs every step —
 host-fed (gfbe_batch_upload from the caller's gfbe_window structures: packing + one H2D copy, solve,
 gather + one D2H copy + unpacking, two batches in flight) and table-fed (gfbe_batch_upload_tables from
 the device-resident feature tables) — plus the host-to-host latency of one gfbe_solve_window call.
@@ -49,19 +54,23 @@ def parse_args(argv=None):
                          "`resident_1024` in the JSON line is the same measurement at the 1024 windows of rounds 1-2")
     ap.add_argument("--landmarks", type=int, default=2000)
     ap.add_argument("--unique", type=int, default=8, help="distinct synthetic windows (tiled to --batch)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0,
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg of the benchmark (roofline, resident_1024, end_to_end, mixed_batch, "
+                         "single-window latencies, cpu_baseline and accuracy, other_configs); the options of the next group only act with it")
+    fl = ap.add_argument_group("legs of --full")
+    fl.add_argument("--cpu-seconds", type=float, default=15.0,
                     help="scales the cpu_baseline leg: at the default, SURVEY section 8d's protocol (median of 200 solves after 20 warm-ups per "
                          "algorithm, 60 more under the reference's 0.04 s cap; ~30 s of CPU work on the GPU box's host), fewer solves below")
-    ap.add_argument("--mixed", type=int, default=256, help="unique windows of the heterogeneous `mixed_batch` leg (0: skip)")
-    ap.add_argument("--mixed-steps", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end_to_end block")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the other_configs block (BASELINE configs 1, 3, 4, 5 beside the oracle)")
-    ap.add_argument("--no-single", action="store_true", help="skip the single-window latency legs (profile runs: their eigen-mode k_marg launches would lead the kernel statistics)")
-    ap.add_argument("--e2e-batch", type=int, default=1024, help="windows per batch of the end-to-end loops")
-    ap.add_argument("--e2e-steps", type=int, default=8)
-    ap.add_argument("--e2e-depth", type=int, default=3, help="batches in flight in the end-to-end loops")
-    ap.add_argument("--e2e-split", type=int, default=0,
+    fl.add_argument("--mixed", type=int, default=256, help="unique windows of the heterogeneous `mixed_batch` leg (0: skip)")
+    fl.add_argument("--mixed-steps", type=int, default=5)
+    fl.add_argument("--no-cpu-baseline", action="store_true")
+    fl.add_argument("--no-e2e", action="store_true", help="skip the end_to_end block")
+    fl.add_argument("--no-other-configs", action="store_true", help="skip the other_configs block (BASELINE configs 1, 3, 4, 5 beside the oracle)")
+    fl.add_argument("--no-single", action="store_true", help="skip the single-window latency legs (profile runs: their eigen-mode k_marg launches would lead the kernel statistics)")
+    fl.add_argument("--e2e-batch", type=int, default=1024, help="windows per batch of the end-to-end loops")
+    fl.add_argument("--e2e-steps", type=int, default=8)
+    fl.add_argument("--e2e-depth", type=int, default=3, help="batches in flight in the end-to-end loops")
+    fl.add_argument("--e2e-split", type=int, default=0,
                     help="gfbe_options.split_batch of the end-to-end loops: the batches in flight already overlap each other, every batch as ONE "
                          "part measured best (1024 windows per batch, three in flight: 48.8k solves/s host-fed; two parts 42.6k, four 33.0k)")
     ap.add_argument("--host-threads", type=int, default=0, help="gfbe_options.host_threads (0: library default)")
@@ -191,6 +200,31 @@ def main():
                           "allreduce_calls_per_iteration": ((hook.calls() - hook_c0) / float(args.steps) - 3.0) / 8.0,
                           "allreduce_bytes_per_solve": (hook.bytes() - hook_b0) / float(args.batch * args.steps)}
     value = solves / elapsed
+    head = {
+        "metric": "sliding-window solves/sec (10-kf, 2k landmarks)", "value": value, "unit": "solves/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True, "scaling": "strong" if shard else "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "BASELINE configs[1]: 10-keyframe VI-wheel window, %d landmarks (K=%d visual factors avg), "
+                               "marginalisation prior n=%d, full optimization() = <=8 dogleg iterations + re-anchor + MARGIN_OLD" %
+                               (args.landmarks, int(np.mean(K_per)), snaps[0]["prior"]["n"]),
+                   "windows_per_gpu": args.batch, "unique_windows": args.unique,
+                   "options": "gfbe_default_options (marg_sqrt = 1 LDL^T, speculative_linearization = 1: the candidate pass of an iteration is its "
+                              "linearisation — same evaluations, same results as with 0, tests/test_gpu_speculative.py)",
+                   "parallelism": ("landmark tiles of every window sharded over %d ranks, RCCL all-reduce of the partial normal equations (%s hook)" % (world, hook_kind)) if shard
+                                  else "windows sharded over %d rank(s), no collective" % world},
+        "landmark_sharding": shard_info, "setup_s": setup_s,
+    }
+
+    if not args.full:
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, batch.download(), abi)
+        batch.free()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(head))
+        return
 
     # ---- correctness of what was timed (cheap): every window converged to the same cost as window 0 of its kind
     res = batch.download()
@@ -278,18 +312,8 @@ def main():
             cpu, accuracy = cpu_baseline(args, abi, synth, snaps, res[: args.unique])
         lat = single_window_latencies(args, gf, torch, be, batch_snaps[0], local_rank, snaps) if not (shard or args.no_single) else None
         out = {
-            "metric": "sliding-window solves/sec (10-kf, 2k landmarks)", "value": value, "unit": "solves/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True, "scaling": "strong" if shard else "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "BASELINE configs[1]: 10-keyframe VI-wheel window, %d landmarks (K=%d visual factors avg), "
-                                   "marginalisation prior n=%d, full optimization() = <=8 dogleg iterations + re-anchor + MARGIN_OLD" %
-                                   (args.landmarks, int(np.mean(K_per)), snaps[0]["prior"]["n"]),
-                       "windows_per_gpu": args.batch, "unique_windows": args.unique,
-                       "options": "gfbe_default_options (marg_sqrt = 1 LDL^T, speculative_linearization = 1: the candidate pass of an iteration is its "
-                                  "linearisation — same evaluations, same results as with 0, tests/test_gpu_speculative.py)",
-                       "parallelism": ("landmark tiles of every window sharded over %d ranks, RCCL all-reduce of the partial normal equations (%s hook)" % (world, hook_kind)) if shard
-                                      else "windows sharded over %d rank(s), no collective" % world},
-            "roofline": roofline, "cpu_baseline": cpu, "accuracy": accuracy, "landmark_sharding": shard_info,
+            **head,
+            "roofline": roofline, "cpu_baseline": cpu, "accuracy": accuracy,
             "ate_vs_oracle_m": accuracy["ate_vs_oracle_m"] if accuracy else None,
             "max_rot_err_rad": accuracy["max_rot_err_rad"] if accuracy else None,
             "mixed_batch": mixed, "single_window": lat,
@@ -297,7 +321,7 @@ def main():
             "single_window_ms": single_ms, "single_window_solves_per_s": (1e3 / single_ms) if single_ms else None,
             "single_window_host_to_host_ms": single_host_ms,
             "device_phase_ms_per_step": phase_ms, "pcie_bytes": io_bytes,
-            "iterations": iters, "final_cost": final_costs, "setup_s": setup_s,
+            "iterations": iters, "final_cost": final_costs,
         }
         if not (shard or args.no_other_configs):
             try:

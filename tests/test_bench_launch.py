@@ -43,6 +43,14 @@ def test_bench_single_rank_launch_check_needs_no_launcher():
     assert json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])["n_gpus"] == 1
 
 
+def test_bench_legs_beyond_the_headline_are_opt_in():
+    """A plain run times the headline only; the other legs run with --full, where the options of their group still select them."""
+    import bench
+    assert bench.parse_args([]).full is False
+    a = bench.parse_args(["--full", "--no-e2e", "--mixed", "0"])
+    assert a.full and a.no_e2e and a.mixed == 0
+
+
 def test_rccl_hook_library_contract():
     so = gf.backend.build_rccl_hook()
     lib = C.CDLL(so)

@@ -1,6 +1,6 @@
 # end_to_end of bench.py for several sizes of the host packing pool (gfbe_options.host_threads)
 for n in ${THREADS:-32 64 128}; do
-  python bench.py --no-cpu-baseline --no-single --mixed 0 --steps 5 --host-threads $n 2>/dev/null > /tmp/e2e_$n.json
+  python bench.py --full --no-cpu-baseline --no-single --mixed 0 --steps 5 --host-threads $n 2>/dev/null > /tmp/e2e_$n.json
   python - $n <<'PY'
 import json, sys
 n = sys.argv[1]
