@@ -748,7 +748,11 @@ gfbe_status gfbe_debug_timing(gfbe_ctx *ctx, gfbe_batch *batch, int32_t w, doubl
 /* Diagnostics: a per-window vector of the LAST linearisation of a solved batch (GFBE_DENSE_DIM doubles each; waits for the solve):
  * which = 0 Gauss-Newton step y of the dense block (Jacobi-scaled), 1 Cauchy direction v, 2 Jacobi scaling s, 3 gradient g.
  * Lets a test compare the two factorisations of gfbe_options.solve_kernel entry by entry. which = 1000 + r: row r of the assembled
- * normal equations H (lower triangle valid); 2000 + r: row r of the Schur term E (73 entries; r = 73: its gradient share). */
+ * normal equations H (lower triangle valid); 2000 + r: row r of the Schur term E (73 entries; r = 73: its gradient share eg).
+ * Coordinates: H and g are unscaled, constant dims removed. E = sum_l w_l h_l h_l^T and eg = sum_l w_l h_l g_l with the UNSCALED pose
+ * columns h_l = H_pl[l] of H and g; only the landmark side is Jacobi-scaled and mu-regularised, through the weight
+ * w_l = s_l^2 / (s_l^2 H_ll + mu clamp(s_l^2 H_ll)), s_l = 1 / (1 + sqrt(H_ll)) fixed at iteration 0 (w_l = 0 for a constant landmark
+ * and one without factors). The dense solve scales H - E afterwards. tests/test_gpu_normal_equations.py compares all four entry by entry. */
 gfbe_status gfbe_debug_vector(gfbe_ctx *ctx, gfbe_batch *batch, int32_t w, int32_t which, double *out);
 
 /* Multi-GPU landmark sharding: when set, the library calls

@@ -7,21 +7,13 @@ import numpy as np
 
 from _gfbe_import import gf
 
+from normal_equations_np import lidar_blocks      # noqa: E402
+
 abi, synth = gf.abi, gf.synth
 
 
 def numpy_lidar_terms(snap, lio):
-    x = snap["pose"][lio["frame"]]
-    R, t = synth.qrot(x[3:]), x[:3]
-    sw = lio["sqrt_info"] * lio["weights"]
-    r = sw * ((lio["normals"] * (lio["pts"] @ R.T + t)).sum(axis=1) + lio["offsets"])
-    nR = lio["normals"] @ R
-    J = np.concatenate([sw[:, None] * lio["normals"], -sw[:, None] * np.cross(nR, lio["pts"])], axis=1)
-    d = lio["huber_delta"]
-    s = r * r
-    rho = np.where(s <= d * d, s, 2 * d * np.sqrt(s) - d * d)
-    scale = np.where(s <= d * d, 1.0, np.sqrt(d / np.sqrt(np.maximum(s, 1e-300))))
-    Jc, rc = J * scale[:, None], r * scale
+    Jc, rc, rho = lidar_blocks(snap, lio)
     return 0.5 * rho.sum(), Jc.T @ rc, Jc.T @ Jc
 
 

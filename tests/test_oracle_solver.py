@@ -7,40 +7,7 @@ from _gfbe_import import gf
 
 abi, synth = gf.abi, gf.synth
 
-# oracle tangent layout (oracle/gfo_solver.cpp)
-T_POSE = lambda k: 6 * k          # noqa: E731
-T_EX, T_TD = 66, 72
-T_SB = lambda k: 73 + 9 * k       # noqa: E731
-T_EXW, T_SX, T_SY, T_SW, T_TDW = 172, 178, 179, 180, 181
-
-
-def numpy_normal_equations(snap, ev):
-    """H = sum J'J, g = sum J'r from the block-CSR factor outputs (robustified)."""
-    H, g = np.zeros((abi.DENSE_DIM, abi.DENSE_DIM)), np.zeros(abi.DENSE_DIM)
-    L = len(snap["para_feature"])
-    Hll, gl, Hpl = np.zeros(L), np.zeros(L), np.zeros((L, 73))
-    for k in range(len(snap["vis_imu_i"])):
-        i, j, l = snap["vis_imu_i"][k], snap["vis_imu_j"][k], snap["vis_feature_index"][k]
-        cols = np.r_[T_POSE(i) + np.arange(6), T_POSE(j) + np.arange(6), T_EX + np.arange(6), T_TD]
-        J = ev["vis_J"][k][:, np.r_[0:18, 19]]
-        w = ev["vis_J"][k][:, 18]
-        r = ev["vis_r"][k]
-        H[np.ix_(cols, cols)] += J.T @ J
-        g[cols] += J.T @ r
-        Hll[l] += w @ w
-        gl[l] += w @ r
-        Hpl[l, cols] += J.T @ w
-    for k, i in enumerate(snap["imu_frame"]):
-        cols = np.r_[T_POSE(i) + np.arange(6), T_SB(i) + np.arange(9), T_POSE(i + 1) + np.arange(6), T_SB(i + 1) + np.arange(9)]
-        J, r = ev["imu_J"][k], ev["imu_r"][k]
-        H[np.ix_(cols, cols)] += J.T @ J
-        g[cols] += J.T @ r
-    for k, i in enumerate(snap.get("wheel_frame", [])):
-        cols = np.r_[T_POSE(i) + np.arange(6), T_POSE(i + 1) + np.arange(6), T_EXW + np.arange(6), T_SX, T_SY, T_SW, T_TDW]
-        J, r = ev["wheel_J"][k], ev["wheel_r"][k]
-        H[np.ix_(cols, cols)] += J.T @ J
-        g[cols] += J.T @ r
-    return H, g, Hll, gl, Hpl
+from normal_equations_np import T_POSE, T_EX, T_TD, T_SB, T_EXW, T_SX, T_SY, T_SW, T_TDW, numpy_normal_equations      # noqa: E402,F401
 
 
 def free_all(snap):
