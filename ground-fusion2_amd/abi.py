@@ -945,3 +945,104 @@ def line_refine(lib, prefix, ctx, windows, sqrt_info=400.0, cauchy_scale=1.0, ma
                         perf=summary_perf(sums[k]), status=rc))
         o += h.n
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Line feature tables (gfbe_ltab_*): FeatureManager::linefeature on the device
+# ---------------------------------------------------------------------------------------------
+class LineTables:
+    """W device-resident line tables behind `lib` (prefix gfbe_, ctx = gfbe_ctx*). Per-table arguments are lists of length W."""
+
+    def __init__(self, lib, prefix, ctx, n_tables=1, capacity=1024):
+        self.lib, self.prefix, self.ctx, self.W, self.cap = lib, prefix, ctx, n_tables, capacity
+        self.h = C.c_void_p()
+        for name in ("create", "add_frame", "triangulate", "remove_back_shift", "remove_back", "remove_front", "refine", "size",
+                     "line_count", "download", "upload"):
+            self._f(name).restype = c_i
+        self._f("destroy").restype = None
+        self._f("refine").argtypes = [C.c_void_p, C.c_void_p, PD, PD, c_d, c_d, c_i, C.POINTER(Summary)]
+        self._check(self._f("create")(self.ctx, int(n_tables), int(capacity), C.byref(self.h)), "create")
+
+    def _f(self, name):
+        return getattr(self.lib, self.prefix + "ltab_" + name)
+
+    def _check(self, rc, what):
+        if rc != OK:
+            raise RuntimeError("%sltab_%s failed with status %d" % (self.prefix, what, rc))
+
+    def close(self):
+        if self.h:
+            self._f("destroy")(self.ctx, self.h)
+            self.h = C.c_void_p()
+
+    def add_frame(self, frame_count, ids, obs4):
+        """ids[w]: ascending line ids; obs4[w]: [n, 4]. Returns counters [W, 2] = [tracked, new]."""
+        off, lid = FeatureTables._ragged(ids, np.int32)
+        ob = np.ascontiguousarray(np.concatenate([np.asarray(r, np.float64).reshape(-1, 4) for r in obs4]))      # (a table may receive no line)
+        assert len(ob) == len(lid)
+        fc, cnt = _i32(frame_count), np.zeros((self.W, 2), np.int32)
+        self._check(self._f("add_frame")(self.ctx, self.h, _pi(fc), _pi(off), _pi(lid), _pd(ob), _pi(cnt)), "add_frame")
+        return cnt
+
+    def triangulate(self, poses, tic_ric):
+        p, e = _f64(poses).reshape(self.W, 11 * 12), _f64(tic_ric).reshape(self.W, 12)
+        self._check(self._f("triangulate")(self.ctx, self.h, _pd(p), _pd(e)), "triangulate")
+
+    def remove_back_shift(self, marg_pr, new_pr):
+        a, b = _f64(marg_pr).reshape(self.W, 12), _f64(new_pr).reshape(self.W, 12)
+        self._check(self._f("remove_back_shift")(self.ctx, self.h, _pd(a), _pd(b)), "remove_back_shift")
+
+    def remove_back(self):
+        self._check(self._f("remove_back")(self.ctx, self.h), "remove_back")
+
+    def remove_front(self, frame_count):
+        fc = _i32(frame_count)
+        self._check(self._f("remove_front")(self.ctx, self.h, _pi(fc)), "remove_front")
+
+    def refine_raw(self, pose7, ex_cam, sqrt_info=400.0, cauchy_scale=1.0, max_num_iterations=8, sums=None):
+        """gfbe_ltab_refine on prepared arrays (pose7 [W][11][7], ex_cam [W][7], float64, contiguous): (status, Summary array)."""
+        sums = (Summary * self.W)() if sums is None else sums
+        rc = self._f("refine")(self.ctx, self.h, _pd(pose7), _pd(ex_cam), float(sqrt_info), float(cauchy_scale), int(max_num_iterations), sums)
+        return rc, sums
+
+    def refine(self, pose7, ex_cam, sqrt_info=400.0, cauchy_scale=1.0, max_num_iterations=8):
+        """onlyLineOpt + removeLineOutlier on every table, in place. Returns one dict per table: summary, perf, status."""
+        p, e = _f64(pose7).reshape(self.W, NFRAMES, 7), _f64(ex_cam).reshape(self.W, 7)
+        rc, sums = self.refine_raw(p, e, sqrt_info, cauchy_scale, max_num_iterations)
+        if rc not in (OK, NO_CONVERGENCE, NUMERICAL_FAILURE):
+            raise RuntimeError("%sltab_refine failed with status %d" % (self.prefix, rc))
+        return [dict(summary=summary_to_dict(sums[w]), perf=summary_perf(sums[w]), status=rc) for w in range(self.W)]
+
+    def size(self):
+        n = np.zeros(self.W, np.int32)
+        self._check(self._f("size")(self.ctx, self.h, _pi(n)), "size")
+        return n
+
+    def line_count(self):
+        n = np.zeros(self.W, np.int32)
+        self._check(self._f("line_count")(self.ctx, self.h, _pi(n)), "line_count")
+        return n
+
+    def download(self, w=0):
+        n = int(self.size()[w])
+        out = dict(line_id=np.zeros(n, np.int32), start_frame=np.zeros(n, np.int32), n_obs=np.zeros(n, np.int32),
+                   obs4=np.zeros((n, NFRAMES, 4)), is_triangulation=np.zeros(n, np.uint8), line_plucker=np.zeros((n, 6)))
+        self._check(self._f("download")(self.ctx, self.h, int(w), _pi(out["line_id"]), _pi(out["start_frame"]), _pi(out["n_obs"]),
+                                        _pd(out["obs4"]), out["is_triangulation"].ctypes.data_as(PU8), _pd(out["line_plucker"])), "download")
+        return out
+
+    def upload(self, w, tab):
+        """Replaces table w by `tab` (the dict download() returns)."""
+        lid, sf, no = _i32(tab["line_id"]), _i32(tab["start_frame"]), _i32(tab["n_obs"])
+        ob, tri, plk = _f64(tab["obs4"]).reshape(-1, NFRAMES, 4), _u8(tab["is_triangulation"]), _f64(tab["line_plucker"]).reshape(-1, 6)
+        n = len(lid)
+        assert len(sf) == n and len(no) == n and len(ob) == n and len(tri) == n and len(plk) == n
+        self._check(self._f("upload")(self.ctx, self.h, int(w), n, _pi(lid), _pi(sf), _pi(no), _pd(ob), tri.ctypes.data_as(PU8), _pd(plk)), "upload")
+
+
+def ltab_to_line_window(tab, pose7, ex_cam):
+    """LineTables.download() -> the line-window dict LineWindowHolder / gfbe_line_refine take (observations packed in line order)."""
+    no = np.asarray(tab["n_obs"])
+    obs = np.concatenate([tab["obs4"][i, :no[i]] for i in range(len(no))]) if len(no) else np.zeros((0, 4))
+    return dict(start_frame=tab["start_frame"], n_obs=tab["n_obs"], obs=obs.reshape(-1, 4), is_triangulation=tab["is_triangulation"],
+                line_plucker=tab["line_plucker"], pose=np.asarray(pose7, float).reshape(NFRAMES, 7), ex_cam=np.asarray(ex_cam, float))

@@ -34,6 +34,9 @@ EXPORTS = [
     "gfbe_pg_eval", "gfbe_pg_solve", "gfbe_lio_linearize", "gfbe_batch_upload_tables", "gfbe_batch_feature_count",
     "gfbe_plane_eval", "gfbe_anchor_eval", "gfbe_orientation_subset_plus", "gfbe_gnss_eval",
     "gfbe_line_eval", "gfbe_line_refine",
+    "gfbe_ltab_create", "gfbe_ltab_destroy", "gfbe_ltab_add_frame", "gfbe_ltab_triangulate", "gfbe_ltab_remove_back_shift",
+    "gfbe_ltab_remove_back", "gfbe_ltab_remove_front", "gfbe_ltab_refine", "gfbe_ltab_size", "gfbe_ltab_line_count",
+    "gfbe_ltab_download", "gfbe_ltab_upload",
 ]
 
 
@@ -190,6 +193,13 @@ class Backend(abi.CApi):
         abi.LineWindowHolder): per window plucker [n][6] (ineligible lines unchanged), keep [n], summary."""
         try:
             return abi.line_refine(self.lib, "gfbe_", self.ctx, windows, sqrt_info, cauchy_scale, max_num_iterations)
+        except RuntimeError as e:
+            raise BackendError("%s: %s" % (e, self._err()))
+
+    def line_tables(self, n_tables=1, capacity=1024):
+        """W device-resident line tables (abi.LineTables: FeatureManager::linefeature and its per-frame operations, gfbe_ltab_*)."""
+        try:
+            return abi.LineTables(self.lib, "gfbe_", self.ctx, n_tables, capacity)
         except RuntimeError as e:
             raise BackendError("%s: %s" % (e, self._err()))
 

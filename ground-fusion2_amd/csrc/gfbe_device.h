@@ -420,14 +420,39 @@ void launch_ftab_count(const FtabDev &T, int cur, int w0, int n, int *counts, hi
 // bases, NPAIR + 1 pair_begin, lm_off); slot_of [n][F] receives the slot of landmark k (list order) for the download
 void launch_ftab_pack(const FtabDev &T, int cur, int w0, int n, const BatchDev &d, const int *layout, int *slot_of, hipStream_t s);
 
+
+// ---- device-resident line tables (gfbe_ltab.hip) and the table-fed line refinement (k_line_refine<true>, gfbe_line.hip)
+enum { LT_NOBS = GFBE_WINDOW_SIZE + 1 };
+struct LtabDev {
+  int W, F;                    // tables, capacity (lines per table)
+  int *count;                  // [W]
+  int *id[2], *start[2], *nobs[2];       // [W][F], ping-pong halves
+  unsigned char *tri[2];       // [W][F] is_triangulation
+  double *plk[2];              // [W][F][6] line_plucker (zeros until triangulated)
+  double *obs[2];              // [W][F][LT_NOBS][4] lineobs
+  int *keep, *dst;             // [W][F] scratch of an erasure: survivor code / destination in the other half
+  int *cnt_scratch;            // [W] lines before the erasure
+  int *err;                    // [W] sticky error flags (capacity / more than LT_NOBS observations)
+  double *row, *plk_out;       // refine scratch: [W][F][line_refine_row_doubles()], [W][F][6]
+  unsigned char *rkeep;        // [W][F] keep flags of the refine
+};
+// one half of the tables as k_line_refine<true> reads it
+struct LineTabView {
+  const int *count, *start, *nobs;
+  const unsigned char *tri;
+  const double *plk, *obs;
+  int F;
+};
+size_t line_refine_row_doubles();
+void launch_line_refine_tables(const LineTabView &T, int n_tables, const double *pose7, const double *ex_cam, double sqrt_info, double cauchy,
+                               int max_it, double *row, double *plk_out, unsigned char *keep, gfbe_summary *sum, hipStream_t s);
+
 }  // namespace gfd
 
-struct gfbe_ftab {
-  gfd::FtabDev d;
-  int cur = 0;
-  std::vector<void *> allocs;
-  // argument staging of the table operations: one device chunk + its pinned host mirror, grown on demand and kept (a
-  // hipMalloc / hipFree pair per argument cost more than the kernels: 0.4 ms per call measured)
+// argument staging of the table operations (gfbe_ftab, gfbe_ltab; used through gfd::Staged, gfbe_tabstage.h)
+struct gfbe_tab_staging {
+  // one device chunk + its pinned host mirror, grown on demand and kept (a hipMalloc / hipFree pair per argument cost more than the
+  // kernels: 0.4 ms per call measured)
   char *stage_d = nullptr, *stage_h = nullptr;
   size_t stage_cap = 0;
   // the operations that return nothing (triangulate, setDepth, the erasing ones) do not wait for the device: their arguments go
@@ -437,9 +462,21 @@ struct gfbe_ftab {
   hipEvent_t ring_ev[RING] = {};
   bool ring_used[RING] = {};
   int ring_next = 0;
+};
+
+struct gfbe_ftab : gfbe_tab_staging {
+  gfd::FtabDev d;
+  int cur = 0;
+  std::vector<void *> allocs;
   // gfbe_batch_upload_tables reads the tables on the context's COPY stream, beside the solves queued on the main one: it waits for
   // ev_ops (recorded on the main stream behind every table operation) and leaves ev_read behind its last reader; the next table
   // operation waits for that one (read_pending)
   hipEvent_t ev_ops = nullptr, ev_read = nullptr;
   bool read_pending = false;
+};
+
+struct gfbe_ltab : gfbe_tab_staging {
+  gfd::LtabDev d;
+  int cur = 0;
+  std::vector<void *> allocs;
 };

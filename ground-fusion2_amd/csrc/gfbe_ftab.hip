@@ -21,6 +21,7 @@
 
 #include "gfbe_device.h"
 #include "gfbe_math.h"
+#include "gfbe_tabstage.h"
 
 using namespace gfd;
 
@@ -31,21 +32,6 @@ constexpr int OW = FT_OW;       // x y z u v vx vy depth
 constexpr int FT_THREADS = 1024;
 
 enum { OP_BACK_SHIFT = 0, OP_BACK = 1, OP_FRONT = 2, OP_OUTLIER = 3, OP_FAILURES = 4 };
-
-__device__ __forceinline__ int block_exclusive_scan(int v, int *total, int *lds /* >= 17 ints */) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o, 64); if (lane >= o) x += y; }
-  if (lane == 63) lds[wave] = x;
-  __syncthreads();
-  if (t == 0) { int run = 0; for (int q = 0; q < FT_THREADS / 64; q++) { const int c = lds[q]; lds[q] = run; run += c; } lds[16] = run; }
-  __syncthreads();
-  const int excl = lds[wave] + x - v;
-  *total = lds[16];
-  __syncthreads();
-  return excl;
-}
 
 __device__ __forceinline__ vec3 mulR(const double *R, const vec3 &a) {   // row-major 3x3
   return mk3(R[0] * a[0] + R[1] * a[1] + R[2] * a[2], R[3] * a[0] + R[4] * a[1] + R[5] * a[2], R[6] * a[0] + R[7] * a[1] + R[8] * a[2]);
@@ -109,7 +95,7 @@ __global__ __launch_bounds__(FT_THREADS) void k_ftab_erase(FtabDev T, int cur, i
     survivors += k != 0;
   }
   int total;
-  int dst = block_exclusive_scan(survivors, &total, lds);
+  int dst = block_exclusive_scan<FT_THREADS>(survivors, &total, lds);
   int *dsti = T.ids_scratch + base;          // destination of feature f in the other buffer
   for (int f = f0; f < f1; f++) dsti[f] = keep[f] ? dst++ : -1;
   if (t == 0) { T.cnt_scratch[w] = n; T.count[w] = total; }
@@ -179,7 +165,7 @@ __global__ __launch_bounds__(FT_THREADS) void k_ftab_add(FtabDev T, int cur, con
   int fresh = 0;
   for (int a = a0; a < a1; a++) fresh += match[j0 + a] < 0;
   int total_new;
-  int dst = n + block_exclusive_scan(fresh, &total_new, lds);
+  int dst = n + block_exclusive_scan<FT_THREADS>(fresh, &total_new, lds);
   if (n + total_new > T.F) { if (t == 0) T.err[w] |= 1; total_new = 0; }
   int tracked = 0, longt = 0;
   for (int a = a0; a < a1; a++) {
@@ -246,7 +232,7 @@ __global__ __launch_bounds__(FT_THREADS) void k_ftab_depth(FtabDev T, int cur, i
   int used = 0;
   for (int f = f0; f < f1; f++) used += nobs[f] >= 4;
   int total;
-  int idx = block_exclusive_scan(used, &total, lds);
+  int idx = block_exclusive_scan<FT_THREADS>(used, &total, lds);
   for (int f = f0; f < f1; f++) {
     if (nobs[f] < 4) continue;
     if (mode == 1) { const double dd = 1.0 / x[offset[w] + idx]; depth[f] = dd; sflag[f] = dd < 0 ? 2 : 1; }
@@ -397,7 +383,7 @@ __global__ __launch_bounds__(FT_THREADS) void k_ftab_outliers(FtabDev T, int cur
     mine += bad;
   }
   int total;
-  int dst = block_exclusive_scan(mine, &total, lds);
+  int dst = block_exclusive_scan<FT_THREADS>(mine, &total, lds);
   // the flagged ids, compacted into LDS; the rank of an id among them is its position in the ascending output
   extern __shared__ int flagged[];
   for (int f = f0; f < f1; f++) if (keep[f]) flagged[dst++] = id[f];
@@ -450,7 +436,7 @@ __global__ __launch_bounds__(FT_THREADS) void k_ftab_landmarks(FtabDev T, int cu
   int mine = 0;
   for (int f = f0; f < f1; f++) mine += nobs[f] >= 4;
   int total;
-  int lidx = block_exclusive_scan(mine, &total, lds);
+  int lidx = block_exclusive_scan<FT_THREADS>(mine, &total, lds);
   // rank inside its bin in list order: RANKERS threads take contiguous pieces of the list and count their landmarks per bin
   // in LDS (bin-major), thread b scans bin b over the rankers, then every ranker numbers its own landmarks — three barriers
   // instead of one block scan per bin
@@ -552,79 +538,6 @@ gfbe_status ft_alloc(gfbe_ctx *c, gfbe_ftab *t, T **p, size_t n) {
   *p = (T *)q;
   return GFBE_OK;
 }
-// Host arguments of one table operation -> the table's staging chunk (one pinned host mirror, ONE host-to-device copy before
-// the launch, ONE device-to-host copy of the output range after it, one wait). `need` = upper bound of the staged bytes.
-// `defer`: an operation without outputs — its arguments go through a slot of the table's ring and nobody waits; every
-// operation runs on the context's stream, so whoever reads a result later (add_frame, check_outliers, size, the solver's
-// hand-over) sees the tables after it.
-struct Staged {
-  gfbe_ctx *c;
-  gfbe_ftab *t;
-  char *bh = nullptr, *bd = nullptr;
-  size_t cap = 0, off = 0, ulo = SIZE_MAX, uhi = 0, dlo = SIZE_MAX, dhi = 0;
-  int slot = -1;
-  bool ok = true;
-  struct Out { void *h; size_t off, bytes; };
-  std::vector<Out> outs;
-  Staged(gfbe_ctx *ctx, gfbe_ftab *tab, size_t need, bool defer = false) : c(ctx), t(tab) {
-    need += 4096;
-    if (defer && t->ring_d && need <= (size_t)gfbe_ftab::RING_SLOT) {
-      slot = t->ring_next;
-      t->ring_next = (slot + 1) % gfbe_ftab::RING;
-      if (t->ring_used[slot]) (void)hipEventSynchronize(t->ring_ev[slot]);
-      bh = t->ring_h + (size_t)slot * gfbe_ftab::RING_SLOT; bd = t->ring_d + (size_t)slot * gfbe_ftab::RING_SLOT; cap = gfbe_ftab::RING_SLOT;
-      return;
-    }
-    if (need > t->stage_cap) {
-      (void)hipStreamSynchronize(ctx_stream(c));
-      if (t->stage_d) (void)hipFree(t->stage_d);
-      if (t->stage_h) (void)hipHostFree(t->stage_h);
-      t->stage_d = t->stage_h = nullptr; t->stage_cap = 0;
-      const size_t ncap = std::max<size_t>(2 * need, (size_t)1 << 20);
-      if (hipMalloc((void **)&t->stage_d, ncap) != hipSuccess || hipHostMalloc((void **)&t->stage_h, ncap) != hipSuccess) { ok = false; return; }
-      t->stage_cap = ncap;
-    }
-    bh = t->stage_h; bd = t->stage_d; cap = t->stage_cap;
-  }
-  ~Staged() { finish(); }
-  template <typename T>
-  T *up(const T *h, size_t n) {
-    const size_t bytes = (std::max<size_t>(n, 1) * sizeof(T) + 255) & ~(size_t)255;
-    if (!ok || off + bytes > cap) { ok = false; return nullptr; }
-    if (h && n) { std::memcpy(bh + off, h, n * sizeof(T)); ulo = std::min(ulo, off); uhi = std::max(uhi, off + n * sizeof(T)); }
-    T *p = (T *)(bd + off);
-    off += bytes;
-    return p;
-  }
-  void flush() {   // before the launch
-    if (ok && uhi > ulo) (void)hipMemcpyAsync(bd + ulo, bh + ulo, uhi - ulo, hipMemcpyHostToDevice, ctx_stream(c));
-  }
-  template <typename T>
-  void down(T *h, const T *dptr, size_t n) {     // (operations with outputs are never deferred)
-    if (!h || !n || !ok || slot >= 0) return;
-    const char *p = (const char *)dptr;
-    if (p >= bd && p < bd + cap) {
-      const size_t o = (size_t)(p - bd);
-      outs.push_back({h, o, n * sizeof(T)});
-      dlo = std::min(dlo, o); dhi = std::max(dhi, o + n * sizeof(T));
-    } else {
-      (void)hipMemcpyAsync(h, dptr, n * sizeof(T), hipMemcpyDeviceToHost, ctx_stream(c));
-    }
-  }
-  void finish() {
-    if (slot >= 0) {     // deferred: mark the slot busy until the stream has passed this point
-      (void)hipEventRecord(t->ring_ev[slot], ctx_stream(c));
-      t->ring_used[slot] = true;
-      slot = -2;
-      return;
-    }
-    if (slot == -2 || !bh) return;
-    if (dhi > dlo) (void)hipMemcpyAsync(bh + dlo, bd + dlo, dhi - dlo, hipMemcpyDeviceToHost, ctx_stream(c));
-    (void)hipStreamSynchronize(ctx_stream(c));
-    for (const Out &o : outs) std::memcpy(o.h, bh + o.off, o.bytes);
-    outs.clear(); dlo = SIZE_MAX; dhi = 0;
-  }
-};
 gfbe_status ft_ready(gfbe_ctx *c, gfbe_ftab *t) {
   if (!c || !t) return GFBE_BAD_INPUT;
   if (ctx_device(c) < 0) return GFBE_NO_DEVICE;

@@ -63,9 +63,15 @@ __global__ __launch_bounds__(256) void k_line_eval(int n, const double *pose, co
   cost_part[k] = c;       // summed in factor order on the host
 }
 
+// The lines of a batch of windows. Host-fed (gfbe_line_refine, TAB = false): a CSR description packed by the host. Table-fed
+// (gfbe_ltab_refine, TAB = true): the device-resident line tables read IN PLACE — window w owns lines [w F, w F + count[w]), line l has
+// nobs[l] observations in its fixed row of GFBE_NFRAMES slots (obs + 4 GFBE_NFRAMES l). No scan, no compaction: a line's observations are
+// contiguous either way, so the kernel walks the same values in the same order and the arithmetic is the same instruction for instruction.
 struct LineBatch {
-  const int *line_off;          // [n_windows + 1]
-  const int *obs_off;           // [n_lines + 1] (over the whole batch)
+  const int *line_off;          // [n_windows + 1]                          (host-fed)
+  const int *obs_off;           // [n_lines + 1] (over the whole batch)     (host-fed)
+  const int *count, *nobs;      // [n_windows], [n_windows][F]              (table-fed)
+  int F;                        // line capacity of a table                 (table-fed)
   const int *start;             // [n_lines]
   const unsigned char *tri;     // [n_lines]
   const double *plk_in;         // [n_lines][6]
@@ -80,19 +86,27 @@ struct LineBatch {
   gfbe_summary *sum;            // [n_windows]
 };
 
+template <bool TAB>
+__device__ __forceinline__ int line_nobs(const LineBatch &P, int l) { return TAB ? P.nobs[l] : P.obs_off[l + 1] - P.obs_off[l]; }
+template <bool TAB>
+__device__ __forceinline__ const double *line_obs(const LineBatch &P, int l) {
+  return P.obs + 4 * (TAB ? (size_t)l * GFBE_NFRAMES : (size_t)P.obs_off[l]);
+}
+template <bool TAB>
 __device__ __forceinline__ bool line_eligible(const LineBatch &P, int l) {
-  return P.obs_off[l + 1] - P.obs_off[l] >= 5 && P.start[l] < GFBE_WINDOW_SIZE - 2 && P.tri[l];   // LINE_MIN_OBS, WINDOW_SIZE - 2
+  return line_nobs<TAB>(P, l) >= 5 && P.start[l] < GFBE_WINDOW_SIZE - 2 && P.tri[l];   // LINE_MIN_OBS, WINDOW_SIZE - 2
 }
 
 // cost of line l at x; with H, g: its Cauchy-corrected normal-equation block and gradient
-template <bool LIN>
+template <bool LIN, bool TAB>
 __device__ double line_lin(const LineBatch &P, int l, const double *x, const LineRT *Bs, const LineRT &Ex, double *H, double *g) {
   double cost = 0.0;
   if (LIN) { for (int q = 0; q < 16; q++) H[q] = 0.0; for (int q = 0; q < 4; q++) g[q] = 0.0; }
-  const int s = P.start[l], o0 = P.obs_off[l], o1 = P.obs_off[l + 1];
-  for (int o = o0; o < o1; o++) {
+  const int s = P.start[l], m = line_nobs<TAB>(P, l);
+  const double *ob = line_obs<TAB>(P, l);
+  for (int k = 0; k < m; k++) {
     double r[2], Jo[8];
-    line_factor<LIN>(Bs[s + o - o0], Ex, x, P.obs + 4 * (size_t)o, P.sqrt_info, r, nullptr, nullptr, LIN ? Jo : nullptr);
+    line_factor<LIN>(Bs[s + k], Ex, x, ob + 4 * k, P.sqrt_info, r, nullptr, nullptr, LIN ? Jo : nullptr);
     double sr;
     cost += line_cauchy(r[0] * r[0] + r[1] * r[1], P.cauchy, &sr);
     if (LIN) {
@@ -157,13 +171,14 @@ __device__ bool chol4_solve(double *A, const double *b, double *y) {
   return true;
 }
 
+template <bool TAB>
 __global__ __launch_bounds__(LR_THREADS) void k_line_refine(LineBatch P) {
   const int w = blockIdx.x, t = threadIdx.x;
   __shared__ LineRT Bs[GFBE_NFRAMES], Cw[GFBE_NFRAMES];
   __shared__ LineRT Ex;
   __shared__ double sh[4][LR_WAVES];
   __shared__ double red[4];
-  const int l0 = P.line_off[w], l1 = P.line_off[w + 1];
+  const int l0 = TAB ? w * P.F : P.line_off[w], l1 = TAB ? l0 + P.count[w] : P.line_off[w + 1];
   const uint64_t t_start = wall_clock64();
   if (t < GFBE_NFRAMES) Bs[t] = line_make_pose(P.pose + (size_t)w * 77 + 7 * t);
   if (t == GFBE_NFRAMES) Ex = line_make_pose(P.ex + (size_t)w * 7);
@@ -171,7 +186,7 @@ __global__ __launch_bounds__(LR_THREADS) void k_line_refine(LineBatch P) {
   if (t < GFBE_NFRAMES) { Cw[t].R = mul(Bs[t].R, Ex.R); Cw[t].t = add(Bs[t].t, mv(Bs[t].R, Ex.t)); }   // Rwc = Rs ric, twc = Ps + Rs tic
   // eligibility count
   double ne = 0.0;
-  for (int l = l0 + t; l < l1; l += LR_THREADS) ne += line_eligible(P, l) ? 1.0 : 0.0;
+  for (int l = l0 + t; l < l1; l += LR_THREADS) ne += line_eligible<TAB>(P, l) ? 1.0 : 0.0;
   lr_reduce(0.0, ne, 0.0, 0.0, false, sh, red);
   const int n_elig = (int)red[1];
   // the loop's scalars live in every thread (the same values everywhere); its per-iteration record in LDS, written by thread 0
@@ -190,12 +205,12 @@ __global__ __launch_bounds__(LR_THREADS) void k_line_refine(LineBatch P) {
   // entry: para_LineFeature = plk_to_orth(plk_to_pose(line_plucker, Rwc, twc)) of the start frame; the first linearisation
   double c = 0.0, x2 = 0.0, gm = 0.0;
   for (int l = l0 + t; l < l1; l += LR_THREADS) {
-    if (!line_eligible(P, l)) continue;
+    if (!line_eligible<TAB>(P, l)) continue;
     double *row = P.row + (size_t)l * LR_ROW, lw[6];
     const int s = P.start[l];
     line_plk_to_pose(P.plk_in + 6 * (size_t)l, Cw[s].R, Cw[s].t, lw);
     line_plk_to_orth(lw, row + LX);
-    c += line_lin<true>(P, l, row + LX, Bs, Ex, row + LH, row + LG);
+    c += line_lin<true, TAB>(P, l, row + LX, Bs, Ex, row + LH, row + LG);
     for (int a = 0; a < 4; a++) { x2 += row[LX + a] * row[LX + a]; row[LS + a] = 1.0 / (1.0 + sqrt(row[LH + 5 * a])); }
     gm = fmax(gm, line_grad_norm(row + LX, row + LG));
   }
@@ -216,7 +231,7 @@ __global__ __launch_bounds__(LR_THREADS) void k_line_refine(LineBatch P) {
     // every line: scaled system, LM diagonal, 4 x 4 solve, model cost change, candidate
     double fail = 0.0, mc = 0.0, st2 = 0.0, cx2 = 0.0;
     for (int l = l0 + t; l < l1; l += LR_THREADS) {
-      if (!line_eligible(P, l)) continue;
+      if (!line_eligible<TAB>(P, l)) continue;
       double *row = P.row + (size_t)l * LR_ROW;
       double Hs[16], A[16], rhs[4], y[4];
       for (int a = 0; a < 4; a++) {
@@ -250,7 +265,7 @@ __global__ __launch_bounds__(LR_THREADS) void k_line_refine(LineBatch P) {
     invalid = 0;
     double cc = 0.0;
     for (int l = l0 + t; l < l1; l += LR_THREADS)
-      if (line_eligible(P, l)) cc += line_lin<false>(P, l, P.row + (size_t)l * LR_ROW + LC, Bs, Ex, nullptr, nullptr);
+      if (line_eligible<TAB>(P, l)) cc += line_lin<false, TAB>(P, l, P.row + (size_t)l * LR_ROW + LC, Bs, Ex, nullptr, nullptr);
     lr_reduce(0.0, cc, 0.0, 0.0, false, sh, red);
     const double cand_cost = red[1];
     record(it, 0, cost);
@@ -265,10 +280,10 @@ __global__ __launch_bounds__(LR_THREADS) void k_line_refine(LineBatch P) {
       decrease = 2.0; reuse = false;
       double g2 = 0.0;
       for (int l = l0 + t; l < l1; l += LR_THREADS) {
-        if (!line_eligible(P, l)) continue;
+        if (!line_eligible<TAB>(P, l)) continue;
         double *row = P.row + (size_t)l * LR_ROW;
         for (int a = 0; a < 4; a++) row[LX + a] = row[LC + a];
-        (void)line_lin<true>(P, l, row + LX, Bs, Ex, row + LH, row + LG);
+        (void)line_lin<true, TAB>(P, l, row + LX, Bs, Ex, row + LH, row + LG);
         g2 = fmax(g2, line_grad_norm(row + LX, row + LG));
       }
       lr_reduce(g2, 0.0, 0.0, 0.0, true, sh, red);
@@ -281,23 +296,24 @@ __global__ __launch_bounds__(LR_THREADS) void k_line_refine(LineBatch P) {
   // exit: setLineOrth (line_plucker = plk_from_pose(orth_to_plk(orth), Rwc, twc)), then removeLineOutlier on the written-back lines
   for (int l = l0 + t; l < l1; l += LR_THREADS) {
     double *out = P.plk_out + 6 * (size_t)l;
-    if (!line_eligible(P, l)) {
+    if (!line_eligible<TAB>(P, l)) {
       for (int a = 0; a < 6; a++) out[a] = P.plk_in[6 * (size_t)l + a];
       P.keep[l] = 1;
       continue;
     }
-    const int s = P.start[l], o0 = P.obs_off[l], o1 = P.obs_off[l + 1];
+    const int s = P.start[l], m = line_nobs<TAB>(P, l);
+    const double *ob = line_obs<TAB>(P, l);
     double lw[6];
     line_orth_to_plk(P.row + (size_t)l * LR_ROW + LX, lw);
     line_plk_from_pose(lw, Cw[s].R, Cw[s].t, out);
     unsigned char keep = 1;
-    if (line_endpoints_bad(out, P.obs + 4 * (size_t)o0)) {
+    if (line_endpoints_bad(out, ob)) {
       keep = 0;
     } else {
       line_plk_to_pose(out, Cw[s].R, Cw[s].t, lw);
       double allerr = 0.0;
-      for (int o = o0; o < o1; o++) {
-        const double err = line_reprojection_error(P.obs + 4 * (size_t)o, Cw[s + o - o0].R, Cw[s + o - o0].t, lw);
+      for (int k = 0; k < m; k++) {
+        const double err = line_reprojection_error(ob + 4 * k, Cw[s + k].R, Cw[s + k].t, lw);
         if (allerr < err) allerr = err;
       }
       if (allerr > 3.0 / 500.0) keep = 0;
@@ -321,6 +337,18 @@ __global__ __launch_bounds__(LR_THREADS) void k_line_refine(LineBatch P) {
   } while (0)
 
 }  // namespace
+
+namespace gfd {
+size_t line_refine_row_doubles() { return LR_ROW; }
+void launch_line_refine_tables(const LineTabView &T, int n_tables, const double *pose7, const double *ex_cam, double sqrt_info, double cauchy,
+                               int max_it, double *row, double *plk_out, unsigned char *keep, gfbe_summary *sum, hipStream_t s) {
+  LineBatch P{};
+  P.count = T.count; P.nobs = T.nobs; P.F = T.F; P.start = T.start; P.tri = T.tri; P.plk_in = T.plk; P.obs = T.obs;
+  P.pose = pose7; P.ex = ex_cam; P.sqrt_info = sqrt_info; P.cauchy = cauchy; P.max_it = std::min(max_it, 15);
+  P.row = row; P.plk_out = plk_out; P.keep = keep; P.sum = sum;
+  hipLaunchKernelGGL(k_line_refine<true>, dim3(n_tables), dim3(LR_THREADS), 0, s, P);
+}
+}  // namespace gfd
 
 extern "C" gfbe_status gfbe_line_eval(gfbe_ctx *c, int32_t n, const double *pose, const double *ex_cam, const double *orth, const double *obs,
                                       double sqrt_info, int32_t robustify, double *r, double *J_pose, double *J_ex, double *J_orth,
@@ -416,7 +444,7 @@ extern "C" gfbe_status gfbe_line_refine(gfbe_ctx *c, int32_t n_windows, const gf
   std::vector<double> h_out((size_t)6 * n_lines);
   std::vector<unsigned char> h_keep(std::max(n_lines, 1));
   std::vector<gfbe_summary> h_sum(n_windows);
-  LineBatch P;
+  LineBatch P{};
   LN_CHECK(c, hipMalloc((void **)&d, up8(b_int) + up8(b_dbl) + up8(b_row) + up8(b_out) + up8(b_sum) + up8(b_tri) + up8(b_tri)));
   {
     char *p = d;
@@ -435,7 +463,7 @@ extern "C" gfbe_status gfbe_line_refine(gfbe_ctx *c, int32_t n_windows, const gf
     LN_CHECK(c, hipMemcpyAsync(d_dbl, dbl.data(), b_dbl, hipMemcpyHostToDevice, s));
     LN_CHECK(c, hipMemcpyAsync(d_tri, h_tri.data(), b_tri, hipMemcpyHostToDevice, s));
   }
-  hipLaunchKernelGGL(k_line_refine, dim3(n_windows), dim3(LR_THREADS), 0, s, P);
+  hipLaunchKernelGGL(k_line_refine<false>, dim3(n_windows), dim3(LR_THREADS), 0, s, P);
   LN_CHECK(c, hipGetLastError());
   if (n_lines) {
     LN_CHECK(c, hipMemcpyAsync(h_out.data(), P.plk_out, b_out, hipMemcpyDeviceToHost, s));

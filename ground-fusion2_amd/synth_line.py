@@ -115,3 +115,71 @@ def line_window(seed=0, n_ok=40, n_short=3, n_late=3, n_untri=2, n_behind=1, n_l
 
 def eligible(lw):
     return (lw["n_obs"] >= LINE_MIN_OBS) & (lw["start_frame"] < WINDOW_SIZE - 2) & (lw["is_triangulation"] != 0)
+
+
+class LineStream:
+    """Frame-by-frame line observations for the line tables (gfbe_ltab_*): a camera rig driving forward with a slow yaw past 3-D
+    segments scattered along its route. Segment k has the line id k; it is observed in a frame when both its endpoints are in front of
+    the camera, inside the field of view and nearer than `max_range`, and the frame lies inside the segment's own life span (a tracker
+    that loses and never re-finds a line) — so ids appear and disappear. noise = 0 gives exact projections of the full segment;
+    otherwise a random part of the segment is projected and perturbed by `noise` (normalised image units), as in line_window().
+
+      pose7(g) -> [p | q(x, y, z, w)] of global frame g;  frame(g) -> (line_id [n] ascending int32, obs4 [n][4])
+      endpoints(k) -> the two 3-D endpoints of segment k in the world;  ex_cam: [tic | q(ric)]
+    """
+
+    def __init__(self, seed=0, n_frames=40, n_segments=120, noise=0.5 / 460.0, step=0.4, max_range=14.0):
+        rng = np.random.default_rng(seed)
+        self.n_frames, self.noise, self.max_range = n_frames, noise, max_range
+        self.ex_cam = np.concatenate([T_BC, _quat_xyzw(R_BC)])
+        yaw0, p0 = rng.uniform(-np.pi, np.pi), rng.normal(0, 5, 3)
+        self.R, self.P = [], []
+        p = p0.copy()
+        for g in range(n_frames):
+            R = _rotz(yaw0 + 0.012 * g + 0.003 * rng.normal())
+            p = p + R @ np.array([step, 0.0, 0.0]) + rng.normal(0, 0.01, 3)
+            self.R.append(R)
+            self.P.append(p.copy())
+        self.A, self.B, self.life = [], [], []
+        for k in range(n_segments):
+            g = int(rng.integers(0, n_frames))                      # the frame the segment is placed ahead of
+            fwd, left, up = self.R[g][:, 0], self.R[g][:, 1], np.array([0.0, 0.0, 1.0])
+            c = self.P[g] + fwd * rng.uniform(4.0, 10.0) + left * rng.uniform(-3.0, 3.0) + up * rng.uniform(-1.0, 2.0)
+            d = rng.normal(size=3)
+            d /= np.linalg.norm(d)
+            half = rng.uniform(0.4, 1.2)
+            self.A.append(c - half * d)
+            self.B.append(c + half * d)
+            on = int(rng.integers(0, n_frames))
+            self.life.append((on if rng.random() < 0.5 else 0, n_frames if rng.random() < 0.6 else on + int(rng.integers(1, 14))))
+        self._rng_seed = seed
+
+    def pose7(self, g):
+        return np.concatenate([self.P[g], _quat_xyzw(self.R[g])])
+
+    def endpoints(self, k):
+        return self.A[k], self.B[k]
+
+    def frame(self, g):
+        rng = np.random.default_rng([self._rng_seed, 7919, g])       # (a frame's observations do not depend on which frames were asked for before)
+        Rwc, twc = self.R[g] @ R_BC, self.P[g] + self.R[g] @ T_BC
+        ids, obs = [], []
+        for k in range(len(self.A)):
+            if not (self.life[k][0] <= g < self.life[k][1]):
+                continue
+            A, B = self.A[k], self.B[k]
+            if self.noise > 0:
+                a, b = np.sort(rng.uniform(0.0, 1.0, 2))
+                a, b = 0.3 * a, 0.7 + 0.3 * b
+                A, B = self.A[k] + a * (self.B[k] - self.A[k]), self.A[k] + b * (self.B[k] - self.A[k])
+            pa, pb = Rwc.T @ (A - twc), Rwc.T @ (B - twc)
+            if min(pa[2], pb[2]) < 0.5 or max(pa[2], pb[2]) > self.max_range:
+                continue
+            o = np.array([pa[0] / pa[2], pa[1] / pa[2], pb[0] / pb[2], pb[1] / pb[2]])
+            if np.abs(o[[0, 2]]).max() > 1.0 or np.abs(o[[1, 3]]).max() > 0.8:
+                continue
+            if self.noise > 0:
+                o = o + rng.normal(0, self.noise, 4)
+            ids.append(k)
+            obs.append(o)
+        return np.array(ids, np.int32), np.array(obs, float).reshape(-1, 4)

@@ -629,6 +629,65 @@ gfbe_status gfbe_line_refine(gfbe_ctx *ctx, int32_t n_windows, const gfbe_line_w
                              gfbe_summary *summary);
 
 /* ------------------------------------------------------------------------------------------
+ * Line feature tables: FeatureManager::linefeature on the device, and the line calls of a use_line frame against it
+ *   addFeatureCheckParallaxwithline -> triangulateLine -> onlyLineOpt (+ removeLineOutlier) -> [optimizationwithLine on the CPU]
+ *   -> slideWindow (removeBackShiftDepthline / removeBackline / removeFrontline)      estimator.cpp:1426-1438, 3859-3899
+ * A gfbe_ltab holds W independent tables in HBM, one per window; every call applies one operation to all W tables, per-table arguments
+ * are arrays of length W. A table is std::list<lineFeaturePerId> in insertion order — the order that defines the line index of
+ * getLineOrthVector / setLineOrth / para_LineFeature[]. Per line: feature_id, start_frame, n_obs (<= GFBE_NFRAMES), the observations
+ * lineobs [x1 y1 x2 y2] (observation k is in frame start_frame + k), is_triangulation and line_plucker[6] in the start frame's camera
+ * frame. line_plucker of a line that was never triangulated is uninitialised memory in the reference (feature_manager.h:139-145); the
+ * table holds zeros there. removed_cnt / all_obs_cnt / ptw1 / ptw2 / line_plk_init are only ever printed by the reference and are not
+ * kept. Erasures keep the order.
+ * Pose arguments as in the point tables: poses [W][11][12] = [P(3) | R(9, row-major)], tic_ric [W][12] — except gfbe_ltab_refine, which
+ * takes the quaternion forms of gfbe_line_window so that it agrees with gfbe_line_refine bit for bit.
+ * Every operation runs in order on the context's stream. The ones without outputs (triangulate, remove_*) copy their arguments and
+ * return without waiting for the device; the ones that hand something back (add_frame, refine, size, line_count, download) and upload
+ * wait for what was enqueued before them. Capacity / observation overflow is raised by gfbe_ltab_add_frame (GFBE_BAD_INPUT, sticky). A
+ * device error of a deferred operation is reported by the next call that synchronises. gfbe_ltab_create leaves *out null and frees
+ * what it had allocated when it fails; without a device every call returns GFBE_NO_DEVICE. line_capacity <= 16384 lines per table.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct gfbe_ltab gfbe_ltab;
+gfbe_status gfbe_ltab_create(gfbe_ctx *ctx, int32_t n_tables, int32_t line_capacity, gfbe_ltab **out);
+void gfbe_ltab_destroy(gfbe_ctx *ctx, gfbe_ltab *t);
+/* Line loop of addFeatureCheckParallaxwithline (feature_manager.cpp:149-170). Table w receives the lines [offset[w], offset[w+1]) —
+ * ascending line_id, the iteration order of the reference's std::map — with observations obs4 [x1 y1 x2 y2]. A known id gets the
+ * observation appended; an unknown id becomes a new line at the end of the list with start_frame = frame_count[w], not triangulated.
+ * counters_out [W][2] = [tracked, new] (may be NULL). The keyframe decision is gfbe_ftab_add_frame's: lines take no part in it. */
+gfbe_status gfbe_ltab_add_frame(gfbe_ctx *ctx, gfbe_ltab *t, const int32_t *frame_count, const int32_t *offset,
+                                const int32_t *line_id, const double *obs4, int32_t *counters_out);
+/* triangulateLine (feature_manager.cpp:1151-1262): every line with n_obs >= LINE_MIN_OBS (5), start_frame < WINDOW_SIZE - 2 that is
+ * not yet triangulated: the plane through the start observation and the camera centre is intersected with the plane of the later
+ * observation whose normal makes the SMALLEST cosine with it (strict <, the first wins); skipped while that cosine is above 0.998.
+ * line_plucker = pipi_plk(pi_i, pi_j), not normalised. */
+gfbe_status gfbe_ltab_triangulate(gfbe_ctx *ctx, gfbe_ltab *t, const double *poses, const double *tic_ric);
+/* Line loop of removeBackShiftDepthline (feature_manager.cpp:1499-1527), applied ONCE per call (the reference nests it inside the
+ * loop over the point features — a misplaced brace): start_frame != 0 is decremented; otherwise observation 0
+ * is dropped, the line is erased when fewer than 2 are left, and else line_plucker moves into the new start frame,
+ * plk_to_pose(line_plucker, new_R^T marg_R, new_R^T (marg_P - new_P)). *_PR = [W][12]. */
+gfbe_status gfbe_ltab_remove_back_shift(gfbe_ctx *ctx, gfbe_ltab *t, const double *marg_PR, const double *new_PR);
+/* Line loops of removeBackline (:896-911, erases at 0 observations left) and removeFrontline (:958-975). */
+gfbe_status gfbe_ltab_remove_back(gfbe_ctx *ctx, gfbe_ltab *t);
+gfbe_status gfbe_ltab_remove_front(gfbe_ctx *ctx, gfbe_ltab *t, const int32_t *frame_count);
+/* onlyLineOpt() + removeLineOutlier(Ps, tic, ric) on every table, what gfbe_line_refine does for host lists, without leaving the
+ * device: refined lines are written back, culled lines erased in order, ineligible lines untouched; a table with fewer than 4 eligible
+ * lines stays as it was (summary.termination = 5). pose7 [W][11][7], ex_cam [W][7] = [p | q(x, y, z, w)] as in gfbe_line_window: with
+ * the same pose bits the result equals gfbe_line_refine's bit for bit. summary [W]; return value: the worst summary status. */
+gfbe_status gfbe_ltab_refine(gfbe_ctx *ctx, gfbe_ltab *t, const double *pose7, const double *ex_cam, double sqrt_info,
+                             double cauchy_scale, int32_t max_num_iterations, gfbe_summary *summary);
+/* linefeature.size() and getLineFeatureCount() (feature_manager.cpp:1013-1027) of every table. */
+gfbe_status gfbe_ltab_size(gfbe_ctx *ctx, gfbe_ltab *t, int32_t *n_lines);
+gfbe_status gfbe_ltab_line_count(gfbe_ctx *ctx, gfbe_ltab *t, int32_t *count);
+/* Snapshot of table w in list order; obs4 [n][11][4] (rows >= n_obs are zero), line_plucker [n][6]. Any pointer may be NULL. With it
+ * the caller builds the gfbe_line_window of gfbe_line_refine and feeds the CPU's optimizationwithLine(). */
+gfbe_status gfbe_ltab_download(gfbe_ctx *ctx, gfbe_ltab *t, int32_t w, int32_t *line_id, int32_t *start_frame, int32_t *n_obs,
+                               double *obs4, uint8_t *is_triangulation, double *line_plucker);
+/* Replaces table w by n lines in the layout of gfbe_ltab_download (what optimizationwithLine()'s setLineOrth and culling left on the
+ * host goes back in). n <= line_capacity, 1 <= n_obs, start_frame + n_obs <= GFBE_NFRAMES. */
+gfbe_status gfbe_ltab_upload(gfbe_ctx *ctx, gfbe_ltab *t, int32_t w, int32_t n, const int32_t *line_id, const int32_t *start_frame,
+                             const int32_t *n_obs, const double *obs4, const uint8_t *is_triangulation, const double *line_plucker);
+
+/* ------------------------------------------------------------------------------------------
  * a4/a5/a7/a9/a10  Factor evaluation on the device, block-CSR output (parity / inspection API).
  * Each evaluates residuals and TANGENT-space Jacobian blocks at the window's current state,
  * exactly what ceres::CostFunction::Evaluate + the manifold lift produce:

@@ -3,51 +3,104 @@ _r = _os.path.dirname(_os.path.abspath(__file__))
 while not _os.path.exists(_os.path.join(_r, "_gfbe_import.py")):
     _r = _os.path.dirname(_r)
 _sys.path[:0] = [_r, _os.path.join(_r, "tests")]   # (measurement scripts: the package root and the test helpers they share)
-"""Timing of gfbe_line_refine (onlyLineOpt + removeLineOutlier on the device): one window and batches of 256 / 1024 / 4096 windows of
-150 eligible lines with 5-11 observations each (NUM_ITERATIONS = 8), and the numpy checker (tests/line_np.py) for scale.
-  call   the whole call on its stream, hipEvents around it: packing, copies both ways, the kernel (median of 5)
-  kernel the longest time one window spent in the kernel (gfbe_summary.ms_solve, device wall clock)
-  host   the call's wall clock on the host (median of 5)"""
+"""Timing of the line-only refinement (onlyLineOpt + removeLineOutlier on the device), host-fed against table-fed, on the same seeded
+windows: 150 eligible lines with 5-11 observations each (NUM_ITERATIONS = 8), for 1 / 256 / 1024 / 4096 windows.
+  host-fed   gfbe_line_refine: the whole list packed on the host and copied up on every call, lines and keep flags copied back
+  table-fed  gfbe_ltab_refine on device-resident line tables that already hold the same lines (re-seeded by upload outside the timed
+             region, since the refine edits the tables): only the poses go up and the summaries come down
+Both legs: the host's clock around the call, which ends synchronised; the legs alternate, REPS repetitions each after one warm-up of
+each; median and spread (max - min). kernel: the longest time one window spent in the kernel (gfbe_summary.ms_solve, device clock).
+The two legs' results are compared bit for bit once per size. Output: stdout, and the same lines into the file given with --out."""
+import argparse
 import time
 
 import numpy as np
-import torch
+import torch  # noqa: F401  (one ROCm runtime per process: torch's goes first)
 
 from _gfbe_import import gf
 import line_np as ln
 
 abi, synth_line = gf.abi, gf.synth_line
+REPS = 7
+
+
+def _table_of(lw, base_id=0):
+    n = len(lw["start_frame"])
+    off = np.concatenate([[0], np.cumsum(lw["n_obs"])]).astype(int)
+    obs4 = np.zeros((n, abi.NFRAMES, 4))
+    for i in range(n):
+        obs4[i, :lw["n_obs"][i]] = lw["obs"][off[i]:off[i + 1]]
+    return dict(line_id=np.arange(n, dtype=np.int32) + base_id, start_frame=lw["start_frame"], n_obs=lw["n_obs"], obs4=obs4,
+                is_triangulation=lw["is_triangulation"], line_plucker=lw["line_plucker"])
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--sizes", default="1,256,1024,4096")
+    args = ap.parse_args()
+    lines = []
+
+    def say(msg):
+        print(msg, flush=True)
+        lines.append(msg)
     be = gf.Backend(0)
-    stream = torch.cuda.Stream(device=0)
-    be.set_stream(stream.cuda_stream)
     base = [synth_line.line_window(seed=900 + k, n_ok=150, n_short=0, n_late=0, n_untri=0, n_behind=0, n_long=0, n_outlier=0)
             for k in range(32)]
     holders = [abi.LineWindowHolder(w) for w in base]
-    print("lines per window %d, observations per window %.0f (mean)" % (holders[0].n, np.mean([len(h.obs) for h in holders])))
-    for nw in (1, 256, 1024, 4096):
+    seeds = [_table_of(w) for w in base]
+    say("lines per window %d, observations per window %.0f (mean); %d repetitions per leg, alternating" %
+        (holders[0].n, np.mean([len(h.obs) for h in holders]), REPS))
+    for nw in [int(x) for x in args.sizes.split(",")]:
         hs = [holders[k % len(holders)] for k in range(nw)]
-        be.line_refine(hs)          # warm-up (module load, first allocation)
-        calls, hosts, kern = [], [], 0.0
-        for _ in range(5):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
+        n_lines = sum(h.n for h in hs)
+        plk, keep, sums_h = np.zeros((n_lines, 6)), np.zeros(n_lines, np.uint8), (abi.Summary * nw)()
+        tabs = be.line_tables(nw, 160)
+        pose7 = np.ascontiguousarray([base[k % len(base)]["pose"] for k in range(nw)])
+        ex = np.ascontiguousarray([base[k % len(base)]["ex_cam"] for k in range(nw)])
+        sums_t = (abi.Summary * nw)()
+
+        def reseed():
+            for w in range(nw):
+                tabs.upload(w, seeds[w % len(seeds)])
+        t_host, t_tab, k_host, k_tab = [], [], 0.0, 0.0
+        for rep in range(REPS + 1):          # (rep 0: warm-up of both legs — module load, first allocations, staging growth)
+            reseed()
             t0 = time.perf_counter()
-            out = be.line_refine(hs)
-            hosts.append(time.perf_counter() - t0)
-            e1.record(stream)
-            e1.synchronize()
-            calls.append(e0.elapsed_time(e1))
-            kern = max(o["perf"]["ms_solve"] for o in out)
-        call, host = sorted(calls)[2], sorted(hosts)[2] * 1e3
-        print("%5d windows: call %8.3f ms (%7.2f us / window), kernel %7.3f ms, host %8.3f ms, iterations %d" %
-              (nw, call, 1e3 * call / nw, kern, host, out[0]["summary"]["iterations"]))
+            rc = abi.line_refine_raw(be.lib, "gfbe_", be.ctx, hs, plucker_out=plk, keep_out=keep, summary=sums_h)[0]
+            t1 = time.perf_counter()
+            rc_t = tabs.refine_raw(pose7, ex, sums=sums_t)[0]
+            t2 = time.perf_counter()
+            assert rc == rc_t and rc in (abi.OK, abi.NO_CONVERGENCE), (rc, rc_t)
+            if rep:
+                t_host.append((t1 - t0) * 1e3)
+                t_tab.append((t2 - t1) * 1e3)
+                k_host = max(k_host, max(sums_h[w].ms_solve for w in range(nw)))
+                k_tab = max(k_tab, max(sums_t[w].ms_solve for w in range(nw)))
+        # the two legs computed the same thing (a few tables; tests/test_gpu_ltab.py compares all of them)
+        o = 0
+        for w in range(min(nw, 3)):
+            got = tabs.download(w)
+            k = keep[o:o + hs[w].n] != 0
+            assert got["line_plucker"].tobytes() == np.ascontiguousarray(plk[o:o + hs[w].n][k]).tobytes(), "table-fed != host-fed"
+            o += hs[w].n
+        tabs.close()
+
+        def stat(t):
+            return float(np.median(t)), float(max(t) - min(t))
+        (mh, sh), (mt, st) = stat(t_host), stat(t_tab)
+        say("%5d windows: host-fed %8.3f ms (spread %6.3f, kernel %6.3f) | table-fed %8.3f ms (spread %6.3f, kernel %6.3f) | "
+            "table-fed / host-fed %.3f, %7.2f -> %7.2f us / window, iterations %d" %
+            (nw, mh, sh, k_host, mt, st, k_tab, mt / mh, 1e3 * mh / nw, 1e3 * mt / nw, sums_t[0].iterations))
+        say("              host-fed  [%s]" % " ".join("%.3f" % t for t in t_host))
+        say("              table-fed [%s]" % " ".join("%.3f" % t for t in t_tab))
     t0 = time.perf_counter()
     for w in base[:4]:
         ln.refine(w)
-    print("numpy checker: %.1f ms / window" % ((time.perf_counter() - t0) / 4 * 1e3))
+    say("numpy checker: %.1f ms / window" % ((time.perf_counter() - t0) / 4 * 1e3))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
 
 
 if __name__ == "__main__":
