@@ -948,6 +948,74 @@ def line_refine(lib, prefix, ctx, windows, sqrt_info=400.0, cauchy_scale=1.0, ma
 
 
 # ---------------------------------------------------------------------------------------------
+# Reduced normal equations of the line factors (gfbe_line_reduce / gfbe_ltab_reduce)
+# ---------------------------------------------------------------------------------------------
+LINE_REDUCE_SOLVE, LINE_REDUCE_MARG_OLD, LINE_REDUCE_DIM = 0, 1, 72
+
+
+class LineReduced(C.Structure):
+    _fields_ = [("struct_size", c_i), ("reserved", c_i), ("H", PD), ("g", PD), ("U", PD), ("bp", PD), ("cost", PD), ("n_eligible", PI),
+                ("n_failed", PI), ("Vinv", PD), ("bl", PD), ("W", PD), ("failed", PU8), ("ms_kernel", PD)]
+
+
+LINE_REDUCE_KEYS = ("H", "g", "U", "bp", "cost", "n_eligible", "n_failed", "Vinv", "bl", "W", "failed", "ms_kernel")
+
+
+def line_reduced_buffers(n_windows, n_lines, want=LINE_REDUCE_KEYS, fill=0):
+    """Output arrays of a reduce call over n_windows windows with n_lines lines in all (the bound of the eligible ones)."""
+    D, W = LINE_REDUCE_DIM, n_windows
+    shapes = dict(H=((W, D, D), np.float64), g=((W, D), np.float64), U=((W, D, D), np.float64), bp=((W, D), np.float64),
+                  cost=((W,), np.float64), n_eligible=((W,), np.int32), n_failed=((W,), np.int32), Vinv=((n_lines, 4, 4), np.float64),
+                  bl=((n_lines, 4), np.float64), W=((n_lines, D, 4), np.float64), failed=((n_lines,), np.uint8),
+                  ms_kernel=((W, 2), np.float64))
+    return {k: np.full(shapes[k][0], fill, shapes[k][1]) for k in want}
+
+
+def line_reduced_struct(bufs):
+    """A gfbe_line_reduced over the arrays of `bufs` (absent keys: NULL). Keep `bufs` alive during the call."""
+    r = LineReduced()
+    r.struct_size = C.sizeof(LineReduced)
+    for k, a in bufs.items():
+        assert a.flags["C_CONTIGUOUS"]
+        setattr(r, k, a.ctypes.data_as(dict(LineReduced._fields_)[k]))
+    return r
+
+
+def _line_reduced_split(bufs):
+    """Per-window views of a reduce call's outputs; the per-line records are cut at the windows' n_eligible."""
+    ne = bufs["n_eligible"]
+    off = np.concatenate([[0], np.cumsum(ne)]).astype(int)
+    out = []
+    for w in range(len(ne)):
+        d = {}
+        for k, a in bufs.items():
+            d[k] = a[off[w]:off[w + 1]] if k in ("Vinv", "bl", "W", "failed") else a[w]
+        out.append(d)
+    return out
+
+
+def line_reduce_raw(lib, prefix, ctx, holders, mode, sqrt_info, huber_width, mu, red):
+    """gfbe_line_reduce over prebuilt LineWindowHolders into the LineReduced `red`; returns the status."""
+    arr = (C.POINTER(LineWindow) * max(len(holders), 1))(*[C.pointer(h.c) for h in holders])
+    f = getattr(lib, prefix + "line_reduce")
+    f.restype = c_i
+    f.argtypes = [C.c_void_p, c_i, C.POINTER(C.POINTER(LineWindow)), c_i, c_d, c_d, c_d, C.POINTER(LineReduced)]
+    return f(ctx, len(holders), arr, int(mode), float(sqrt_info), float(huber_width), float(mu), C.byref(red) if red is not None else None)
+
+
+def line_reduce(lib, prefix, ctx, windows, mode=LINE_REDUCE_SOLVE, sqrt_info=400.0, huber_width=1.0, mu=0.0, want=LINE_REDUCE_KEYS):
+    """Reduced normal equations of the line factors of each window (line-window dicts or LineWindowHolders). One dict per window:
+    H [72][72], g, U, bp, cost, n_eligible, n_failed, and the records Vinv, bl, W, failed of its eligible lines."""
+    holders = [w if isinstance(w, LineWindowHolder) else LineWindowHolder(w) for w in windows]
+    want = tuple(want) + tuple(k for k in ("n_eligible",) if k not in want)
+    bufs = line_reduced_buffers(len(holders), sum(h.n for h in holders), want)
+    rc = line_reduce_raw(lib, prefix, ctx, holders, mode, sqrt_info, huber_width, mu, line_reduced_struct(bufs))
+    if rc != OK:
+        raise RuntimeError("%sline_reduce failed with status %d" % (prefix, rc))
+    return _line_reduced_split(bufs)
+
+
+# ---------------------------------------------------------------------------------------------
 # Line feature tables (gfbe_ltab_*): FeatureManager::linefeature on the device
 # ---------------------------------------------------------------------------------------------
 class LineTables:
@@ -1012,6 +1080,24 @@ class LineTables:
         if rc not in (OK, NO_CONVERGENCE, NUMERICAL_FAILURE):
             raise RuntimeError("%sltab_refine failed with status %d" % (self.prefix, rc))
         return [dict(summary=summary_to_dict(sums[w]), perf=summary_perf(sums[w]), status=rc) for w in range(self.W)]
+
+    def reduce_raw(self, pose7, ex_cam, mode, sqrt_info, huber_width, mu, red):
+        """gfbe_ltab_reduce on prepared arrays (pose7 [W][11][7], ex_cam [W][7], float64, contiguous) into the LineReduced `red`."""
+        f = self._f("reduce")
+        f.restype = c_i
+        f.argtypes = [C.c_void_p, C.c_void_p, c_i, PD, PD, c_d, c_d, c_d, C.POINTER(LineReduced)]
+        return f(self.ctx, self.h, int(mode), _pd(pose7), _pd(ex_cam), float(sqrt_info), float(huber_width), float(mu),
+                 C.byref(red) if red is not None else None)
+
+    def reduce(self, pose7, ex_cam, mode=LINE_REDUCE_SOLVE, sqrt_info=400.0, huber_width=1.0, mu=0.0, want=LINE_REDUCE_KEYS):
+        """Reduced normal equations of the line factors of every table, read in place (abi.line_reduce's result per table)."""
+        p, e = _f64(pose7).reshape(self.W, NFRAMES, 7), _f64(ex_cam).reshape(self.W, 7)
+        want = tuple(want) + tuple(k for k in ("n_eligible",) if k not in want)
+        bufs = line_reduced_buffers(self.W, int(self.size().sum()), want)
+        rc = self.reduce_raw(p, e, mode, sqrt_info, huber_width, mu, line_reduced_struct(bufs))
+        if rc != OK:
+            raise RuntimeError("%sltab_reduce failed with status %d" % (self.prefix, rc))
+        return _line_reduced_split(bufs)
 
     def size(self):
         n = np.zeros(self.W, np.int32)

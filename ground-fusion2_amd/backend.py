@@ -33,7 +33,7 @@ EXPORTS = [
     "gfbe_ftab_triangulate", "gfbe_ftab_check_outliers", "gfbe_ftab_size", "gfbe_ftab_download", "gfbe_slide_window_state",
     "gfbe_pg_eval", "gfbe_pg_solve", "gfbe_lio_linearize", "gfbe_batch_upload_tables", "gfbe_batch_feature_count",
     "gfbe_plane_eval", "gfbe_anchor_eval", "gfbe_orientation_subset_plus", "gfbe_gnss_eval",
-    "gfbe_line_eval", "gfbe_line_refine",
+    "gfbe_line_eval", "gfbe_line_refine", "gfbe_line_reduce", "gfbe_ltab_reduce",
     "gfbe_ltab_create", "gfbe_ltab_destroy", "gfbe_ltab_add_frame", "gfbe_ltab_triangulate", "gfbe_ltab_remove_back_shift",
     "gfbe_ltab_remove_back", "gfbe_ltab_remove_front", "gfbe_ltab_refine", "gfbe_ltab_size", "gfbe_ltab_line_count",
     "gfbe_ltab_download", "gfbe_ltab_upload",
@@ -193,6 +193,15 @@ class Backend(abi.CApi):
         abi.LineWindowHolder): per window plucker [n][6] (ineligible lines unchanged), keep [n], summary."""
         try:
             return abi.line_refine(self.lib, "gfbe_", self.ctx, windows, sqrt_info, cauchy_scale, max_num_iterations)
+        except RuntimeError as e:
+            raise BackendError("%s: %s" % (e, self._err()))
+
+    def line_reduce(self, windows, mode=abi.LINE_REDUCE_SOLVE, sqrt_info=400.0, huber_width=1.0, mu=0.0, want=abi.LINE_REDUCE_KEYS):
+        """The line loops of optimizationwithLine() linearised and reduced onto the 72 pose / extrinsic dims (dims 0..71 of the dense
+        block): per window H [72][72], g, U, bp, cost, n_eligible, n_failed and the per-line records Vinv, bl, W, failed. For device-
+        resident tables: line_tables(...).reduce(...)."""
+        try:
+            return abi.line_reduce(self.lib, "gfbe_", self.ctx, windows, mode, sqrt_info, huber_width, mu, want)
         except RuntimeError as e:
             raise BackendError("%s: %s" % (e, self._err()))
 

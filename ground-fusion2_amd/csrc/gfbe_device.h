@@ -479,4 +479,6 @@ struct gfbe_ltab : gfbe_tab_staging {
   gfd::LtabDev d;
   int cur = 0;
   std::vector<void *> allocs;
+  char *reduce_d = nullptr;      // gfbe_ltab_reduce's scratch and output staging, kept between calls (gfbe_line_reduce.hip)
+  size_t reduce_cap = 0;
 };

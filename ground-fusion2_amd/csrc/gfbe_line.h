@@ -144,6 +144,116 @@ GF_HD void line_factor(const LineRT &B, const LineRT &E, const double *orth, con
   }
 }
 
+// ---- the line loops of optimizationwithLine (estimator.cpp:4566-4598, 4736-4771): per-line pieces of the reduced normal equations
+//      (csrc/gfbe_line_reduce.hip; compiled for the host by tests/line_reduce_host_shim.cpp)
+// ceres::HuberLoss(a): returns 1/2 rho(s), *sqrt_rho1 = sqrt(rho'(s)) (rho'' <= 0: the corrector scales r and J by it). a <= 0: no loss.
+GF_HD double line_huber(double s, double a, double *sqrt_rho1) {
+  const double b = a * a;
+  if (a > 0.0 && s > b) {
+    const double r = sqrt(s);
+    *sqrt_rho1 = sqrt(fmax(2.2250738585072014e-308, a / r));
+    return 0.5 * (2.0 * a * r - b);
+  }
+  *sqrt_rho1 = 1.0;
+  return 0.5 * s;
+}
+// V' = V + mu diag(clamp(diag V, 1e-6, 1e32)); Vinv = V'^-1 through the Cholesky factor (lower triangle computed, mirrored: symmetric
+// bit for bit). false: a pivot that is not positive and finite — Vinv is then not written.
+GF_HD bool line_chol4_inv(const double *V, double mu, double *Vinv) {
+  double L[16], M[16];
+  for (int q = 0; q < 16; q++) { L[q] = 0.0; M[q] = 0.0; }
+  for (int j = 0; j < 4; j++) {
+    double d = V[5 * j] + mu * fmin(fmax(V[5 * j], 1e-6), 1e32);
+    for (int k = 0; k < j; k++) d -= L[4 * j + k] * L[4 * j + k];
+    if (!(d > 0.0 && d <= 1.7976931348623157e308)) return false;
+    const double ljj = sqrt(d);
+    L[5 * j] = ljj;
+    for (int i = j + 1; i < 4; i++) {
+      double s = V[4 * i + j];
+      for (int k = 0; k < j; k++) s -= L[4 * i + k] * L[4 * j + k];
+      L[4 * i + j] = s / ljj;
+    }
+  }
+  for (int j = 0; j < 4; j++) {      // M = L^-1, column by column
+    M[5 * j] = 1.0 / L[5 * j];
+    for (int i = j + 1; i < 4; i++) {
+      double s = 0.0;
+      for (int k = j; k < i; k++) s -= L[4 * i + k] * M[4 * k + j];
+      M[4 * i + j] = s / L[5 * i];
+    }
+  }
+  for (int i = 0; i < 4; i++)        // Vinv = M^T M
+    for (int j = 0; j <= i; j++) {
+      double s = 0.0;
+      for (int k = i; k < 4; k++) s += M[4 * k + i] * M[4 * k + j];
+      Vinv[4 * i + j] = s; Vinv[4 * j + i] = s;
+    }
+  return true;
+}
+// One line with m observations in frames start .. start + m - 1, the first k0 of them skipped, at the world line `orth`:
+//   Wrow [72][4]: W_l = sum Jp^T Jl (rows 6 f .. 6 f + 5 of an observing pose f, rows 66 .. 71 the extrinsic, zero elsewhere)
+//   Jrec [m][LINE_JREC]: per observation r (2), Jp (2 x 6), Je (2 x 6) after the loss — what U and bp are summed from
+//   V'^-1 [4][4], bl [4], cost = sum 1/2 rho.   Returns false when V' has no Cholesky factor.
+enum { LINE_JREC = 26, LINE_NP = 72 };
+GF_HD bool line_reduce_line(const LineRT *Bs, const LineRT &Ex, const double *orth, int start, int k0, int m, const double *ob,
+                            double sqrt_info, double huber, double mu, double *Wrow, double *Jrec, double *Vinv, double *bl, double *cost) {
+  double V[16], b4[4], We[24], c = 0.0;
+  for (int q = 0; q < 16; q++) V[q] = 0.0;
+  for (int q = 0; q < 4; q++) b4[q] = 0.0;
+  for (int q = 0; q < 24; q++) We[q] = 0.0;
+  for (int q = 0; q < LINE_NP * 4; q++) Wrow[q] = 0.0;
+  for (int k = k0; k < m; k++) {
+    double r[2], Jp[14], Je[14], Jo[8], sr;
+    line_factor<true>(Bs[start + k], Ex, orth, ob + 4 * k, sqrt_info, r, Jp, Je, Jo);
+    c += line_huber(r[0] * r[0] + r[1] * r[1], huber, &sr);
+    double *rec = Jrec + (size_t)LINE_JREC * k;
+    rec[0] = r[0] = r[0] * sr; rec[1] = r[1] = r[1] * sr;
+    for (int i = 0; i < 2; i++)
+      for (int a = 0; a < 6; a++) {
+        rec[2 + 6 * i + a] = Jp[7 * i + a] = Jp[7 * i + a] * sr;
+        rec[14 + 6 * i + a] = Je[7 * i + a] = Je[7 * i + a] * sr;
+      }
+    for (int q = 0; q < 8; q++) Jo[q] *= sr;
+    double *Wp = Wrow + 24 * (start + k);
+    for (int a = 0; a < 4; a++) {
+      b4[a] += Jo[a] * r[0] + Jo[4 + a] * r[1];
+      for (int b = 0; b < 4; b++) V[4 * a + b] += Jo[a] * Jo[b] + Jo[4 + a] * Jo[4 + b];
+    }
+    for (int a = 0; a < 6; a++)
+      for (int b = 0; b < 4; b++) {
+        Wp[4 * a + b] = Jp[a] * Jo[b] + Jp[7 + a] * Jo[4 + b];
+        We[4 * a + b] += Je[a] * Jo[b] + Je[7 + a] * Jo[4 + b];
+      }
+  }
+  for (int q = 0; q < 24; q++) Wrow[4 * 66 + q] = We[q];
+  for (int q = 0; q < 4; q++) bl[q] = b4[q];
+  *cost = c;
+  return line_chol4_inv(V, mu, Vinv);
+}
+// Y = W V'^-1, one row
+GF_HD void line_Y_row(const double *w, const double *Vinv, double *y) {
+  for (int a = 0; a < 4; a++) y[a] = w[0] * Vinv[a] + w[1] * Vinv[4 + a] + w[2] * Vinv[8 + a] + w[3] * Vinv[12 + a];
+}
+
+// ---- a batch's line list as the kernels read it (k_line_refine, k_line_reduce). B: a structure with the members line_off, obs_off
+//      (host-fed CSR: TAB = false) or count, nobs, F (the line tables in place: TAB = true), and start, tri, obs for both.
+#if defined(__HIPCC__)
+enum { LINE_TAB_NOBS = 11, LINE_WINDOW = 10 };      // observation slots of a table row (WINDOW_SIZE + 1), WINDOW_SIZE
+#ifdef GFBE_NFRAMES      // (the kernels include gfbe_device.h first; the host shims of the tests do not know the ABI header)
+static_assert(LINE_TAB_NOBS == GFBE_NFRAMES && LINE_WINDOW == GFBE_WINDOW_SIZE, "gfbe_line.h: window constants differ from gfbe.h");
+#endif
+template <bool TAB, class B>
+__device__ __forceinline__ int line_nobs(const B &P, int l) { return TAB ? P.nobs[l] : P.obs_off[l + 1] - P.obs_off[l]; }
+template <bool TAB, class B>
+__device__ __forceinline__ const double *line_obs(const B &P, int l) {
+  return P.obs + 4 * (TAB ? (size_t)l * LINE_TAB_NOBS : (size_t)P.obs_off[l]);
+}
+template <bool TAB, class B>
+__device__ __forceinline__ bool line_eligible(const B &P, int l) {
+  return line_nobs<TAB>(P, l) >= 5 && P.start[l] < LINE_WINDOW - 2 && P.tri[l];   // LINE_MIN_OBS, WINDOW_SIZE - 2
+}
+#endif
+
 // ---- removeLineOutlier (feature_manager.cpp:1372-1460)
 // pi_from_ppp(x1, x2, x3) with x1 = the camera centre (0): [(x1 - x3) x (x2 - x3) | -x3 . (x1 x x2)]
 GF_HD void line_plane_through_origin(const vec3 &x2, const vec3 &x3, double *pi) {

@@ -86,16 +86,7 @@ struct LineBatch {
   gfbe_summary *sum;            // [n_windows]
 };
 
-template <bool TAB>
-__device__ __forceinline__ int line_nobs(const LineBatch &P, int l) { return TAB ? P.nobs[l] : P.obs_off[l + 1] - P.obs_off[l]; }
-template <bool TAB>
-__device__ __forceinline__ const double *line_obs(const LineBatch &P, int l) {
-  return P.obs + 4 * (TAB ? (size_t)l * GFBE_NFRAMES : (size_t)P.obs_off[l]);
-}
-template <bool TAB>
-__device__ __forceinline__ bool line_eligible(const LineBatch &P, int l) {
-  return line_nobs<TAB>(P, l) >= 5 && P.start[l] < GFBE_WINDOW_SIZE - 2 && P.tri[l];   // LINE_MIN_OBS, WINDOW_SIZE - 2
-}
+// (line_nobs / line_obs / line_eligible over either description: gfbe_line.h, shared with gfbe_line_reduce.hip)
 
 // cost of line l at x; with H, g: its Cauchy-corrected normal-equation block and gradient
 template <bool LIN, bool TAB>

@@ -313,6 +313,7 @@ void gfbe_ltab_destroy(gfbe_ctx *c, gfbe_ltab *t) {
   if (!t) return;
   if (c && ctx_device(c) >= 0) (void)hipStreamSynchronize(ctx_stream(c));
   for (void *p : t->allocs) (void)hipFree(p);
+  if (t->reduce_d) (void)hipFree(t->reduce_d);
   if (t->stage_d) (void)hipFree(t->stage_d);
   if (t->stage_h) (void)hipHostFree(t->stage_h);
   if (t->ring_d) (void)hipFree(t->ring_d);

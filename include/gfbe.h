@@ -629,8 +629,53 @@ gfbe_status gfbe_line_refine(gfbe_ctx *ctx, int32_t n_windows, const gfbe_line_w
                              gfbe_summary *summary);
 
 /* ------------------------------------------------------------------------------------------
+ * Reduced normal equations of a window's line factors: the line loops of optimizationwithLine() (estimator.cpp:4566-4598 for the solve,
+ * :4736-4771 for MARGIN_OLD) linearised with respect to the poses, the camera extrinsic and the lines, the 4-dimensional line blocks
+ * eliminated. With x_p the 72 tangent dims [pose 0 .. pose 10 (dp, dtheta) | ex_cam (dp, dtheta)] and x_l the orthonormal 4 dims of line l:
+ *     U = sum Jp^T Jp (72 x 72), bp = sum Jp^T r; per line V_l = sum Jl^T Jl, bl = sum Jl^T r, W_l = sum Jp^T Jl (72 x 4)
+ *     V'_l = V_l + mu diag(clamp(diag V_l, 1e-6, 1e32));   H = U - sum_l W_l V'_l^-1 W_l^T;   g = bp - sum_l W_l V'_l^-1 bl
+ * r, Jp, Jl: lineProjectionFactor::Evaluate after ceres::HuberLoss(huber_width) and its corrector (rho'' <= 0: r and J scaled by
+ * sqrt(rho')); huber_width <= 0: no loss. The reference uses sqrt_info = 400, HuberLoss(1.0) (estimator.cpp:4342). Lines enter through
+ * getLineOrthVector as in gfbe_line_refine.
+ * THE 72 DIMS ARE, IN THIS ORDER, DIMS 0..71 OF THE WINDOW'S DENSE BLOCK (poses 0..65, camera extrinsic 66..71):
+ * joining H, g into the window solve is a plain add into the leading 72 x 72 corner / the first 72 entries.
+ * mode GFBE_LINE_REDUCE_SOLVE: every line of gfbe_line_refine's predicate (n_obs >= 5, start_frame < GFBE_WINDOW_SIZE - 2,
+ *   is_triangulation), list order, every observation including the start frame's own. There is no "fewer than 4 lines" exit here.
+ * mode GFBE_LINE_REDUCE_MARG_OLD: of those only the lines with start_frame == 0, and their observation in frame 0 is skipped: the rows
+ *   and columns of pose 0 are exactly zero. "Eligible" below means the lines that enter in the given mode.
+ * A line whose V'_l has no Cholesky factor (a pivot that is not positive and finite) is left out of EVERY sum (U, bp and cost too),
+ * flagged in `failed` and counted in n_failed. Observation values are not validated (gfbe_line_refine does not either): a NaN
+ * observation makes its line such a line and nothing else.
+ * Outputs: caller-owned, any pointer may be NULL. Per-line records are concatenated over the windows in list order of the eligible
+ * lines; size them for the total number of lines, sum(n_eligible) records are written.
+ * ------------------------------------------------------------------------------------------ */
+enum { GFBE_LINE_REDUCE_SOLVE = 0, GFBE_LINE_REDUCE_MARG_OLD = 1, GFBE_LINE_REDUCE_DIM = 72 };
+typedef struct gfbe_line_reduced {
+  int32_t struct_size;                /* sizeof(gfbe_line_reduced) as the caller was built (refused otherwise: GFBE_BAD_INPUT) */
+  int32_t reserved;                   /* 0 */
+  double *H;                          /* [W][72][72] full, symmetric bit for bit */
+  double *g;                          /* [W][72] */
+  double *U;                          /* [W][72][72] the unreduced pose / extrinsic block */
+  double *bp;                         /* [W][72] */
+  double *cost;                       /* [W] sum of 1/2 rho */
+  int32_t *n_eligible;                /* [W] */
+  int32_t *n_failed;                  /* [W] */
+  double *Vinv;                       /* [.][4][4] V'_l^-1 (symmetric bit for bit) */
+  double *bl;                         /* [.][4] */
+  double *W;                          /* [.][72][4] */
+  uint8_t *failed;                    /* [.] 1: left out (its Vinv, bl, W are not meaningful) */
+  double *ms_kernel;                  /* [W][2] the window's time in the kernel, and the part of it in the matrix-core contraction
+                                         loop (device clock, like gfbe_summary.ms_solve) */
+} gfbe_line_reduced;
+/* Host-fed: the windows of gfbe_line_refine. GFBE_BAD_INPUT (bad mode, negative or non-finite mu, wrong struct_size of either
+ * structure, observations past the window), GFBE_NO_DEVICE, GFBE_DEVICE_ERROR: no output has been touched. */
+gfbe_status gfbe_line_reduce(gfbe_ctx *ctx, int32_t n_windows, const gfbe_line_window *const *win, int32_t mode, double sqrt_info,
+                             double huber_width, double mu, gfbe_line_reduced *out);
+
+/* ------------------------------------------------------------------------------------------
  * Line feature tables: FeatureManager::linefeature on the device, and the line calls of a use_line frame against it
- *   addFeatureCheckParallaxwithline -> triangulateLine -> onlyLineOpt (+ removeLineOutlier) -> [optimizationwithLine on the CPU]
+ *   addFeatureCheckParallaxwithline -> triangulateLine -> onlyLineOpt (+ removeLineOutlier) -> [optimizationwithLine on the CPU; its
+ *   line loops reduced on the device by gfbe_ltab_reduce]
  *   -> slideWindow (removeBackShiftDepthline / removeBackline / removeFrontline)      estimator.cpp:1426-1438, 3859-3899
  * A gfbe_ltab holds W independent tables in HBM, one per window; every call applies one operation to all W tables, per-table arguments
  * are arrays of length W. A table is std::list<lineFeaturePerId> in insertion order — the order that defines the line index of
@@ -675,6 +720,12 @@ gfbe_status gfbe_ltab_remove_front(gfbe_ctx *ctx, gfbe_ltab *t, const int32_t *f
  * the same pose bits the result equals gfbe_line_refine's bit for bit. summary [W]; return value: the worst summary status. */
 gfbe_status gfbe_ltab_refine(gfbe_ctx *ctx, gfbe_ltab *t, const double *pose7, const double *ex_cam, double sqrt_info,
                              double cauchy_scale, int32_t max_num_iterations, gfbe_summary *summary);
+/* gfbe_line_reduce on every table, read in place: the tables are not changed. pose7 [W][11][7], ex_cam [W][7] as for
+ * gfbe_ltab_refine; with the same pose bits every output equals gfbe_line_reduce's on the downloaded list bit for bit. The call's
+ * device scratch and output staging (4.8 KB per line slot, min(W, 256) x (largest table + 8) slots, plus the outputs asked for) stays on
+ * the table handle between calls, grows to the largest size ever needed and is released by gfbe_ltab_destroy. */
+gfbe_status gfbe_ltab_reduce(gfbe_ctx *ctx, gfbe_ltab *t, int32_t mode, const double *pose7, const double *ex_cam, double sqrt_info,
+                             double huber_width, double mu, gfbe_line_reduced *out);
 /* linefeature.size() and getLineFeatureCount() (feature_manager.cpp:1013-1027) of every table. */
 gfbe_status gfbe_ltab_size(gfbe_ctx *ctx, gfbe_ltab *t, int32_t *n_lines);
 gfbe_status gfbe_ltab_line_count(gfbe_ctx *ctx, gfbe_ltab *t, int32_t *count);

@@ -10,7 +10,13 @@ windows: 150 eligible lines with 5-11 observations each (NUM_ITERATIONS = 8), fo
              region, since the refine edits the tables): only the poses go up and the summaries come down
 Both legs: the host's clock around the call, which ends synchronised; the legs alternate, REPS repetitions each after one warm-up of
 each; median and spread (max - min). kernel: the longest time one window spent in the kernel (gfbe_summary.ms_solve, device clock).
-The two legs' results are compared bit for bit once per size. Output: stdout, and the same lines into the file given with --out."""
+The two legs' results are compared bit for bit once per size. Output: stdout, and the same lines into the file given with --out.
+
+--reduce: the same measurement for the reduced normal equations of the line factors (gfbe_line_reduce host-fed against gfbe_ltab_reduce
+table-fed, solve mode, HuberLoss(1.0), mu = 0; outputs asked for: H, g, cost, the counts and ms_kernel — what the join into the window
+solve takes; the per-line records stay on the device side of this measurement). The tables are not edited by the call, so they are
+seeded once. kernel / mfma: the longest time one window spent in the kernel and in its matrix-core contraction loop (ms_kernel, device
+clock); the sum over the windows divided by the 256 workgroups in flight estimates the kernel's own duration for the large batches."""
 import argparse
 import time
 
@@ -34,10 +40,56 @@ def _table_of(lw, base_id=0):
                 is_triangulation=lw["is_triangulation"], line_plucker=lw["line_plucker"])
 
 
+def reduce_leg(be, base, holders, seeds, sizes, say):
+    import line_reduce_np as lrn
+    want = ("H", "g", "cost", "n_eligible", "n_failed", "ms_kernel")
+    for nw in sizes:
+        hs = [holders[k % len(holders)] for k in range(nw)]
+        tabs = be.line_tables(nw, 160)
+        for w in range(nw):
+            tabs.upload(w, seeds[w % len(seeds)])
+        pose7 = np.ascontiguousarray([base[k % len(base)]["pose"] for k in range(nw)])
+        ex = np.ascontiguousarray([base[k % len(base)]["ex_cam"] for k in range(nw)])
+        bh, bt = abi.line_reduced_buffers(nw, 1, want), abi.line_reduced_buffers(nw, 1, want)
+        rh, rt = abi.line_reduced_struct(bh), abi.line_reduced_struct(bt)
+        t_host, t_tab = [], []
+        for rep in range(REPS + 1):          # (rep 0: warm-up of both legs)
+            t0 = time.perf_counter()
+            rc = abi.line_reduce_raw(be.lib, "gfbe_", be.ctx, hs, 0, 400.0, 1.0, 0.0, rh)
+            t1 = time.perf_counter()
+            rc_t = tabs.reduce_raw(pose7, ex, 0, 400.0, 1.0, 0.0, rt)
+            t2 = time.perf_counter()
+            assert rc == abi.OK and rc_t == abi.OK, (rc, rc_t)
+            if rep:
+                t_host.append((t1 - t0) * 1e3)
+                t_tab.append((t2 - t1) * 1e3)
+        for k in ("H", "g", "cost", "n_eligible", "n_failed"):
+            assert bh[k].tobytes() == bt[k].tobytes(), "table-fed != host-fed: " + k
+        assert not bt["n_failed"].any()
+        tabs.close()
+
+        def stat(t):
+            return float(np.median(t)), float(max(t) - min(t))
+        (mh, sh), (mt, st) = stat(t_host), stat(t_tab)
+        ms = bt["ms_kernel"]
+        say("%5d windows: host-fed %8.3f ms (spread %6.3f) | table-fed %8.3f ms (spread %6.3f) | table-fed / host-fed %.3f, "
+            "%7.2f -> %7.2f us / window | in the kernel per window: max %.3f ms, mean %.3f ms, matrix-core loop %.1f %% of it; "
+            "sum / 256 workgroups %.3f ms | eligible lines %d" %
+            (nw, mh, sh, mt, st, mt / mh, 1e3 * mh / nw, 1e3 * mt / nw, ms[:, 0].max(), ms[:, 0].mean(),
+             100.0 * ms[:, 1].sum() / ms[:, 0].sum(), ms[:, 0].sum() / min(nw, 256), int(bt["n_eligible"][0])))
+        say("              host-fed  [%s]" % " ".join("%.3f" % t for t in t_host))
+        say("              table-fed [%s]" % " ".join("%.3f" % t for t in t_tab))
+    t0 = time.perf_counter()
+    for w in base[:2]:
+        lrn.reduce(w)
+    say("numpy checker (FP64): %.1f ms / window" % ((time.perf_counter() - t0) / 2 * 1e3))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--sizes", default="1,256,1024,4096")
+    ap.add_argument("--reduce", action="store_true", help="time gfbe_line_reduce / gfbe_ltab_reduce instead of the refinement")
     args = ap.parse_args()
     lines = []
 
@@ -51,6 +103,12 @@ def main():
     seeds = [_table_of(w) for w in base]
     say("lines per window %d, observations per window %.0f (mean); %d repetitions per leg, alternating" %
         (holders[0].n, np.mean([len(h.obs) for h in holders]), REPS))
+    if args.reduce:
+        reduce_leg(be, base, holders, seeds, [int(x) for x in args.sizes.split(",")], say)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     for nw in [int(x) for x in args.sizes.split(",")]:
         hs = [holders[k % len(holders)] for k in range(nw)]
         n_lines = sum(h.n for h in hs)
