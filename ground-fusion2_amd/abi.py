@@ -1016,6 +1016,124 @@ def line_reduce(lib, prefix, ctx, windows, mode=LINE_REDUCE_SOLVE, sqrt_info=400
 
 
 # ---------------------------------------------------------------------------------------------
+# The step half of a joint iteration over the line blocks (gfbe_line_step / gfbe_ltab_step / gfbe_ltab_commit)
+# ---------------------------------------------------------------------------------------------
+class LineReducedV(C.Structure):
+    """gfbe_line_reduced at its current size: LineReduced (the size before the member V, still admitted by the library) plus V."""
+    _fields_ = LineReduced._fields_ + [("V", PD)]
+
+
+LINE_RECORD_KEYS = ("Vinv", "bl", "W", "V", "failed")
+LINE_REDUCE_KEYS_V = LINE_REDUCE_KEYS + ("V",)
+
+
+def line_reduced_buffers_v(n_windows, n_lines, want=LINE_REDUCE_KEYS_V, fill=0):
+    """line_reduced_buffers with the record V [n_lines][10] (lower triangle of V_l, row-major)."""
+    bufs = line_reduced_buffers(n_windows, n_lines, tuple(k for k in want if k != "V"), fill)
+    if "V" in want:
+        bufs["V"] = np.full((n_lines, 10), fill, np.float64)
+    return bufs
+
+
+def line_reduced_struct_v(bufs):
+    """A gfbe_line_reduced (current size) over the arrays of `bufs` (absent keys: NULL). Keep `bufs` alive during the call."""
+    r = LineReducedV()
+    r.struct_size = C.sizeof(LineReducedV)
+    for k, a in bufs.items():
+        assert a.flags["C_CONTIGUOUS"]
+        setattr(r, k, a.ctypes.data_as(dict(LineReducedV._fields_)[k]))
+    return r
+
+
+def _line_split(bufs, ne, per_line):
+    off = np.concatenate([[0], np.cumsum(ne)]).astype(int)
+    return [{k: (a[off[w]:off[w + 1]] if k in per_line else a[w]) for k, a in bufs.items()} for w in range(len(ne))]
+
+
+def line_reduce_v(lib, prefix, ctx, windows, mode=LINE_REDUCE_SOLVE, sqrt_info=400.0, huber_width=1.0, mu=0.0, want=LINE_REDUCE_KEYS_V):
+    """line_reduce through the current structure: the same outputs plus the record V."""
+    holders = [w if isinstance(w, LineWindowHolder) else LineWindowHolder(w) for w in windows]
+    want = tuple(want) + tuple(k for k in ("n_eligible",) if k not in want)
+    bufs = line_reduced_buffers_v(len(holders), sum(h.n for h in holders), want)
+    red = line_reduced_struct_v(bufs)
+    arr = (C.POINTER(LineWindow) * max(len(holders), 1))(*[C.pointer(h.c) for h in holders])
+    f = getattr(lib, prefix + "line_reduce")
+    f.restype = c_i
+    f.argtypes = [C.c_void_p, c_i, C.POINTER(C.POINTER(LineWindow)), c_i, c_d, c_d, c_d, C.c_void_p]
+    rc = f(ctx, len(holders), arr, int(mode), float(sqrt_info), float(huber_width), float(mu), C.byref(red))
+    if rc != OK:
+        raise RuntimeError("%sline_reduce failed with status %d" % (prefix, rc))
+    return _line_split(bufs, bufs["n_eligible"], LINE_RECORD_KEYS)
+
+
+class LineStepped(C.Structure):
+    _fields_ = [("struct_size", c_i), ("reserved", c_i), ("gram", PD), ("total", PD), ("coef", PD), ("invalid", PU8), ("y_l", PD),
+                ("v_l", PD), ("orth_cand", PD), ("plucker_cand", PD), ("pose_cand", PD), ("ex_cand", PD), ("cost_cand", PD), ("ms_kernel", PD)]
+
+
+LINE_STEP_KEYS = ("gram", "total", "coef", "invalid", "y_l", "v_l", "orth_cand", "plucker_cand", "pose_cand", "ex_cand", "cost_cand", "ms_kernel")
+LINE_STEP_PER_LINE = ("y_l", "v_l", "orth_cand", "plucker_cand")
+
+
+def line_stepped_buffers(n_windows, n_lines, want=LINE_STEP_KEYS, fill=0):
+    """Output arrays of a step call over n_windows windows with n_lines entering lines in all (or a bound of them)."""
+    W = n_windows
+    shapes = dict(gram=((W, 8), np.float64), total=((W, 8), np.float64), coef=((W, 4), np.float64), invalid=((W,), np.uint8),
+                  y_l=((n_lines, 4), np.float64), v_l=((n_lines, 4), np.float64), orth_cand=((n_lines, 4), np.float64),
+                  plucker_cand=((n_lines, 6), np.float64), pose_cand=((W, NFRAMES, 7), np.float64), ex_cand=((W, 7), np.float64),
+                  cost_cand=((W,), np.float64), ms_kernel=((W,), np.float64))
+    return {k: np.full(shapes[k][0], fill, shapes[k][1]) for k in want}
+
+
+def line_stepped_struct(bufs):
+    r = LineStepped()
+    r.struct_size = C.sizeof(LineStepped)
+    for k, a in bufs.items():
+        assert a.flags["C_CONTIGUOUS"]
+        setattr(r, k, a.ctypes.data_as(dict(LineStepped._fields_)[k]))
+    return r
+
+
+def line_step_raw(lib, prefix, ctx, holders, red, sqrt_info, huber_width, mu, y_p, v_p, rest, radius, stepped):
+    """gfbe_line_step over prebuilt LineWindowHolders; red: LineReducedV over the records (or None), stepped: LineStepped (or None);
+    y_p, v_p [W][72], rest [W][8], radius [W] float64 contiguous. Returns the status."""
+    arr = (C.POINTER(LineWindow) * max(len(holders), 1))(*[C.pointer(h.c) for h in holders])
+    f = getattr(lib, prefix + "line_step")
+    f.restype = c_i
+    f.argtypes = [C.c_void_p, c_i, C.POINTER(C.POINTER(LineWindow)), C.c_void_p, c_d, c_d, c_d, PD, PD, PD, PD, C.c_void_p]
+    return f(ctx, len(holders), arr, C.byref(red) if red is not None else None, float(sqrt_info), float(huber_width), float(mu),
+             _pd(y_p), _pd(v_p), _pd(rest), _pd(radius), C.byref(stepped) if stepped is not None else None)
+
+
+def line_records_pack(records):
+    """The record arrays of gfbe_line_step, concatenated over the windows: records = one dict per window with Vinv, bl, W, V, failed."""
+    ne = np.array([len(r["failed"]) for r in records], np.int32)
+    shapes = dict(Vinv=(4, 4), bl=(4,), W=(LINE_REDUCE_DIM, 4), V=(10,))
+    rb = dict(n_eligible=ne if len(ne) else np.zeros(1, np.int32))
+    for k, sh in shapes.items():
+        parts = [_f64(r[k]).reshape((-1,) + sh) for r in records]
+        a = np.concatenate(parts) if parts else np.zeros((0,) + sh)
+        rb[k] = np.ascontiguousarray(a if len(a) else np.zeros((1,) + sh))
+    f = np.concatenate([_u8(r["failed"]) for r in records]) if len(records) else np.zeros(0, np.uint8)
+    rb["failed"] = np.ascontiguousarray(f if len(f) else np.zeros(1, np.uint8))
+    return rb, ne
+
+
+def line_step(lib, prefix, ctx, windows, records, y_p, v_p, rest, radius, sqrt_info=400.0, huber_width=1.0, mu=0.0, want=LINE_STEP_KEYS):
+    """The step half for each window. records: one dict per window with Vinv, bl, W, V, failed of its entering lines (what line_reduce_v
+    returned). One dict per window: gram, total, coef, invalid, y_l, v_l, orth_cand, plucker_cand, pose_cand, ex_cand, cost_cand."""
+    holders = [w if isinstance(w, LineWindowHolder) else LineWindowHolder(w) for w in windows]
+    nW = len(holders)
+    rb, ne = line_records_pack(records)
+    bufs = line_stepped_buffers(nW, max(int(ne.sum()), 1), want)
+    rc = line_step_raw(lib, prefix, ctx, holders, line_reduced_struct_v(rb), sqrt_info, huber_width, mu, _f64(y_p).reshape(nW, LINE_REDUCE_DIM),
+                       _f64(v_p).reshape(nW, LINE_REDUCE_DIM), _f64(rest).reshape(nW, 8), _f64(radius).reshape(nW), line_stepped_struct(bufs))
+    if rc != OK:
+        raise RuntimeError("%sline_step failed with status %d" % (prefix, rc))
+    return _line_split(bufs, ne, LINE_STEP_PER_LINE)
+
+
+# ---------------------------------------------------------------------------------------------
 # Line feature tables (gfbe_ltab_*): FeatureManager::linefeature on the device
 # ---------------------------------------------------------------------------------------------
 class LineTables:
@@ -1085,7 +1203,7 @@ class LineTables:
         """gfbe_ltab_reduce on prepared arrays (pose7 [W][11][7], ex_cam [W][7], float64, contiguous) into the LineReduced `red`."""
         f = self._f("reduce")
         f.restype = c_i
-        f.argtypes = [C.c_void_p, C.c_void_p, c_i, PD, PD, c_d, c_d, c_d, C.POINTER(LineReduced)]
+        f.argtypes = [C.c_void_p, C.c_void_p, c_i, PD, PD, c_d, c_d, c_d, C.c_void_p]      # (LineReduced or LineReducedV: both sizes are admitted)
         return f(self.ctx, self.h, int(mode), _pd(pose7), _pd(ex_cam), float(sqrt_info), float(huber_width), float(mu),
                  C.byref(red) if red is not None else None)
 
@@ -1103,6 +1221,51 @@ class LineTables:
         n = np.zeros(self.W, np.int32)
         self._check(self._f("size")(self.ctx, self.h, _pi(n)), "size")
         return n
+
+    def reduce_v(self, pose7, ex_cam, mode=LINE_REDUCE_SOLVE, sqrt_info=400.0, huber_width=1.0, mu=0.0, want=LINE_REDUCE_KEYS_V):
+        """reduce() through the current structure: the same outputs plus the record V."""
+        p, e = _f64(pose7).reshape(self.W, NFRAMES, 7), _f64(ex_cam).reshape(self.W, 7)
+        want = tuple(want) + tuple(k for k in ("n_eligible",) if k not in want)
+        bufs = line_reduced_buffers_v(self.W, int(self.size().sum()), want)
+        rc = self.reduce_raw(p, e, mode, sqrt_info, huber_width, mu, line_reduced_struct_v(bufs))
+        if rc != OK:
+            raise RuntimeError("%sltab_reduce failed with status %d" % (self.prefix, rc))
+        return _line_split(bufs, bufs["n_eligible"], LINE_RECORD_KEYS)
+
+    def keep_records(self, on=True):
+        """gfbe_ltab_keep_records: while on, a solve-mode reduce leaves its per-line records on the handle for step()."""
+        f = self._f("keep_records")
+        f.restype = c_i
+        f.argtypes = [C.c_void_p, C.c_void_p, c_i]
+        self._check(f(self.ctx, self.h, int(bool(on))), "keep_records")
+
+    def step_raw(self, pose7, ex_cam, sqrt_info, huber_width, y_p, v_p, rest, radius, stepped):
+        """gfbe_ltab_step on prepared arrays (float64, contiguous) into the LineStepped `stepped`; returns the status."""
+        f = self._f("step")
+        f.restype = c_i
+        f.argtypes = [C.c_void_p, C.c_void_p, PD, PD, c_d, c_d, PD, PD, PD, PD, C.c_void_p]
+        return f(self.ctx, self.h, _pd(pose7), _pd(ex_cam), float(sqrt_info), float(huber_width), _pd(y_p), _pd(v_p), _pd(rest), _pd(radius),
+                 C.byref(stepped) if stepped is not None else None)
+
+    def step(self, pose7, ex_cam, y_p, v_p, rest, radius, n_eligible, sqrt_info=400.0, huber_width=1.0, want=LINE_STEP_KEYS):
+        """The step half on every table from the records the last solve-mode reduce kept (abi.line_step's result per table).
+        n_eligible [W]: the entering lines per table, as that reduce reported them (they cut the per-line arrays)."""
+        p, e = _f64(pose7).reshape(self.W, NFRAMES, 7), _f64(ex_cam).reshape(self.W, 7)
+        ne = _i32(n_eligible).reshape(self.W)
+        bufs = line_stepped_buffers(self.W, max(int(ne.sum()), 1), want)
+        rc = self.step_raw(p, e, sqrt_info, huber_width, _f64(y_p).reshape(self.W, LINE_REDUCE_DIM), _f64(v_p).reshape(self.W, LINE_REDUCE_DIM),
+                           _f64(rest).reshape(self.W, 8), _f64(radius).reshape(self.W), line_stepped_struct(bufs))
+        if rc != OK:
+            raise RuntimeError("%sltab_step failed with status %d" % (self.prefix, rc))
+        return _line_split(bufs, ne, LINE_STEP_PER_LINE)
+
+    def commit(self, accept):
+        """gfbe_ltab_commit: tables with accept[w] != 0 take the candidate lines of the last step()."""
+        a = _u8(accept).reshape(self.W)
+        f = self._f("commit")
+        f.restype = c_i
+        f.argtypes = [C.c_void_p, C.c_void_p, PU8]
+        self._check(f(self.ctx, self.h, a.ctypes.data_as(PU8)), "commit")
 
     def line_count(self):
         n = np.zeros(self.W, np.int32)

@@ -34,6 +34,7 @@ EXPORTS = [
     "gfbe_pg_eval", "gfbe_pg_solve", "gfbe_lio_linearize", "gfbe_batch_upload_tables", "gfbe_batch_feature_count",
     "gfbe_plane_eval", "gfbe_anchor_eval", "gfbe_orientation_subset_plus", "gfbe_gnss_eval",
     "gfbe_line_eval", "gfbe_line_refine", "gfbe_line_reduce", "gfbe_ltab_reduce",
+    "gfbe_line_step", "gfbe_ltab_keep_records", "gfbe_ltab_step", "gfbe_ltab_commit",
     "gfbe_ltab_create", "gfbe_ltab_destroy", "gfbe_ltab_add_frame", "gfbe_ltab_triangulate", "gfbe_ltab_remove_back_shift",
     "gfbe_ltab_remove_back", "gfbe_ltab_remove_front", "gfbe_ltab_refine", "gfbe_ltab_size", "gfbe_ltab_line_count",
     "gfbe_ltab_download", "gfbe_ltab_upload",
@@ -202,6 +203,22 @@ class Backend(abi.CApi):
         resident tables: line_tables(...).reduce(...)."""
         try:
             return abi.line_reduce(self.lib, "gfbe_", self.ctx, windows, mode, sqrt_info, huber_width, mu, want)
+        except RuntimeError as e:
+            raise BackendError("%s: %s" % (e, self._err()))
+
+    def line_reduce_v(self, windows, mode=abi.LINE_REDUCE_SOLVE, sqrt_info=400.0, huber_width=1.0, mu=0.0, want=abi.LINE_REDUCE_KEYS_V):
+        """line_reduce with the record V (the lower triangle of V_l without mu) beside Vinv, bl, W, failed: what line_step takes."""
+        try:
+            return abi.line_reduce_v(self.lib, "gfbe_", self.ctx, windows, mode, sqrt_info, huber_width, mu, want)
+        except RuntimeError as e:
+            raise BackendError("%s: %s" % (e, self._err()))
+
+    def line_step(self, windows, records, y_p, v_p, rest, radius, sqrt_info=400.0, huber_width=1.0, mu=0.0, want=abi.LINE_STEP_KEYS):
+        """The step half of a joint iteration over the line blocks (gfbe_line_step): back-substitution, the lines' dogleg shares, the
+        dogleg coefficients from rest + shares, the candidate lines / poses and the candidate line cost. records: line_reduce_v's result.
+        For device-resident tables: line_tables(...).keep_records() / reduce_v / step / commit."""
+        try:
+            return abi.line_step(self.lib, "gfbe_", self.ctx, windows, records, y_p, v_p, rest, radius, sqrt_info, huber_width, mu, want)
         except RuntimeError as e:
             raise BackendError("%s: %s" % (e, self._err()))
 

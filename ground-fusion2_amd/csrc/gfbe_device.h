@@ -481,4 +481,22 @@ struct gfbe_ltab : gfbe_tab_staging {
   std::vector<void *> allocs;
   char *reduce_d = nullptr;      // gfbe_ltab_reduce's scratch and output staging, kept between calls (gfbe_line_reduce.hip)
   size_t reduce_cap = 0;
+  // the step half of a joint iteration (gfbe_ltab_keep_records / gfbe_ltab_step / gfbe_ltab_commit, gfbe_line_step.hip)
+  unsigned long long gen = 0;    // bumped by every operation that may change the tables
+  bool keep_records = false;
+  char *rec_d = nullptr;         // the per-line store of a solve-mode reduce: rec_off [W + 1], then Vinv, bl, W, V, failed per line slot
+  size_t rec_cap = 0;
+  bool rec_valid = false;
+  unsigned long long rec_gen = 0;
+  double rec_mu = 0.0;
+  std::vector<double> rec_pose;  // [W][77] poses then [W][7] extrinsics of that reduce, bit for bit
+  std::vector<int> rec_off, rec_ne;      // [W + 1] first slot of a table, [W] entering lines
+  const double *rec_Vinv = nullptr, *rec_bl = nullptr, *rec_W = nullptr, *rec_V = nullptr;
+  const unsigned char *rec_failed = nullptr;
+  const int *rec_off_d = nullptr;
+  char *step_d = nullptr;        // gfbe_ltab_step's inputs, outputs and the candidates, kept between calls
+  size_t step_cap = 0;
+  bool cand_valid = false;
+  const double *cand_plk = nullptr;      // [slots][6]
+  const int *cand_lineof = nullptr, *cand_ne = nullptr;      // [slots] line of a record, [W] entering lines
 };

@@ -194,9 +194,11 @@ GF_HD bool line_chol4_inv(const double *V, double mu, double *Vinv) {
 //   Wrow [72][4]: W_l = sum Jp^T Jl (rows 6 f .. 6 f + 5 of an observing pose f, rows 66 .. 71 the extrinsic, zero elsewhere)
 //   Jrec [m][LINE_JREC]: per observation r (2), Jp (2 x 6), Je (2 x 6) after the loss — what U and bp are summed from
 //   V'^-1 [4][4], bl [4], cost = sum 1/2 rho.   Returns false when V' has no Cholesky factor.
+//   Vlow [10] (optional): the lower triangle of V_l without the mu term, row-major — the record of the step side (gfbe_line_step.hip)
 enum { LINE_JREC = 26, LINE_NP = 72 };
 GF_HD bool line_reduce_line(const LineRT *Bs, const LineRT &Ex, const double *orth, int start, int k0, int m, const double *ob,
-                            double sqrt_info, double huber, double mu, double *Wrow, double *Jrec, double *Vinv, double *bl, double *cost) {
+                            double sqrt_info, double huber, double mu, double *Wrow, double *Jrec, double *Vinv, double *bl, double *cost,
+                            double *Vlow = nullptr) {
   double V[16], b4[4], We[24], c = 0.0;
   for (int q = 0; q < 16; q++) V[q] = 0.0;
   for (int q = 0; q < 4; q++) b4[q] = 0.0;
@@ -228,11 +230,104 @@ GF_HD bool line_reduce_line(const LineRT *Bs, const LineRT &Ex, const double *or
   for (int q = 0; q < 24; q++) Wrow[4 * 66 + q] = We[q];
   for (int q = 0; q < 4; q++) bl[q] = b4[q];
   *cost = c;
+  if (Vlow)
+    for (int i = 0, q = 0; i < 4; i++)
+      for (int j = 0; j <= i; j++) Vlow[q++] = V[4 * i + j];
   return line_chol4_inv(V, mu, Vinv);
 }
 // Y = W V'^-1, one row
 GF_HD void line_Y_row(const double *w, const double *Vinv, double *y) {
   for (int a = 0; a < 4; a++) y[a] = w[0] * Vinv[a] + w[1] * Vinv[4 + a] + w[2] * Vinv[8 + a] + w[3] * Vinv[12 + a];
+}
+
+// ---- the step half of a joint iteration over the line blocks (csrc/gfbe_line_step.hip, include/gfbe.h: gfbe_line_step; compiled for
+//      the host by tests/line_step_host_shim.cpp). The scalar landmark code of the window solve (k_lm_step, k_step, k_candidate)
+//      generalised to a 4-dimensional block: line columns unscaled, the block's metric d2 = clamp(diag V, 1e-6, 1e32).
+// One line's back-substitution and dogleg shares. W [72][4], Vinv [16], bl [4], Vlow [10] (lower triangle of V without mu), yp / vp [72]
+// the pose / extrinsic Gauss-Newton and Cauchy directions, x [4] the line. yl = Vinv (bl - W^T yp), vl = bl / d2,
+// p = [G2, N2, gy, vHv, vHy, yHy, |x - Plus(x, -bl)|_inf, |x|^2]. W is streamed once for both products.
+GF_HD void line_step_shares(const double *W, const double *Vinv, const double *bl, const double *Vlow, const double *yp, const double *vp,
+                            const double *x, double *yl, double *vl, double *p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  W = (const double *)__builtin_assume_aligned(W, 32);      // (a record: 2304 bytes from a 256-byte aligned base)
+#endif
+  double wy[4] = {0.0, 0.0, 0.0, 0.0}, wv[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int r = 0; r < 72; r++) {
+    const double w0 = W[4 * r], w1 = W[4 * r + 1], w2 = W[4 * r + 2], w3 = W[4 * r + 3], y = yp[r], v = vp[r];
+    wy[0] += w0 * y; wy[1] += w1 * y; wy[2] += w2 * y; wy[3] += w3 * y;
+    wv[0] += w0 * v; wv[1] += w1 * v; wv[2] += w2 * v; wv[3] += w3 * v;
+  }
+  double V[16], d2[4], rhs[4];
+  for (int i = 0, q = 0; i < 4; i++)
+    for (int j = 0; j <= i; j++) { V[4 * i + j] = Vlow[q]; V[4 * j + i] = Vlow[q]; q++; }
+  for (int a = 0; a < 4; a++) { d2[a] = fmin(fmax(V[5 * a], 1e-6), 1e32); vl[a] = bl[a] / d2[a]; rhs[a] = bl[a] - wy[a]; }
+  for (int a = 0; a < 4; a++) yl[a] = Vinv[4 * a] * rhs[0] + Vinv[4 * a + 1] * rhs[1] + Vinv[4 * a + 2] * rhs[2] + Vinv[4 * a + 3] * rhs[3];
+  double Vv[4], Vy[4];
+  for (int a = 0; a < 4; a++) {
+    Vv[a] = V[4 * a] * vl[0] + V[4 * a + 1] * vl[1] + V[4 * a + 2] * vl[2] + V[4 * a + 3] * vl[3];
+    Vy[a] = V[4 * a] * yl[0] + V[4 * a + 1] * yl[1] + V[4 * a + 2] * yl[2] + V[4 * a + 3] * yl[3];
+  }
+  for (int k = 0; k < 8; k++) p[k] = 0.0;
+  double vwv = 0.0, vwy = 0.0, ywv = 0.0, ywy = 0.0, vVv = 0.0, vVy = 0.0, yVy = 0.0;
+  for (int a = 0; a < 4; a++) {
+    p[0] += bl[a] * bl[a] / d2[a];
+    p[1] += d2[a] * yl[a] * yl[a];
+    p[2] += bl[a] * yl[a];
+    vwv += vl[a] * wv[a]; vwy += vl[a] * wy[a]; ywv += yl[a] * wv[a]; ywy += yl[a] * wy[a];
+    vVv += vl[a] * Vv[a]; vVy += vl[a] * Vy[a]; yVy += yl[a] * Vy[a];
+    p[7] += x[a] * x[a];
+  }
+  p[3] = 2.0 * vwv + vVv;
+  p[4] = vwy + ywv + vVy;
+  p[5] = 2.0 * ywy + yVy;
+  double nb[4] = {-bl[0], -bl[1], -bl[2], -bl[3]}, xm[4];
+  line_orth_plus(x, nb, xm);
+  for (int a = 0; a < 4; a++) p[6] = fmax(p[6], fabs(x[a] - xm[a]));
+}
+// DoglegStrategy::ComputeStep's three branches and the model change, from the window's totals T = [G2, N2, gy, vHv, vHy, yHy, ..]
+// (the rule of k_step, gfbe_kernels.hip, restated): step = c1 v + c2 y. coef = [c1, c2, step_norm, model_change]; returns the branch:
+// 0 Gauss-Newton step inside the radius, 1 Cauchy point on or outside it, 2 the dogleg's crossing of the boundary.
+GF_HD int line_dogleg(const double *T, double radius, double *coef) {
+  const double G2 = T[0], N2 = T[1], gy = T[2], vHv = T[3], vHy = T[4], yHy = T[5];
+  const double alpha = G2 / vHv;
+  const double g_norm = sqrt(G2), gn_norm = sqrt(N2);
+  double c1, c2, step_norm;
+  int branch;
+  if (gn_norm <= radius) { c1 = 0.0; c2 = -1.0; step_norm = gn_norm; branch = 0; }
+  else if (g_norm * alpha >= radius) { c1 = -radius / g_norm; c2 = 0.0; step_norm = radius; branch = 1; }
+  else {
+    const double b_dot_a = alpha * gy;
+    const double a_sq = (alpha * g_norm) * (alpha * g_norm);
+    const double bma = a_sq - 2.0 * b_dot_a + N2;
+    const double cc = b_dot_a - a_sq;
+    const double dd = sqrt(cc * cc + bma * (radius * radius - a_sq));
+    const double beta = (cc <= 0.0) ? (dd - cc) / bma : (radius * radius - a_sq) / (dd + cc);
+    c1 = -alpha * (1.0 - beta); c2 = -beta;
+    step_norm = sqrt(fmax(0.0, c1 * c1 * G2 + 2.0 * c1 * c2 * gy + c2 * c2 * N2));
+    branch = 2;
+  }
+  coef[0] = c1; coef[1] = c2; coef[2] = step_norm;
+  coef[3] = -(c1 * G2 + c2 * gy) - 0.5 * (c1 * c1 * vHv + 2.0 * c1 * c2 * vHy + c2 * c2 * yHy);
+  return branch;
+}
+// One line's candidate: xc = Plus(x, c1 vl + c2 yl); its cost (sum of 1/2 rho_huber over its m observations, none skipped) at the
+// candidate poses Bc / extrinsic Exc; plk = setLineOrth: xc expressed in the candidate start frame's camera Cs = (Rwc, twc).
+GF_HD double line_step_candidate(const LineRT *Bc, const LineRT &Exc, const LineRT &Cs, const double *x, const double *yl, const double *vl,
+                                 double c1, double c2, int start, int m, const double *ob, double sqrt_info, double huber, double *xc,
+                                 double *plk) {
+  double dl[4];
+  for (int a = 0; a < 4; a++) dl[a] = c1 * vl[a] + c2 * yl[a];
+  line_orth_plus(x, dl, xc);
+  double cost = 0.0;
+  for (int k = 0; k < m; k++) {
+    double r[2], sr;
+    line_factor<false>(Bc[start + k], Exc, xc, ob + 4 * k, sqrt_info, r, nullptr, nullptr, nullptr);
+    cost += line_huber(r[0] * r[0] + r[1] * r[1], huber, &sr);
+  }
+  double lw[6];
+  line_orth_to_plk(xc, lw);
+  line_plk_from_pose(lw, Cs.R, Cs.t, plk);
+  return cost;
 }
 
 // ---- a batch's line list as the kernels read it (k_line_refine, k_line_reduce). B: a structure with the members line_off, obs_off

@@ -54,12 +54,12 @@ struct ReduceBatch {
   const int *rec_off;                  // [n_windows] first record slot of a window (prefix of the line counts)
   // scratch, per workgroup slab [gridDim.x][slab_lines]
   int *lineof;
-  double *Wrow, *Jrec, *Vinv, *bl;
+  double *Wrow, *Jrec, *Vinv, *bl, *Vl;       // (Vl: the lower triangle of V_l, the step side's record)
   unsigned char *failed;
   // outputs (null: not wanted)
   double *H, *g, *U, *bp, *cost, *ms;
   int *n_elig, *n_failed;
-  double *oVinv, *obl, *oW;
+  double *oVinv, *obl, *oW, *oV;
   unsigned char *ofailed;
 };
 
@@ -109,6 +109,7 @@ __global__ __launch_bounds__(RC_THREADS) void k_line_reduce(ReduceBatch P) {
   const size_t slab = (size_t)blockIdx.x * P.slab_lines;
   int *lineof = P.lineof + slab;
   double *Wrow = P.Wrow + slab * RC_WROW, *Jrec = P.Jrec + slab * RC_JROW, *Vinv = P.Vinv + slab * 16, *bl = P.bl + slab * 4;
+  double *Vl = P.Vl + slab * 10;
   unsigned char *failed = P.failed + slab;
   // the frame-sum entries of this thread
   int tf[RC_TPT], ta[RC_TPT], ta2[RC_TPT], tb[RC_TPT], tb2[RC_TPT];
@@ -159,7 +160,8 @@ __global__ __launch_bounds__(RC_THREADS) void k_line_reduce(ReduceBatch P) {
       line_plk_to_pose(P.plk_in + 6 * (size_t)l, Cw[s].R, Cw[s].t, lw);     // para_LineFeature = plk_to_orth(plk_to_pose(line_plucker, Rwc, twc))
       line_plk_to_orth(lw, x);
       const bool ok = line_reduce_line(Bs, Ex, x, s, k0, line_nobs<TAB>(P, l), line_obs<TAB>(P, l), P.sqrt_info, P.huber, P.mu,
-                                       Wrow + (size_t)q * RC_WROW, Jrec + (size_t)q * RC_JROW, Vinv + (size_t)q * 16, bl + (size_t)q * 4, &c);
+                                       Wrow + (size_t)q * RC_WROW, Jrec + (size_t)q * RC_JROW, Vinv + (size_t)q * 16, bl + (size_t)q * 4, &c,
+                                       Vl + (size_t)q * 10);
       failed[q] = ok ? 0 : 1;
       if (ok) csum += c; else nfail += 1.0;
     }
@@ -264,6 +266,7 @@ __global__ __launch_bounds__(RC_THREADS) void k_line_reduce(ReduceBatch P) {
     if (P.oVinv) for (int i = t; i < n_elig * 16; i += RC_THREADS) P.oVinv[ro * 16 + i] = failed[i >> 4] ? 0.0 : Vinv[i];
     if (P.obl) for (int i = t; i < n_elig * 4; i += RC_THREADS) P.obl[ro * 4 + i] = failed[i >> 2] ? 0.0 : bl[i];
     if (P.oW) for (int i = t; i < n_elig * RC_WROW; i += RC_THREADS) P.oW[ro * RC_WROW + i] = failed[i / RC_WROW] ? 0.0 : Wrow[i];
+    if (P.oV) for (int i = t; i < n_elig * 10; i += RC_THREADS) P.oV[ro * 10 + i] = failed[i / 10] ? 0.0 : Vl[i];
     if (P.ofailed) for (int i = t; i < n_elig; i += RC_THREADS) P.ofailed[ro + i] = failed[i];
     if (t == 0) {
       if (P.cost) P.cost[w] = red[0];
@@ -282,19 +285,29 @@ __global__ __launch_bounds__(RC_THREADS) void k_line_reduce(ReduceBatch P) {
   } while (0)
 
 bool reduce_args_ok(gfbe_ctx *c, const char *who, int32_t mode, double mu, const gfbe_line_reduced *out) {
-  if (!out || out->struct_size != (int32_t)sizeof(gfbe_line_reduced)) { ctx_set_error(c, (std::string(who) + ": gfbe_line_reduced ABI mismatch").c_str()); return false; }
+  // (both sizes of the structure are admitted: a caller built before the member V existed sees no change)
+  if (!out || (out->struct_size != (int32_t)sizeof(gfbe_line_reduced) && out->struct_size != GFBE_LINE_REDUCED_SIZE_V0)) { ctx_set_error(c, (std::string(who) + ": gfbe_line_reduced ABI mismatch").c_str()); return false; }
   if (mode != GFBE_LINE_REDUCE_SOLVE && mode != GFBE_LINE_REDUCE_MARG_OLD) return false;
   return mu >= 0.0 && std::isfinite(mu);
+}
+// the caller's structure at the library's size (V = NULL for the smaller one)
+gfbe_line_reduced reduced_full(const gfbe_line_reduced *out) {
+  gfbe_line_reduced r{};
+  std::memcpy(&r, out, (size_t)out->struct_size);
+  if (out->struct_size == GFBE_LINE_REDUCED_SIZE_V0) r.V = nullptr;
+  return r;
 }
 
 // Launch and hand-over shared by the two entry points. P: the line inputs on the device; nlines [W]: lines per window (the record
 // slots). h_pose / h_ex (table-fed): the poses on the host, copied into the call's allocation. cache (table-fed): the table handle's
 // scratch allocation, kept between calls and grown on demand — a per-frame caller pays no hipMalloc / hipFree; without it the
-// allocation lives for the call (the host-fed entry point, as gfbe_line_refine).
+// allocation lives for the call (the host-fed entry point, as gfbe_line_refine). keep (table-fed, solve mode, gfbe_ltab_keep_records on):
+// the per-line records are written into the store on the table handle instead of the call's allocation — the same values from the same
+// kernel, so the call's outputs keep their bits — and stay there for gfbe_ltab_step.
 struct ReduceCache { char **d; size_t *cap; };
 template <bool TAB>
-gfbe_status reduce_run(gfbe_ctx *c, ReduceBatch P, int W, const std::vector<int> &nlines, gfbe_line_reduced *out, const double *h_pose,
-                       const double *h_ex, ReduceCache cache) {
+gfbe_status reduce_run(gfbe_ctx *c, ReduceBatch P, int W, const std::vector<int> &nlines, const gfbe_line_reduced *out, const double *h_pose,
+                       const double *h_ex, ReduceCache cache, gfbe_ltab *keep = nullptr) {
   hipStream_t s = ctx_stream(c);
   gfbe_status st = GFBE_OK;
   std::vector<int> rec_off(W + 1, 0);
@@ -304,9 +317,9 @@ gfbe_status reduce_run(gfbe_ctx *c, ReduceBatch P, int W, const std::vector<int>
   const int grid = std::min(W, (int)RC_MAX_GRID);
   const size_t slab_lines = (size_t)maxl + RC_CHUNK, S = (size_t)grid * slab_lines;
   auto up8 = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const bool rec = out->Vinv || out->bl || out->W || out->failed;
+  const bool rec = out->Vinv || out->bl || out->W || out->failed || out->V;
   char *d = nullptr;
-  std::vector<double> hH, hU, hg, hbp, hcost, hms, hV, hb, hW;
+  std::vector<double> hH, hU, hg, hbp, hcost, hms, hV, hb, hW, hVl;
   std::vector<int> hne(W), hnf(W);
   std::vector<unsigned char> hf;
   // the layout of the call's one device allocation: laid out once from a null base for its size, then from the allocation
@@ -319,15 +332,26 @@ gfbe_status reduce_run(gfbe_ctx *c, ReduceBatch P, int W, const std::vector<int>
     if (h_pose) { P.pose = (double *)take(8 * 77 * (size_t)W); P.ex = (double *)take(8 * 7 * (size_t)W); }
     P.lineof = (int *)take(sizeof(int) * S);
     P.Wrow = (double *)take(8 * S * RC_WROW); P.Jrec = (double *)take(8 * S * RC_JROW);
-    P.Vinv = (double *)take(8 * S * 16); P.bl = (double *)take(8 * S * 4); P.failed = (unsigned char *)take(S);
+    P.Vinv = (double *)take(8 * S * 16); P.bl = (double *)take(8 * S * 4); P.Vl = (double *)take(8 * S * 10); P.failed = (unsigned char *)take(S);
     P.H = out->H ? (double *)take(8 * n5k) : nullptr; P.U = out->U ? (double *)take(8 * n5k) : nullptr;
     P.g = (double *)take(8 * n72); P.bp = (double *)take(8 * n72);
     P.cost = (double *)take(8 * (size_t)W); P.ms = out->ms_kernel ? (double *)take(16 * (size_t)W) : nullptr;
     P.n_elig = (int *)take(4 * (size_t)W); P.n_failed = (int *)take(4 * (size_t)W);
-    if (rec) {
+    if (rec && !keep) {
       P.oVinv = out->Vinv ? (double *)take(8 * N * 16) : nullptr; P.obl = out->bl ? (double *)take(8 * N * 4) : nullptr;
-      P.oW = out->W ? (double *)take(8 * N * RC_WROW) : nullptr; P.ofailed = (unsigned char *)take(N + 1);
+      P.oW = out->W ? (double *)take(8 * N * RC_WROW) : nullptr; P.oV = out->V ? (double *)take(8 * N * 10) : nullptr;
+      P.ofailed = (unsigned char *)take(N + 1);
     }
+    return (size_t)(p - p0);
+  };
+  // the store on the table handle: rec_off, then every record array at full size
+  int *k_off = nullptr;
+  auto keep_layout = [&](char *p) -> size_t {
+    char *const p0 = p;
+    auto take = [&](size_t bytes) { char *q = p; p += up8(bytes); return q; };
+    k_off = (int *)take(sizeof(int) * (W + 1));
+    P.oVinv = (double *)take(8 * N * 16); P.obl = (double *)take(8 * N * 4); P.oW = (double *)take(8 * N * RC_WROW);
+    P.oV = (double *)take(8 * N * 10); P.ofailed = (unsigned char *)take(N + 1);
     return (size_t)(p - p0);
   };
   {
@@ -340,6 +364,18 @@ gfbe_status reduce_run(gfbe_ctx *c, ReduceBatch P, int W, const std::vector<int>
       if (cache.d) { *cache.d = d; *cache.cap = need; }
     }
     (void)layout(d);
+    if (keep) {
+      keep->rec_valid = false; keep->cand_valid = false;
+      const size_t kneed = keep_layout(nullptr);
+      if (keep->rec_cap < kneed) {
+        RD_CHECK(c, hipStreamSynchronize(s));
+        if (keep->rec_d) { (void)hipFree(keep->rec_d); keep->rec_d = nullptr; keep->rec_cap = 0; }
+        RD_CHECK(c, hipMalloc((void **)&keep->rec_d, kneed));
+        keep->rec_cap = kneed;
+      }
+      (void)keep_layout(keep->rec_d);
+      RD_CHECK(c, hipMemcpyAsync(k_off, rec_off.data(), sizeof(int) * (W + 1), hipMemcpyHostToDevice, s));
+    }
     P.n_windows = W; P.slab_lines = (int)slab_lines;
     if (h_pose) {
       RD_CHECK(c, hipMemcpyAsync((void *)P.pose, h_pose, 8 * 77 * (size_t)W, hipMemcpyHostToDevice, s));
@@ -362,6 +398,7 @@ gfbe_status reduce_run(gfbe_ctx *c, ReduceBatch P, int W, const std::vector<int>
   if (out->bl) RD_DOWN(hb, P.obl, N * 4);
   if (out->W) RD_DOWN(hW, P.oW, N * RC_WROW);
   if (out->failed) RD_DOWN(hf, P.ofailed, N);
+  if (out->V) RD_DOWN(hVl, P.oV, N * 10);
 #undef RD_DOWN
   RD_CHECK(c, hipStreamSynchronize(s));
   // (outputs are written only once the whole call has succeeded)
@@ -381,8 +418,16 @@ gfbe_status reduce_run(gfbe_ctx *c, ReduceBatch P, int W, const std::vector<int>
       if (out->bl && n) std::memcpy(out->bl + o * 4, hb.data() + from * 4, 8 * n * 4);
       if (out->W && n) std::memcpy(out->W + o * RC_WROW, hW.data() + from * RC_WROW, 8 * n * RC_WROW);
       if (out->failed && n) std::memcpy(out->failed + o, hf.data() + from, n);
+      if (out->V && n) std::memcpy(out->V + o * 10, hVl.data() + from * 10, 8 * n * 10);
       o += n;
     }
+  }
+  if (keep) {
+    keep->rec_Vinv = P.oVinv; keep->rec_bl = P.obl; keep->rec_W = P.oW; keep->rec_V = P.oV; keep->rec_failed = P.ofailed; keep->rec_off_d = k_off;
+    keep->rec_off = rec_off; keep->rec_ne.assign(hne.begin(), hne.end());
+    keep->rec_pose.assign(h_pose, h_pose + 77 * (size_t)W);
+    keep->rec_pose.insert(keep->rec_pose.end(), h_ex, h_ex + 7 * (size_t)W);
+    keep->rec_mu = P.mu; keep->rec_gen = keep->gen; keep->rec_valid = true;
   }
 done:
   if (d && !cache.d) (void)hipFree(d);
@@ -395,6 +440,7 @@ extern "C" gfbe_status gfbe_line_reduce(gfbe_ctx *c, int32_t n_windows, const gf
                                         double huber_width, double mu, gfbe_line_reduced *out) {
   if (!c || n_windows < 0 || (n_windows > 0 && !win)) return GFBE_BAD_INPUT;
   if (!reduce_args_ok(c, "gfbe_line_reduce", mode, mu, out)) return GFBE_BAD_INPUT;
+  const gfbe_line_reduced full = reduced_full(out);
   // the windows: sizes, frames and pointers (the checks of gfbe_line_refine; observation VALUES are not looked at)
   std::vector<int> line_off(n_windows + 1, 0), nlines(n_windows, 0);
   size_t n_obs_total = 0;
@@ -461,7 +507,7 @@ extern "C" gfbe_status gfbe_line_reduce(gfbe_ctx *c, int32_t n_windows, const gf
     RD_CHECK(c, hipMemcpyAsync(d_dbl, dbl.data(), b_dbl, hipMemcpyHostToDevice, s));
     RD_CHECK(c, hipMemcpyAsync(d_tri, h_tri.data(), b_tri, hipMemcpyHostToDevice, s));
   }
-  st = reduce_run<false>(c, P, n_windows, nlines, out, nullptr, nullptr, ReduceCache{nullptr, nullptr});     // (synchronises the stream: the packed host buffers stay alive until then)
+  st = reduce_run<false>(c, P, n_windows, nlines, &full, nullptr, nullptr, ReduceCache{nullptr, nullptr});     // (synchronises the stream: the packed host buffers stay alive until then)
 done:
   if (d) { (void)hipStreamSynchronize(s); (void)hipFree(d); }
   return st;
@@ -471,6 +517,7 @@ extern "C" gfbe_status gfbe_ltab_reduce(gfbe_ctx *c, gfbe_ltab *t, int32_t mode,
                                         double huber_width, double mu, gfbe_line_reduced *out) {
   if (!c) return GFBE_BAD_INPUT;
   if (!reduce_args_ok(c, "gfbe_ltab_reduce", mode, mu, out)) return GFBE_BAD_INPUT;
+  const gfbe_line_reduced full = reduced_full(out);
   if (ctx_device(c) < 0) { ctx_set_error(c, "gfbe_ltab_reduce: HIP device context required (no CPU fallback)"); return GFBE_NO_DEVICE; }
   if (!t || !pose7 || !ex_cam) return GFBE_BAD_INPUT;
   const int W = t->d.W, b = t->cur;
@@ -484,7 +531,8 @@ extern "C" gfbe_status gfbe_ltab_reduce(gfbe_ctx *c, gfbe_ltab *t, int32_t mode,
   P.count = t->d.count; P.nobs = t->d.nobs[b]; P.F = t->d.F; P.start = t->d.start[b]; P.tri = t->d.tri[b]; P.plk_in = t->d.plk[b];
   P.obs = t->d.obs[b];
   P.sqrt_info = sqrt_info; P.huber = huber_width; P.mu = mu; P.mode = mode;
-  st = reduce_run<true>(c, P, W, nlines, out, pose7, ex_cam, ReduceCache{&t->reduce_d, &t->reduce_cap});
+  st = reduce_run<true>(c, P, W, nlines, &full, pose7, ex_cam, ReduceCache{&t->reduce_d, &t->reduce_cap},
+                        t->keep_records && mode == GFBE_LINE_REDUCE_SOLVE ? t : nullptr);
 done:
   return st;
 }

@@ -264,6 +264,7 @@ gfbe_status lt_erase(gfbe_ctx *c, gfbe_ltab *t, int op, const double *a, const d
   gfbe_status st = lt_ready(c, t);
   if (st != GFBE_OK) return st;
   const int W = t->d.W;
+  t->gen++;      // (records of a reduce before this operation no longer describe the tables: gfbe_ltab_step refuses them)
   {
     Staged s(c, t, (size_t)W * 256 + 8 * 256, /*defer=*/true);
     double *da = a ? s.up(a, 12 * (size_t)W) : nullptr, *db = b ? s.up(b, 12 * (size_t)W) : nullptr;
@@ -314,6 +315,8 @@ void gfbe_ltab_destroy(gfbe_ctx *c, gfbe_ltab *t) {
   if (c && ctx_device(c) >= 0) (void)hipStreamSynchronize(ctx_stream(c));
   for (void *p : t->allocs) (void)hipFree(p);
   if (t->reduce_d) (void)hipFree(t->reduce_d);
+  if (t->rec_d) (void)hipFree(t->rec_d);
+  if (t->step_d) (void)hipFree(t->step_d);
   if (t->stage_d) (void)hipFree(t->stage_d);
   if (t->stage_h) (void)hipHostFree(t->stage_h);
   if (t->ring_d) (void)hipFree(t->ring_d);
@@ -335,6 +338,7 @@ gfbe_status gfbe_ltab_add_frame(gfbe_ctx *c, gfbe_ltab *t, const int32_t *frame_
       if (line_id[k] <= line_id[k - 1]) { ctx_set_error(c, "gfbe_ltab_add_frame: line ids of a table must be strictly ascending"); return GFBE_BAD_INPUT; }
   }
   std::vector<int> err(W, 0);
+  t->gen++;
   {
     Staged s(c, t, (size_t)M * (OW * 8 + 8) + (size_t)W * 64 + 16 * 256);
     int *dfc = s.up(frame_count, W), *doff = s.up(offset, W + 1), *dlid = s.up(line_id, M);
@@ -362,6 +366,7 @@ gfbe_status gfbe_ltab_triangulate(gfbe_ctx *c, gfbe_ltab *t, const double *poses
   if (st != GFBE_OK) return st;
   if (!poses || !tic_ric) return GFBE_BAD_INPUT;
   const int W = t->d.W;
+  t->gen++;
   {
     Staged s(c, t, (size_t)W * 144 * 8 + 8 * 256, /*defer=*/true);
     double *dp = s.up(poses, 132 * (size_t)W), *de = s.up(tic_ric, 12 * (size_t)W);
@@ -390,6 +395,7 @@ gfbe_status gfbe_ltab_refine(gfbe_ctx *c, gfbe_ltab *t, const double *pose7, con
   if (!pose7 || !ex_cam || !summary || !(cauchy_scale > 0.0) || max_num_iterations < 0) return GFBE_BAD_INPUT;
   const int W = t->d.W, b = t->cur;
   std::vector<gfbe_summary> h_sum(W);
+  t->gen++;
   {
     Staged s(c, t, (size_t)W * (84 * 8 + sizeof(gfbe_summary)) + 8 * 256);
     double *dp = s.up(pose7, 77 * (size_t)W), *de = s.up(ex_cam, 7 * (size_t)W);
@@ -464,6 +470,7 @@ gfbe_status gfbe_ltab_upload(gfbe_ctx *c, gfbe_ltab *t, int32_t w, int32_t n, co
     if (start[i] < 0 || nobs[i] < 1 || start[i] + nobs[i] > NOBS) { ctx_set_error(c, "gfbe_ltab_upload: a line's observations must lie in frames 0 .. WINDOW_SIZE"); return GFBE_BAD_INPUT; }
   const size_t base = (size_t)w * t->d.F;
   const int b = t->cur;
+  t->gen++;
   {
     // one staged copy up, then device-to-device into the table's arrays; observation rows past n_obs are stored as zeros
     const size_t N = (size_t)std::max(n, 1);

@@ -666,11 +666,66 @@ typedef struct gfbe_line_reduced {
   uint8_t *failed;                    /* [.] 1: left out (its Vinv, bl, W are not meaningful) */
   double *ms_kernel;                  /* [W][2] the window's time in the kernel, and the part of it in the matrix-core contraction
                                          loop (device clock, like gfbe_summary.ms_solve) */
+  double *V;                          /* [.][10] the lower triangle of V_l WITHOUT the mu term, row-major (00 10 11 20 21 22 30 31 32 33):
+                                         what the step side needs beside V'_l^-1, which does not give V_l back when a diagonal is
+                                         clamped. A caller built before this member existed passes the smaller struct_size
+                                         (GFBE_LINE_REDUCED_SIZE_V0); both sizes are admitted, and the smaller one means V = NULL. */
 } gfbe_line_reduced;
+#define GFBE_LINE_REDUCED_SIZE_V0 ((int32_t)offsetof(gfbe_line_reduced, V))
 /* Host-fed: the windows of gfbe_line_refine. GFBE_BAD_INPUT (bad mode, negative or non-finite mu, wrong struct_size of either
  * structure, observations past the window), GFBE_NO_DEVICE, GFBE_DEVICE_ERROR: no output has been touched. */
 gfbe_status gfbe_line_reduce(gfbe_ctx *ctx, int32_t n_windows, const gfbe_line_window *const *win, int32_t mode, double sqrt_info,
                              double huber_width, double mu, gfbe_line_reduced *out);
+
+/* ------------------------------------------------------------------------------------------
+ * The step half of a joint trust-region iteration over the line blocks (solve mode only; MARG_OLD has no step): everything the
+ * iteration does with the line blocks once the pose / extrinsic directions exist. The scalar landmark code of the window solve,
+ * generalised to a 4-dimensional block in the coordinates of gfbe_line_reduce:
+ *   - line columns are NOT Jacobi-scaled; the block's metric is d2_l = clamp(diag V_l, 1e-6, 1e32), the diagonal of the V'_l term above.
+ *     While no diagonal is clamped every scalar below is invariant under Ceres' column scaling; with a clamped diagonal it is not (Ceres
+ *     clamps the scaled diagonal) - a deviation, stated in DESIGN.md section 10.3;
+ *   - pose / extrinsic vectors are in the same unscaled tangent coordinates as H, g.
+ * Inputs per window: y_p [72] the caller's Gauss-Newton direction, (H_all + mu D^2) y = g_all; v_p [72] its D^-2 g_all; rest [8] the
+ * eight scalars of everything that is not a line block, p = [G2, N2, gy, vHv, vHy, yHy, max|gradient|, |x|^2]; radius; the poses and
+ * ex_cam the records were reduced at; mu, the one they were reduced with (V'_l^-1 carries it; it is validated and not used again).
+ * Per entering, non-failed line with the records Vinv, bl, W, V:
+ *     y_l = Vinv (bl - W^T y_p);   v_l = bl / d2_l
+ *     G2 = sum bl^2 / d2;  N2 = sum d2 y_l^2;  gy = bl . y_l
+ *     vHv = 2 v_l . W^T v_p + v_l^T V_l v_l;   vHy = v_l . W^T y_p + y_l . W^T v_p + v_l^T V_l y_l;   yHy = 2 y_l . W^T y_p + y_l^T V_l y_l
+ *     max |x_l - Plus(x_l, -bl)|_inf (the gradient norm as Ceres takes it through the manifold);   |x_l|^2 over the four parameters
+ * total = rest + the line shares (entry 6: the larger), summed in a fixed order. alpha = G2 / vHv; c1, c2, step_norm, model_change by
+ * the three-branch dogleg rule of the window solve (Gauss-Newton inside the radius: 0, -1; Cauchy point outside: -radius / |g|, 0;
+ * else the point of the dogleg on the boundary), step = c1 v + c2 y. model_change <= 0 (or NaN): invalid = 1, no candidate is formed -
+ * every candidate array holds its input, cost_cand the largest double - and the caller raises mu and reduces again (HandleInvalidStep).
+ * Otherwise delta_l = c1 v_l + c2 y_l, x_l' = LineOrthParameterization::Plus(x_l, delta_l); candidate poses and extrinsic =
+ * Plus(., c1 v_p + c2 y_p) of the pose blocks; plucker_cand = x_l' expressed in the CANDIDATE start frame's camera (setLineOrth);
+ * cost_cand = sum of 1/2 rho_huber over the entering lines' observations at the candidate poses and lines.
+ * A failed line takes part in nothing: y_l = v_l = 0, orth_cand = x_l and plucker_cand = its input, bit for bit.
+ * Per-line arrays are concatenated over the windows in the order of the records. Any pointer may be NULL.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct gfbe_line_stepped {
+  int32_t struct_size;                /* sizeof(gfbe_line_stepped) as the caller was built (refused otherwise: GFBE_BAD_INPUT) */
+  int32_t reserved;                   /* 0 */
+  double *gram;                       /* [W][8] the line shares */
+  double *total;                      /* [W][8] rest + gram */
+  double *coef;                       /* [W][4] c1, c2, step_norm, model_change */
+  uint8_t *invalid;                   /* [W] */
+  double *y_l;                        /* [.][4] */
+  double *v_l;                        /* [.][4] */
+  double *orth_cand;                  /* [.][4] */
+  double *plucker_cand;               /* [.][6] in the candidate start frame's camera frame */
+  double *pose_cand;                  /* [W][11][7] */
+  double *ex_cand;                    /* [W][7] */
+  double *cost_cand;                  /* [W] */
+  double *ms_kernel;                  /* [W] the window's time in the kernel (device clock) */
+} gfbe_line_stepped;
+/* Host-fed, stateless: win and rec are the windows gfbe_line_reduce ran on (solve mode) and what it wrote for them - Vinv, bl, W, V,
+ * failed, n_eligible, all required. y_p, v_p [W][72], rest [W][8], radius [W]. GFBE_BAD_INPUT: a wrong struct_size of any structure, a
+ * missing record array, n_eligible that is not the windows' own count, a negative or non-finite mu or radius, a non-finite y_p, v_p or
+ * rest. GFBE_NO_DEVICE, GFBE_DEVICE_ERROR as elsewhere. On any error no output has been touched. */
+gfbe_status gfbe_line_step(gfbe_ctx *ctx, int32_t n_windows, const gfbe_line_window *const *win, const gfbe_line_reduced *rec,
+                           double sqrt_info, double huber_width, double mu, const double *y_p, const double *v_p, const double *rest,
+                           const double *radius, gfbe_line_stepped *out);
 
 /* ------------------------------------------------------------------------------------------
  * Line feature tables: FeatureManager::linefeature on the device, and the line calls of a use_line frame against it
@@ -726,6 +781,24 @@ gfbe_status gfbe_ltab_refine(gfbe_ctx *ctx, gfbe_ltab *t, const double *pose7, c
  * the table handle between calls, grows to the largest size ever needed and is released by gfbe_ltab_destroy. */
 gfbe_status gfbe_ltab_reduce(gfbe_ctx *ctx, gfbe_ltab *t, int32_t mode, const double *pose7, const double *ex_cam, double sqrt_info,
                              double huber_width, double mu, gfbe_line_reduced *out);
+/* The step half against the tables (the product path; conventions: gfbe_line_step above). A joint iteration is
+ *   gfbe_ltab_reduce -> the caller's 72-dim solve -> gfbe_ltab_step -> the caller's accept test -> gfbe_ltab_commit.
+ * gfbe_ltab_keep_records: off by default (behaviour and memory as without it). While on, gfbe_ltab_reduce in solve mode also leaves every
+ *   entering line's Vinv, bl, W, V, failed in a per-line store on the table handle (2.5 KB per line slot, one slot per line of the
+ *   tables; grown on demand, released by gfbe_ltab_destroy), together with the mu and the pose bits of the call. The line's
+ *   orthonormal form is not stored: the step forms it from the table and the poses with the operations of the reduce, the same bits.
+ *   The outputs of gfbe_ltab_reduce keep their bits. Switching it off drops the store's contents.
+ * gfbe_ltab_step: reads that store and the tables in place, keeps the candidates on the handle and copies down only what `out` asks
+ *   for. y_p, v_p [W][72], rest [W][8], radius [W]. GFBE_BAD_INPUT when no records are held, when any gfbe_ltab_* operation has changed
+ *   the tables since the reduce that wrote them (a generation counter on the handle), or when pose7 / ex_cam differ in any bit from the
+ *   reduce's. With the same bits every output equals gfbe_line_step's on the downloaded list, bit for bit.
+ * gfbe_ltab_commit: tables with accept[w] != 0 take their candidate Pluecker vectors (the entering, non-failed lines); every other
+ *   table, every non-entering line and every failed line keeps its bits. Deferred like the other table operations without outputs.
+ *   It invalidates the records and the candidates: the next step needs a new reduce. GFBE_BAD_INPUT without candidates. */
+gfbe_status gfbe_ltab_keep_records(gfbe_ctx *ctx, gfbe_ltab *t, int32_t on);
+gfbe_status gfbe_ltab_step(gfbe_ctx *ctx, gfbe_ltab *t, const double *pose7, const double *ex_cam, double sqrt_info, double huber_width,
+                           const double *y_p, const double *v_p, const double *rest, const double *radius, gfbe_line_stepped *out);
+gfbe_status gfbe_ltab_commit(gfbe_ctx *ctx, gfbe_ltab *t, const uint8_t *accept /*[W]*/);
 /* linefeature.size() and getLineFeatureCount() (feature_manager.cpp:1013-1027) of every table. */
 gfbe_status gfbe_ltab_size(gfbe_ctx *ctx, gfbe_ltab *t, int32_t *n_lines);
 gfbe_status gfbe_ltab_line_count(gfbe_ctx *ctx, gfbe_ltab *t, int32_t *count);

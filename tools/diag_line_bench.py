@@ -16,7 +16,14 @@ The two legs' results are compared bit for bit once per size. Output: stdout, an
 table-fed, solve mode, HuberLoss(1.0), mu = 0; outputs asked for: H, g, cost, the counts and ms_kernel — what the join into the window
 solve takes; the per-line records stay on the device side of this measurement). The tables are not edited by the call, so they are
 seeded once. kernel / mfma: the longest time one window spent in the kernel and in its matrix-core contraction loop (ms_kernel, device
-clock); the sum over the windows divided by the 256 workgroups in flight estimates the kernel's own duration for the large batches."""
+clock); the sum over the windows divided by the 256 workgroups in flight estimates the kernel's own duration for the large batches.
+
+--step: the same measurement for the step half of a joint iteration (gfbe_line_step host-fed against gfbe_ltab_step table-fed on the
+records a solve-mode gfbe_ltab_reduce kept on the handle; outputs asked for: total, coef, invalid, cost_cand, ms_kernel - what the
+caller's accept test takes; the candidates stay on the device). y_p, v_p, rest: seeded, the radius large (the Gauss-Newton branch).
+gfbe_ltab_reduce on the same tables is timed in the same repetitions, for scale. kernel: the sum of the windows' times in k_line_step
+divided by the workgroups in flight (device clock), and the bytes of the records it streams (2544 per entering line: W, Vinv, bl, V)
+over that time as a fraction of the 8 TB/s HBM peak."""
 import argparse
 import time
 
@@ -85,11 +92,69 @@ def reduce_leg(be, base, holders, seeds, sizes, say):
     say("numpy checker (FP64): %.1f ms / window" % ((time.perf_counter() - t0) / 2 * 1e3))
 
 
+def step_leg(be, base, holders, seeds, sizes, say):
+    want_r = ("H", "g", "cost", "n_eligible", "n_failed", "ms_kernel")
+    want_s = ("total", "coef", "invalid", "cost_cand", "ms_kernel")
+    rng = np.random.default_rng(5)
+    for nw in sizes:
+        hs = [holders[k % len(holders)] for k in range(nw)]
+        tabs = be.line_tables(nw, 160)
+        for w in range(nw):
+            tabs.upload(w, seeds[w % len(seeds)])
+        tabs.keep_records(True)
+        pose7 = np.ascontiguousarray([base[k % len(base)]["pose"] for k in range(nw)])
+        ex = np.ascontiguousarray([base[k % len(base)]["ex_cam"] for k in range(nw)])
+        # the records for the host-fed leg, once (not timed)
+        recs = be.line_reduce_v(hs, 0, 400.0, 1.0, 0.0, ("n_eligible",) + abi.LINE_RECORD_KEYS)
+        rb, ne = abi.line_records_pack(recs)
+        red_h = abi.line_reduced_struct_v(rb)
+        y, v = rng.normal(0, 1e-3, (nw, 72)), rng.normal(0, 1e-3, (nw, 72))
+        rest = np.abs(rng.normal(1, 0.1, (nw, 8))) * np.array([1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0])
+        radius = np.full(nw, 1e4)
+        br = abi.line_reduced_buffers(nw, 1, want_r)
+        rr = abi.line_reduced_struct(br)
+        bh, bt = abi.line_stepped_buffers(nw, 1, want_s), abi.line_stepped_buffers(nw, 1, want_s)
+        sh_, st_ = abi.line_stepped_struct(bh), abi.line_stepped_struct(bt)
+        t_host, t_tab, t_red = [], [], []
+        for rep in range(REPS + 1):          # (rep 0: warm-up of every leg)
+            t0 = time.perf_counter()
+            rc_r = tabs.reduce_raw(pose7, ex, 0, 400.0, 1.0, 0.0, rr)
+            t1 = time.perf_counter()
+            rc_t = tabs.step_raw(pose7, ex, 400.0, 1.0, y, v, rest, radius, st_)
+            t2 = time.perf_counter()
+            rc_h = abi.line_step_raw(be.lib, "gfbe_", be.ctx, hs, red_h, 400.0, 1.0, 0.0, y, v, rest, radius, sh_)
+            t3 = time.perf_counter()
+            assert rc_r == abi.OK and rc_t == abi.OK and rc_h == abi.OK, (rc_r, rc_t, rc_h)
+            if rep:
+                t_red.append((t1 - t0) * 1e3)
+                t_tab.append((t2 - t1) * 1e3)
+                t_host.append((t3 - t2) * 1e3)
+        for k in ("total", "coef", "invalid", "cost_cand"):
+            assert bh[k].tobytes() == bt[k].tobytes(), "table-fed != host-fed: " + k
+        tabs.close()
+
+        def stat(t):
+            return float(np.median(t)), float(max(t) - min(t))
+        (mh, sh), (mt, st), (mr, sr) = stat(t_host), stat(t_tab), stat(t_red)
+        ms = bt["ms_kernel"]
+        kern = ms.sum() / min(nw, 256)
+        nbytes = 2544.0 * float(ne.sum())
+        say("%5d windows: step host-fed %8.3f ms (spread %6.3f) | step table-fed %8.3f ms (spread %6.3f), %7.2f us / window | "
+            "gfbe_ltab_reduce, records kept %8.3f ms (spread %6.3f) | k_line_step per window: max %.4f ms, mean %.4f ms; sum / %d workgroups "
+            "%.4f ms = %.1f GB/s over the records' %.1f MB, %.2f %% of 8 TB/s | entering lines %d, invalid %d" %
+            (nw, mh, sh, mt, st, 1e3 * mt / nw, mr, sr, ms.max(), ms.mean(), min(nw, 256), kern, nbytes / kern * 1e-6, nbytes * 1e-6,
+             100.0 * nbytes / kern * 1e-6 / 8000.0, int(ne[0]), int(bt["invalid"].sum())))
+        say("              step host-fed  [%s]" % " ".join("%.3f" % t for t in t_host))
+        say("              step table-fed [%s]" % " ".join("%.3f" % t for t in t_tab))
+        say("              ltab_reduce    [%s]" % " ".join("%.3f" % t for t in t_red))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--sizes", default="1,256,1024,4096")
     ap.add_argument("--reduce", action="store_true", help="time gfbe_line_reduce / gfbe_ltab_reduce instead of the refinement")
+    ap.add_argument("--step", action="store_true", help="time gfbe_line_step / gfbe_ltab_step (and gfbe_ltab_reduce on the same tables)")
     args = ap.parse_args()
     lines = []
 
@@ -103,8 +168,8 @@ def main():
     seeds = [_table_of(w) for w in base]
     say("lines per window %d, observations per window %.0f (mean); %d repetitions per leg, alternating" %
         (holders[0].n, np.mean([len(h.obs) for h in holders]), REPS))
-    if args.reduce:
-        reduce_leg(be, base, holders, seeds, [int(x) for x in args.sizes.split(",")], say)
+    if args.reduce or args.step:
+        (step_leg if args.step else reduce_leg)(be, base, holders, seeds, [int(x) for x in args.sizes.split(",")], say)
         if args.out:
             with open(args.out, "w") as f:
                 f.write("\n".join(lines) + "\n")
