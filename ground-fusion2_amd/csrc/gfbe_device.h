@@ -436,16 +436,16 @@ struct LtabDev {
   double *row, *plk_out;       // refine scratch: [W][F][line_refine_row_doubles()], [W][F][6]
   unsigned char *rkeep;        // [W][F] keep flags of the refine
 };
-// one half of the tables as k_line_refine<true> reads it
-struct LineTabView {
-  const int *count, *start, *nobs;
-  const unsigned char *tri;
-  const double *plk, *obs;
-  int F;
-};
+struct LineList;              // a batch's line list as the line kernels read it (gfbe_line.h); of the tables: ltab_line_list (gfbe_line_batch.h)
 size_t line_refine_row_doubles();
-void launch_line_refine_tables(const LineTabView &T, int n_tables, const double *pose7, const double *ex_cam, double sqrt_info, double cauchy,
-                               int max_it, double *row, double *plk_out, unsigned char *keep, gfbe_summary *sum, hipStream_t s);
+void launch_line_refine_tables(const LineList &L, int n_tables, double sqrt_info, double cauchy, int max_it, double *row, double *plk_out,
+                               unsigned char *keep, gfbe_summary *sum, hipStream_t s);
+
+// a device allocation kept between calls and grown on demand (grow, gfbe_line_batch.h)
+struct DevBuf {
+  char *d = nullptr;
+  size_t cap = 0;
+};
 
 }  // namespace gfd
 
@@ -479,13 +479,11 @@ struct gfbe_ltab : gfbe_tab_staging {
   gfd::LtabDev d;
   int cur = 0;
   std::vector<void *> allocs;
-  char *reduce_d = nullptr;      // gfbe_ltab_reduce's scratch and output staging, kept between calls (gfbe_line_reduce.hip)
-  size_t reduce_cap = 0;
+  gfd::DevBuf reduce_buf;        // gfbe_ltab_reduce's scratch and output staging, kept between calls (gfbe_line_reduce.hip)
   // the step half of a joint iteration (gfbe_ltab_keep_records / gfbe_ltab_step / gfbe_ltab_commit, gfbe_line_step.hip)
   unsigned long long gen = 0;    // bumped by every operation that may change the tables
   bool keep_records = false;
-  char *rec_d = nullptr;         // the per-line store of a solve-mode reduce: rec_off [W + 1], then Vinv, bl, W, V, failed per line slot
-  size_t rec_cap = 0;
+  gfd::DevBuf rec_buf;           // the per-line store of a solve-mode reduce: rec_off [W + 1], then Vinv, bl, W, V, failed per line slot
   bool rec_valid = false;
   unsigned long long rec_gen = 0;
   double rec_mu = 0.0;
@@ -494,8 +492,7 @@ struct gfbe_ltab : gfbe_tab_staging {
   const double *rec_Vinv = nullptr, *rec_bl = nullptr, *rec_W = nullptr, *rec_V = nullptr;
   const unsigned char *rec_failed = nullptr;
   const int *rec_off_d = nullptr;
-  char *step_d = nullptr;        // gfbe_ltab_step's inputs, outputs and the candidates, kept between calls
-  size_t step_cap = 0;
+  gfd::DevBuf step_buf;          // gfbe_ltab_step's inputs, outputs and the candidates, kept between calls
   bool cand_valid = false;
   const double *cand_plk = nullptr;      // [slots][6]
   const int *cand_lineof = nullptr, *cand_ne = nullptr;      // [slots] line of a record, [W] entering lines

@@ -1,5 +1,7 @@
 // gfbe_line.h — line landmarks: the orthonormal line representation, the line projection factor and the culling test, as
-// __host__ __device__ functions used by csrc/gfbe_line.hip (and compiled for the host by tests/line_host_shim.cpp).
+// __host__ __device__ functions used by csrc/gfbe_line.hip (and compiled for the host by tests/line_host_shim.cpp); the line list of a
+// batch (LineList) and the kernel-side pieces gfbe_line.hip, gfbe_line_reduce.hip and gfbe_line_step.hip share: the accessors, a
+// window's prologue, the rank of the entering lines and the fixed-order workgroup reduction.
 // Reference semantics:
 //   plk_to_orth / orth_to_plk / plk_to_pose / plk_from_pose   utility/line_geometry.cpp:56-113, 181-200
 //   lineProjectionFactor::Evaluate                            factor/line_projection_factor.cpp:18-231
@@ -9,6 +11,9 @@
 // Plücker lines are [n(3) | v(3)] (moment, direction); orthonormal lines [theta(3) | phi]. Poses are [p(3) | q(x, y, z, w)].
 #pragma once
 #include "gfbe_math.h"
+#ifdef GFBE_NFRAMES      // (a kernel translation unit: line_rank scans with block_exclusive_scan)
+#include "gfbe_tabstage.h"
+#endif
 
 namespace gfd {
 
@@ -330,22 +335,95 @@ GF_HD double line_step_candidate(const LineRT *Bc, const LineRT &Exc, const Line
   return cost;
 }
 
-// ---- a batch's line list as the kernels read it (k_line_refine, k_line_reduce). B: a structure with the members line_off, obs_off
-//      (host-fed CSR: TAB = false) or count, nobs, F (the line tables in place: TAB = true), and start, tri, obs for both.
-#if defined(__HIPCC__)
-enum { LINE_TAB_NOBS = 11, LINE_WINDOW = 10 };      // observation slots of a table row (WINDOW_SIZE + 1), WINDOW_SIZE
-#ifdef GFBE_NFRAMES      // (the kernels include gfbe_device.h first; the host shims of the tests do not know the ABI header)
-static_assert(LINE_TAB_NOBS == GFBE_NFRAMES && LINE_WINDOW == GFBE_WINDOW_SIZE, "gfbe_line.h: window constants differ from gfbe.h");
-#endif
-template <bool TAB, class B>
-__device__ __forceinline__ int line_nobs(const B &P, int l) { return TAB ? P.nobs[l] : P.obs_off[l + 1] - P.obs_off[l]; }
-template <bool TAB, class B>
-__device__ __forceinline__ const double *line_obs(const B &P, int l) {
-  return P.obs + 4 * (TAB ? (size_t)l * LINE_TAB_NOBS : (size_t)P.obs_off[l]);
+// ---- a batch's line list as the kernels of gfbe_line.hip, gfbe_line_reduce.hip and gfbe_line_step.hip read it. Host-fed (TAB = false):
+//      a CSR description packed by the host (upload_line_windows, gfbe_line_batch.h). Table-fed (TAB = true): the device-resident line
+//      tables read IN PLACE (ltab_line_list) — window w owns lines [w F, w F + count[w]), line l has nobs[l] observations in its fixed
+//      row of GFBE_NFRAMES slots. No scan, no compaction: a line's observations are contiguous either way, so the kernels walk the same
+//      values in the same order and the arithmetic is the same instruction for instruction.
+struct LineList {
+  const int *line_off;          // [n_windows + 1]                          (host-fed)
+  const int *obs_off;           // [n_lines + 1] (over the whole batch)     (host-fed)
+  const int *count, *nobs;      // [n_windows], [n_windows][F]              (table-fed)
+  int F;                        // line capacity of a table                 (table-fed)
+  const int *start;             // [n_lines]
+  const unsigned char *tri;     // [n_lines]
+  const double *plk_in;         // [n_lines][6]
+  const double *obs;            // [n_obs][4]
+  const double *pose;           // [n_windows][11][7]
+  const double *ex;             // [n_windows][7]
+};
+
+#if defined(__HIPCC__) && defined(GFBE_NFRAMES)      // (the kernels include gfbe_device.h first; the host shims of the tests do not know the ABI header)
+template <bool TAB>
+__device__ __forceinline__ int line_nobs(const LineList &L, int l) { return TAB ? L.nobs[l] : L.obs_off[l + 1] - L.obs_off[l]; }
+template <bool TAB>
+__device__ __forceinline__ const double *line_obs(const LineList &L, int l) {
+  return L.obs + 4 * (TAB ? (size_t)l * GFBE_NFRAMES : (size_t)L.obs_off[l]);
 }
-template <bool TAB, class B>
-__device__ __forceinline__ bool line_eligible(const B &P, int l) {
-  return line_nobs<TAB>(P, l) >= 5 && P.start[l] < LINE_WINDOW - 2 && P.tri[l];   // LINE_MIN_OBS, WINDOW_SIZE - 2
+template <bool TAB>
+__device__ __forceinline__ bool line_eligible(const LineList &L, int l) {
+  return line_nobs<TAB>(L, l) >= 5 && L.start[l] < GFBE_WINDOW_SIZE - 2 && L.tri[l];   // LINE_MIN_OBS, WINDOW_SIZE - 2
+}
+// the lines [*l0, *l1) of window w
+template <bool TAB>
+__device__ __forceinline__ void line_range(const LineList &L, int w, int *l0, int *l1) {
+  *l0 = TAB ? w * L.F : L.line_off[w];
+  *l1 = TAB ? *l0 + L.count[w] : L.line_off[w + 1];
+}
+// A window's prologue, in two halves with a workgroup barrier between them (the barrier stays in the kernel, which stages its own
+// data beside these): the poses and the extrinsic of window w into LDS, then the cameras Rwc = Rs ric, twc = Ps + Rs tic.
+__device__ __forceinline__ void line_stage_poses(const LineList &L, int w, LineRT *Bs, LineRT *Ex) {
+  const int t = threadIdx.x;
+  if (t < GFBE_NFRAMES) Bs[t] = line_make_pose(L.pose + (size_t)w * 77 + 7 * t);
+  if (t == GFBE_NFRAMES) *Ex = line_make_pose(L.ex + (size_t)w * 7);
+}
+__device__ __forceinline__ void line_stage_cameras(const LineRT *Bs, const LineRT &Ex, LineRT *Cw) {
+  const int t = threadIdx.x;
+  if (t < GFBE_NFRAMES) { Cw[t].R = mul(Bs[t].R, Ex.R); Cw[t].t = add(Bs[t].t, mv(Bs[t].R, Ex.t)); }
+}
+// Fixed-order reduction of NQ per-thread values over a workgroup of WAVES waves: the shuffle tree within a wave, then the waves in
+// index order starting from 0.0; bit q of maxmask: entry q is a maximum (fmax(0.0, .)) instead of a sum. Every thread gets all NQ
+// results in v. sh: NQ * WAVES doubles of LDS. The order — and so every bit — is that of block_reduce_multi (gfbe_devutil.h); this one
+// runs the NQ trees interleaved in one basic block and has every thread add the waves' values itself, two barriers in all:
+// block_reduce_multi's tree-and-store per quantity and its third barrier measured 5 - 10 % on a window's time in k_line_step and 2 % in
+// k_line_refine, whose windows are a few dozen microseconds of dependent work between reductions.
+template <int NQ, int WAVES>
+__device__ __forceinline__ void line_block_reduce(double (&v)[NQ], unsigned maxmask, double *sh) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+    for (int q = 0; q < NQ; q++) {
+      const double u = __shfl_down(v[q], o, 64);
+      v[q] = ((maxmask >> q) & 1) ? fmax(v[q], u) : v[q] + u;
+    }
+  if ((t & 63) == 0)
+#pragma unroll
+    for (int q = 0; q < NQ; q++) sh[q * WAVES + (t >> 6)] = v[q];
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < NQ; q++) {
+    double a = 0.0;
+#pragma unroll
+    for (int k = 0; k < WAVES; k++) a = ((maxmask >> q) & 1) ? fmax(a, sh[q * WAVES + k]) : a + sh[q * WAVES + k];
+    v[q] = a;
+  }
+  __syncthreads();
+}
+// rank: the lines of [l0, l1) that `enters` admits, in list order (block scan) — lineof[q] = the q-th of them, for q < cap (nothing is
+// written past the slots); returns their count, at most cap. The caller fences and barriers before it reads lineof.
+template <int THREADS, class Pred>
+__device__ __forceinline__ int line_rank(int l0, int l1, Pred enters, int *lineof, int *scan_lds /* >= 17 ints */, int cap = 0x7fffffff) {
+  int n = 0;
+  for (int c0 = l0; c0 < l1; c0 += THREADS) {
+    const int l = c0 + (int)threadIdx.x;
+    const int e = (l < l1 && enters(l)) ? 1 : 0;
+    int total;
+    const int at = n + block_exclusive_scan<THREADS>(e, &total, scan_lds);
+    if (e && at < cap) lineof[at] = l;
+    n += total;
+  }
+  return min(n, cap);
 }
 #endif
 

@@ -28,6 +28,7 @@
 
 #include "gfbe_device.h"
 #include "gfbe_line.h"
+#include "gfbe_line_batch.h"
 
 using namespace gfd;
 
@@ -63,21 +64,9 @@ __global__ __launch_bounds__(256) void k_line_eval(int n, const double *pose, co
   cost_part[k] = c;       // summed in factor order on the host
 }
 
-// The lines of a batch of windows. Host-fed (gfbe_line_refine, TAB = false): a CSR description packed by the host. Table-fed
-// (gfbe_ltab_refine, TAB = true): the device-resident line tables read IN PLACE — window w owns lines [w F, w F + count[w]), line l has
-// nobs[l] observations in its fixed row of GFBE_NFRAMES slots (obs + 4 GFBE_NFRAMES l). No scan, no compaction: a line's observations are
-// contiguous either way, so the kernel walks the same values in the same order and the arithmetic is the same instruction for instruction.
+// the lines of a batch of windows (host-fed or the tables in place: LineList, gfbe_line.h), the loop's parameters, scratch and outputs
 struct LineBatch {
-  const int *line_off;          // [n_windows + 1]                          (host-fed)
-  const int *obs_off;           // [n_lines + 1] (over the whole batch)     (host-fed)
-  const int *count, *nobs;      // [n_windows], [n_windows][F]              (table-fed)
-  int F;                        // line capacity of a table                 (table-fed)
-  const int *start;             // [n_lines]
-  const unsigned char *tri;     // [n_lines]
-  const double *plk_in;         // [n_lines][6]
-  const double *obs;            // [n_obs][4]
-  const double *pose;           // [n_windows][11][7]
-  const double *ex;             // [n_windows][7]
+  LineList L;
   double sqrt_info, cauchy;
   int max_it;
   double *row;                  // [n_lines][LR_ROW]
@@ -86,15 +75,14 @@ struct LineBatch {
   gfbe_summary *sum;            // [n_windows]
 };
 
-// (line_nobs / line_obs / line_eligible over either description: gfbe_line.h, shared with gfbe_line_reduce.hip)
-
 // cost of line l at x; with H, g: its Cauchy-corrected normal-equation block and gradient
 template <bool LIN, bool TAB>
 __device__ double line_lin(const LineBatch &P, int l, const double *x, const LineRT *Bs, const LineRT &Ex, double *H, double *g) {
+  const LineList &L = P.L;
   double cost = 0.0;
   if (LIN) { for (int q = 0; q < 16; q++) H[q] = 0.0; for (int q = 0; q < 4; q++) g[q] = 0.0; }
-  const int s = P.start[l], m = line_nobs<TAB>(P, l);
-  const double *ob = line_obs<TAB>(P, l);
+  const int s = L.start[l], m = line_nobs<TAB>(L, l);
+  const double *ob = line_obs<TAB>(L, l);
   for (int k = 0; k < m; k++) {
     double r[2], Jo[8];
     line_factor<LIN>(Bs[s + k], Ex, x, ob + 4 * k, P.sqrt_info, r, nullptr, nullptr, LIN ? Jo : nullptr);
@@ -119,25 +107,6 @@ __device__ double line_grad_norm(const double *x, const double *g) {
   line_orth_plus(x, mg, xp);
   for (int a = 0; a < 4; a++) m = fmax(m, fabs(x[a] - xp[a]));
   return m;
-}
-
-// Fixed-order reduction of four per-thread values over the workgroup: entry 0 by max when max0, the others by sum. Every thread gets
-// the results in out[4].
-__device__ void lr_reduce(double v0, double v1, double v2, double v3, bool max0, double (*sh)[LR_WAVES], double *out) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double a = __shfl_down(v0, o, 64), b = __shfl_down(v1, o, 64), c = __shfl_down(v2, o, 64), d = __shfl_down(v3, o, 64);
-    v0 = max0 ? fmax(v0, a) : v0 + a; v1 += b; v2 += c; v3 += d;
-  }
-  if ((t & 63) == 0) { sh[0][t >> 6] = v0; sh[1][t >> 6] = v1; sh[2][t >> 6] = v2; sh[3][t >> 6] = v3; }
-  __syncthreads();
-  if (t < 4) {
-    double v = 0.0;
-    for (int q = 0; q < LR_WAVES; q++) v = (max0 && t == 0) ? fmax(v, sh[t][q]) : v + sh[t][q];
-    out[t] = v;
-  }
-  __syncthreads();
 }
 
 // 4 x 4 SPD solve A y = b by Cholesky; false if a pivot is not positive (or not a number)
@@ -165,20 +134,27 @@ __device__ bool chol4_solve(double *A, const double *b, double *y) {
 template <bool TAB>
 __global__ __launch_bounds__(LR_THREADS) void k_line_refine(LineBatch P) {
   const int w = blockIdx.x, t = threadIdx.x;
+  const LineList &L = P.L;
   __shared__ LineRT Bs[GFBE_NFRAMES], Cw[GFBE_NFRAMES];
   __shared__ LineRT Ex;
-  __shared__ double sh[4][LR_WAVES];
-  __shared__ double red[4];
-  const int l0 = TAB ? w * P.F : P.line_off[w], l1 = TAB ? l0 + P.count[w] : P.line_off[w + 1];
+  __shared__ double sh[4 * LR_WAVES];
+  // the per-window sums: four per-thread values through the fixed-order reduction (line_block_reduce, gfbe_line.h), entry 0 by max
+  // when max0; every thread gets the results in red[4]
+  double red[4];
+  auto reduce4 = [&](double v0, double v1, double v2, double v3, bool max0) {
+    red[0] = v0; red[1] = v1; red[2] = v2; red[3] = v3;
+    line_block_reduce<4, LR_WAVES>(red, max0 ? 1u : 0u, sh);
+  };
+  int l0, l1;
+  line_range<TAB>(L, w, &l0, &l1);
   const uint64_t t_start = wall_clock64();
-  if (t < GFBE_NFRAMES) Bs[t] = line_make_pose(P.pose + (size_t)w * 77 + 7 * t);
-  if (t == GFBE_NFRAMES) Ex = line_make_pose(P.ex + (size_t)w * 7);
+  line_stage_poses(L, w, Bs, &Ex);
   __syncthreads();
-  if (t < GFBE_NFRAMES) { Cw[t].R = mul(Bs[t].R, Ex.R); Cw[t].t = add(Bs[t].t, mv(Bs[t].R, Ex.t)); }   // Rwc = Rs ric, twc = Ps + Rs tic
+  line_stage_cameras(Bs, Ex, Cw);
   // eligibility count
   double ne = 0.0;
-  for (int l = l0 + t; l < l1; l += LR_THREADS) ne += line_eligible<TAB>(P, l) ? 1.0 : 0.0;
-  lr_reduce(0.0, ne, 0.0, 0.0, false, sh, red);
+  for (int l = l0 + t; l < l1; l += LR_THREADS) ne += line_eligible<TAB>(L, l) ? 1.0 : 0.0;
+  reduce4(0.0, ne, 0.0, 0.0, false);
   const int n_elig = (int)red[1];
   // the loop's scalars live in every thread (the same values everywhere); its per-iteration record in LDS, written by thread 0
   __shared__ double hist[16];
@@ -187,7 +163,7 @@ __global__ __launch_bounds__(LR_THREADS) void k_line_refine(LineBatch P) {
   auto record = [&](int i, int a, double v) { if (t == 0) { hist[i] = v; acc[i] = (unsigned char)a; } };
   if (n_elig < 4) {      // `if (feature_index < 3) return;` — nothing solved, nothing written back, removeLineOutlier not called
     for (int l = l0 + t; l < l1; l += LR_THREADS) {
-      for (int a = 0; a < 6; a++) P.plk_out[6 * (size_t)l + a] = P.plk_in[6 * (size_t)l + a];
+      for (int a = 0; a < 6; a++) P.plk_out[6 * (size_t)l + a] = L.plk_in[6 * (size_t)l + a];
       P.keep[l] = 1;
     }
     if (t == 0) { gfbe_summary sm{}; sm.status = GFBE_OK; sm.termination = 5; P.sum[w] = sm; }
@@ -196,16 +172,16 @@ __global__ __launch_bounds__(LR_THREADS) void k_line_refine(LineBatch P) {
   // entry: para_LineFeature = plk_to_orth(plk_to_pose(line_plucker, Rwc, twc)) of the start frame; the first linearisation
   double c = 0.0, x2 = 0.0, gm = 0.0;
   for (int l = l0 + t; l < l1; l += LR_THREADS) {
-    if (!line_eligible<TAB>(P, l)) continue;
+    if (!line_eligible<TAB>(L, l)) continue;
     double *row = P.row + (size_t)l * LR_ROW, lw[6];
-    const int s = P.start[l];
-    line_plk_to_pose(P.plk_in + 6 * (size_t)l, Cw[s].R, Cw[s].t, lw);
+    const int s = L.start[l];
+    line_plk_to_pose(L.plk_in + 6 * (size_t)l, Cw[s].R, Cw[s].t, lw);
     line_plk_to_orth(lw, row + LX);
     c += line_lin<true, TAB>(P, l, row + LX, Bs, Ex, row + LH, row + LG);
     for (int a = 0; a < 4; a++) { x2 += row[LX + a] * row[LX + a]; row[LS + a] = 1.0 / (1.0 + sqrt(row[LH + 5 * a])); }
     gm = fmax(gm, line_grad_norm(row + LX, row + LG));
   }
-  lr_reduce(gm, c, x2, 0.0, true, sh, red);
+  reduce4(gm, c, x2, 0.0, true);
   double cost = red[1], gmax = red[0], x_norm = sqrt(red[2]), radius = 1e4, decrease = 2.0;
   const double initial_cost = cost;
   if (t < 16) { hist[t] = 0.0; acc[t] = 0; }
@@ -222,7 +198,7 @@ __global__ __launch_bounds__(LR_THREADS) void k_line_refine(LineBatch P) {
     // every line: scaled system, LM diagonal, 4 x 4 solve, model cost change, candidate
     double fail = 0.0, mc = 0.0, st2 = 0.0, cx2 = 0.0;
     for (int l = l0 + t; l < l1; l += LR_THREADS) {
-      if (!line_eligible<TAB>(P, l)) continue;
+      if (!line_eligible<TAB>(L, l)) continue;
       double *row = P.row + (size_t)l * LR_ROW;
       double Hs[16], A[16], rhs[4], y[4];
       for (int a = 0; a < 4; a++) {
@@ -245,7 +221,7 @@ __global__ __launch_bounds__(LR_THREADS) void k_line_refine(LineBatch P) {
       line_orth_plus(row + LX, d, row + LC);
       for (int a = 0; a < 4; a++) { const double df = row[LC + a] - row[LX + a]; st2 += df * df; cx2 += row[LC + a] * row[LC + a]; }
     }
-    lr_reduce(fail, mc, st2, cx2, true, sh, red);
+    reduce4(fail, mc, st2, cx2, true);
     const double model_change = red[1], step2 = red[2], cand_x2 = red[3];
     if (red[0] != 0.0 || !(model_change > 0.0)) {      // invalid step
       record(it, 0, cost);
@@ -256,8 +232,8 @@ __global__ __launch_bounds__(LR_THREADS) void k_line_refine(LineBatch P) {
     invalid = 0;
     double cc = 0.0;
     for (int l = l0 + t; l < l1; l += LR_THREADS)
-      if (line_eligible<TAB>(P, l)) cc += line_lin<false, TAB>(P, l, P.row + (size_t)l * LR_ROW + LC, Bs, Ex, nullptr, nullptr);
-    lr_reduce(0.0, cc, 0.0, 0.0, false, sh, red);
+      if (line_eligible<TAB>(L, l)) cc += line_lin<false, TAB>(P, l, P.row + (size_t)l * LR_ROW + LC, Bs, Ex, nullptr, nullptr);
+    reduce4(0.0, cc, 0.0, 0.0, false);
     const double cand_cost = red[1];
     record(it, 0, cost);
     if (sqrt(step2) <= 1e-8 * (x_norm + 1e-8)) { termination = 2; status = GFBE_OK; break; }
@@ -271,13 +247,13 @@ __global__ __launch_bounds__(LR_THREADS) void k_line_refine(LineBatch P) {
       decrease = 2.0; reuse = false;
       double g2 = 0.0;
       for (int l = l0 + t; l < l1; l += LR_THREADS) {
-        if (!line_eligible<TAB>(P, l)) continue;
+        if (!line_eligible<TAB>(L, l)) continue;
         double *row = P.row + (size_t)l * LR_ROW;
         for (int a = 0; a < 4; a++) row[LX + a] = row[LC + a];
         (void)line_lin<true, TAB>(P, l, row + LX, Bs, Ex, row + LH, row + LG);
         g2 = fmax(g2, line_grad_norm(row + LX, row + LG));
       }
-      lr_reduce(g2, 0.0, 0.0, 0.0, true, sh, red);
+      reduce4(g2, 0.0, 0.0, 0.0, true);
       gmax = red[0];
     } else {
       record(it, 0, cost);
@@ -287,13 +263,13 @@ __global__ __launch_bounds__(LR_THREADS) void k_line_refine(LineBatch P) {
   // exit: setLineOrth (line_plucker = plk_from_pose(orth_to_plk(orth), Rwc, twc)), then removeLineOutlier on the written-back lines
   for (int l = l0 + t; l < l1; l += LR_THREADS) {
     double *out = P.plk_out + 6 * (size_t)l;
-    if (!line_eligible<TAB>(P, l)) {
-      for (int a = 0; a < 6; a++) out[a] = P.plk_in[6 * (size_t)l + a];
+    if (!line_eligible<TAB>(L, l)) {
+      for (int a = 0; a < 6; a++) out[a] = L.plk_in[6 * (size_t)l + a];
       P.keep[l] = 1;
       continue;
     }
-    const int s = P.start[l], m = line_nobs<TAB>(P, l);
-    const double *ob = line_obs<TAB>(P, l);
+    const int s = L.start[l], m = line_nobs<TAB>(L, l);
+    const double *ob = line_obs<TAB>(L, l);
     double lw[6];
     line_orth_to_plk(P.row + (size_t)l * LR_ROW + LX, lw);
     line_plk_from_pose(lw, Cw[s].R, Cw[s].t, out);
@@ -321,21 +297,14 @@ __global__ __launch_bounds__(LR_THREADS) void k_line_refine(LineBatch P) {
   }
 }
 
-#define LN_CHECK(c, call)                                                                                      \
-  do {                                                                                                         \
-    hipError_t e_ = (call);                                                                                    \
-    if (e_ != hipSuccess) { ctx_set_error(c, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); st = GFBE_DEVICE_ERROR; goto done; } \
-  } while (0)
-
 }  // namespace
 
 namespace gfd {
 size_t line_refine_row_doubles() { return LR_ROW; }
-void launch_line_refine_tables(const LineTabView &T, int n_tables, const double *pose7, const double *ex_cam, double sqrt_info, double cauchy,
-                               int max_it, double *row, double *plk_out, unsigned char *keep, gfbe_summary *sum, hipStream_t s) {
+void launch_line_refine_tables(const LineList &L, int n_tables, double sqrt_info, double cauchy, int max_it, double *row, double *plk_out,
+                               unsigned char *keep, gfbe_summary *sum, hipStream_t s) {
   LineBatch P{};
-  P.count = T.count; P.nobs = T.nobs; P.F = T.F; P.start = T.start; P.tri = T.tri; P.plk_in = T.plk; P.obs = T.obs;
-  P.pose = pose7; P.ex = ex_cam; P.sqrt_info = sqrt_info; P.cauchy = cauchy; P.max_it = std::min(max_it, 15);
+  P.L = L; P.sqrt_info = sqrt_info; P.cauchy = cauchy; P.max_it = std::min(max_it, 15);
   P.row = row; P.plk_out = plk_out; P.keep = keep; P.sum = sum;
   hipLaunchKernelGGL(k_line_refine<true>, dim3(n_tables), dim3(LR_THREADS), 0, s, P);
 }
@@ -353,22 +322,22 @@ extern "C" gfbe_status gfbe_line_eval(gfbe_ctx *c, int32_t n, const double *pose
   const size_t np = (size_t)7 * n, no = (size_t)4 * n, nr = (size_t)2 * n, nj = (size_t)14 * n, nk = (size_t)8 * n;
   double *dpose, *dex, *dorth, *dobs, *dr, *djp, *dje, *djo, *dc;
   std::vector<double> hc(n);
-  LN_CHECK(c, hipMalloc((void **)&d, sizeof(double) * (np + 7 + 2 * no + nr + 2 * nj + nk + n)));
+  LINE_CHECK(c, hipMalloc((void **)&d, sizeof(double) * (np + 7 + 2 * no + nr + 2 * nj + nk + n)));
   dpose = d; dex = dpose + np; dorth = dex + 7; dobs = dorth + no; dr = dobs + no; djp = dr + nr; dje = djp + nj; djo = dje + nj; dc = djo + nk;
-  LN_CHECK(c, hipMemcpyAsync(dpose, pose, sizeof(double) * np, hipMemcpyHostToDevice, s));
-  LN_CHECK(c, hipMemcpyAsync(dex, ex_cam, sizeof(double) * 7, hipMemcpyHostToDevice, s));
-  LN_CHECK(c, hipMemcpyAsync(dorth, orth, sizeof(double) * no, hipMemcpyHostToDevice, s));
-  LN_CHECK(c, hipMemcpyAsync(dobs, obs, sizeof(double) * no, hipMemcpyHostToDevice, s));
+  LINE_CHECK(c, hipMemcpyAsync(dpose, pose, sizeof(double) * np, hipMemcpyHostToDevice, s));
+  LINE_CHECK(c, hipMemcpyAsync(dex, ex_cam, sizeof(double) * 7, hipMemcpyHostToDevice, s));
+  LINE_CHECK(c, hipMemcpyAsync(dorth, orth, sizeof(double) * no, hipMemcpyHostToDevice, s));
+  LINE_CHECK(c, hipMemcpyAsync(dobs, obs, sizeof(double) * no, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_line_eval, dim3((n + 255) / 256), dim3(256), 0, s, n, dpose, dex, dorth, dobs, sqrt_info, robustify ? 1 : 0,
                      r ? dr : nullptr, J_pose ? djp : nullptr, J_ex ? dje : nullptr, J_orth ? djo : nullptr, dc);
-  LN_CHECK(c, hipGetLastError());
-  LN_CHECK(c, hipMemcpyAsync(hc.data(), dc, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-  LN_CHECK(c, hipStreamSynchronize(s));
+  LINE_CHECK(c, hipGetLastError());
+  LINE_CHECK(c, hipMemcpyAsync(hc.data(), dc, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+  LINE_CHECK(c, hipStreamSynchronize(s));
   // (outputs are written only once the whole evaluation has succeeded)
-  if (r) LN_CHECK(c, hipMemcpy(r, dr, sizeof(double) * nr, hipMemcpyDeviceToHost));
-  if (J_pose) LN_CHECK(c, hipMemcpy(J_pose, djp, sizeof(double) * nj, hipMemcpyDeviceToHost));
-  if (J_ex) LN_CHECK(c, hipMemcpy(J_ex, dje, sizeof(double) * nj, hipMemcpyDeviceToHost));
-  if (J_orth) LN_CHECK(c, hipMemcpy(J_orth, djo, sizeof(double) * nk, hipMemcpyDeviceToHost));
+  if (r) LINE_CHECK(c, hipMemcpy(r, dr, sizeof(double) * nr, hipMemcpyDeviceToHost));
+  if (J_pose) LINE_CHECK(c, hipMemcpy(J_pose, djp, sizeof(double) * nj, hipMemcpyDeviceToHost));
+  if (J_ex) LINE_CHECK(c, hipMemcpy(J_ex, dje, sizeof(double) * nj, hipMemcpyDeviceToHost));
+  if (J_orth) LINE_CHECK(c, hipMemcpy(J_orth, djo, sizeof(double) * nk, hipMemcpyDeviceToHost));
   if (cost) { double tot = 0.0; for (int k = 0; k < n; k++) tot += hc[k]; *cost = tot; }
 done:
   if (d) (void)hipFree(d);
@@ -379,89 +348,38 @@ extern "C" gfbe_status gfbe_line_refine(gfbe_ctx *c, int32_t n_windows, const gf
                                         double cauchy_scale, int32_t max_num_iterations, double *plucker_out, uint8_t *keep_out,
                                         gfbe_summary *summary) {
   if (!c || n_windows < 0 || (n_windows > 0 && (!win || !summary)) || !(cauchy_scale > 0.0) || max_num_iterations < 0) return GFBE_BAD_INPUT;
-  // the windows: sizes, frames and pointers
-  std::vector<int> line_off(n_windows + 1, 0);
-  size_t n_obs_total = 0;
-  for (int w = 0; w < n_windows; w++) {
-    const gfbe_line_window *L = win[w];
-    if (!L || L->struct_size != (int32_t)sizeof(gfbe_line_window)) { ctx_set_error(c, "gfbe_line_refine: gfbe_line_window ABI mismatch"); return GFBE_BAD_INPUT; }
-    if (L->n_lines < 0 || (L->n_lines > 0 && (!L->start_frame || !L->n_obs || !L->is_triangulation || !L->line_plucker))) return GFBE_BAD_INPUT;
-    size_t no = 0;
-    for (int i = 0; i < L->n_lines; i++) {
-      const int s = L->start_frame[i], k = L->n_obs[i];
-      if (s < 0 || k < 0 || s + k > GFBE_NFRAMES) { ctx_set_error(c, "gfbe_line_refine: a line's observations run past the window"); return GFBE_BAD_INPUT; }
-      no += (size_t)k;
-    }
-    if (no > 0 && !L->obs) return GFBE_BAD_INPUT;
-    if ((size_t)line_off[w] + (size_t)L->n_lines > (size_t)INT32_MAX / 64 || n_obs_total + no > (size_t)INT32_MAX / 8) return GFBE_BAD_INPUT;
-    line_off[w + 1] = line_off[w] + L->n_lines;
-    n_obs_total += no;
-  }
-  const int n_lines = n_windows ? line_off[n_windows] : 0;
+  LineWindows B;
+  if (!check_line_windows(c, "gfbe_line_refine", n_windows, win, (size_t)INT32_MAX / 64, B)) return GFBE_BAD_INPUT;
+  const int n_lines = B.n_lines();
   if (n_lines > 0 && (!plucker_out || !keep_out)) return GFBE_BAD_INPUT;
   if (ctx_device(c) < 0) { ctx_set_error(c, "gfbe_line_refine: HIP device context required (no CPU fallback)"); return GFBE_NO_DEVICE; }
   if (n_windows == 0) return GFBE_OK;
-  // pack: ints (line_off, obs_off, start), then doubles (plucker, obs, poses, extrinsics), then the triangulation flags
-  std::vector<int> ints((size_t)n_windows + 1 + 2 * (size_t)n_lines + 1);
-  int *h_line_off = ints.data(), *h_obs_off = h_line_off + n_windows + 1, *h_start = h_obs_off + n_lines + 1;
-  std::vector<double> dbl((size_t)6 * n_lines + 4 * n_obs_total + 84 * (size_t)n_windows);
-  double *h_plk = dbl.data(), *h_obs = h_plk + 6 * (size_t)n_lines, *h_pose = h_obs + 4 * n_obs_total, *h_ex = h_pose + 77 * (size_t)n_windows;
-  std::vector<unsigned char> h_tri(std::max(n_lines, 1));
-  {
-    size_t o = 0;
-    for (int w = 0; w < n_windows; w++) {
-      const gfbe_line_window *L = win[w];
-      h_line_off[w] = line_off[w];
-      std::memcpy(h_pose + 77 * (size_t)w, L->pose, sizeof(double) * 77);
-      std::memcpy(h_ex + 7 * (size_t)w, L->ex_cam, sizeof(double) * 7);
-      size_t lo = 0;
-      for (int i = 0; i < L->n_lines; i++) {
-        const int l = line_off[w] + i;
-        h_obs_off[l] = (int)o; h_start[l] = L->start_frame[i]; h_tri[l] = L->is_triangulation[i] ? 1 : 0;
-        std::memcpy(h_plk + 6 * (size_t)l, L->line_plucker + 6 * (size_t)i, sizeof(double) * 6);
-        if (L->n_obs[i] > 0) std::memcpy(h_obs + 4 * o, L->obs + 4 * lo, sizeof(double) * 4 * L->n_obs[i]);
-        o += L->n_obs[i]; lo += L->n_obs[i];
-      }
-    }
-    h_line_off[n_windows] = n_lines;
-    h_obs_off[n_lines] = (int)o;
-  }
   hipStream_t s = ctx_stream(c);
   gfbe_status st = GFBE_OK;
-  char *d = nullptr;
-  const size_t b_int = sizeof(int) * ints.size(), b_dbl = sizeof(double) * dbl.size(), b_row = sizeof(double) * LR_ROW * (size_t)n_lines,
-               b_out = sizeof(double) * 6 * (size_t)n_lines, b_sum = sizeof(gfbe_summary) * (size_t)n_windows, b_tri = h_tri.size();
-  auto up8 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t b_out = sizeof(double) * 6 * (size_t)n_lines, b_sum = sizeof(gfbe_summary) * (size_t)n_windows;
   std::vector<double> h_out((size_t)6 * n_lines);
   std::vector<unsigned char> h_keep(std::max(n_lines, 1));
   std::vector<gfbe_summary> h_sum(n_windows);
+  LineUpload U;
   LineBatch P{};
-  LN_CHECK(c, hipMalloc((void **)&d, up8(b_int) + up8(b_dbl) + up8(b_row) + up8(b_out) + up8(b_sum) + up8(b_tri) + up8(b_tri)));
-  {
-    char *p = d;
-    int *d_int = (int *)p; p += up8(b_int);
-    double *d_dbl = (double *)p; p += up8(b_dbl);
-    P.row = (double *)p; p += up8(b_row);
-    P.plk_out = (double *)p; p += up8(b_out);
-    P.sum = (gfbe_summary *)p; p += up8(b_sum);
-    unsigned char *d_tri = (unsigned char *)p; p += up8(b_tri);
-    P.keep = (unsigned char *)p;
-    P.line_off = d_int; P.obs_off = d_int + (h_obs_off - h_line_off); P.start = d_int + (h_start - h_line_off);
-    P.plk_in = d_dbl; P.obs = d_dbl + (h_obs - h_plk); P.pose = d_dbl + (h_pose - h_plk); P.ex = d_dbl + (h_ex - h_plk);
-    P.tri = d_tri;
-    P.sqrt_info = sqrt_info; P.cauchy = cauchy_scale; P.max_it = std::min<int>(max_num_iterations, 15);
-    LN_CHECK(c, hipMemcpyAsync(d_int, ints.data(), b_int, hipMemcpyHostToDevice, s));
-    LN_CHECK(c, hipMemcpyAsync(d_dbl, dbl.data(), b_dbl, hipMemcpyHostToDevice, s));
-    LN_CHECK(c, hipMemcpyAsync(d_tri, h_tri.data(), b_tri, hipMemcpyHostToDevice, s));
-  }
+  // the kernel's scratch rows and outputs, behind the packed windows in the call's one allocation
+  auto layout = [&](char *base) {
+    Arena a(base);
+    P.row = a.take<double>((size_t)LR_ROW * n_lines); P.plk_out = a.take<double>((size_t)6 * n_lines);
+    P.sum = a.take<gfbe_summary>(n_windows); P.keep = a.take<unsigned char>(std::max(n_lines, 1));
+    return a.off;
+  };
+  LINE_CHECK(c, upload_line_windows(s, n_windows, win, B, layout(nullptr), U));
+  (void)layout(U.extra);
+  P.L = U.L; P.sqrt_info = sqrt_info; P.cauchy = cauchy_scale; P.max_it = std::min<int>(max_num_iterations, 15);
   hipLaunchKernelGGL(k_line_refine<false>, dim3(n_windows), dim3(LR_THREADS), 0, s, P);
-  LN_CHECK(c, hipGetLastError());
+  LINE_CHECK(c, hipGetLastError());
   if (n_lines) {
-    LN_CHECK(c, hipMemcpyAsync(h_out.data(), P.plk_out, b_out, hipMemcpyDeviceToHost, s));
-    LN_CHECK(c, hipMemcpyAsync(h_keep.data(), P.keep, (size_t)n_lines, hipMemcpyDeviceToHost, s));
+    LINE_CHECK(c, hipMemcpyAsync(h_out.data(), P.plk_out, b_out, hipMemcpyDeviceToHost, s));
+    LINE_CHECK(c, hipMemcpyAsync(h_keep.data(), P.keep, (size_t)n_lines, hipMemcpyDeviceToHost, s));
   }
-  LN_CHECK(c, hipMemcpyAsync(h_sum.data(), P.sum, b_sum, hipMemcpyDeviceToHost, s));
-  LN_CHECK(c, hipStreamSynchronize(s));
+  LINE_CHECK(c, hipMemcpyAsync(h_sum.data(), P.sum, b_sum, hipMemcpyDeviceToHost, s));
+  LINE_CHECK(c, hipStreamSynchronize(s));
   {
     int worst = GFBE_OK;
     for (int w = 0; w < n_windows; w++) worst = std::max(worst, (int)h_sum[w].status);
@@ -470,6 +388,6 @@ extern "C" gfbe_status gfbe_line_refine(gfbe_ctx *c, int32_t n_windows, const gf
     st = (gfbe_status)worst;
   }
 done:
-  if (d) (void)hipFree(d);
+  if (U.d) (void)hipFree(U.d);
   return st;
 }

@@ -6,7 +6,7 @@
 //
 // Shape: ONE WORKGROUP PER WINDOW AT A TIME (a workgroup walks windows blockIdx.x, blockIdx.x + gridDim.x, ...; its scratch slab is
 // its own, so a window's bits do not depend on the batch). Per window:
-//   rank    the eligible lines in list order (block scan), rank -> line
+//   rank    the eligible lines in list order (line_rank, gfbe_line.h), rank -> line
 //   lines   a thread owns eligible lines t, t + 256, ...: line_reduce_line (gfbe_line.h) — every observation's factor with all three
 //           Jacobians, V_l, bl, the 6 x 4 blocks of W_l, the 4 x 4 Cholesky and V'^-1 — into the line's scratch row
 //   chunks  RC_CHUNK lines at a time are staged in LDS as Y = W V'^-1 and W, [line][k][80 rows] (leading dimension 80 = 16 mod 32
@@ -27,7 +27,7 @@
 
 #include "gfbe_device.h"
 #include "gfbe_line.h"
-#include "gfbe_tabstage.h"
+#include "gfbe_line_batch.h"
 
 using namespace gfd;
 
@@ -42,13 +42,7 @@ enum { RC_THREADS = 256, RC_WAVES = 4, RC_CHUNK = 8, RC_LD = 80, RC_NP = LINE_NP
 static_assert(RC_NT * 256 + RC_TASKS <= RC_STAGE, "the finish phase reuses the chunk staging area");
 
 struct ReduceBatch {
-  // the lines, as LineBatch of gfbe_line.hip: host-fed CSR or the tables in place
-  const int *line_off, *obs_off;       // host-fed
-  const int *count, *nobs;             // table-fed
-  int F;
-  const int *start;
-  const unsigned char *tri;
-  const double *plk_in, *obs, *pose, *ex;
+  LineList L;                          // the lines: host-fed CSR or the tables in place (gfbe_line.h)
   double sqrt_info, huber, mu;
   int mode, n_windows, slab_lines;     // slab_lines: line slots of one workgroup's scratch slab
   const int *rec_off;                  // [n_windows] first record slot of a window (prefix of the line counts)
@@ -63,10 +57,10 @@ struct ReduceBatch {
   unsigned char *ofailed;
 };
 
-// the lines that enter: the predicate of gfbe_line_refine (gfbe_line.h), and in MARG_OLD mode only those that start in frame 0
+// the lines that enter: line_eligible (gfbe_line.h), and in MARG_OLD mode only those that start in frame 0
 template <bool TAB>
 __device__ __forceinline__ bool rb_eligible(const ReduceBatch &P, int l) {
-  return line_eligible<TAB>(P, l) && (P.mode == GFBE_LINE_REDUCE_SOLVE || P.start[l] == 0);
+  return line_eligible<TAB>(P.L, l) && (P.mode == GFBE_LINE_REDUCE_SOLVE || P.L.start[l] == 0);
 }
 
 // offsets of the two products of frame-sum entry e (0..89) in an observation record [r(2) | Jp(2 x 6) | Je(2 x 6)]:
@@ -81,29 +75,17 @@ __device__ void rc_decode(int e, int *a, int *a2, int *b, int *b2) {
   else { i = e - 84; *a = 14 + i; *a2 = 20 + i; *b = 0; *b2 = 1; }
 }
 
-// fixed-order sum of two per-thread values over the workgroup (wave shuffle tree, then the waves in order); every thread gets both
-__device__ void rc_reduce2(double v0, double v1, double (*sh)[RC_WAVES], double *out) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { v0 += __shfl_down(v0, o, 64); v1 += __shfl_down(v1, o, 64); }
-  if ((t & 63) == 0) { sh[0][t >> 6] = v0; sh[1][t >> 6] = v1; }
-  __syncthreads();
-  double a = 0.0, b = 0.0;
-  for (int q = 0; q < RC_WAVES; q++) { a += sh[0][q]; b += sh[1][q]; }
-  out[0] = a; out[1] = b;
-  __syncthreads();
-}
-
 template <bool TAB>
 __global__ __launch_bounds__(RC_THREADS) void k_line_reduce(ReduceBatch P) {
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, lr = lane & 15, lk = lane >> 4;
+  const LineList &L = P.L;
   __shared__ LineRT Bs[GFBE_NFRAMES], Cw[GFBE_NFRAMES];
   __shared__ LineRT Ex;
   __shared__ double stage[RC_STAGE];
   __shared__ double sJ[RC_CHUNK * RC_JROW];
   __shared__ double sbl[RC_CHUNK][4];
   __shared__ int smeta[RC_CHUNK][3];           // start, first observation, observations (0: the line is not in the sums)
-  __shared__ double sh[2][RC_WAVES];
+  __shared__ double sh[2 * RC_WAVES];
   __shared__ int scan_lds[20];
   double *sY = stage, *sW = stage + RC_CHUNK * 4 * RC_LD;
   const size_t slab = (size_t)blockIdx.x * P.slab_lines;
@@ -133,41 +115,33 @@ __global__ __launch_bounds__(RC_THREADS) void k_line_reduce(ReduceBatch P) {
   for (int w = blockIdx.x; w < P.n_windows; w += gridDim.x) {
     const uint64_t t_start = P.ms ? wall_clock64() : 0;      // (the clock is read only when ms_kernel is asked for)
     uint64_t t_mfma = 0;
-    const int l0 = TAB ? w * P.F : P.line_off[w], l1 = TAB ? l0 + P.count[w] : P.line_off[w + 1];
+    int l0, l1;
+    line_range<TAB>(L, w, &l0, &l1);
     __syncthreads();                               // (the previous window's readers of LDS are done)
-    if (t < GFBE_NFRAMES) Bs[t] = line_make_pose(P.pose + (size_t)w * 77 + 7 * t);
-    if (t == GFBE_NFRAMES) Ex = line_make_pose(P.ex + (size_t)w * 7);
+    line_stage_poses(L, w, Bs, &Ex);
     for (int q = t; q < RC_STAGE; q += RC_THREADS) stage[q] = 0.0;      // (rows 72..79 of every operand stay zero)
     __syncthreads();
-    if (t < GFBE_NFRAMES) { Cw[t].R = mul(Bs[t].R, Ex.R); Cw[t].t = add(Bs[t].t, mv(Bs[t].R, Ex.t)); }   // Rwc = Rs ric, twc = Ps + Rs tic
+    line_stage_cameras(Bs, Ex, Cw);
     // ---- rank: eligible lines in list order
-    int n_elig = 0;
-    for (int c0 = l0; c0 < l1; c0 += RC_THREADS) {
-      const int l = c0 + t;
-      const int e = (l < l1 && rb_eligible<TAB>(P, l)) ? 1 : 0;
-      int total;
-      const int ex = block_exclusive_scan<RC_THREADS>(e, &total, scan_lds);
-      if (e) lineof[n_elig + ex] = l;
-      n_elig += total;
-    }
+    const int n_elig = line_rank<RC_THREADS>(l0, l1, [&](int l) { return rb_eligible<TAB>(P, l); }, lineof, scan_lds);
     __threadfence();
     __syncthreads();
     // ---- lines
     double csum = 0.0, nfail = 0.0;
     for (int q = t; q < n_elig; q += RC_THREADS) {
-      const int l = lineof[q], s = P.start[l];
+      const int l = lineof[q], s = L.start[l];
       double lw[6], x[4], c;
-      line_plk_to_pose(P.plk_in + 6 * (size_t)l, Cw[s].R, Cw[s].t, lw);     // para_LineFeature = plk_to_orth(plk_to_pose(line_plucker, Rwc, twc))
+      line_plk_to_pose(L.plk_in + 6 * (size_t)l, Cw[s].R, Cw[s].t, lw);     // para_LineFeature = plk_to_orth(plk_to_pose(line_plucker, Rwc, twc))
       line_plk_to_orth(lw, x);
-      const bool ok = line_reduce_line(Bs, Ex, x, s, k0, line_nobs<TAB>(P, l), line_obs<TAB>(P, l), P.sqrt_info, P.huber, P.mu,
+      const bool ok = line_reduce_line(Bs, Ex, x, s, k0, line_nobs<TAB>(L, l), line_obs<TAB>(L, l), P.sqrt_info, P.huber, P.mu,
                                        Wrow + (size_t)q * RC_WROW, Jrec + (size_t)q * RC_JROW, Vinv + (size_t)q * 16, bl + (size_t)q * 4, &c,
                                        Vl + (size_t)q * 10);
       failed[q] = ok ? 0 : 1;
       if (ok) csum += c; else nfail += 1.0;
     }
     __threadfence();
-    double red[2];
-    rc_reduce2(csum, nfail, sh, red);
+    double red[2] = {csum, nfail};                 // the window's cost and failure count: fixed-order sums (line_block_reduce, gfbe_line.h)
+    line_block_reduce<2, RC_WAVES>(red, 0u, sh);
     // ---- chunks
     dbl4 acc[4];
 #pragma unroll
@@ -180,7 +154,7 @@ __global__ __launch_bounds__(RC_THREADS) void k_line_reduce(ReduceBatch P) {
       if (t < RC_CHUNK) {
         const bool in = t < nc && !failed[q0 + t];
         const int l = in ? lineof[q0 + t] : 0;
-        smeta[t][0] = in ? P.start[l] : 0; smeta[t][1] = k0; smeta[t][2] = in ? line_nobs<TAB>(P, l) : 0;
+        smeta[t][0] = in ? L.start[l] : 0; smeta[t][1] = k0; smeta[t][2] = in ? line_nobs<TAB>(L, l) : 0;
       }
       if (t < RC_CHUNK * 4) {
         const int c = t >> 2;
@@ -278,12 +252,6 @@ __global__ __launch_bounds__(RC_THREADS) void k_line_reduce(ReduceBatch P) {
   }
 }
 
-#define RD_CHECK(c, call)                                                                                      \
-  do {                                                                                                         \
-    hipError_t e_ = (call);                                                                                    \
-    if (e_ != hipSuccess) { ctx_set_error(c, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); st = GFBE_DEVICE_ERROR; goto done; } \
-  } while (0)
-
 bool reduce_args_ok(gfbe_ctx *c, const char *who, int32_t mode, double mu, const gfbe_line_reduced *out) {
   // (both sizes of the structure are admitted: a caller built before the member V existed sees no change)
   if (!out || (out->struct_size != (int32_t)sizeof(gfbe_line_reduced) && out->struct_size != GFBE_LINE_REDUCED_SIZE_V0)) { ctx_set_error(c, (std::string(who) + ": gfbe_line_reduced ABI mismatch").c_str()); return false; }
@@ -299,15 +267,14 @@ gfbe_line_reduced reduced_full(const gfbe_line_reduced *out) {
 }
 
 // Launch and hand-over shared by the two entry points. P: the line inputs on the device; nlines [W]: lines per window (the record
-// slots). h_pose / h_ex (table-fed): the poses on the host, copied into the call's allocation. cache (table-fed): the table handle's
+// slots). h_pose / h_ex (table-fed): the poses on the host, copied into the call's allocation. kept (table-fed): the table handle's
 // scratch allocation, kept between calls and grown on demand — a per-frame caller pays no hipMalloc / hipFree; without it the
 // allocation lives for the call (the host-fed entry point, as gfbe_line_refine). keep (table-fed, solve mode, gfbe_ltab_keep_records on):
 // the per-line records are written into the store on the table handle instead of the call's allocation — the same values from the same
 // kernel, so the call's outputs keep their bits — and stay there for gfbe_ltab_step.
-struct ReduceCache { char **d; size_t *cap; };
 template <bool TAB>
 gfbe_status reduce_run(gfbe_ctx *c, ReduceBatch P, int W, const std::vector<int> &nlines, const gfbe_line_reduced *out, const double *h_pose,
-                       const double *h_ex, ReduceCache cache, gfbe_ltab *keep = nullptr) {
+                       const double *h_ex, DevBuf *kept, gfbe_ltab *keep = nullptr) {
   hipStream_t s = ctx_stream(c);
   gfbe_status st = GFBE_OK;
   std::vector<int> rec_off(W + 1, 0);
@@ -316,91 +283,69 @@ gfbe_status reduce_run(gfbe_ctx *c, ReduceBatch P, int W, const std::vector<int>
   const size_t N = (size_t)rec_off[W], n72 = (size_t)W * RC_NP, n5k = n72 * RC_NP;
   const int grid = std::min(W, (int)RC_MAX_GRID);
   const size_t slab_lines = (size_t)maxl + RC_CHUNK, S = (size_t)grid * slab_lines;
-  auto up8 = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const bool rec = out->Vinv || out->bl || out->W || out->failed || out->V;
-  char *d = nullptr;
+  DevBuf own, &buf = kept ? *kept : own;
   std::vector<double> hH, hU, hg, hbp, hcost, hms, hV, hb, hW, hVl;
   std::vector<int> hne(W), hnf(W);
   std::vector<unsigned char> hf;
-  // the layout of the call's one device allocation: laid out once from a null base for its size, then from the allocation
+  // the call's one device allocation
   int *d_rec = nullptr;
-  auto layout = [&](char *p) -> size_t {
-    char *const p0 = p;
-    auto take = [&](size_t bytes) { char *q = p; p += up8(bytes); return q; };
-    d_rec = (int *)take(sizeof(int) * (W + 1));
+  auto layout = [&](char *base) {
+    Arena a(base);
+    d_rec = a.take<int>(W + 1);
     P.rec_off = d_rec;
-    if (h_pose) { P.pose = (double *)take(8 * 77 * (size_t)W); P.ex = (double *)take(8 * 7 * (size_t)W); }
-    P.lineof = (int *)take(sizeof(int) * S);
-    P.Wrow = (double *)take(8 * S * RC_WROW); P.Jrec = (double *)take(8 * S * RC_JROW);
-    P.Vinv = (double *)take(8 * S * 16); P.bl = (double *)take(8 * S * 4); P.Vl = (double *)take(8 * S * 10); P.failed = (unsigned char *)take(S);
-    P.H = out->H ? (double *)take(8 * n5k) : nullptr; P.U = out->U ? (double *)take(8 * n5k) : nullptr;
-    P.g = (double *)take(8 * n72); P.bp = (double *)take(8 * n72);
-    P.cost = (double *)take(8 * (size_t)W); P.ms = out->ms_kernel ? (double *)take(16 * (size_t)W) : nullptr;
-    P.n_elig = (int *)take(4 * (size_t)W); P.n_failed = (int *)take(4 * (size_t)W);
+    if (h_pose) { P.L.pose = a.take<double>(77 * (size_t)W); P.L.ex = a.take<double>(7 * (size_t)W); }
+    P.lineof = a.take<int>(S);
+    P.Wrow = a.take<double>(S * RC_WROW); P.Jrec = a.take<double>(S * RC_JROW);
+    P.Vinv = a.take<double>(S * 16); P.bl = a.take<double>(S * 4); P.Vl = a.take<double>(S * 10); P.failed = a.take<unsigned char>(S);
+    P.H = out->H ? a.take<double>(n5k) : nullptr; P.U = out->U ? a.take<double>(n5k) : nullptr;
+    P.g = a.take<double>(n72); P.bp = a.take<double>(n72);
+    P.cost = a.take<double>(W); P.ms = out->ms_kernel ? a.take<double>(2 * (size_t)W) : nullptr;
+    P.n_elig = a.take<int>(W); P.n_failed = a.take<int>(W);
     if (rec && !keep) {
-      P.oVinv = out->Vinv ? (double *)take(8 * N * 16) : nullptr; P.obl = out->bl ? (double *)take(8 * N * 4) : nullptr;
-      P.oW = out->W ? (double *)take(8 * N * RC_WROW) : nullptr; P.oV = out->V ? (double *)take(8 * N * 10) : nullptr;
-      P.ofailed = (unsigned char *)take(N + 1);
+      P.oVinv = out->Vinv ? a.take<double>(N * 16) : nullptr; P.obl = out->bl ? a.take<double>(N * 4) : nullptr;
+      P.oW = out->W ? a.take<double>(N * RC_WROW) : nullptr; P.oV = out->V ? a.take<double>(N * 10) : nullptr;
+      P.ofailed = a.take<unsigned char>(N + 1);
     }
-    return (size_t)(p - p0);
+    return a.off;
   };
   // the store on the table handle: rec_off, then every record array at full size
   int *k_off = nullptr;
-  auto keep_layout = [&](char *p) -> size_t {
-    char *const p0 = p;
-    auto take = [&](size_t bytes) { char *q = p; p += up8(bytes); return q; };
-    k_off = (int *)take(sizeof(int) * (W + 1));
-    P.oVinv = (double *)take(8 * N * 16); P.obl = (double *)take(8 * N * 4); P.oW = (double *)take(8 * N * RC_WROW);
-    P.oV = (double *)take(8 * N * 10); P.ofailed = (unsigned char *)take(N + 1);
-    return (size_t)(p - p0);
+  auto keep_layout = [&](char *base) {
+    Arena a(base);
+    k_off = a.take<int>(W + 1);
+    P.oVinv = a.take<double>(N * 16); P.obl = a.take<double>(N * 4); P.oW = a.take<double>(N * RC_WROW);
+    P.oV = a.take<double>(N * 10); P.ofailed = a.take<unsigned char>(N + 1);
+    return a.off;
   };
-  {
-    const size_t need = layout(nullptr);
-    if (cache.d && *cache.cap >= need) {
-      d = *cache.d;
-    } else {
-      if (cache.d && *cache.d) { RD_CHECK(c, hipStreamSynchronize(s)); (void)hipFree(*cache.d); *cache.d = nullptr; *cache.cap = 0; }
-      RD_CHECK(c, hipMalloc((void **)&d, need));
-      if (cache.d) { *cache.d = d; *cache.cap = need; }
-    }
-    (void)layout(d);
-    if (keep) {
-      keep->rec_valid = false; keep->cand_valid = false;
-      const size_t kneed = keep_layout(nullptr);
-      if (keep->rec_cap < kneed) {
-        RD_CHECK(c, hipStreamSynchronize(s));
-        if (keep->rec_d) { (void)hipFree(keep->rec_d); keep->rec_d = nullptr; keep->rec_cap = 0; }
-        RD_CHECK(c, hipMalloc((void **)&keep->rec_d, kneed));
-        keep->rec_cap = kneed;
-      }
-      (void)keep_layout(keep->rec_d);
-      RD_CHECK(c, hipMemcpyAsync(k_off, rec_off.data(), sizeof(int) * (W + 1), hipMemcpyHostToDevice, s));
-    }
-    P.n_windows = W; P.slab_lines = (int)slab_lines;
-    if (h_pose) {
-      RD_CHECK(c, hipMemcpyAsync((void *)P.pose, h_pose, 8 * 77 * (size_t)W, hipMemcpyHostToDevice, s));
-      RD_CHECK(c, hipMemcpyAsync((void *)P.ex, h_ex, 8 * 7 * (size_t)W, hipMemcpyHostToDevice, s));
-    }
-    RD_CHECK(c, hipMemcpyAsync(d_rec, rec_off.data(), sizeof(int) * (W + 1), hipMemcpyHostToDevice, s));
+  LINE_CHECK(c, lay_out(s, buf, layout));
+  if (keep) {
+    keep->rec_valid = false; keep->cand_valid = false;
+    LINE_CHECK(c, lay_out(s, keep->rec_buf, keep_layout));
+    LINE_CHECK(c, hipMemcpyAsync(k_off, rec_off.data(), sizeof(int) * (W + 1), hipMemcpyHostToDevice, s));
   }
+  P.n_windows = W; P.slab_lines = (int)slab_lines;
+  if (h_pose) {
+    LINE_CHECK(c, hipMemcpyAsync((void *)P.L.pose, h_pose, 8 * 77 * (size_t)W, hipMemcpyHostToDevice, s));
+    LINE_CHECK(c, hipMemcpyAsync((void *)P.L.ex, h_ex, 8 * 7 * (size_t)W, hipMemcpyHostToDevice, s));
+  }
+  LINE_CHECK(c, hipMemcpyAsync(d_rec, rec_off.data(), sizeof(int) * (W + 1), hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_line_reduce<TAB>, dim3(grid), dim3(RC_THREADS), 0, s, P);
-  RD_CHECK(c, hipGetLastError());
-#define RD_DOWN(vec, dptr, n) do { vec.resize(std::max<size_t>(n, 1)); if (n) RD_CHECK(c, hipMemcpyAsync(vec.data(), dptr, sizeof(vec[0]) * (n), hipMemcpyDeviceToHost, s)); } while (0)
-  if (out->H) RD_DOWN(hH, P.H, n5k);
-  if (out->U) RD_DOWN(hU, P.U, n5k);
-  if (out->g) RD_DOWN(hg, P.g, n72);
-  if (out->bp) RD_DOWN(hbp, P.bp, n72);
-  if (out->cost) RD_DOWN(hcost, P.cost, (size_t)W);
-  if (out->ms_kernel) RD_DOWN(hms, P.ms, 2 * (size_t)W);
-  RD_DOWN(hne, P.n_elig, (size_t)W);
-  RD_DOWN(hnf, P.n_failed, (size_t)W);
-  if (out->Vinv) RD_DOWN(hV, P.oVinv, N * 16);
-  if (out->bl) RD_DOWN(hb, P.obl, N * 4);
-  if (out->W) RD_DOWN(hW, P.oW, N * RC_WROW);
-  if (out->failed) RD_DOWN(hf, P.ofailed, N);
-  if (out->V) RD_DOWN(hVl, P.oV, N * 10);
-#undef RD_DOWN
-  RD_CHECK(c, hipStreamSynchronize(s));
+  LINE_CHECK(c, hipGetLastError());
+  if (out->H) LINE_CHECK(c, download(hH, P.H, n5k, s));
+  if (out->U) LINE_CHECK(c, download(hU, P.U, n5k, s));
+  if (out->g) LINE_CHECK(c, download(hg, P.g, n72, s));
+  if (out->bp) LINE_CHECK(c, download(hbp, P.bp, n72, s));
+  if (out->cost) LINE_CHECK(c, download(hcost, P.cost, (size_t)W, s));
+  if (out->ms_kernel) LINE_CHECK(c, download(hms, P.ms, 2 * (size_t)W, s));
+  LINE_CHECK(c, download(hne, P.n_elig, (size_t)W, s));
+  LINE_CHECK(c, download(hnf, P.n_failed, (size_t)W, s));
+  if (out->Vinv) LINE_CHECK(c, download(hV, P.oVinv, N * 16, s));
+  if (out->bl) LINE_CHECK(c, download(hb, P.obl, N * 4, s));
+  if (out->W) LINE_CHECK(c, download(hW, P.oW, N * RC_WROW, s));
+  if (out->failed) LINE_CHECK(c, download(hf, P.ofailed, N, s));
+  if (out->V) LINE_CHECK(c, download(hVl, P.oV, N * 10, s));
+  LINE_CHECK(c, hipStreamSynchronize(s));
   // (outputs are written only once the whole call has succeeded)
   if (out->H) std::memcpy(out->H, hH.data(), 8 * n5k);
   if (out->U) std::memcpy(out->U, hU.data(), 8 * n5k);
@@ -430,7 +375,7 @@ gfbe_status reduce_run(gfbe_ctx *c, ReduceBatch P, int W, const std::vector<int>
     keep->rec_mu = P.mu; keep->rec_gen = keep->gen; keep->rec_valid = true;
   }
 done:
-  if (d && !cache.d) (void)hipFree(d);
+  if (own.d) (void)hipFree(own.d);
   return st;
 }
 
@@ -441,75 +386,21 @@ extern "C" gfbe_status gfbe_line_reduce(gfbe_ctx *c, int32_t n_windows, const gf
   if (!c || n_windows < 0 || (n_windows > 0 && !win)) return GFBE_BAD_INPUT;
   if (!reduce_args_ok(c, "gfbe_line_reduce", mode, mu, out)) return GFBE_BAD_INPUT;
   const gfbe_line_reduced full = reduced_full(out);
-  // the windows: sizes, frames and pointers (the checks of gfbe_line_refine; observation VALUES are not looked at)
-  std::vector<int> line_off(n_windows + 1, 0), nlines(n_windows, 0);
-  size_t n_obs_total = 0;
-  for (int w = 0; w < n_windows; w++) {
-    const gfbe_line_window *L = win[w];
-    if (!L || L->struct_size != (int32_t)sizeof(gfbe_line_window)) { ctx_set_error(c, "gfbe_line_reduce: gfbe_line_window ABI mismatch"); return GFBE_BAD_INPUT; }
-    if (L->n_lines < 0 || (L->n_lines > 0 && (!L->start_frame || !L->n_obs || !L->is_triangulation || !L->line_plucker))) return GFBE_BAD_INPUT;
-    size_t no = 0;
-    for (int i = 0; i < L->n_lines; i++) {
-      const int s = L->start_frame[i], k = L->n_obs[i];
-      if (s < 0 || k < 0 || s + k > GFBE_NFRAMES) { ctx_set_error(c, "gfbe_line_reduce: a line's observations run past the window"); return GFBE_BAD_INPUT; }
-      no += (size_t)k;
-    }
-    if (no > 0 && !L->obs) return GFBE_BAD_INPUT;
-    if ((size_t)line_off[w] + (size_t)L->n_lines > (size_t)INT32_MAX / 512 || n_obs_total + no > (size_t)INT32_MAX / 8) return GFBE_BAD_INPUT;
-    line_off[w + 1] = line_off[w] + L->n_lines;
-    nlines[w] = L->n_lines;
-    n_obs_total += no;
-  }
+  LineWindows B;
+  if (!check_line_windows(c, "gfbe_line_reduce", n_windows, win, (size_t)INT32_MAX / 512, B)) return GFBE_BAD_INPUT;
   if (ctx_device(c) < 0) { ctx_set_error(c, "gfbe_line_reduce: HIP device context required (no CPU fallback)"); return GFBE_NO_DEVICE; }
   if (n_windows == 0) return GFBE_OK;
-  const int n_lines = line_off[n_windows];
-  // pack as gfbe_line_refine does: ints (line_off, obs_off, start), doubles (plucker, obs, poses, extrinsics), the triangulation flags
-  std::vector<int> ints((size_t)n_windows + 1 + 2 * (size_t)n_lines + 1);
-  int *h_line_off = ints.data(), *h_obs_off = h_line_off + n_windows + 1, *h_start = h_obs_off + n_lines + 1;
-  std::vector<double> dbl((size_t)6 * n_lines + 4 * n_obs_total + 84 * (size_t)n_windows);
-  double *h_plk = dbl.data(), *h_obs = h_plk + 6 * (size_t)n_lines, *h_pose = h_obs + 4 * n_obs_total, *h_ex = h_pose + 77 * (size_t)n_windows;
-  std::vector<unsigned char> h_tri(std::max(n_lines, 1));
-  {
-    size_t o = 0;
-    for (int w = 0; w < n_windows; w++) {
-      const gfbe_line_window *L = win[w];
-      h_line_off[w] = line_off[w];
-      std::memcpy(h_pose + 77 * (size_t)w, L->pose, sizeof(double) * 77);
-      std::memcpy(h_ex + 7 * (size_t)w, L->ex_cam, sizeof(double) * 7);
-      size_t lo = 0;
-      for (int i = 0; i < L->n_lines; i++) {
-        const int l = line_off[w] + i;
-        h_obs_off[l] = (int)o; h_start[l] = L->start_frame[i]; h_tri[l] = L->is_triangulation[i] ? 1 : 0;
-        std::memcpy(h_plk + 6 * (size_t)l, L->line_plucker + 6 * (size_t)i, sizeof(double) * 6);
-        if (L->n_obs[i] > 0) std::memcpy(h_obs + 4 * o, L->obs + 4 * lo, sizeof(double) * 4 * L->n_obs[i]);
-        o += L->n_obs[i]; lo += L->n_obs[i];
-      }
-    }
-    h_line_off[n_windows] = n_lines;
-    h_obs_off[n_lines] = (int)o;
-  }
+  std::vector<int> nlines(n_windows);
+  for (int w = 0; w < n_windows; w++) nlines[w] = B.line_off[w + 1] - B.line_off[w];
   hipStream_t s = ctx_stream(c);
   gfbe_status st = GFBE_OK;
-  char *d = nullptr;
-  const size_t b_int = sizeof(int) * ints.size(), b_dbl = sizeof(double) * dbl.size(), b_tri = h_tri.size();
-  auto up8 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  LineUpload U;
   ReduceBatch P{};
-  RD_CHECK(c, hipMalloc((void **)&d, up8(b_int) + up8(b_dbl) + up8(b_tri)));
-  {
-    int *d_int = (int *)d;
-    double *d_dbl = (double *)(d + up8(b_int));
-    unsigned char *d_tri = (unsigned char *)(d + up8(b_int) + up8(b_dbl));
-    P.line_off = d_int; P.obs_off = d_int + (h_obs_off - h_line_off); P.start = d_int + (h_start - h_line_off);
-    P.plk_in = d_dbl; P.obs = d_dbl + (h_obs - h_plk); P.pose = d_dbl + (h_pose - h_plk); P.ex = d_dbl + (h_ex - h_plk);
-    P.tri = d_tri;
-    P.sqrt_info = sqrt_info; P.huber = huber_width; P.mu = mu; P.mode = mode;
-    RD_CHECK(c, hipMemcpyAsync(d_int, ints.data(), b_int, hipMemcpyHostToDevice, s));
-    RD_CHECK(c, hipMemcpyAsync(d_dbl, dbl.data(), b_dbl, hipMemcpyHostToDevice, s));
-    RD_CHECK(c, hipMemcpyAsync(d_tri, h_tri.data(), b_tri, hipMemcpyHostToDevice, s));
-  }
-  st = reduce_run<false>(c, P, n_windows, nlines, &full, nullptr, nullptr, ReduceCache{nullptr, nullptr});     // (synchronises the stream: the packed host buffers stay alive until then)
+  LINE_CHECK(c, upload_line_windows(s, n_windows, win, B, 0, U));
+  P.L = U.L; P.sqrt_info = sqrt_info; P.huber = huber_width; P.mu = mu; P.mode = mode;
+  st = reduce_run<false>(c, P, n_windows, nlines, &full, nullptr, nullptr, nullptr);     // (synchronises the stream: the packed host buffers stay alive until then)
 done:
-  if (d) { (void)hipStreamSynchronize(s); (void)hipFree(d); }
+  if (U.d) { (void)hipStreamSynchronize(s); (void)hipFree(U.d); }
   return st;
 }
 
@@ -520,18 +411,17 @@ extern "C" gfbe_status gfbe_ltab_reduce(gfbe_ctx *c, gfbe_ltab *t, int32_t mode,
   const gfbe_line_reduced full = reduced_full(out);
   if (ctx_device(c) < 0) { ctx_set_error(c, "gfbe_ltab_reduce: HIP device context required (no CPU fallback)"); return GFBE_NO_DEVICE; }
   if (!t || !pose7 || !ex_cam) return GFBE_BAD_INPUT;
-  const int W = t->d.W, b = t->cur;
+  const int W = t->d.W;
   hipStream_t s = ctx_stream(c);
   gfbe_status st = GFBE_OK;
   std::vector<int> nlines(W);
   ReduceBatch P{};
   // the tables' sizes (the record slots and the scratch slab) come down first: the one wait of the call besides the results'
-  RD_CHECK(c, hipMemcpyAsync(nlines.data(), t->d.count, sizeof(int) * W, hipMemcpyDeviceToHost, s));
-  RD_CHECK(c, hipStreamSynchronize(s));
-  P.count = t->d.count; P.nobs = t->d.nobs[b]; P.F = t->d.F; P.start = t->d.start[b]; P.tri = t->d.tri[b]; P.plk_in = t->d.plk[b];
-  P.obs = t->d.obs[b];
+  LINE_CHECK(c, hipMemcpyAsync(nlines.data(), t->d.count, sizeof(int) * W, hipMemcpyDeviceToHost, s));
+  LINE_CHECK(c, hipStreamSynchronize(s));
+  P.L = ltab_line_list(*t, nullptr, nullptr);      // (reduce_run copies the poses up)
   P.sqrt_info = sqrt_info; P.huber = huber_width; P.mu = mu; P.mode = mode;
-  st = reduce_run<true>(c, P, W, nlines, &full, pose7, ex_cam, ReduceCache{&t->reduce_d, &t->reduce_cap},
+  st = reduce_run<true>(c, P, W, nlines, &full, pose7, ex_cam, &t->reduce_buf,
                         t->keep_records && mode == GFBE_LINE_REDUCE_SOLVE ? t : nullptr);
 done:
   return st;

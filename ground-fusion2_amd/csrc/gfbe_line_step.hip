@@ -6,10 +6,10 @@
 //
 // Shape: ONE WORKGROUP PER WINDOW AT A TIME (a workgroup walks windows blockIdx.x, blockIdx.x + gridDim.x, ...); thread t owns the
 // entering lines t, t + 256, ... Per window:
-//   rank     the entering lines in list order (block scan), as k_line_reduce ranks them: record q belongs to the q-th of them
+//   rank     the entering lines in list order (line_rank, gfbe_line.h: the rank k_line_reduce takes): record q belongs to the q-th of them
 //   phase 1  y_p, v_p staged in LDS; a thread streams its line's W (288 doubles) ONCE for both W^T y_p and W^T v_p, forms y_l, v_l and
 //            the eight shares (line_step_shares); vector ALU work: the right-hand side is two columns wide, a 16-wide matrix-core tile
-//            would be 7/8 padding. The shares go through the fixed-order reduction of k_line_refine (wave shuffle tree, then the waves
+//            would be 7/8 padding. The shares go through line_block_reduce (gfbe_line.h: wave shuffle tree, then the waves
 //            in order through LDS); every thread adds `rest` and takes the same dogleg branch from the broadcast totals
 //   phase 2  threads 0..11 form the candidate poses / extrinsic with the device's pose_plus; a thread forms its lines' candidates and
 //            their cost (line_factor without Jacobians + line_huber) and the candidate Plücker vector in the candidate start camera
@@ -25,6 +25,7 @@
 #include "gfbe_device.h"
 #include "gfbe_factors.h"
 #include "gfbe_line.h"
+#include "gfbe_line_batch.h"
 #include "gfbe_tabstage.h"
 
 using namespace gfd;
@@ -35,13 +36,7 @@ enum { LS_THREADS = 256, LS_WAVES = 4, LS_NP = LINE_NP, LS_WROW = LINE_NP * 4, L
 #define LS_COST_INVALID 1.7976931348623157e308
 
 struct StepBatch {
-  // the lines, as ReduceBatch of gfbe_line_reduce.hip: host-fed CSR or the tables in place
-  const int *line_off, *obs_off;       // host-fed
-  const int *count, *nobs;             // table-fed
-  int F;
-  const int *start;
-  const unsigned char *tri;
-  const double *plk_in, *obs, *pose, *ex;
+  LineList L;                          // the lines: host-fed CSR or the tables in place (gfbe_line.h)
   double sqrt_info, huber;
   int n_windows;
   const int *rec_off;                  // [n_windows + 1] first record slot of a window
@@ -59,70 +54,39 @@ struct StepBatch {
   int *n_elig;
 };
 
-// fixed-order reduction of eight per-thread values over the workgroup (wave shuffle tree, then the waves in order); entry 6 is a
-// maximum, the others are sums; every thread gets all eight
-__device__ void ls_reduce8(double *v, double (*sh)[LS_WAVES]) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      const double u = __shfl_down(v[k], o, 64);
-      v[k] = (k == 6) ? fmax(v[k], u) : v[k] + u;
-    }
-  if ((t & 63) == 0)
-    for (int k = 0; k < 8; k++) sh[k][t >> 6] = v[k];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    double a = 0.0;
-    for (int q = 0; q < LS_WAVES; q++) a = (k == 6) ? fmax(a, sh[k][q]) : a + sh[k][q];
-    v[k] = a;
-  }
-  __syncthreads();
-}
-
 template <bool TAB>
 __global__ __launch_bounds__(LS_THREADS) void k_line_step(StepBatch P) {
   const int t = threadIdx.x;
+  const LineList &L = P.L;
   __shared__ LineRT Bs[GFBE_NFRAMES], Cw[GFBE_NFRAMES], Bc[GFBE_NFRAMES], Cc[GFBE_NFRAMES];
   __shared__ LineRT Ex, Exc;
   __shared__ double syp[LS_NP], svp[LS_NP];
-  __shared__ double sh[8][LS_WAVES];
+  __shared__ double sh[8 * LS_WAVES];
   __shared__ int scan_lds[20];
   for (int w = blockIdx.x; w < P.n_windows; w += gridDim.x) {
     const uint64_t t_start = P.ms ? wall_clock64() : 0;
-    const int l0 = TAB ? w * P.F : P.line_off[w], l1 = TAB ? l0 + P.count[w] : P.line_off[w + 1];
+    int l0, l1;
+    line_range<TAB>(L, w, &l0, &l1);
     const size_t ro = (size_t)P.rec_off[w];
     const int cap = P.rec_off[w + 1] - P.rec_off[w];       // record slots of this window: nothing is written past them
-    const double *pose = P.pose + (size_t)w * 77, *ex = P.ex + (size_t)w * 7;
+    const double *pose = L.pose + (size_t)w * 77, *ex = L.ex + (size_t)w * 7;
     __syncthreads();                               // (the previous window's readers of LDS are done)
-    if (t < GFBE_NFRAMES) Bs[t] = line_make_pose(pose + 7 * t);
-    if (t == GFBE_NFRAMES) Ex = line_make_pose(ex);
+    line_stage_poses(L, w, Bs, &Ex);
     if (t >= 64 && t < 64 + LS_NP) { syp[t - 64] = P.yp[(size_t)w * LS_NP + t - 64]; svp[t - 64] = P.vp[(size_t)w * LS_NP + t - 64]; }
     __syncthreads();
-    if (t < GFBE_NFRAMES) { Cw[t].R = mul(Bs[t].R, Ex.R); Cw[t].t = add(Bs[t].t, mv(Bs[t].R, Ex.t)); }   // Rwc = Rs ric, twc = Ps + Rs tic
+    line_stage_cameras(Bs, Ex, Cw);
     // ---- rank: the entering lines in list order (the predicate of gfbe_line_reduce in solve mode)
     int *lineof = P.lineof + ro;
-    int n_elig = 0;
-    for (int c0 = l0; c0 < l1; c0 += LS_THREADS) {
-      const int l = c0 + t;
-      const int e = (l < l1 && line_eligible<TAB>(P, l)) ? 1 : 0;
-      int total;
-      const int at = n_elig + block_exclusive_scan<LS_THREADS>(e, &total, scan_lds);
-      if (e && at < cap) lineof[at] = l;
-      n_elig += total;
-    }
-    n_elig = min(n_elig, cap);
+    const int n_elig = line_rank<LS_THREADS>(l0, l1, [&](int l) { return line_eligible<TAB>(L, l); }, lineof, scan_lds, cap);
     __threadfence();
     __syncthreads();
     // ---- phase 1: back-substitution and the shares
     double p[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int q = t; q < n_elig; q += LS_THREADS) {
       const size_t slot = ro + q;
-      const int l = lineof[q], s = P.start[l];
+      const int l = lineof[q], s = L.start[l];
       double lw[6], x[4], yl[4] = {0.0, 0.0, 0.0, 0.0}, vl[4] = {0.0, 0.0, 0.0, 0.0};
-      line_plk_to_pose(P.plk_in + 6 * (size_t)l, Cw[s].R, Cw[s].t, lw);     // getLineOrthVector, as the reduce formed it
+      line_plk_to_pose(L.plk_in + 6 * (size_t)l, Cw[s].R, Cw[s].t, lw);     // getLineOrthVector, as the reduce formed it
       line_plk_to_orth(lw, x);
       if (!P.failed[slot]) {
         double sp[8];
@@ -132,7 +96,7 @@ __global__ __launch_bounds__(LS_THREADS) void k_line_step(StepBatch P) {
       }
       for (int a = 0; a < 4; a++) { P.yl[slot * 4 + a] = yl[a]; P.vl[slot * 4 + a] = vl[a]; P.xc[slot * 4 + a] = x[a]; }
     }
-    ls_reduce8(p, sh);
+    line_block_reduce<8, LS_WAVES>(p, 1u << 6, sh);      // (fixed order; entry 6 is a maximum)
     double tot[8], coef[4];
     const double *rest = P.rest + (size_t)w * 8;
 #pragma unroll
@@ -152,7 +116,7 @@ __global__ __launch_bounds__(LS_THREADS) void k_line_step(StepBatch P) {
       if (t == GFBE_NFRAMES) for (int a = 0; a < 7; a++) P.ex_c[(size_t)w * 7 + a] = ex[a];
       for (int q = t; q < n_elig; q += LS_THREADS) {
         const int l = lineof[q];
-        for (int a = 0; a < 6; a++) P.plkc[(ro + q) * 6 + a] = P.plk_in[6 * (size_t)l + a];
+        for (int a = 0; a < 6; a++) P.plkc[(ro + q) * 6 + a] = L.plk_in[6 * (size_t)l + a];
       }
     } else {
       if (t <= GFBE_NFRAMES) {                     // candidate poses / extrinsic = pose_plus(., c1 v_p + c2 y_p)
@@ -165,27 +129,27 @@ __global__ __launch_bounds__(LS_THREADS) void k_line_step(StepBatch P) {
         if (t < GFBE_NFRAMES) Bc[t] = line_make_pose(y7); else Exc = line_make_pose(y7);
       }
       __syncthreads();
-      if (t < GFBE_NFRAMES) { Cc[t].R = mul(Bc[t].R, Exc.R); Cc[t].t = add(Bc[t].t, mv(Bc[t].R, Exc.t)); }
+      line_stage_cameras(Bc, Exc, Cc);
       __syncthreads();
       for (int q = t; q < n_elig; q += LS_THREADS) {
         const size_t slot = ro + q;
-        const int l = lineof[q], s = P.start[l];
+        const int l = lineof[q], s = L.start[l];
         if (P.failed[slot]) {                      // a failed line takes part in nothing: its candidate is its input, bit for bit
-          for (int a = 0; a < 6; a++) P.plkc[slot * 6 + a] = P.plk_in[6 * (size_t)l + a];
+          for (int a = 0; a < 6; a++) P.plkc[slot * 6 + a] = L.plk_in[6 * (size_t)l + a];
           continue;
         }
         double x[4], yl[4], vl[4], xc[4], plk[6];
         for (int a = 0; a < 4; a++) { x[a] = P.xc[slot * 4 + a]; yl[a] = P.yl[slot * 4 + a]; vl[a] = P.vl[slot * 4 + a]; }   // (this thread's own stores)
-        csum += line_step_candidate(Bc, Exc, Cc[s], x, yl, vl, coef[0], coef[1], s, line_nobs<TAB>(P, l), line_obs<TAB>(P, l), P.sqrt_info,
+        csum += line_step_candidate(Bc, Exc, Cc[s], x, yl, vl, coef[0], coef[1], s, line_nobs<TAB>(L, l), line_obs<TAB>(L, l), P.sqrt_info,
                                     P.huber, xc, plk);
         for (int a = 0; a < 4; a++) P.xc[slot * 4 + a] = xc[a];
         for (int a = 0; a < 6; a++) P.plkc[slot * 6 + a] = plk[a];
       }
     }
-    double c8[8] = {csum, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    ls_reduce8(c8, sh);
+    double c1[1] = {csum};
+    line_block_reduce<1, LS_WAVES>(c1, 0u, sh);
     if (t == 0) {
-      P.cost[w] = invalid ? LS_COST_INVALID : c8[0];
+      P.cost[w] = invalid ? LS_COST_INVALID : c1[0];
       P.invalid[w] = invalid ? 1 : 0;
       P.n_elig[w] = n_elig;
       if (P.ms) P.ms[w] = (double)(wall_clock64() - t_start) * 1e-5;      // (100 MHz device wall clock)
@@ -206,12 +170,6 @@ __global__ __launch_bounds__(256) void k_line_commit(double *plk, const unsigned
     plk[6 * (size_t)lineof[ro + q] + a] = plkc[(ro + q) * 6 + a];
   }
 }
-
-#define LS_CHECK(c, call)                                                                                      \
-  do {                                                                                                         \
-    hipError_t e_ = (call);                                                                                    \
-    if (e_ != hipSuccess) { ctx_set_error(c, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); st = GFBE_DEVICE_ERROR; goto done; } \
-  } while (0)
 
 bool all_finite(const double *p, size_t n) {
   for (size_t i = 0; i < n; i++)
@@ -237,78 +195,63 @@ bool step_inputs_ok(gfbe_ctx *c, const char *who, int W, const double *yp, const
 
 // Launch and hand-over shared by the two entry points. P: the line inputs and the records on the device; rec_off [W + 1]: the record
 // slots; ne [W]: the entering lines of a window (what the reduce reported). h_pose / h_ex, d_rec_off (table-fed): the poses on the host,
-// copied into the call's allocation, and the slots already on the device. cache (table-fed): the allocation stays on the table handle —
+// copied into the call's allocation, and the slots already on the device. kept (table-fed): the allocation stays on the table handle —
 // it holds the candidates gfbe_ltab_commit reads.
-struct StepCache { char **d; size_t *cap; };
 template <bool TAB>
 gfbe_status step_run(gfbe_ctx *c, StepBatch P, int W, const std::vector<int> &rec_off, const std::vector<int> &ne, const double *yp,
                      const double *vp, const double *rest, const double *radius, const double *h_pose, const double *h_ex,
-                     const int *d_rec_off, gfbe_line_stepped *out, StepCache cache, StepBatch *laid = nullptr) {
+                     const int *d_rec_off, gfbe_line_stepped *out, DevBuf *kept, StepBatch *laid = nullptr) {
   hipStream_t s = ctx_stream(c);
   gfbe_status st = GFBE_OK;
   const size_t N = (size_t)rec_off[W], nw = (size_t)W;
   const int grid = std::min(W, (int)LS_MAX_GRID);
-  auto up8 = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  char *d = nullptr;
+  DevBuf own, &buf = kept ? *kept : own;
   double *d_yp = nullptr, *d_vp = nullptr, *d_rest = nullptr, *d_radius = nullptr, *d_pose = nullptr, *d_ex = nullptr;
   int *d_off = nullptr;
   std::vector<double> hgram, htotal, hcoef, hyl, hvl, hxc, hplk, hpose, hex, hcost, hms;
   std::vector<unsigned char> hinv;
-  auto layout = [&](char *p) -> size_t {
-    char *const p0 = p;
-    auto take = [&](size_t bytes) { char *q = p; p += up8(bytes); return q; };
-    d_yp = (double *)take(8 * nw * LS_NP); d_vp = (double *)take(8 * nw * LS_NP); d_rest = (double *)take(8 * nw * 8); d_radius = (double *)take(8 * nw);
-    if (h_pose) { d_pose = (double *)take(8 * 77 * nw); d_ex = (double *)take(8 * 7 * nw); }
-    if (!d_rec_off) d_off = (int *)take(sizeof(int) * (nw + 1));
-    P.lineof = (int *)take(sizeof(int) * (N + 1));
-    P.yl = (double *)take(8 * N * 4); P.vl = (double *)take(8 * N * 4); P.xc = (double *)take(8 * N * 4); P.plkc = (double *)take(8 * N * 6);
-    P.gram = (double *)take(8 * nw * 8); P.total = (double *)take(8 * nw * 8); P.coef = (double *)take(8 * nw * 4);
-    P.pose_c = (double *)take(8 * nw * 77); P.ex_c = (double *)take(8 * nw * 7); P.cost = (double *)take(8 * nw);
-    P.ms = out->ms_kernel ? (double *)take(8 * nw) : nullptr;
-    P.invalid = (unsigned char *)take(nw); P.n_elig = (int *)take(sizeof(int) * nw);
-    return (size_t)(p - p0);
+  auto layout = [&](char *base) {
+    Arena a(base);
+    d_yp = a.take<double>(nw * LS_NP); d_vp = a.take<double>(nw * LS_NP); d_rest = a.take<double>(nw * 8); d_radius = a.take<double>(nw);
+    if (h_pose) { d_pose = a.take<double>(77 * nw); d_ex = a.take<double>(7 * nw); }
+    if (!d_rec_off) d_off = a.take<int>(nw + 1);
+    P.lineof = a.take<int>(N + 1);
+    P.yl = a.take<double>(N * 4); P.vl = a.take<double>(N * 4); P.xc = a.take<double>(N * 4); P.plkc = a.take<double>(N * 6);
+    P.gram = a.take<double>(nw * 8); P.total = a.take<double>(nw * 8); P.coef = a.take<double>(nw * 4);
+    P.pose_c = a.take<double>(nw * 77); P.ex_c = a.take<double>(nw * 7); P.cost = a.take<double>(nw);
+    P.ms = out->ms_kernel ? a.take<double>(nw) : nullptr;
+    P.invalid = a.take<unsigned char>(nw); P.n_elig = a.take<int>(nw);
+    return a.off;
   };
-  {
-    const size_t need = layout(nullptr);
-    if (cache.d && *cache.cap >= need) {
-      d = *cache.d;
-    } else {
-      if (cache.d && *cache.d) { LS_CHECK(c, hipStreamSynchronize(s)); (void)hipFree(*cache.d); *cache.d = nullptr; *cache.cap = 0; }
-      LS_CHECK(c, hipMalloc((void **)&d, need));
-      if (cache.d) { *cache.d = d; *cache.cap = need; }
-    }
-    (void)layout(d);
-    P.n_windows = W; P.yp = d_yp; P.vp = d_vp; P.rest = d_rest; P.radius = d_radius;
-    LS_CHECK(c, hipMemcpyAsync(d_yp, yp, 8 * nw * LS_NP, hipMemcpyHostToDevice, s));
-    LS_CHECK(c, hipMemcpyAsync(d_vp, vp, 8 * nw * LS_NP, hipMemcpyHostToDevice, s));
-    LS_CHECK(c, hipMemcpyAsync(d_rest, rest, 8 * nw * 8, hipMemcpyHostToDevice, s));
-    LS_CHECK(c, hipMemcpyAsync(d_radius, radius, 8 * nw, hipMemcpyHostToDevice, s));
-    if (h_pose) {
-      P.pose = d_pose; P.ex = d_ex;
-      LS_CHECK(c, hipMemcpyAsync(d_pose, h_pose, 8 * 77 * nw, hipMemcpyHostToDevice, s));
-      LS_CHECK(c, hipMemcpyAsync(d_ex, h_ex, 8 * 7 * nw, hipMemcpyHostToDevice, s));
-    }
-    if (d_rec_off) P.rec_off = d_rec_off;
-    else { P.rec_off = d_off; LS_CHECK(c, hipMemcpyAsync(d_off, rec_off.data(), sizeof(int) * (nw + 1), hipMemcpyHostToDevice, s)); }
-    if (laid) *laid = P;
+  LINE_CHECK(c, lay_out(s, buf, layout));
+  P.n_windows = W; P.yp = d_yp; P.vp = d_vp; P.rest = d_rest; P.radius = d_radius;
+  LINE_CHECK(c, hipMemcpyAsync(d_yp, yp, 8 * nw * LS_NP, hipMemcpyHostToDevice, s));
+  LINE_CHECK(c, hipMemcpyAsync(d_vp, vp, 8 * nw * LS_NP, hipMemcpyHostToDevice, s));
+  LINE_CHECK(c, hipMemcpyAsync(d_rest, rest, 8 * nw * 8, hipMemcpyHostToDevice, s));
+  LINE_CHECK(c, hipMemcpyAsync(d_radius, radius, 8 * nw, hipMemcpyHostToDevice, s));
+  if (h_pose) {
+    P.L.pose = d_pose; P.L.ex = d_ex;
+    LINE_CHECK(c, hipMemcpyAsync(d_pose, h_pose, 8 * 77 * nw, hipMemcpyHostToDevice, s));
+    LINE_CHECK(c, hipMemcpyAsync(d_ex, h_ex, 8 * 7 * nw, hipMemcpyHostToDevice, s));
   }
+  if (d_rec_off) P.rec_off = d_rec_off;
+  else { P.rec_off = d_off; LINE_CHECK(c, hipMemcpyAsync(d_off, rec_off.data(), sizeof(int) * (nw + 1), hipMemcpyHostToDevice, s)); }
+  if (laid) *laid = P;
   hipLaunchKernelGGL(k_line_step<TAB>, dim3(grid), dim3(LS_THREADS), 0, s, P);
-  LS_CHECK(c, hipGetLastError());
-#define LS_DOWN(vec, dptr, n) do { vec.resize(std::max<size_t>(n, 1)); if (n) LS_CHECK(c, hipMemcpyAsync(vec.data(), dptr, sizeof(vec[0]) * (n), hipMemcpyDeviceToHost, s)); } while (0)
-  if (out->gram) LS_DOWN(hgram, P.gram, nw * 8);
-  if (out->total) LS_DOWN(htotal, P.total, nw * 8);
-  if (out->coef) LS_DOWN(hcoef, P.coef, nw * 4);
-  if (out->invalid) LS_DOWN(hinv, P.invalid, nw);
-  if (out->y_l) LS_DOWN(hyl, P.yl, N * 4);
-  if (out->v_l) LS_DOWN(hvl, P.vl, N * 4);
-  if (out->orth_cand) LS_DOWN(hxc, P.xc, N * 4);
-  if (out->plucker_cand) LS_DOWN(hplk, P.plkc, N * 6);
-  if (out->pose_cand) LS_DOWN(hpose, P.pose_c, nw * 77);
-  if (out->ex_cand) LS_DOWN(hex, P.ex_c, nw * 7);
-  if (out->cost_cand) LS_DOWN(hcost, P.cost, nw);
-  if (out->ms_kernel) LS_DOWN(hms, P.ms, nw);
-#undef LS_DOWN
-  LS_CHECK(c, hipStreamSynchronize(s));
+  LINE_CHECK(c, hipGetLastError());
+  if (out->gram) LINE_CHECK(c, download(hgram, P.gram, nw * 8, s));
+  if (out->total) LINE_CHECK(c, download(htotal, P.total, nw * 8, s));
+  if (out->coef) LINE_CHECK(c, download(hcoef, P.coef, nw * 4, s));
+  if (out->invalid) LINE_CHECK(c, download(hinv, P.invalid, nw, s));
+  if (out->y_l) LINE_CHECK(c, download(hyl, P.yl, N * 4, s));
+  if (out->v_l) LINE_CHECK(c, download(hvl, P.vl, N * 4, s));
+  if (out->orth_cand) LINE_CHECK(c, download(hxc, P.xc, N * 4, s));
+  if (out->plucker_cand) LINE_CHECK(c, download(hplk, P.plkc, N * 6, s));
+  if (out->pose_cand) LINE_CHECK(c, download(hpose, P.pose_c, nw * 77, s));
+  if (out->ex_cand) LINE_CHECK(c, download(hex, P.ex_c, nw * 7, s));
+  if (out->cost_cand) LINE_CHECK(c, download(hcost, P.cost, nw, s));
+  if (out->ms_kernel) LINE_CHECK(c, download(hms, P.ms, nw, s));
+  LINE_CHECK(c, hipStreamSynchronize(s));
   // (outputs are written only once the whole call has succeeded)
   if (out->gram) std::memcpy(out->gram, hgram.data(), 8 * nw * 8);
   if (out->total) std::memcpy(out->total, htotal.data(), 8 * nw * 8);
@@ -330,7 +273,7 @@ gfbe_status step_run(gfbe_ctx *c, StepBatch P, int W, const std::vector<int> &re
     }
   }
 done:
-  if (d && !cache.d) { (void)hipStreamSynchronize(s); (void)hipFree(d); }
+  if (own.d) { (void)hipStreamSynchronize(s); (void)hipFree(own.d); }
   return st;
 }
 
@@ -351,95 +294,41 @@ extern "C" gfbe_status gfbe_line_step(gfbe_ctx *c, int32_t n_windows, const gfbe
     return GFBE_BAD_INPUT;
   }
   if (!step_inputs_ok(c, "gfbe_line_step", n_windows, y_p, v_p, rest, radius)) return GFBE_BAD_INPUT;
-  // the windows: the checks of gfbe_line_reduce, and the records must be these windows' own
-  std::vector<int> line_off(n_windows + 1, 0), rec_off(n_windows + 1, 0), ne(n_windows, 0);
-  size_t n_obs_total = 0;
+  // the windows, and the records must be these windows' own
+  LineWindows B;
+  if (!check_line_windows(c, "gfbe_line_step", n_windows, win, (size_t)INT32_MAX / 512, B)) return GFBE_BAD_INPUT;
+  std::vector<int> rec_off(n_windows + 1, 0);
   for (int w = 0; w < n_windows; w++) {
-    const gfbe_line_window *L = win[w];
-    if (!L || L->struct_size != (int32_t)sizeof(gfbe_line_window)) { ctx_set_error(c, "gfbe_line_step: gfbe_line_window ABI mismatch"); return GFBE_BAD_INPUT; }
-    if (L->n_lines < 0 || (L->n_lines > 0 && (!L->start_frame || !L->n_obs || !L->is_triangulation || !L->line_plucker))) return GFBE_BAD_INPUT;
-    size_t no = 0;
-    int entering = 0;
-    for (int i = 0; i < L->n_lines; i++) {
-      const int s = L->start_frame[i], k = L->n_obs[i];
-      if (s < 0 || k < 0 || s + k > GFBE_NFRAMES) { ctx_set_error(c, "gfbe_line_step: a line's observations run past the window"); return GFBE_BAD_INPUT; }
-      no += (size_t)k;
-      entering += (k >= 5 && s < GFBE_WINDOW_SIZE - 2 && L->is_triangulation[i]) ? 1 : 0;
-    }
-    if (no > 0 && !L->obs) return GFBE_BAD_INPUT;
-    if (rec->n_eligible[w] != entering) { ctx_set_error(c, "gfbe_line_step: n_eligible is not the window's count of entering lines"); return GFBE_BAD_INPUT; }
-    if ((size_t)line_off[w] + (size_t)L->n_lines > (size_t)INT32_MAX / 512 || n_obs_total + no > (size_t)INT32_MAX / 8) return GFBE_BAD_INPUT;
-    line_off[w + 1] = line_off[w] + L->n_lines;
-    rec_off[w + 1] = rec_off[w] + entering;
-    ne[w] = entering;
-    n_obs_total += no;
+    if (rec->n_eligible[w] != B.entering[w]) { ctx_set_error(c, "gfbe_line_step: n_eligible is not the window's count of entering lines"); return GFBE_BAD_INPUT; }
+    rec_off[w + 1] = rec_off[w] + B.entering[w];
   }
   if (ctx_device(c) < 0) { ctx_set_error(c, "gfbe_line_step: HIP device context required (no CPU fallback)"); return GFBE_NO_DEVICE; }
   if (n_windows == 0) return GFBE_OK;
-  const int n_lines = line_off[n_windows];
   const size_t N = (size_t)rec_off[n_windows];
-  // pack as gfbe_line_reduce does: ints (line_off, obs_off, start), doubles (plucker, obs, poses, extrinsics), the triangulation flags
-  std::vector<int> ints((size_t)n_windows + 1 + 2 * (size_t)n_lines + 1);
-  int *h_line_off = ints.data(), *h_obs_off = h_line_off + n_windows + 1, *h_start = h_obs_off + n_lines + 1;
-  std::vector<double> dbl((size_t)6 * n_lines + 4 * n_obs_total + 84 * (size_t)n_windows);
-  double *h_plk = dbl.data(), *h_obs = h_plk + 6 * (size_t)n_lines, *h_pose = h_obs + 4 * n_obs_total, *h_ex = h_pose + 77 * (size_t)n_windows;
-  std::vector<unsigned char> h_tri(std::max(n_lines, 1));
-  {
-    size_t o = 0;
-    for (int w = 0; w < n_windows; w++) {
-      const gfbe_line_window *L = win[w];
-      h_line_off[w] = line_off[w];
-      std::memcpy(h_pose + 77 * (size_t)w, L->pose, sizeof(double) * 77);
-      std::memcpy(h_ex + 7 * (size_t)w, L->ex_cam, sizeof(double) * 7);
-      size_t lo = 0;
-      for (int i = 0; i < L->n_lines; i++) {
-        const int l = line_off[w] + i;
-        h_obs_off[l] = (int)o; h_start[l] = L->start_frame[i]; h_tri[l] = L->is_triangulation[i] ? 1 : 0;
-        std::memcpy(h_plk + 6 * (size_t)l, L->line_plucker + 6 * (size_t)i, sizeof(double) * 6);
-        if (L->n_obs[i] > 0) std::memcpy(h_obs + 4 * o, L->obs + 4 * lo, sizeof(double) * 4 * L->n_obs[i]);
-        o += L->n_obs[i]; lo += L->n_obs[i];
-      }
-    }
-    h_line_off[n_windows] = n_lines;
-    h_obs_off[n_lines] = (int)o;
-  }
   hipStream_t s = ctx_stream(c);
   gfbe_status st = GFBE_OK;
-  char *d = nullptr;
-  auto up8 = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_int = sizeof(int) * ints.size(), b_dbl = sizeof(double) * dbl.size(), b_tri = h_tri.size();
-  const size_t b_rec[5] = {8 * N * 16, 8 * N * 4, 8 * N * LS_WROW, 8 * N * 10, N + 1};
+  LineUpload U;
   StepBatch P{};
-  {
-    size_t need = up8(b_int) + up8(b_dbl) + up8(b_tri);
-    for (size_t b : b_rec) need += up8(b);
-    LS_CHECK(c, hipMalloc((void **)&d, need));
-    char *p = d;
-    auto take = [&](size_t bytes) { char *q = p; p += up8(bytes); return q; };
-    int *d_int = (int *)take(b_int);
-    double *d_dbl = (double *)take(b_dbl);
-    unsigned char *d_tri = (unsigned char *)take(b_tri);
-    double *d_Vinv = (double *)take(b_rec[0]), *d_bl = (double *)take(b_rec[1]), *d_W = (double *)take(b_rec[2]), *d_V = (double *)take(b_rec[3]);
-    unsigned char *d_failed = (unsigned char *)take(b_rec[4]);
-    P.line_off = d_int; P.obs_off = d_int + (h_obs_off - h_line_off); P.start = d_int + (h_start - h_line_off);
-    P.plk_in = d_dbl; P.obs = d_dbl + (h_obs - h_plk); P.pose = d_dbl + (h_pose - h_plk); P.ex = d_dbl + (h_ex - h_plk);
-    P.tri = d_tri;
-    P.Vinv = d_Vinv; P.bl = d_bl; P.W = d_W; P.V = d_V; P.failed = d_failed;
-    P.sqrt_info = sqrt_info; P.huber = huber_width;
-    LS_CHECK(c, hipMemcpyAsync(d_int, ints.data(), b_int, hipMemcpyHostToDevice, s));
-    LS_CHECK(c, hipMemcpyAsync(d_dbl, dbl.data(), b_dbl, hipMemcpyHostToDevice, s));
-    LS_CHECK(c, hipMemcpyAsync(d_tri, h_tri.data(), b_tri, hipMemcpyHostToDevice, s));
-    if (N) {
-      LS_CHECK(c, hipMemcpyAsync(d_Vinv, rec->Vinv, b_rec[0], hipMemcpyHostToDevice, s));
-      LS_CHECK(c, hipMemcpyAsync(d_bl, rec->bl, b_rec[1], hipMemcpyHostToDevice, s));
-      LS_CHECK(c, hipMemcpyAsync(d_W, rec->W, b_rec[2], hipMemcpyHostToDevice, s));
-      LS_CHECK(c, hipMemcpyAsync(d_V, rec->V, b_rec[3], hipMemcpyHostToDevice, s));
-      LS_CHECK(c, hipMemcpyAsync(d_failed, rec->failed, N, hipMemcpyHostToDevice, s));
-    }
+  // the records, behind the packed windows in the call's one allocation
+  auto layout = [&](char *base) {
+    Arena a(base);
+    P.Vinv = a.take<double>(N * 16); P.bl = a.take<double>(N * 4); P.W = a.take<double>(N * LS_WROW); P.V = a.take<double>(N * 10);
+    P.failed = a.take<unsigned char>(N + 1);
+    return a.off;
+  };
+  LINE_CHECK(c, upload_line_windows(s, n_windows, win, B, layout(nullptr), U));
+  (void)layout(U.extra);
+  P.L = U.L; P.sqrt_info = sqrt_info; P.huber = huber_width;
+  if (N) {
+    LINE_CHECK(c, hipMemcpyAsync((void *)P.Vinv, rec->Vinv, 8 * N * 16, hipMemcpyHostToDevice, s));
+    LINE_CHECK(c, hipMemcpyAsync((void *)P.bl, rec->bl, 8 * N * 4, hipMemcpyHostToDevice, s));
+    LINE_CHECK(c, hipMemcpyAsync((void *)P.W, rec->W, 8 * N * LS_WROW, hipMemcpyHostToDevice, s));
+    LINE_CHECK(c, hipMemcpyAsync((void *)P.V, rec->V, 8 * N * 10, hipMemcpyHostToDevice, s));
+    LINE_CHECK(c, hipMemcpyAsync((void *)P.failed, rec->failed, N, hipMemcpyHostToDevice, s));
   }
-  st = step_run<false>(c, P, n_windows, rec_off, ne, y_p, v_p, rest, radius, nullptr, nullptr, nullptr, out, StepCache{nullptr, nullptr});   // (synchronises the stream)
+  st = step_run<false>(c, P, n_windows, rec_off, B.entering, y_p, v_p, rest, radius, nullptr, nullptr, nullptr, out, nullptr);   // (synchronises the stream)
 done:
-  if (d) { (void)hipStreamSynchronize(s); (void)hipFree(d); }
+  if (U.d) { (void)hipStreamSynchronize(s); (void)hipFree(U.d); }
   return st;
 }
 
@@ -458,7 +347,7 @@ extern "C" gfbe_status gfbe_ltab_step(gfbe_ctx *c, gfbe_ltab *t, const double *p
   if (!stepped_ok(c, "gfbe_ltab_step", out)) return GFBE_BAD_INPUT;
   if (ctx_device(c) < 0) { ctx_set_error(c, "gfbe_ltab_step: HIP device context required (no CPU fallback)"); return GFBE_NO_DEVICE; }
   if (!t || !pose7 || !ex_cam) return GFBE_BAD_INPUT;
-  const int W = t->d.W, b = t->cur;
+  const int W = t->d.W;
   if (!step_inputs_ok(c, "gfbe_ltab_step", W, y_p, v_p, rest, radius)) return GFBE_BAD_INPUT;
   if (!t->keep_records || !t->rec_valid) { ctx_set_error(c, "gfbe_ltab_step: no records are held (gfbe_ltab_keep_records, then gfbe_ltab_reduce in solve mode)"); return GFBE_BAD_INPUT; }
   if (t->rec_gen != t->gen) { ctx_set_error(c, "gfbe_ltab_step: the tables have changed since the reduce that wrote the records"); return GFBE_BAD_INPUT; }
@@ -468,13 +357,12 @@ extern "C" gfbe_status gfbe_ltab_step(gfbe_ctx *c, gfbe_ltab *t, const double *p
   }
   t->cand_valid = false;
   StepBatch P{};
-  P.count = t->d.count; P.nobs = t->d.nobs[b]; P.F = t->d.F; P.start = t->d.start[b]; P.tri = t->d.tri[b]; P.plk_in = t->d.plk[b];
-  P.obs = t->d.obs[b];
+  P.L = ltab_line_list(*t, nullptr, nullptr);      // (step_run copies the poses up)
   P.Vinv = t->rec_Vinv; P.bl = t->rec_bl; P.W = t->rec_W; P.V = t->rec_V; P.failed = t->rec_failed;
   P.sqrt_info = sqrt_info; P.huber = huber_width;
   StepBatch laid{};
   const gfbe_status st = step_run<true>(c, P, W, t->rec_off, t->rec_ne, y_p, v_p, rest, radius, pose7, ex_cam, t->rec_off_d, out,
-                                        StepCache{&t->step_d, &t->step_cap}, &laid);
+                                        &t->step_buf, &laid);
   if (st != GFBE_OK) return st;
   // the candidates stay in the handle's allocation for gfbe_ltab_commit
   t->cand_lineof = laid.lineof; t->cand_plk = laid.plkc; t->cand_ne = laid.n_elig;

@@ -21,6 +21,7 @@
 
 #include "gfbe_device.h"
 #include "gfbe_line.h"
+#include "gfbe_line_batch.h"
 #include "gfbe_tabstage.h"
 
 using namespace gfd;
@@ -314,9 +315,8 @@ void gfbe_ltab_destroy(gfbe_ctx *c, gfbe_ltab *t) {
   if (!t) return;
   if (c && ctx_device(c) >= 0) (void)hipStreamSynchronize(ctx_stream(c));
   for (void *p : t->allocs) (void)hipFree(p);
-  if (t->reduce_d) (void)hipFree(t->reduce_d);
-  if (t->rec_d) (void)hipFree(t->rec_d);
-  if (t->step_d) (void)hipFree(t->step_d);
+  for (const DevBuf *b : {&t->reduce_buf, &t->rec_buf, &t->step_buf})
+    if (b->d) (void)hipFree(b->d);
   if (t->stage_d) (void)hipFree(t->stage_d);
   if (t->stage_h) (void)hipHostFree(t->stage_h);
   if (t->ring_d) (void)hipFree(t->ring_d);
@@ -393,7 +393,7 @@ gfbe_status gfbe_ltab_refine(gfbe_ctx *c, gfbe_ltab *t, const double *pose7, con
   gfbe_status st = lt_ready(c, t);
   if (st != GFBE_OK) return st;
   if (!pose7 || !ex_cam || !summary || !(cauchy_scale > 0.0) || max_num_iterations < 0) return GFBE_BAD_INPUT;
-  const int W = t->d.W, b = t->cur;
+  const int W = t->d.W;
   std::vector<gfbe_summary> h_sum(W);
   t->gen++;
   {
@@ -402,8 +402,7 @@ gfbe_status gfbe_ltab_refine(gfbe_ctx *c, gfbe_ltab *t, const double *pose7, con
     gfbe_summary *dsum = s.up<gfbe_summary>(nullptr, W);
     if (!s.ok) { ctx_set_error(c, "gfbe_ltab_refine: staging allocation failed"); return GFBE_DEVICE_ERROR; }
     s.flush();
-    const LineTabView v{t->d.count, t->d.start[b], t->d.nobs[b], t->d.tri[b], t->d.plk[b], t->d.obs[b], t->d.F};
-    launch_line_refine_tables(v, W, dp, de, sqrt_info, cauchy_scale, max_num_iterations, t->d.row, t->d.plk_out, t->d.rkeep, dsum, ctx_stream(c));
+    launch_line_refine_tables(ltab_line_list(*t, dp, de), W, sqrt_info, cauchy_scale, max_num_iterations, t->d.row, t->d.plk_out, t->d.rkeep, dsum, ctx_stream(c));
     // setLineOrth + the erasures of removeLineOutlier, in place: refined lines written back, culled lines erased in order
     lt_erase_launch(c, t, OP_REFINE, nullptr, nullptr, nullptr);
     s.down(h_sum.data(), dsum, W);

@@ -163,6 +163,30 @@ def test_batch_of_257(be, mu):
     assert not fails, "\n".join(fails)
 
 
+def test_batch_of_1025_walks_a_workgroup_to_a_second_window(be):
+    """k_line_step runs at most 1024 workgroups: in a batch of 1025 the workgroup of window 0 goes on to window 1024. Small windows
+    (8 lines, 5 of them entering) with distinct seeds, the radii cycling through a small, a middle and a large one; windows 0, 1, 1023
+    and 1024 of the batch against the same windows stepped alone, bit for bit on every output."""
+    W = 1025
+    lws = [gf.synth_line.line_window(seed=7000 + k, n_ok=5, n_short=1, n_late=1, n_untri=1, n_behind=0, n_long=0, n_outlier=0) for k in range(W)]
+    assert all(len(lw["n_obs"]) == 8 and int(lr.entering(lw, lr.SOLVE).sum()) >= 5 for lw in lws)
+    holders = [abi.LineWindowHolder(lw) for lw in lws]
+    keys = ("n_eligible", "n_failed") + abi.LINE_RECORD_KEYS
+    reds = be.line_reduce_v(holders, lr.SOLVE, 400.0, 1.0, 0.0, keys)
+    assert all(int(r["n_eligible"]) >= 5 and int(r["n_failed"]) == 0 for r in reds)
+    rng = np.random.default_rng(1025)
+    y, v = rng.normal(0, 1e-3, (W, 72)), rng.normal(0, 1e-3, (W, 72))
+    rest = np.abs(rng.normal(1, 0.1, (W, 8)))
+    radius = np.array([1e-3, 1.0, 1e4])[np.arange(W) % 3]
+    res = be.line_step(holders, reds, y, v, rest, radius)
+    assert not all(int(r["invalid"]) for r in res)
+    for w in (0, 1, 1023, 1024):
+        alone = be.line_step([holders[w]], [reds[w]], y[w], v[w], rest[w], radius[w:w + 1])[0]
+        assert len(alone["y_l"]) == int(reds[w]["n_eligible"]) and np.isfinite(alone["cost_cand"])
+        assert not same_bits(alone, res[w]), (w, same_bits(alone, res[w]))
+    assert same_bits(res[0], res[1024])      # (distinct windows: the comparison above is not of one window with itself)
+
+
 def _upload(tabs, w, lw):
     n = len(lw["n_obs"])
     off = np.concatenate([[0], np.cumsum(lw["n_obs"])]).astype(int)
