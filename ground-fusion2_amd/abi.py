@@ -1295,3 +1295,118 @@ def ltab_to_line_window(tab, pose7, ex_cam):
     obs = np.concatenate([tab["obs4"][i, :no[i]] for i in range(len(no))]) if len(no) else np.zeros((0, 4))
     return dict(start_frame=tab["start_frame"], n_obs=tab["n_obs"], obs=obs.reshape(-1, 4), is_triangulation=tab["is_triangulation"],
                 line_plucker=tab["line_plucker"], pose=np.asarray(pose7, float).reshape(NFRAMES, 7), ex_cam=np.asarray(ex_cam, float))
+
+
+# ---------------------------------------------------------------------------------------------
+# Voxel map of the LiDAR odometry (gfbe_vmap_*): map_incremental, lasermap_fov_segment, the association of addSurfCostFactor
+# ---------------------------------------------------------------------------------------------
+class VmapOptions(C.Structure):
+    _fields_ = [("struct_size", c_i), ("max_num_points_in_voxel", c_i), ("voxel_neighborhood", c_i), ("max_number_neighbors", c_i),
+                ("min_number_neighbors", c_i), ("threshold_voxel_occupancy", c_i), ("num_closest_neighbors", c_i), ("max_num_residuals", c_i),
+                ("size_voxel_map", c_d), ("min_distance_points", c_d), ("max_distance", c_d), ("max_dist_to_plane_icp", c_d),
+                ("power_planarity", c_d), ("weight_alpha", c_d), ("weight_neighborhood", c_d)]
+
+
+def vmap_default_options(lib, prefix="gfbe_"):
+    o = VmapOptions()
+    f = getattr(lib, prefix + "vmap_default_options")
+    f.restype = None
+    f(C.byref(o))
+    return o
+
+
+class VoxelMap:
+    """A device-resident voxel map behind `lib` (prefix gfbe_, ctx = gfbe_ctx*). options: fields of gfbe_vmap_options."""
+    PI16 = C.POINTER(C.c_int16)
+
+    def __init__(self, lib, prefix, ctx, voxel_capacity=1 << 16, **options):
+        self.lib, self.prefix, self.ctx, self.cap = lib, prefix, ctx, voxel_capacity
+        self.h = C.c_void_p()
+        self.opt = vmap_default_options(lib, prefix)
+        for k, v in options.items():
+            if not hasattr(self.opt, k):
+                raise TypeError("gfbe_vmap_options has no field %r" % k)
+            setattr(self.opt, k, v)
+        for name in ("create", "add_points", "erase_far", "size", "download", "upload", "associate", "linearize", "localizability"):
+            self._f(name).restype = c_i
+        self._f("destroy").restype = None
+        self._f("linearize").argtypes = [C.c_void_p, C.c_void_p, c_i, c_d, PD, PD, PD, PD, PD, PD, PD]
+        self._check(self._f("create")(self.ctx, int(voxel_capacity), C.byref(self.opt), C.byref(self.h)), "create")
+
+    def _f(self, name):
+        return getattr(self.lib, self.prefix + "vmap_" + name)
+
+    def _check(self, rc, what):
+        if rc != OK:
+            raise RuntimeError("%svmap_%s failed with status %d" % (self.prefix, what, rc))
+
+    def close(self):
+        if self.h:
+            self._f("destroy")(self.ctx, self.h)
+            self.h = C.c_void_p()
+
+    def add_points(self, pts_world, min_num_points=0):
+        p = _f64(pts_world).reshape(-1, 3)
+        self._check(self._f("add_points")(self.ctx, self.h, len(p), _pd(p), int(min_num_points)), "add_points")
+
+    def erase_far(self, location):
+        loc = _f64(location).reshape(3)
+        self._check(self._f("erase_far")(self.ctx, self.h, _pd(loc)), "erase_far")
+
+    def size(self):
+        """dict(n_voxels, n_points, n_skipped, overflow)."""
+        v = (c_i * 4)()
+        self._check(self._f("size")(self.ctx, self.h, C.byref(v, 0), C.byref(v, 4), C.byref(v, 8), C.byref(v, 12)), "size")
+        return dict(n_voxels=v[0], n_points=v[1], n_skipped=v[2], overflow=v[3])
+
+    def download(self):
+        """Voxels in ascending key order: dict(keys [nv, 3] int16, counts [nv], points [np, 3])."""
+        sz = self.size()
+        nv, npt = sz["n_voxels"], sz["n_points"]
+        keys, counts, pts = np.zeros((nv, 3), np.int16), np.zeros(nv, np.int32), np.zeros((npt, 3))
+        self._check(self._f("download")(self.ctx, self.h, keys.ctypes.data_as(self.PI16), _pi(counts), _pd(pts)), "download")
+        return dict(keys=keys, counts=counts, points=pts)
+
+    def upload(self, keys, counts, points):
+        k, cn, p = np.ascontiguousarray(keys, np.int16).reshape(-1, 3), _i32(counts), _f64(points).reshape(-1, 3)
+        assert len(k) == len(cn) and int(cn.sum()) == len(p)
+        self._check(self._f("upload")(self.ctx, self.h, len(k), k.ctypes.data_as(self.PI16), _pi(cn), _pd(p)), "upload")
+
+    def associate(self, ct, raw_pts, alpha, pose_begin, pose_end=None, frame_init=False):
+        """The loop body of addSurfCostFactor for a scan: dict(n_res, src, pts, normals, offsets, alpha, weights, neighbor_count, a2D,
+        neighbor_visit, n_nan). The rows also stay on the handle for linearize() / localizability()."""
+        raw = _f64(raw_pts).reshape(-1, 3)
+        n = len(raw)
+        al = _f64(alpha if alpha is not None else np.zeros(n))
+        pb = _f64(pose_begin)
+        pe = _f64(pose_end if pose_end is not None else pose_begin)
+        R = max(1, min(n * self.opt.num_closest_neighbors, self.opt.max_num_residuals))
+        src, pts, nrm, off, alo, w = np.zeros(R, np.int32), np.zeros((R, 3)), np.zeros((R, 3)), np.zeros(R), np.zeros(R), np.zeros(R)
+        cnt, a2d = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1))
+        vis = np.full((max(n, 1), self.opt.max_number_neighbors), -1, np.int32)
+        nres, nnan = c_i(0), c_i(0)
+        self._check(self._f("associate")(self.ctx, self.h, int(ct), n, _pd(raw), _pd(al), _pd(pb), _pd(pe), int(bool(frame_init)), C.byref(nres),
+                                         _pi(src), _pd(pts), _pd(nrm), _pd(off), _pd(alo), _pd(w), _pi(cnt), _pd(a2d), C.byref(nnan), _pi(vis)), "associate")
+        r = nres.value
+        return dict(n_res=r, src=src[:r], pts=pts[:r], normals=nrm[:r], offsets=off[:r], alpha=alo[:r], weights=w[:r],
+                    neighbor_count=cnt[:n], a2D=a2d[:n], neighbor_visit=vis[:n], n_nan=nnan.value)
+
+    def linearize_raw(self, ct, sqrt_info, pose_begin, pose_end=None):
+        """gfbe_vmap_linearize: (status, dict(H, g, cost)) on the rows held on the handle."""
+        dn = 12 if ct else 6
+        pb = _f64(pose_begin)
+        pe = _f64(pose_end if pose_end is not None else pose_begin)
+        H, g, cost = np.zeros((dn, dn)), np.zeros(dn), np.zeros(1)
+        rc = self._f("linearize")(self.ctx, self.h, int(ct), float(sqrt_info), _pd(pb), _pd(pe), None, None, _pd(H), _pd(g), _pd(cost))
+        return rc, dict(H=H, g=g, cost=float(cost[0]))
+
+    def linearize(self, ct, sqrt_info, pose_begin, pose_end=None):
+        rc, out = self.linearize_raw(ct, sqrt_info, pose_begin, pose_end)
+        self._check(rc, "linearize")
+        return out
+
+    def localizability(self):
+        """checkLocalizability on the held normals: (sv [3] descending, degenerate)."""
+        sv, deg = np.zeros(3), c_i(0)
+        self._check(self._f("localizability")(self.ctx, self.h, _pd(sv), C.byref(deg)), "localizability")
+        return sv, bool(deg.value)

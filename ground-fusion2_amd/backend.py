@@ -38,6 +38,8 @@ EXPORTS = [
     "gfbe_ltab_create", "gfbe_ltab_destroy", "gfbe_ltab_add_frame", "gfbe_ltab_triangulate", "gfbe_ltab_remove_back_shift",
     "gfbe_ltab_remove_back", "gfbe_ltab_remove_front", "gfbe_ltab_refine", "gfbe_ltab_size", "gfbe_ltab_line_count",
     "gfbe_ltab_download", "gfbe_ltab_upload",
+    "gfbe_vmap_default_options", "gfbe_vmap_create", "gfbe_vmap_destroy", "gfbe_vmap_add_points", "gfbe_vmap_erase_far", "gfbe_vmap_size",
+    "gfbe_vmap_download", "gfbe_vmap_upload", "gfbe_vmap_associate", "gfbe_vmap_linearize", "gfbe_vmap_localizability",
 ]
 
 
@@ -226,6 +228,14 @@ class Backend(abi.CApi):
         """W device-resident line tables (abi.LineTables: FeatureManager::linefeature and its per-frame operations, gfbe_ltab_*)."""
         try:
             return abi.LineTables(self.lib, "gfbe_", self.ctx, n_tables, capacity)
+        except RuntimeError as e:
+            raise BackendError("%s: %s" % (e, self._err()))
+
+    def voxel_map(self, voxel_capacity=1 << 16, **options):
+        """A device-resident voxel map of the LiDAR odometry (abi.VoxelMap: map_incremental, lasermap_fov_segment and the scan-to-map
+        association of addSurfCostFactor, gfbe_vmap_*). options: fields of gfbe_vmap_options."""
+        try:
+            return abi.VoxelMap(self.lib, "gfbe_", self.ctx, voxel_capacity, **options)
         except RuntimeError as e:
             raise BackendError("%s: %s" % (e, self._err()))
 

@@ -441,6 +441,12 @@ size_t line_refine_row_doubles();
 void launch_line_refine_tables(const LineList &L, int n_tables, double sqrt_info, double cauchy, int max_it, double *row, double *plk_out,
                                unsigned char *keep, gfbe_summary *sum, hipStream_t s);
 
+// k_lio on residual arrays that already live on the device (gfbe_lio.hip; gfbe_vmap_linearize): same grid, kernel and host sum as
+// gfbe_lio_linearize
+gfbe_status lio_linearize_device(gfbe_ctx *c, int32_t ct, int32_t n, const double *pts, const double *normals, const double *offsets, const double *alpha,
+                                 const double *weights, double sqrt_info, const double *pose_begin, const double *pose_end, double *r, double *J,
+                                 double *H, double *g, double *cost);
+
 // a device allocation kept between calls and grown on demand (grow, gfbe_line_batch.h)
 struct DevBuf {
   char *d = nullptr;

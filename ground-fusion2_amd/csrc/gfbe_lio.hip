@@ -16,31 +16,12 @@
 #include <vector>
 
 #include "gfbe_device.h"
+#include "gfbe_lio_pose.h"
 
 using namespace gfd;
 
 namespace {
 
-struct Qx { double x, y, z, w; };
-__device__ __forceinline__ Qx qmulx(Qx a, Qx b) {
-  return {a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y, a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x,
-          a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w, a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z};
-}
-__device__ __forceinline__ void qrotx(Qx q, double R[9]) {
-  const double x = q.x, y = q.y, z = q.z, w = q.w;
-  R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - z * w); R[2] = 2 * (x * z + y * w);
-  R[3] = 2 * (x * y + z * w); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - x * w);
-  R[6] = 2 * (x * z - y * w); R[7] = 2 * (y * z + x * w); R[8] = 1 - 2 * (x * x + y * y);
-}
-__device__ __forceinline__ Qx slerpx(Qx a, double t, Qx b) {   // Eigen::QuaternionBase::slerp
-  const double one = 1.0 - 2.220446049250313e-16;
-  const double d = a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w, ad = fabs(d);
-  double s0, s1;
-  if (ad >= one) { s0 = 1.0 - t; s1 = t; }
-  else { const double th = acos(ad), st = sin(th); s0 = sin((1.0 - t) * th) / st; s1 = sin(t * th) / st; }
-  if (d < 0) s1 = -s1;
-  return {s0 * a.x + s1 * b.x, s0 * a.y + s1 * b.y, s0 * a.z + s1 * b.z, s0 * a.w + s1 * b.w};
-}
 __device__ __forceinline__ void q_br(Qx q, double sgn, double M[9]) {   // bottom-right 3x3 of Qleft (+1) / Qright (-1)
   M[0] = q.w; M[1] = -sgn * q.z; M[2] = sgn * q.y; M[3] = sgn * q.z; M[4] = q.w; M[5] = -sgn * q.x; M[6] = -sgn * q.y; M[7] = sgn * q.x; M[8] = q.w;
 }
@@ -73,18 +54,9 @@ __global__ __launch_bounds__(LIO_THREADS) void k_lio(int n, const double *pts, c
   for (int k = blockIdx.x * LIO_THREADS + t; k < n; k += gridDim.x * LIO_THREADS) {
     const double *p = pts + 3 * (size_t)k, *nv = normals + 3 * (size_t)k;
     const double wgt = weights[k];
-    double Jk[DN], rk, R[9], al = 0.0;
-    Qx qs = qb;
-    double ts[3] = {pb[0], pb[1], pb[2]};
-    if (CT) {
-      al = alpha[k];
-      const Qx s = slerpx(qb, al, qe);
-      const double nn = sqrt(s.x * s.x + s.y * s.y + s.z * s.z + s.w * s.w);
-      qs = {s.x / nn, s.y / nn, s.z / nn, s.w / nn};
-      for (int a = 0; a < 3; a++) ts[a] = pb[a] * (1 - al) + pe[a] * al;
-    }
-    qrotx(qs, R);
-    const double pw[3] = {R[0] * p[0] + R[1] * p[1] + R[2] * p[2] + ts[0], R[3] * p[0] + R[4] * p[1] + R[5] * p[2] + ts[1], R[6] * p[0] + R[7] * p[1] + R[8] * p[2] + ts[2]};
+    double Jk[DN], rk, R[9], pw[3], al = 0.0;
+    if (CT) al = alpha[k];
+    lio_world_point(CT, qb, qe, pb, pe, al, p, R, pw);
     rk = sqrt_info * wgt * (nv[0] * pw[0] + nv[1] * pw[1] + nv[2] * pw[2] + offsets[k]);
     const double nR[3] = {nv[0] * R[0] + nv[1] * R[3] + nv[2] * R[6], nv[0] * R[1] + nv[1] * R[4] + nv[2] * R[7], nv[0] * R[2] + nv[1] * R[5] + nv[2] * R[8]};
     const double jrs[3] = {-wgt * (nR[1] * p[2] - nR[2] * p[1]), -wgt * (nR[2] * p[0] - nR[0] * p[2]), -wgt * (nR[0] * p[1] - nR[1] * p[0])};
@@ -142,11 +114,11 @@ __global__ __launch_bounds__(LIO_THREADS) void k_lio(int n, const double *pts, c
 
 }  // namespace
 
-extern "C" gfbe_status gfbe_lio_linearize(gfbe_ctx *c, int32_t ct, int32_t n, const double *pts, const double *normals, const double *offsets,
-                                          const double *alpha, const double *weights, double sqrt_info, const double *pose_begin,
-                                          const double *pose_end, double *r, double *J, double *H, double *g, double *cost) {
-  if (!c || n < 0 || !pose_begin || (n > 0 && (!pts || !normals || !offsets)) || (ct && (!alpha || !pose_end))) return GFBE_BAD_INPUT;
-  if (ctx_device(c) < 0) return GFBE_NO_DEVICE;
+// dev_in: the five residual arrays (pts, normals, offsets, alpha, weights) already on the device (gfbe_vmap_linearize: the
+// association held on a voxel map handle); only the two poses are staged then. Same grid, same kernel, same host sum as the host-fed call.
+static gfbe_status lio_run(gfbe_ctx *c, int32_t ct, int32_t n, const double *pts, const double *normals, const double *offsets, const double *alpha,
+                           const double *weights, bool dev_in, double sqrt_info, const double *pose_begin, const double *pose_end, double *r, double *J,
+                           double *H, double *g, double *cost) {
   const int dn = ct ? 12 : 6;
   hipStream_t s = ctx_stream(c);
   // One host-to-device copy in, one device-to-host copy out, through the context's scratch and its pinned mirror (round 5: the call
@@ -154,19 +126,19 @@ extern "C" gfbe_status gfbe_lio_linearize(gfbe_ctx *c, int32_t ct, int32_t n, co
   //   in  : pts [3 n] | normals [3 n] | offsets [n] | alpha [n] | weights [n] | pose_begin [7] | pose_end [7] (+ 2 of padding)
   //   out : partial sums [G][LIO_PART] | r [n] | J [n][dn]      (r, J only when asked for)
   const int G = std::max(1, std::min(256, (n + LIO_THREADS - 1) / LIO_THREADS));
-  const size_t nn = (size_t)std::max(n, 1);
-  const size_t in_d = 9 * nn + 16, out_d = (size_t)G * LIO_PART + (r ? nn : 0) + (J ? (size_t)dn * nn : 0);
+  const size_t nn = (size_t)std::max(n, 1), arr_d = dev_in ? 0 : 9 * nn;
+  const size_t in_d = arr_d + 16, out_d = (size_t)G * LIO_PART + (r ? nn : 0) + (J ? (size_t)dn * nn : 0);
   double *dev = (double *)ctx_scratch(c, sizeof(double) * (in_d + out_d));
   double *pin = (double *)ctx_scratch_pinned(c, sizeof(double) * (in_d + out_d));
-  if (!dev || !pin) { ctx_set_error(c, "gfbe_lio_linearize: device / pinned allocation failed"); return GFBE_DEVICE_ERROR; }
-  double *hp = pin, *hn = hp + 3 * nn, *ho = hn + 3 * nn, *ha = ho + nn, *hw = ha + nn, *hb = hw + nn, *he = hb + 8;
-  if (n > 0) {
+  if (!dev || !pin) { ctx_set_error(c, dev_in ? "gfbe_vmap_linearize: device / pinned allocation failed" : "gfbe_lio_linearize: device / pinned allocation failed"); return GFBE_DEVICE_ERROR; }
+  double *hp = pin, *hn = hp + 3 * nn, *ho = hn + 3 * nn, *ha = ho + nn, *hw = ha + nn, *hb = pin + arr_d, *he = hb + 8;
+  if (n > 0 && !dev_in) {
     std::memcpy(hp, pts, sizeof(double) * 3 * n); std::memcpy(hn, normals, sizeof(double) * 3 * n); std::memcpy(ho, offsets, sizeof(double) * n);
     if (ct) std::memcpy(ha, alpha, sizeof(double) * n); else std::memset(ha, 0, sizeof(double) * n);
     if (weights) std::memcpy(hw, weights, sizeof(double) * n); else std::fill(hw, hw + n, 1.0);
   }
   std::memcpy(hb, pose_begin, sizeof(double) * 7); std::memcpy(he, pose_end ? pose_end : pose_begin, sizeof(double) * 7);
-  double *dp = dev, *dnv = dp + 3 * nn, *doff = dnv + 3 * nn, *dal = doff + nn, *dw = dal + nn, *dpb = dw + nn, *dpe = dpb + 8;
+  const double *dp = dev, *dnv = dp + 3 * nn, *doff = dnv + 3 * nn, *dal = doff + nn, *dw = dal + nn, *dpb = dev + arr_d, *dpe = dpb + 8;
   double *dpart = dev + in_d, *dr = dpart + (size_t)G * LIO_PART, *dJ = dr + (r ? nn : 0);
   gfbe_status st = GFBE_OK;
   // A scan of the reference's size (lidarodom.cpp:929-1071 produces ~2 000 residuals per ICP iteration) is three dependent latencies —
@@ -176,9 +148,10 @@ extern "C" gfbe_status gfbe_lio_linearize(gfbe_ctx *c, int32_t ct, int32_t n, co
   // copies, which stream faster than a kernel's loads across the bus.
   const bool zero_copy = n <= LIO_ZERO_COPY_N;
   if (zero_copy) {
-    dp = pin; dnv = dp + 3 * nn; doff = dnv + 3 * nn; dal = doff + nn; dw = dal + nn; dpb = dw + nn; dpe = dpb + 8;
+    dp = pin; dnv = dp + 3 * nn; doff = dnv + 3 * nn; dal = doff + nn; dw = dal + nn; dpb = pin + arr_d; dpe = dpb + 8;
     dpart = pin + in_d; dr = dpart + (size_t)G * LIO_PART; dJ = dr + (r ? nn : 0);
   } else if (hipMemcpyAsync(dev, pin, sizeof(double) * in_d, hipMemcpyHostToDevice, s) != hipSuccess) st = GFBE_DEVICE_ERROR;
+  if (dev_in) { dp = pts; dnv = normals; doff = offsets; dal = alpha; dw = weights; }
   if (st == GFBE_OK) {
     if (ct) hipLaunchKernelGGL(k_lio<1>, dim3(G), dim3(LIO_THREADS), 0, s, n, dp, dnv, doff, dal, dw, sqrt_info, dpb, dpe, r ? dr : nullptr, J ? dJ : nullptr, dpart);
     else hipLaunchKernelGGL(k_lio<0>, dim3(G), dim3(LIO_THREADS), 0, s, n, dp, dnv, doff, dal, dw, sqrt_info, dpb, dpe, r ? dr : nullptr, J ? dJ : nullptr, dpart);
@@ -196,6 +169,22 @@ extern "C" gfbe_status gfbe_lio_linearize(gfbe_ctx *c, int32_t ct, int32_t n, co
       if (J && n) std::memcpy(J, hJ, sizeof(double) * dn * n);
     }
   }
-  if (st != GFBE_OK) ctx_set_error(c, "gfbe_lio_linearize: copy / launch failed");
+  if (st != GFBE_OK) ctx_set_error(c, dev_in ? "gfbe_vmap_linearize: copy / launch failed" : "gfbe_lio_linearize: copy / launch failed");
   return st;
 }
+
+extern "C" gfbe_status gfbe_lio_linearize(gfbe_ctx *c, int32_t ct, int32_t n, const double *pts, const double *normals, const double *offsets,
+                                          const double *alpha, const double *weights, double sqrt_info, const double *pose_begin,
+                                          const double *pose_end, double *r, double *J, double *H, double *g, double *cost) {
+  if (!c || n < 0 || !pose_begin || (n > 0 && (!pts || !normals || !offsets)) || (ct && (!alpha || !pose_end))) return GFBE_BAD_INPUT;
+  if (ctx_device(c) < 0) return GFBE_NO_DEVICE;
+  return lio_run(c, ct, n, pts, normals, offsets, alpha, weights, false, sqrt_info, pose_begin, pose_end, r, J, H, g, cost);
+}
+
+namespace gfd {
+gfbe_status lio_linearize_device(gfbe_ctx *c, int32_t ct, int32_t n, const double *pts, const double *normals, const double *offsets, const double *alpha,
+                                 const double *weights, double sqrt_info, const double *pose_begin, const double *pose_end, double *r, double *J,
+                                 double *H, double *g, double *cost) {
+  return lio_run(c, ct, n, pts, normals, offsets, alpha, weights, true, sqrt_info, pose_begin, pose_end, r, J, H, g, cost);
+}
+}  // namespace gfd

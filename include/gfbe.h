@@ -514,7 +514,7 @@ gfbe_status gfbe_pg_solve(gfbe_ctx *ctx, int32_t n_poses, const double *pose_in,
 /* ------------------------------------------------------------------------------------------
  * f4  LIO scan residuals (BASELINE configs[4]): point-to-plane factors of the LiDAR
  *     odometry, evaluated and reduced to normal equations on the device (the voxel neighbour search that produces
- *     the planes stays on the CPU):
+ *     the planes runs on the device too: the voxel map section below, gfbe_vmap_associate / gfbe_vmap_linearize):
  *       LidarPlaneNormFactor::Evaluate     lio/src/liw/lidarFactor.cpp:18-51   (ct = 0: one pose [t | q(x,y,z,w)])
  *       CTLidarPlaneNormFactor::Evaluate   lio/src/liw/lidarFactor.cpp:59-120  (ct = 1: begin and end pose, the point
  *                                          is taken at slerp(alpha) / lerp(alpha) between them)
@@ -528,6 +528,76 @@ gfbe_status gfbe_lio_linearize(gfbe_ctx *ctx, int32_t ct, int32_t n, const doubl
                                const double *offsets, const double *alpha, const double *weights, double sqrt_info,
                                const double *pose_begin, const double *pose_end, double *r, double *J, double *H,
                                double *g, double *cost);
+
+/* ------------------------------------------------------------------------------------------
+ * f4b Device voxel map and scan-to-map association (lio/src/liw/lio/lidarodom.cpp): the step that produces the rows of
+ *     gfbe_lio_linearize, without a trip through host memory.
+ *       map_incremental / addPointToMap :1167-1266   gfbe_vmap_add_points
+ *       lasermap_fov_segment            :1268-1284   gfbe_vmap_erase_far
+ *       addSurfCostFactor, loop body    :929-1071    gfbe_vmap_associate (searchNeighbors :1086-1165,
+ *                                                    computeNeighborhoodDistribution :887-927)
+ *       checkLocalizability             :811-885     gfbe_vmap_localizability
+ *     Conventions of gfbe_ltab: operations run in order on the context's stream; add_points / erase_far / upload return
+ *     without waiting (arguments that do not fit a staging slot are waited for); without a GPU every entry point
+ *     returns GFBE_NO_DEVICE. A voxel key is (short)(p / size_voxel_map) per axis, truncated toward zero; a point with
+ *     |p / size| >= 32767 on an axis is skipped and counted. An add that would pass voxel_capacity changes nothing and
+ *     raises a sticky overflow flag: gfbe_vmap_size reports it and gfbe_vmap_associate returns GFBE_BAD_INPUT from then
+ *     on. No output depends on the table's layout or on the order in which workgroups ran. INTEGRATION.md lists the
+ *     deviations from the reference (voxel_neighborhood 3 refused, ties by visit order, NaN a2D dropped and counted).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct gfbe_vmap_options {
+  int32_t struct_size;               /* sizeof(gfbe_vmap_options) as the caller was built (refused otherwise) */
+  int32_t max_num_points_in_voxel;   /* 20 (1..32) */
+  int32_t voxel_neighborhood;        /* 1 (0..2) */
+  int32_t max_number_neighbors;      /* 20 (1..32) */
+  int32_t min_number_neighbors;      /* 20 */
+  int32_t threshold_voxel_occupancy; /* 1 */
+  int32_t num_closest_neighbors;     /* 1 (1..max_number_neighbors) */
+  int32_t max_num_residuals;         /* 2000 */
+  double size_voxel_map;             /* 0.2 */
+  double min_distance_points;        /* 0.05 */
+  double max_distance;               /* 500 */
+  double max_dist_to_plane_icp;      /* 0.3 */
+  double power_planarity;            /* 2 */
+  double weight_alpha;               /* 0.9 */
+  double weight_neighborhood;        /* 0.1 */
+} gfbe_vmap_options;
+void gfbe_vmap_default_options(gfbe_vmap_options *opt);
+
+typedef struct gfbe_vmap gfbe_vmap;
+/* opt NULL: the defaults. GFBE_BAD_INPUT: wrong struct_size, an option outside its range, voxel_capacity outside 1 .. 2^21. */
+gfbe_status gfbe_vmap_create(gfbe_ctx *ctx, int32_t voxel_capacity, const gfbe_vmap_options *opt, gfbe_vmap **out);
+void gfbe_vmap_destroy(gfbe_ctx *ctx, gfbe_vmap *map);
+/* map_incremental: equal to adding pts_world [n][3] one after another in input order. */
+gfbe_status gfbe_vmap_add_points(gfbe_ctx *ctx, gfbe_vmap *map, int32_t n, const double *pts_world, int32_t min_num_points);
+/* lasermap_fov_segment: a voxel goes when its FIRST point is farther than max_distance from location [3]. */
+gfbe_status gfbe_vmap_erase_far(gfbe_ctx *ctx, gfbe_vmap *map, const double *location);
+/* any output may be NULL; waits for the operations queued before it */
+gfbe_status gfbe_vmap_size(gfbe_ctx *ctx, gfbe_vmap *map, int32_t *n_voxels, int32_t *n_points, int32_t *n_skipped,
+                           int32_t *overflow);
+/* Voxels in ascending (x, y, z) key order: keys [n_voxels][3], counts [n_voxels], points [n_points][3] concatenated in
+ * voxel order, insertion order inside a voxel. upload replaces the map's contents (for tests and for seeding a map). */
+gfbe_status gfbe_vmap_download(gfbe_ctx *ctx, gfbe_vmap *map, int16_t *keys, int32_t *counts, double *points);
+gfbe_status gfbe_vmap_upload(gfbe_ctx *ctx, gfbe_vmap *map, int32_t n_voxels, const int16_t *keys, const int32_t *counts,
+                             const double *points);
+/* The loop body of addSurfCostFactor for a whole scan: raw_pts [n][3], alpha [n] (ct = 1), poses [t | q(x,y,z,w)] as in
+ * gfbe_lio_linearize; frame_init != 0: 2 voxels visited, occupancy threshold 1. Outputs in keypoint order, cut at
+ * max_num_residuals (any may be NULL; they hold up to min(n * num_closest_neighbors, max_num_residuals) rows): n_res,
+ * src [n_res] keypoint index, pts [n_res][3] (ct = 1: the raw point; ct = 0: point_end), normals, offsets, alpha_out,
+ * weights; per keypoint neighbor_count [n], a2D [n], neighbor_visit [n][max_number_neighbors] (the neighbours' identities: their
+ * index in the search's visit order, voxels kxx, kyy, kzz then the point's place, -1 behind the last); n_nan: keypoints dropped
+ * for a NaN a2D. The rows stay on the handle. */
+gfbe_status gfbe_vmap_associate(gfbe_ctx *ctx, gfbe_vmap *map, int32_t ct, int32_t n, const double *raw_pts,
+                                const double *alpha, const double *pose_begin, const double *pose_end, int32_t frame_init,
+                                int32_t *n_res, int32_t *src, double *pts, double *normals, double *offsets,
+                                double *alpha_out, double *weights, int32_t *neighbor_count, double *a2D, int32_t *n_nan,
+                                int32_t *neighbor_visit);
+/* gfbe_lio_linearize on the rows held on the handle (bit-identical to the host-fed call on the downloaded rows).
+ * GFBE_BAD_INPUT when the map changed after the last associate, or ct differs from the association's. */
+gfbe_status gfbe_vmap_linearize(gfbe_ctx *ctx, gfbe_vmap *map, int32_t ct, double sqrt_info, const double *pose_begin,
+                                const double *pose_end, double *r, double *J, double *H, double *g, double *cost);
+/* checkLocalizability on the held normals: sv [3] descending, degenerate = N <= 10 || mean(sv) < 10 || sv[2] < 7. */
+gfbe_status gfbe_vmap_localizability(gfbe_ctx *ctx, gfbe_vmap *map, double *sv, int32_t *degenerate);
 
 /* ------------------------------------------------------------------------------------------
  * f2  Optional in-window factors. PlaneFactor and PoseAnchorFactor run INSIDE
