@@ -497,38 +497,39 @@ class CApi:
         return out
 
     # ---- pre-integration
-    def preintegrate_imu(self, intervals, lin_ba, lin_bg, noise):
-        """intervals: list of (samples[n,7], first[6])."""
+    def _preintegrate(self, name, intervals, lin, lin_w, noise, out_w, rec_t):
+        """intervals: list of (samples[k,7], first[6]); lin: [lin_w] for every interval, or [n, lin_w] per interval."""
         n = len(intervals)
         off = np.zeros(n + 1, np.int32)
         off[1:] = np.cumsum([len(s) for s, _ in intervals])
-        samples = _f64(np.concatenate([s for s, _ in intervals]))
-        first = _f64(np.array([f for _, f in intervals]))
-        lin = _f64(np.tile(np.concatenate([lin_ba, lin_bg]), (n, 1)))
-        out = np.zeros((n, IMU_DOUBLES))
+        samples = _f64(np.concatenate([np.asarray(s, float).reshape(-1, 7) for s, _ in intervals])) if n else np.zeros((0, 7))
+        first = _f64(np.array([f for _, f in intervals], float).reshape(n, 6))
+        lin = np.asarray(lin, float)
+        if lin.ndim == 1:
+            lin = np.tile(lin, (n, 1))
+        if lin.shape != (n, lin_w):
+            raise ValueError("%s: linearisation point of shape %s, expected (%d,) or (%d, %d)" % (name, lin.shape, lin_w, n, lin_w))
+        lin = _f64(lin)
+        out = np.zeros((n, out_w))
         nz = _f64(noise)
-        f = self._fn("preintegrate_imu")
+        f = self._fn(name)
         f.restype = c_i
-        args = [n, _pi(off), _pd(samples), _pd(first), _pd(lin), _pd(nz), C.cast(out.ctypes.data, C.POINTER(ImuPreint))]
+        args = [n, _pi(off), _pd(samples), _pd(first), _pd(lin), _pd(nz), C.cast(out.ctypes.data, C.POINTER(rec_t))]
         rc = f(*(([self.head] if self.prefix == "gfbe_" else []) + args))
-        self.check(rc, "preintegrate_imu")
+        self.check(rc, name)
         return out
 
+    def preintegrate_imu(self, intervals, lin_ba, lin_bg, noise):
+        """intervals: list of (samples[k,7], first[6]). lin_ba, lin_bg: [3] each (one linearisation point for every interval) or
+        [n, 3] each (one per interval: the C ABI's lin_ba_bg [n][6])."""
+        lin_ba, lin_bg = np.asarray(lin_ba, float), np.asarray(lin_bg, float)
+        if lin_ba.ndim != lin_bg.ndim:
+            raise ValueError("preintegrate_imu: lin_ba and lin_bg must both be [3] or both [n, 3]")
+        return self._preintegrate("preintegrate_imu", intervals, np.concatenate([lin_ba, lin_bg], axis=-1), 6, noise, IMU_DOUBLES, ImuPreint)
+
     def preintegrate_wheel(self, intervals, lin, noise):
-        n = len(intervals)
-        off = np.zeros(n + 1, np.int32)
-        off[1:] = np.cumsum([len(s) for s, _ in intervals])
-        samples = _f64(np.concatenate([s for s, _ in intervals]))
-        first = _f64(np.array([f for _, f in intervals]))
-        linv = _f64(np.tile(np.asarray(lin, float), (n, 1)))
-        out = np.zeros((n, WHEEL_DOUBLES))
-        nz = _f64(noise)
-        f = self._fn("preintegrate_wheel")
-        f.restype = c_i
-        args = [n, _pi(off), _pd(samples), _pd(first), _pd(linv), _pd(nz), C.cast(out.ctypes.data, C.POINTER(WheelPreint))]
-        rc = f(*(([self.head] if self.prefix == "gfbe_" else []) + args))
-        self.check(rc, "preintegrate_wheel")
-        return out
+        """lin: sx, sy, sw, td as [4] (for every interval) or [n, 4] (one per interval)."""
+        return self._preintegrate("preintegrate_wheel", intervals, lin, 4, noise, WHEEL_DOUBLES, WheelPreint)
 
     # ---- the whole optimization() call
     def solve(self, snap, margin_flag=MARGIN_NONE):

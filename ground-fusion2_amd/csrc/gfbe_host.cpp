@@ -1851,7 +1851,19 @@ extern "C" gfbe_status gfbe_eval_factors(gfbe_ctx *c, const gfbe_window *win, in
 template <typename REC_T>
 static gfbe_status preint_common(gfbe_ctx *c, int n, const int32_t *offset, const double *samples, const double *first,
                                  const double *lin, int lin_w, const double *noise, int n_noise, REC_T *out, bool imu) {
-  if (!c || n <= 0 || !offset || !samples || !out) return GFBE_BAD_INPUT;
+  if (!c) return GFBE_BAD_INPUT;
+  const char *who = imu ? "gfbe_preintegrate_imu: " : "gfbe_preintegrate_wheel: ";
+  // everything is checked on the host before a byte is copied or a kernel is launched: the kernels index samples[] by offset[]
+  if (n <= 0 || !offset || !out) { c->err = std::string(who) + "n_interval <= 0, or offset / out is NULL"; return GFBE_BAD_INPUT; }
+  if (!first || !lin || !noise) { c->err = std::string(who) + "first, lin and noise are required (NULL given)"; return GFBE_BAD_INPUT; }
+  if (offset[0] < 0) { c->err = std::string(who) + "offset[0] = " + std::to_string(offset[0]) + " is negative"; return GFBE_BAD_INPUT; }
+  for (int k = 0; k < n; k++)
+    if (offset[k + 1] < offset[k]) {
+      c->err = std::string(who) + "offset[" + std::to_string(k + 1) + "] = " + std::to_string(offset[k + 1]) + " < offset[" + std::to_string(k) +
+               "] = " + std::to_string(offset[k]) + " (offsets must not decrease)";
+      return GFBE_BAD_INPUT;
+    }
+  if (offset[n] > 0 && !samples) { c->err = std::string(who) + "samples is NULL with offset[n] > 0"; return GFBE_BAD_INPUT; }
   if (c->device < 0 || !c->stream) { c->err = "HIP device context required (no CPU fallback)"; return GFBE_NO_DEVICE; }
   const int tot = offset[n];
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
@@ -1871,10 +1883,10 @@ static gfbe_status preint_common(gfbe_ctx *c, int n, const int32_t *offset, cons
   char *base = c->scratch, *pin = c->scratch_pin;
   const size_t o_off = 0, o_s = o_off + b_off, o_f = o_s + b_s, o_l = o_f + b_f, o_n = o_l + b_l, o_o = o_n + b_n;
   std::memcpy(pin + o_off, offset, sizeof(int) * (n + 1));
-  std::memcpy(pin + o_s, samples, sizeof(double) * 7 * tot);
-  if (first) std::memcpy(pin + o_f, first, sizeof(double) * 6 * n);
-  if (lin) std::memcpy(pin + o_l, lin, sizeof(double) * lin_w * n);
-  if (noise) std::memcpy(pin + o_n, noise, sizeof(double) * n_noise);
+  if (tot) std::memcpy(pin + o_s, samples, sizeof(double) * 7 * tot);
+  std::memcpy(pin + o_f, first, sizeof(double) * 6 * n);
+  std::memcpy(pin + o_l, lin, sizeof(double) * lin_w * n);
+  std::memcpy(pin + o_n, noise, sizeof(double) * n_noise);
   int *d_off = (int *)(base + o_off);
   double *d_s = (double *)(base + o_s), *d_f = (double *)(base + o_f), *d_l = (double *)(base + o_l), *d_n = (double *)(base + o_n);
   REC_T *d_o = (REC_T *)(base + o_o);

@@ -912,6 +912,11 @@ gfbe_status gfbe_eval_factors(gfbe_ctx *ctx, const gfbe_window *win, int32_t rob
  * Sample rows: IMU [dt ax ay az gx gy gz], wheel [dt vx vy vz gx gy gz]. first_* is the
  * (acc_0,gyr_0)/(vel_0,gyr_0) the interval was constructed with. noise: ACC_N GYR_N ACC_W GYR_W
  * (integration_base.h:30-36) / VEL_N_wheel GYR_N_wheel (wheel_integration_base.h:32-36).
+ * An empty interval (offset[k] == offset[k+1]) gives the record the reference's constructor leaves: the identity jacobian (wheel:
+ * zero), zero covariance, the identity quaternion, sum_dt = 0, and first_* / lin_* passed through.
+ * Every argument is checked on the host before anything is copied or launched. GFBE_BAD_INPUT, with a gfbe_last_error text and
+ * no output touched: n_interval <= 0; offset[0] < 0 or offset[k+1] < offset[k] for any k; a NULL offset, first_*, lin_*, noise or
+ * out (all are required: there is no default linearisation point or noise); a NULL samples unless offset[n_interval] == 0.
  * ------------------------------------------------------------------------------------------ */
 gfbe_status gfbe_preintegrate_imu(gfbe_ctx *ctx, int32_t n_interval, const int32_t *offset,
                                   const double *samples, const double *first_acc_gyr /*[n][6]*/,
