@@ -1316,6 +1316,37 @@ def vmap_default_options(lib, prefix="gfbe_"):
     return o
 
 
+class VregOptions(C.Structure):
+    _fields_ = [("struct_size", c_i), ("max_num_iteration", c_i), ("lm_max_num_iterations", c_i), ("min_num_residuals", c_i),
+                ("laser_point_cov", c_d), ("huber_delta", c_d), ("beta_location_consistency", c_d), ("beta_orientation_consistency", c_d),
+                ("beta_small_velocity", c_d), ("thres_translation_norm", c_d), ("thres_orientation_norm", c_d)]
+
+
+class VregSummary(C.Structure):
+    _fields_ = [("outer_iterations", c_i), ("converged", c_i), ("too_few_residuals", c_i), ("no_residuals", c_i), ("degenerate", c_i),
+                ("sv", c_d * 3), ("n_res", c_i * 32), ("lm_iterations", c_i * 32), ("lm_accepted", c_i * 32), ("lm_termination", c_i * 32),
+                ("cost_initial", c_d * 32), ("cost_final", c_d * 32), ("diff_trans", c_d * 32), ("diff_rot", c_d * 32), ("pose_trace", (c_d * 14) * 32)]
+
+
+def vreg_default_options(lib, prefix="gfbe_"):
+    o = VregOptions()
+    f = getattr(lib, prefix + "vreg_default_options")
+    f.restype = None
+    f(C.byref(o))
+    return o
+
+
+def vreg_summary_to_dict(sm):
+    d = dict(outer_iterations=sm.outer_iterations, converged=sm.converged, too_few_residuals=sm.too_few_residuals, no_residuals=sm.no_residuals,
+             degenerate=sm.degenerate, sv=np.array(sm.sv[:]))
+    for k in ("n_res", "lm_iterations", "lm_accepted", "lm_termination"):
+        d[k] = np.array(getattr(sm, k)[:], np.int32)
+    for k in ("cost_initial", "cost_final", "diff_trans", "diff_rot"):
+        d[k] = np.array(getattr(sm, k)[:])
+    d["pose_trace"] = np.array([row[:] for row in sm.pose_trace])
+    return d
+
+
 class VoxelMap:
     """A device-resident voxel map behind `lib` (prefix gfbe_, ctx = gfbe_ctx*). options: fields of gfbe_vmap_options."""
     PI16 = C.POINTER(C.c_int16)
@@ -1328,7 +1359,7 @@ class VoxelMap:
             if not hasattr(self.opt, k):
                 raise TypeError("gfbe_vmap_options has no field %r" % k)
             setattr(self.opt, k, v)
-        for name in ("create", "add_points", "erase_far", "size", "download", "upload", "associate", "linearize", "localizability"):
+        for name in ("create", "add_points", "erase_far", "size", "download", "upload", "associate", "linearize", "localizability", "register", "add_scan"):
             self._f(name).restype = c_i
         self._f("destroy").restype = None
         self._f("linearize").argtypes = [C.c_void_p, C.c_void_p, c_i, c_d, PD, PD, PD, PD, PD, PD, PD]
@@ -1411,3 +1442,39 @@ class VoxelMap:
         sv, deg = np.zeros(3), c_i(0)
         self._check(self._f("localizability")(self.ctx, self.h, _pd(sv), C.byref(deg)), "localizability")
         return sv, bool(deg.value)
+
+    def register_raw(self, ct, raw_pts, alpha, pose_begin, pose_end=None, prev_translation=None, prev_rotation=None, frame_init=False, **options):
+        """gfbe_vmap_register: (status, pose_begin, pose_end, summary dict). options: fields of gfbe_vreg_options."""
+        o = vreg_default_options(self.lib, self.prefix)
+        for k, v in options.items():
+            if not hasattr(o, k):
+                raise TypeError("gfbe_vreg_options has no field %r" % k)
+            setattr(o, k, v)
+        raw = _f64(raw_pts).reshape(-1, 3)
+        n = len(raw)
+        al = _f64(alpha if alpha is not None else np.zeros(n))
+        pb = _f64(pose_begin)
+        pe = _f64(pose_end if pose_end is not None else pose_begin)
+        pt = _pd(_f64(prev_translation)) if prev_translation is not None else None
+        pr = _pd(_f64(prev_rotation)) if prev_rotation is not None else None
+        ob, oe, sm = np.full(7, np.nan), np.full(7, np.nan), VregSummary()
+        rc = self._f("register")(self.ctx, self.h, C.byref(o), int(ct), n, _pd(raw), _pd(al), _pd(pb), _pd(pe), pt, pr, int(bool(frame_init)), _pd(ob), _pd(oe),
+                                 C.byref(sm))
+        return rc, ob, oe, vreg_summary_to_dict(sm)
+
+    def register(self, ct, raw_pts, alpha, pose_begin, pose_end=None, prev_translation=None, prev_rotation=None, frame_init=False, **options):
+        """One lidarodom::optimize on the device: (pose_begin, pose_end, summary dict); the last association stays on the handle."""
+        rc, ob, oe, sm = self.register_raw(ct, raw_pts, alpha, pose_begin, pose_end, prev_translation, prev_rotation, frame_init, **options)
+        self._check(rc, "register")
+        return ob, oe, sm
+
+    def add_scan(self, ct, raw_pts, alpha, pose_begin, pose_end=None, min_num_points=0, want_world=False):
+        """transformKeypoints + map_incremental on the device; want_world: the world points [n, 3] (waits for them)."""
+        raw = _f64(raw_pts).reshape(-1, 3)
+        n = len(raw)
+        al = _f64(alpha if alpha is not None else np.zeros(n))
+        pb = _f64(pose_begin)
+        pe = _f64(pose_end if pose_end is not None else pose_begin)
+        out = np.zeros((n, 3)) if want_world else None
+        self._check(self._f("add_scan")(self.ctx, self.h, int(ct), n, _pd(raw), _pd(al), _pd(pb), _pd(pe), int(min_num_points), _pd(out) if want_world else None), "add_scan")
+        return out

@@ -40,6 +40,7 @@ EXPORTS = [
     "gfbe_ltab_download", "gfbe_ltab_upload",
     "gfbe_vmap_default_options", "gfbe_vmap_create", "gfbe_vmap_destroy", "gfbe_vmap_add_points", "gfbe_vmap_erase_far", "gfbe_vmap_size",
     "gfbe_vmap_download", "gfbe_vmap_upload", "gfbe_vmap_associate", "gfbe_vmap_linearize", "gfbe_vmap_localizability",
+    "gfbe_vreg_default_options", "gfbe_vmap_register", "gfbe_vmap_add_scan",
 ]
 
 

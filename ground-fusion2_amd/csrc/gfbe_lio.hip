@@ -22,20 +22,6 @@ using namespace gfd;
 
 namespace {
 
-__device__ __forceinline__ void q_br(Qx q, double sgn, double M[9]) {   // bottom-right 3x3 of Qleft (+1) / Qright (-1)
-  M[0] = q.w; M[1] = -sgn * q.z; M[2] = sgn * q.y; M[3] = sgn * q.z; M[4] = q.w; M[5] = -sgn * q.x; M[6] = -sgn * q.y; M[7] = sgn * q.x; M[8] = q.w;
-}
-__device__ __forceinline__ void inv3(const double A[9], double B[9]) {
-  const double c0 = A[4] * A[8] - A[5] * A[7], c1 = A[5] * A[6] - A[3] * A[8], c2 = A[3] * A[7] - A[4] * A[6];
-  const double det = A[0] * c0 + A[1] * c1 + A[2] * c2;
-  B[0] = c0 / det; B[1] = (A[2] * A[7] - A[1] * A[8]) / det; B[2] = (A[1] * A[5] - A[2] * A[4]) / det;
-  B[3] = c1 / det; B[4] = (A[0] * A[8] - A[2] * A[6]) / det; B[5] = (A[2] * A[3] - A[0] * A[5]) / det;
-  B[6] = c2 / det; B[7] = (A[1] * A[6] - A[0] * A[7]) / det; B[8] = (A[0] * A[4] - A[1] * A[3]) / det;
-}
-__device__ __forceinline__ void mm3(const double *A, const double *B, double *C) {
-  for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) { double s = 0; for (int k = 0; k < 3; k++) s += A[3 * i + k] * B[3 * k + j]; C[3 * i + j] = s; }
-}
-
 constexpr int LIO_THREADS = 256;
 constexpr int LIO_ZERO_COPY_N = 8192;     // gfbe_lio_linearize: scans up to this many residuals are read from / written to pinned host memory by the kernel itself
 constexpr int LIO_PART = 12 * 13 / 2 + 12 + 1;   // lower triangle of J^T J (78) + J^T r (12) + cost
@@ -54,37 +40,9 @@ __global__ __launch_bounds__(LIO_THREADS) void k_lio(int n, const double *pts, c
   for (int k = blockIdx.x * LIO_THREADS + t; k < n; k += gridDim.x * LIO_THREADS) {
     const double *p = pts + 3 * (size_t)k, *nv = normals + 3 * (size_t)k;
     const double wgt = weights[k];
-    double Jk[DN], rk, R[9], pw[3], al = 0.0;
+    double Jk[DN], rk, al = 0.0;
     if (CT) al = alpha[k];
-    lio_world_point(CT, qb, qe, pb, pe, al, p, R, pw);
-    rk = sqrt_info * wgt * (nv[0] * pw[0] + nv[1] * pw[1] + nv[2] * pw[2] + offsets[k]);
-    const double nR[3] = {nv[0] * R[0] + nv[1] * R[3] + nv[2] * R[6], nv[0] * R[1] + nv[1] * R[4] + nv[2] * R[7], nv[0] * R[2] + nv[1] * R[5] + nv[2] * R[8]};
-    const double jrs[3] = {-wgt * (nR[1] * p[2] - nR[2] * p[1]), -wgt * (nR[2] * p[0] - nR[0] * p[2]), -wgt * (nR[0] * p[1] - nR[1] * p[0])};
-    if (!CT) {
-      for (int a = 0; a < 3; a++) { Jk[a] = sqrt_info * wgt * nv[a]; Jk[3 + a] = sqrt_info * jrs[a]; }
-    } else {
-      const Qx qbi = {-qb.x, -qb.y, -qb.z, qb.w};
-      const Qx rd = qmulx(qbi, qe);
-      const Qx rds = slerpx({0, 0, 0, 1}, al, rd);
-      double Rds[9], Ql_s[9], Ql_d[9], Qr_s[9], Qr_d[9], inv[9], T1[9], Jb[9], Je[9];
-      qrotx(rds, Rds);
-      q_br(rds, +1, Ql_s); q_br(rd, +1, Ql_d); q_br(rds, -1, Qr_s); q_br(rd, -1, Qr_d);
-      inv3(Ql_d, inv); mm3(Ql_s, inv, T1);
-      for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-          double s = 0;
-          for (int m = 0; m < 3; m++) s += Rds[3 * m + i] * (((m == j) ? 1.0 : 0.0) - al * T1[3 * m + j]);
-          Jb[3 * i + j] = s;
-        }
-      inv3(Qr_d, inv); mm3(Qr_s, inv, T1);
-      for (int q = 0; q < 9; q++) Je[q] = al * T1[q];
-      for (int a = 0; a < 3; a++) {
-        Jk[a] = sqrt_info * wgt * nv[a] * (1 - al);
-        Jk[6 + a] = sqrt_info * wgt * nv[a] * al;
-        Jk[3 + a] = sqrt_info * (jrs[0] * Jb[a] + jrs[1] * Jb[3 + a] + jrs[2] * Jb[6 + a]);
-        Jk[9 + a] = sqrt_info * (jrs[0] * Je[a] + jrs[1] * Je[3 + a] + jrs[2] * Je[6 + a]);
-      }
-    }
+    lio_row<CT>(p, nv, offsets[k], wgt, al, sqrt_info, qb, qe, pb, pe, Jk, &rk);
     if (r_out) r_out[k] = rk;
     if (J_out) for (int a = 0; a < DN; a++) J_out[(size_t)DN * k + a] = Jk[a];
     int e = 0;

@@ -36,40 +36,13 @@
 #include "gfbe_lio_pose.h"
 #include "gfbe_tabstage.h"
 #include "gfbe_vmap.h"
+#include "gfbe_vmap_impl.h"
 
 using namespace gfd;
 
-struct gfbe_vmap : gfbe_tab_staging {
-  gfbe_vmap_options opt;
-  int cap = 0, slots = 0, P = 0;
-  unsigned long long *keys[2] = {};     // [slots]
-  int *cnt[2] = {};                     // [slots]
-  double *pts[2] = {};                  // [slots][P][3]
-  int cur = 0;
-  int *meta = nullptr;                  // [VM_META]
-  int *part = nullptr;                  // [2][slots / 256] per-workgroup survivor counts of erase_far
-  std::vector<void *> allocs;
-  gfd::DevBuf add_buf, kp_buf, sort_buf;
-  // the association held on the handle: [max_num_residuals] each
-  int *res_src = nullptr;
-  double *res_pts = nullptr, *res_nrm = nullptr, *res_off = nullptr, *res_al = nullptr, *res_w = nullptr;
-  unsigned long long gen = 0, assoc_gen = 0;     // gen: bumped by every operation that may change the map
-  bool assoc_valid = false;
-  int assoc_ct = 0, n_res = 0;
-};
-
 namespace {
 
-enum { M_VOX = 0, M_PTS, M_SKIP, M_OVER, M_GO, M_NRES, M_NAN, M_TOTAL, VM_META };
 constexpr int VM_THREADS = 1024;
-
-struct VmDev {
-  unsigned long long *keys;
-  int *cnt;
-  double *pts;
-  int mask, P, cap;
-  int *meta;
-};
 
 __device__ __forceinline__ unsigned long long vm_load_key(const unsigned long long *p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -107,6 +80,15 @@ __global__ __launch_bounds__(256) void k_vm_keys(int n, const double *pts, doubl
   uint64_t k;
   key[i] = vmap_key(pts + 3 * (size_t)i, size, &k) ? k : VM_INVALID;
   idx[i] = i;
+}
+// the world point of every scan point at its pose (transformKeypoints)
+__global__ __launch_bounds__(256) void k_vm_world(int n, int ct, const double *raw, const double *alpha, const double *pb, const double *pe, double *out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const Qx qb = {pb[3], pb[4], pb[5], pb[6]}, qe = {pe[3], pe[4], pe[5], pe[6]};
+  double R[9], pw[3];
+  lio_world_point(ct, qb, qe, pb, pe, ct ? alpha[i] : 0.0, raw + 3 * (size_t)i, R, pw);
+  for (int a = 0; a < 3; a++) out[3 * (size_t)i + a] = pw[a];
 }
 // per sorted position: an out-of-range point; the head of a run whose voxel would be created
 __global__ __launch_bounds__(256) void k_vm_probe(VmDev V, int n, const unsigned long long *skey, int min_num_points, int *isnew, int *skip) {
@@ -230,9 +212,11 @@ struct AssocArgs {
   int *kp_nan;               // [n] dropped for a NaN a2D
   int *kp_vis;               // [n][K] visit index of the neighbours in the (voxel, point) order of the search, -1 behind the last
   double *kp_a2d, *kp_nrm, *kp_w, *kp_pt, *kp_off;     // [n], [n][3], [n], [n][3], [n][ncn]
+  const int *skip;           // device flag (or NULL): non-zero = k_vm_assoc / k_vm_compact return at once (the registration loop has ended)
 };
 __global__ __launch_bounds__(64) void k_vm_assoc(VmDev V, AssocArgs A) {
   const int kp = blockIdx.x, lane = threadIdx.x;
+  if (A.skip && *A.skip) return;      // (grid-uniform)
   __shared__ int s_slot[125], s_off[126];
   __shared__ double s_bd[VM_MAXP], s_nd[64];
   __shared__ int s_bc[VM_MAXP], s_br[VM_MAXP], s_nr[64];
@@ -328,6 +312,7 @@ __global__ __launch_bounds__(64) void k_vm_assoc(VmDev V, AssocArgs A) {
 struct ResOut { int *src; double *pts, *nrm, *off, *al, *w; };
 __global__ __launch_bounds__(VM_THREADS) void k_vm_compact(VmDev V, AssocArgs A, ResOut O, int max_res) {
   __shared__ int lds[20];
+  if (A.skip && *A.skip) return;
   const int t = threadIdx.x, chunk = (A.n + VM_THREADS - 1) / VM_THREADS, k0 = min(A.n, t * chunk), k1 = min(A.n, k0 + chunk);
   int mine = 0, nan = 0, total, tnan;
   for (int k = k0; k < k1; k++) { mine += __popc(A.kp_mask[k]); nan += A.kp_nan[k]; }
@@ -403,6 +388,25 @@ gfbe_status vm_alloc(gfbe_ctx *c, gfbe_vmap *m, T **p, size_t n, int fill) {
 template <typename T>
 T *vm_carve(char *&p, size_t n) { T *r = (T *)p; p += (std::max<size_t>(n, 1) * sizeof(T) + 255) & ~(size_t)255; return r; }
 
+// the per-keypoint scratch of one association and the options it reads (raw, alpha, pb, pe, skip are the caller's)
+gfbe_status vm_assoc_args(gfbe_ctx *c, gfbe_vmap *m, int ct, int n, int frame_init, AssocArgs *out) {
+  const gfbe_vmap_options &o = m->opt;
+  const size_t N = (size_t)std::max(n, 1);
+  VM_CHECK(c, grow(ctx_stream(c), m->kp_buf, 3 * ((N * 4 + 255) & ~(size_t)255) + ((N * 4 * o.max_number_neighbors + 255) & ~(size_t)255) + 2 * ((N * 8 + 255) & ~(size_t)255) + 2 * ((N * 24 + 255) & ~(size_t)255) +
+                                     ((N * 8 * o.num_closest_neighbors + 255) & ~(size_t)255)));
+  char *p = m->kp_buf.d;
+  AssocArgs A;
+  A.n = n; A.ct = ct ? 1 : 0; A.v = frame_init ? 2 : o.voxel_neighborhood; A.thr = frame_init ? 1 : o.threshold_voxel_occupancy;
+  A.K = o.max_number_neighbors; A.min_nn = o.min_number_neighbors; A.ncn = o.num_closest_neighbors;
+  A.size = o.size_voxel_map; A.max_plane = o.max_dist_to_plane_icp; A.power = o.power_planarity; A.w_alpha = o.weight_alpha; A.w_nb = o.weight_neighborhood;
+  A.kp_cnt = vm_carve<int>(p, N); A.kp_mask = vm_carve<unsigned int>(p, N); A.kp_nan = vm_carve<int>(p, N); A.kp_vis = vm_carve<int>(p, N * o.max_number_neighbors);
+  A.kp_a2d = vm_carve<double>(p, N); A.kp_w = vm_carve<double>(p, N); A.kp_nrm = vm_carve<double>(p, 3 * N); A.kp_pt = vm_carve<double>(p, 3 * N);
+  A.kp_off = vm_carve<double>(p, N * o.num_closest_neighbors);
+  A.raw = A.alpha = A.pb = A.pe = nullptr; A.skip = nullptr;
+  *out = A;
+  return GFBE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -463,35 +467,77 @@ gfbe_status gfbe_vmap_create(gfbe_ctx *c, int32_t voxel_capacity, const gfbe_vma
   return GFBE_OK;
 }
 
+// the add_points pipeline on points already on the device (din [n][3], valid on the stream until the last kernel below has run)
+static gfbe_status vm_add_device(gfbe_ctx *c, gfbe_vmap *m, int n, const double *din, int min_num_points, unsigned long long *key, unsigned long long *skey,
+                                 int *idx, int *sidx, int *isnew, int *skip, int *added, size_t tmp_bytes) {
+  hipStream_t s = ctx_stream(c);
+  const size_t N = (size_t)n;
+  const VmDev V = vm_dev(m, m->cur);
+  const unsigned g = (unsigned)((N + 255) / 256);
+  hipLaunchKernelGGL(k_vm_keys, dim3(g), dim3(256), 0, s, n, din, m->opt.size_voxel_map, key, idx);
+  VM_CHECK(c, rocprim::radix_sort_pairs(m->sort_buf.d, tmp_bytes, key, skey, idx, sidx, N, 0, 49, s));      // (stable: input order inside a voxel)
+  hipLaunchKernelGGL(k_vm_probe, dim3(g), dim3(256), 0, s, V, n, skey, min_num_points, isnew, skip);
+  hipLaunchKernelGGL(k_vm_admit, dim3(1), dim3(VM_THREADS), 0, s, V, n, isnew, skip);
+  hipLaunchKernelGGL(k_vm_insert, dim3(g), dim3(256), 0, s, V, n, skey, sidx, din, m->opt.size_voxel_map, m->opt.min_distance_points, min_num_points, added);
+  hipLaunchKernelGGL(k_vm_added, dim3(1), dim3(VM_THREADS), 0, s, V, n, added);
+  return GFBE_OK;
+}
+struct AddScratch { unsigned long long *key, *skey; int *idx, *sidx, *isnew, *skip, *added; double *world; size_t tmp_bytes; };
+// scratch: key, idx, sorted key, sorted idx, isnew, skip, added (+ world points [n][3] when asked for)
+static gfbe_status vm_add_scratch(gfbe_ctx *c, gfbe_vmap *m, int n, bool world, AddScratch *a) {
+  hipStream_t s = ctx_stream(c);
+  const size_t N = (size_t)n;
+  VM_CHECK(c, grow(s, m->add_buf, 2 * ((N * 8 + 255) & ~(size_t)255) + 5 * ((N * 4 + 255) & ~(size_t)255) + (world ? ((N * 24 + 255) & ~(size_t)255) : 0)));
+  char *p = m->add_buf.d;
+  a->key = vm_carve<unsigned long long>(p, N); a->skey = vm_carve<unsigned long long>(p, N);
+  a->idx = vm_carve<int>(p, N); a->sidx = vm_carve<int>(p, N); a->isnew = vm_carve<int>(p, N); a->skip = vm_carve<int>(p, N); a->added = vm_carve<int>(p, N);
+  a->world = world ? vm_carve<double>(p, 3 * N) : nullptr;
+  a->tmp_bytes = 0;
+  VM_CHECK(c, rocprim::radix_sort_pairs(nullptr, a->tmp_bytes, a->key, a->skey, a->idx, a->sidx, N, 0, 49, s));
+  VM_CHECK(c, grow(s, m->sort_buf, std::max<size_t>(a->tmp_bytes, 256)));
+  return GFBE_OK;
+}
+
 gfbe_status gfbe_vmap_add_points(gfbe_ctx *c, gfbe_vmap *m, int32_t n, const double *pts_world, int32_t min_num_points) {
   gfbe_status st = vm_ready(c, m);
   if (st != GFBE_OK) return st;
   if (n < 0 || (n > 0 && !pts_world)) return GFBE_BAD_INPUT;
   if (n == 0) return GFBE_OK;
-  hipStream_t s = ctx_stream(c);
   m->gen++;
-  // scratch: key, idx, sorted key, sorted idx, isnew, skip, added
   const size_t N = (size_t)n;
-  VM_CHECK(c, grow(s, m->add_buf, 2 * ((N * 8 + 255) & ~(size_t)255) + 5 * ((N * 4 + 255) & ~(size_t)255)));
-  char *p = m->add_buf.d;
-  unsigned long long *key = vm_carve<unsigned long long>(p, N), *skey = vm_carve<unsigned long long>(p, N);
-  int *idx = vm_carve<int>(p, N), *sidx = vm_carve<int>(p, N), *isnew = vm_carve<int>(p, N), *skip = vm_carve<int>(p, N), *added = vm_carve<int>(p, N);
-  size_t tmp_bytes = 0;
-  VM_CHECK(c, rocprim::radix_sort_pairs(nullptr, tmp_bytes, key, skey, idx, sidx, N, 0, 49, s));
-  VM_CHECK(c, grow(s, m->sort_buf, std::max<size_t>(tmp_bytes, 256)));
+  AddScratch a;
+  if ((st = vm_add_scratch(c, m, n, false, &a)) != GFBE_OK) return st;
   {
     Staged sg(c, m, N * 24 + 1024, /*defer=*/true);
     double *din = sg.up(pts_world, 3 * N);
     if (!sg.ok) { ctx_set_error(c, "gfbe_vmap_add_points: staging allocation failed"); return GFBE_DEVICE_ERROR; }
     sg.flush();
-    const VmDev V = vm_dev(m, m->cur);
-    const unsigned g = (unsigned)((N + 255) / 256);
-    hipLaunchKernelGGL(k_vm_keys, dim3(g), dim3(256), 0, s, n, din, m->opt.size_voxel_map, key, idx);
-    VM_CHECK(c, rocprim::radix_sort_pairs(m->sort_buf.d, tmp_bytes, key, skey, idx, sidx, N, 0, 49, s));      // (stable: input order inside a voxel)
-    hipLaunchKernelGGL(k_vm_probe, dim3(g), dim3(256), 0, s, V, n, skey, min_num_points, isnew, skip);
-    hipLaunchKernelGGL(k_vm_admit, dim3(1), dim3(VM_THREADS), 0, s, V, n, isnew, skip);
-    hipLaunchKernelGGL(k_vm_insert, dim3(g), dim3(256), 0, s, V, n, skey, sidx, din, m->opt.size_voxel_map, m->opt.min_distance_points, min_num_points, added);
-    hipLaunchKernelGGL(k_vm_added, dim3(1), dim3(VM_THREADS), 0, s, V, n, added);
+    if ((st = vm_add_device(c, m, n, din, min_num_points, a.key, a.skey, a.idx, a.sidx, a.isnew, a.skip, a.added, a.tmp_bytes)) != GFBE_OK) return st;
+  }
+  VM_CHECK(c, hipGetLastError());
+  return GFBE_OK;
+}
+
+// transformKeypoints (lidarodom.cpp:509-532) on the device, then the add_points pipeline on the device buffer
+gfbe_status gfbe_vmap_add_scan(gfbe_ctx *c, gfbe_vmap *m, int32_t ct, int32_t n, const double *raw_pts, const double *alpha, const double *pose_begin,
+                               const double *pose_end, int32_t min_num_points, double *pts_world_out) {
+  gfbe_status st = vm_ready(c, m);
+  if (st != GFBE_OK) return st;
+  if (n < 0 || !pose_begin || (n > 0 && !raw_pts) || (ct && (!pose_end || (n > 0 && !alpha)))) return GFBE_BAD_INPUT;
+  if (n == 0) return GFBE_OK;
+  hipStream_t s = ctx_stream(c);
+  m->gen++;
+  const size_t N = (size_t)n;
+  AddScratch a;
+  if ((st = vm_add_scratch(c, m, n, true, &a)) != GFBE_OK) return st;
+  {
+    Staged sg(c, m, N * 32 + 2048, /*defer=*/pts_world_out == nullptr);
+    const double *draw = sg.up(raw_pts, 3 * N), *dal = sg.up(ct ? alpha : nullptr, N), *dpb = sg.up(pose_begin, 7), *dpe = sg.up(pose_end ? pose_end : pose_begin, 7);
+    if (!sg.ok) { ctx_set_error(c, "gfbe_vmap_add_scan: staging allocation failed"); return GFBE_DEVICE_ERROR; }
+    sg.flush();
+    hipLaunchKernelGGL(k_vm_world, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, n, ct ? 1 : 0, draw, dal, dpb, dpe, a.world);
+    if ((st = vm_add_device(c, m, n, a.world, min_num_points, a.key, a.skey, a.idx, a.sidx, a.isnew, a.skip, a.added, a.tmp_bytes)) != GFBE_OK) return st;
+    if (pts_world_out) VM_CHECK(c, hipMemcpyAsync(pts_world_out, a.world, sizeof(double) * 3 * N, hipMemcpyDeviceToHost, s));
   }
   VM_CHECK(c, hipGetLastError());
   return GFBE_OK;
@@ -609,16 +655,8 @@ gfbe_status gfbe_vmap_associate(gfbe_ctx *c, gfbe_vmap *m, int32_t ct, int32_t n
   const gfbe_vmap_options &o = m->opt;
   const size_t N = (size_t)std::max(n, 1);
   m->assoc_valid = false;
-  VM_CHECK(c, grow(s, m->kp_buf, 3 * ((N * 4 + 255) & ~(size_t)255) + ((N * 4 * o.max_number_neighbors + 255) & ~(size_t)255) + 2 * ((N * 8 + 255) & ~(size_t)255) + 2 * ((N * 24 + 255) & ~(size_t)255) +
-                                     ((N * 8 * o.num_closest_neighbors + 255) & ~(size_t)255)));
-  char *p = m->kp_buf.d;
   AssocArgs A;
-  A.n = n; A.ct = ct ? 1 : 0; A.v = frame_init ? 2 : o.voxel_neighborhood; A.thr = frame_init ? 1 : o.threshold_voxel_occupancy;
-  A.K = o.max_number_neighbors; A.min_nn = o.min_number_neighbors; A.ncn = o.num_closest_neighbors;
-  A.size = o.size_voxel_map; A.max_plane = o.max_dist_to_plane_icp; A.power = o.power_planarity; A.w_alpha = o.weight_alpha; A.w_nb = o.weight_neighborhood;
-  A.kp_cnt = vm_carve<int>(p, N); A.kp_mask = vm_carve<unsigned int>(p, N); A.kp_nan = vm_carve<int>(p, N); A.kp_vis = vm_carve<int>(p, N * o.max_number_neighbors);
-  A.kp_a2d = vm_carve<double>(p, N); A.kp_w = vm_carve<double>(p, N); A.kp_nrm = vm_carve<double>(p, 3 * N); A.kp_pt = vm_carve<double>(p, 3 * N);
-  A.kp_off = vm_carve<double>(p, N * o.num_closest_neighbors);
+  if ((st = vm_assoc_args(c, m, ct, n, frame_init, &A)) != GFBE_OK) return st;
   int hmeta[VM_META] = {0};
   {
     Staged sg(c, m, N * 32 + 4096);
@@ -684,3 +722,21 @@ gfbe_status gfbe_vmap_localizability(gfbe_ctx *c, gfbe_vmap *m, double *sv, int3
 }
 
 }  // extern "C"
+
+// ---- what the registration loop (gfbe_vreg.hip) enqueues from this file's kernels: every argument is already on the device
+namespace gfd {
+gfbe_status vmap_enqueue_assoc(gfbe_ctx *c, gfbe_vmap *m, int ct, int n, const double *d_raw, const double *d_alpha, const double *d_pb, const double *d_pe,
+                               int frame_init, const int *d_skip) {
+  AssocArgs A;
+  const gfbe_status st = vm_assoc_args(c, m, ct, n, frame_init, &A);
+  if (st != GFBE_OK) return st;
+  A.raw = d_raw; A.alpha = d_alpha; A.pb = d_pb; A.pe = d_pe; A.skip = d_skip;
+  const VmDev V = vm_dev(m, m->cur);
+  if (n > 0) hipLaunchKernelGGL(k_vm_assoc, dim3(n), dim3(64), 0, ctx_stream(c), V, A);
+  hipLaunchKernelGGL(k_vm_compact, dim3(1), dim3(VM_THREADS), 0, ctx_stream(c), V, A, ResOut{m->res_src, m->res_pts, m->res_nrm, m->res_off, m->res_al, m->res_w}, m->opt.max_num_residuals);
+  return GFBE_OK;
+}
+void vmap_enqueue_local(gfbe_ctx *c, gfbe_vmap *m, double *d_out4) {
+  hipLaunchKernelGGL(k_vm_local, dim3(1), dim3(256), 0, ctx_stream(c), vm_dev(m, m->cur), m->res_nrm, d_out4);
+}
+}  // namespace gfd

@@ -600,6 +600,63 @@ gfbe_status gfbe_vmap_linearize(gfbe_ctx *ctx, gfbe_vmap *map, int32_t ct, doubl
 gfbe_status gfbe_vmap_localizability(gfbe_ctx *ctx, gfbe_vmap *map, double *sv, int32_t *degenerate);
 
 /* ------------------------------------------------------------------------------------------
+ * f4c Scan-to-map registration loop on the device: one call of lidarodom::optimize from the head of its ICP loop to the
+ *     loop's end (lio/src/liw/lio/lidarodom.cpp:534-748; gridSampling in front of the loop stays with the caller):
+ *       the ICP loop, exit test           lidarodom.cpp:534-748      gfbe_vmap_register
+ *       addSurfCostFactor                 :929-1071                  (gfbe_vmap_associate's kernels, at the current poses)
+ *       point-to-plane factors            lidarFactor.cpp:18-120     (the rows of gfbe_lio_linearize) under HuberLoss(0.5)
+ *       Location / Rotation / SmallVelocity consistency factors      lidarFactor.cpp:125-219 (ct = 1 only, no loss)
+ *       Plus: q * deltaQ(d), normalised   poseParameterization.cpp:31-50
+ *       checkLocalizability               lidarodom.cpp:811-885      (on the last association)
+ *       transformKeypoints + map_incremental  :509-532, :758, :1167-1266   gfbe_vmap_add_scan
+ *     The inner solve is Ceres 1.14's Levenberg-Marquardt with the rules gfbe_pg_solve follows (radius 1e4, Jacobi
+ *     scaling, diagonal clamp, step quality 1e-3, the three tolerances); lm_termination: 0 iteration cap, 1 function
+ *     tolerance, 2 parameter tolerance, 3 gradient tolerance, 4 radius / five invalid steps in a row. The loop and its
+ *     decisions run on the device: one upload, a fixed sequence of launches, one host wait. ct = 0: pose_begin is the
+ *     pose (as in gfbe_vmap_associate), pose_end is carried unchanged (NULL: a copy of pose_begin's input).
+ *     Deviations: the acos of the exit test is clamped to [-1, 1]; an association without residuals
+ *     ends the loop (no_residuals = 1, poses as they are); a solve Ceres would call unusable returns
+ *     GFBE_NUMERICAL_FAILURE with every output written at the last accepted poses.
+ *     GFBE_BAD_INPUT: as gfbe_vmap_associate, a wrong struct_size, an option out of range, the sticky overflow flag
+ *     (outputs untouched). On GFBE_OK the handle holds the last association (gfbe_vmap_linearize / _localizability).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct gfbe_vreg_options {
+  int32_t struct_size;                 /* refused when it differs, as gfbe_vmap_options */
+  int32_t max_num_iteration;           /* 10 (1..32)  outer ICP iterations */
+  int32_t lm_max_num_iterations;       /* 5  (0..16)  options.max_num_iterations of the inner solve */
+  int32_t min_num_residuals;           /* 300: reported only, as the reference only prints */
+  double laser_point_cov;              /* 0.001; sqrt_info of the factors = sqrt(1 / laser_point_cov) */
+  double huber_delta;                  /* 0.5; <= 0: no loss */
+  double beta_location_consistency;    /* 1.0 */
+  double beta_orientation_consistency; /* 1.0 */
+  double beta_small_velocity;          /* 0.0 */
+  double thres_translation_norm;       /* 0.01 m */
+  double thres_orientation_norm;       /* 0.1 deg */
+} gfbe_vreg_options;
+
+typedef struct gfbe_vreg_summary {      /* every field written whenever the call returns GFBE_OK */
+  int32_t outer_iterations, converged, too_few_residuals, no_residuals, degenerate;
+  double sv[3];
+  int32_t n_res[32], lm_iterations[32], lm_accepted[32];   /* lm_accepted: bit i = inner step i was accepted */
+  int32_t lm_termination[32];                              /* codes as gfbe_pg_solve's summary uses them */
+  double cost_initial[32], cost_final[32], diff_trans[32], diff_rot[32];
+  double pose_trace[32][14];                               /* [begin | end] after each outer iteration */
+} gfbe_vreg_summary;
+
+void gfbe_vreg_default_options(gfbe_vreg_options *opt);
+/* opt NULL: the defaults. prev_translation [3], prev_rotation [4] (x,y,z,w): the previous frame's end pose (ct = 1; NULL: zero /
+ * identity, the reference's first frames). summary may be NULL; pose_end_out may be NULL for ct = 0. */
+gfbe_status gfbe_vmap_register(gfbe_ctx *ctx, gfbe_vmap *map, const gfbe_vreg_options *opt, int32_t ct, int32_t n,
+                               const double *raw_pts, const double *alpha, const double *pose_begin, const double *pose_end,
+                               const double *prev_translation, const double *prev_rotation, int32_t frame_init,
+                               double *pose_begin_out, double *pose_end_out, gfbe_vreg_summary *summary);
+/* The scan's world points (lio_world_point on the device) added to the map as gfbe_vmap_add_points adds them; returns
+ * without waiting unless pts_world_out [n][3] is given. */
+gfbe_status gfbe_vmap_add_scan(gfbe_ctx *ctx, gfbe_vmap *map, int32_t ct, int32_t n, const double *raw_pts,
+                               const double *alpha, const double *pose_begin, const double *pose_end,
+                               int32_t min_num_points, double *pts_world_out /* [n][3], may be NULL */);
+
+/* ------------------------------------------------------------------------------------------
  * f2  Optional in-window factors. PlaneFactor and PoseAnchorFactor run INSIDE
  *     gfbe_solve_window / gfbe_batch_solve when gfbe_window.use_plane / use_anchor are set (see gfbe_window); the
  *     functions below evaluate them stand-alone. The GNSS factors run inside the solve and MARGIN_OLD as well when

@@ -63,11 +63,53 @@ def timed(f):
     return (time.perf_counter() - t) * 1e3
 
 
+def register_leg(sizes, out):
+    """gfbe_vmap_register (ct = 1, default options) beside the host-driven loop it replaces: per outer iteration one synchronised
+    associate and lm_iterations + 1 synchronised linearize calls, the counts taken from the register call's own summary."""
+    be = gf.Backend(device=0)
+    lines = ["registration loop: gfbe_vmap_register (one host wait) against the same number of synchronised associate / linearize calls, %d keypoints, ct = 1, ms" % N_KP,
+             "median [max - min] of %d repetitions after a warm-up; host clock around the call(s)" % REPS, ""]
+    pb = np.array([0.0, 0.0, 1.0, 0, 0, 0, 1.0])
+    pe = np.array([0.02, 0.01, 1.0, 0, 0, np.sin(0.005), np.cos(0.005)])
+    for n_map in sizes:
+        rng = np.random.default_rng(n_map)
+        world, kp, _ = scene(n_map, rng)
+        raw = np.ascontiguousarray(kp - [0, 0, 1.0])
+        alpha = np.ascontiguousarray(rng.uniform(0, 1, N_KP))
+        dm = be.voxel_map(max(1 << 12, n_map // 4))
+        dm.add_points(world)
+        sb, se = pb + [0.01, -0.01, 0.02, 0, 0, 0, 0], pe + [0.01, -0.01, 0.02, 0, 0, 0, 0]
+        _, _, sm = dm.register(1, raw, alpha, sb, se, pb[:3], pb[3:])
+        K = sm["outer_iterations"]
+        calls = [(1, int(sm["lm_iterations"][k]) + 1) for k in range(K)]
+
+        def host_driven():
+            for _, nl in calls:
+                dm.associate(1, raw, alpha, sb, se)
+                for _ in range(nl):
+                    dm.linearize(1, 31.6, sb, se)
+        tr, th = [], []
+        for i in range(REPS + 1):
+            x, y = timed(lambda: dm.register(1, raw, alpha, sb, se, pb[:3], pb[3:])), timed(host_driven)
+            if i:
+                tr.append(x)
+                th.append(y)
+        lines.append("map %d points: %d outer iterations, n_res %d, %d associate + %d linearize calls" % (dm.size()["n_points"], K, sm["n_res"][0], K, sum(c[1] for c in calls)))
+        lines.append("  register %8.3f [%6.3f]   host-driven calls %8.3f [%6.3f]" % (np.median(tr), max(tr) - min(tr), np.median(th), max(th) - min(th)))
+        print("\n".join(lines[-2:]), flush=True)
+        dm.close()
+    with open(out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="20000,200000,2000000")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "vmap_bench.txt"))
+    ap.add_argument("--register", action="store_true", help="the registration loop leg (written to profiles/vreg_bench.txt)")
     a = ap.parse_args()
+    if a.register:
+        return register_leg([int(s) for s in a.sizes.split(",")], os.path.join(ROOT, "profiles", "vreg_bench.txt"))
     shim, orc = build_shim(), oracle_lib.load()
     be = gf.Backend(device=0)
     lines = ["voxel map: device (gfbe_vmap_*) against a single-thread host restatement (std::unordered_map), %d keypoints, ms" % N_KP,
