@@ -6,6 +6,7 @@
 // Reference being replaced: Estimator::optimization()
 //   Ground-Fusion++/vins_estimator/src/estimator/estimator.cpp:2951-3698
 #include "gfbe_device.h"
+#include "gfbe_upload.h"
 #include <algorithm>
 #include <atomic>
 #include <condition_variable>
@@ -485,23 +486,14 @@ void prof_collect(gfbe_ctx *c) {
 // hipMalloc), the second pass hands out the pointers. The arrays the host fills come FIRST ("upload region"): they have a
 // mirror at the same offsets in one pinned host buffer, the packing threads write straight into that mirror, and the whole
 // region crosses PCIe as ONE hipMemcpyAsync. Only the arrays the kernels expect zeroed are cleared (one hipMemsetAsync).
+// (the upload region's part of the sequence is upload_region, gfbe_upload.h: the same sizes over the slab and over the mirror)
 template <typename T>
 gfbe_status dev_alloc(gfbe_ctx *c, gfbe_batch *b, T **p, size_t n) {
-  const size_t bytes = (std::max<size_t>(n, 1) * sizeof(T) + 255) & ~(size_t)255;
+  const size_t bytes = slab_bytes_of<T>(n);
   if (b->dry) { b->slab_bytes += bytes; *p = nullptr; return GFBE_OK; }
   if (b->slab_off + bytes > b->slab_bytes) { c->err = "batch slab overrun"; return GFBE_DEVICE_ERROR; }
   *p = (T *)(b->slab + b->slab_off);
   b->slab_off += bytes;
-  return GFBE_OK;
-}
-// an array of the upload region: device pointer + its pinned host mirror (valid in the second pass)
-template <typename T>
-gfbe_status up_alloc(gfbe_ctx *c, gfbe_batch *b, T **p, T **h, size_t n) {
-  const size_t off = b->dry ? b->slab_bytes : b->slab_off;
-  gfbe_status st = dev_alloc(c, b, p, n);
-  if (st != GFBE_OK) return st;
-  if (b->dry) { *h = nullptr; b->up_bytes = b->slab_bytes; }
-  else *h = (T *)(b->up_h + off);
   return GFBE_OK;
 }
 // the smallest cached slab that fits (and is not more than twice too large), else a new one
@@ -596,125 +588,21 @@ void host_parallel(gfbe_ctx *c, int n, const std::function<void(int)> &fn, bool 
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
-// Upload: pack windows into the device layout.
+// Upload: pack windows into the device layout. The host arithmetic (validation, landmark layout, the upload region and its
+// packing) is gfbe_upload.h; the phases below are the HIP half, in the order upload_one runs them.
 // ---------------------------------------------------------------------------------------------
 namespace {
-// what the scan of one window's factor list leaves for the fill pass
-struct WinScan {
-  int L = 0, K = 0, slots = 0, n_tiles = 0;
-  int sf_tile_begin[NF + 1];
-  int pair_begin[NPAIR + 1];
-  std::vector<int> slot_rel;      // ABI landmark -> slot relative to the window's first slot
-  std::vector<unsigned char> lstart, lm;
-  std::string err;
-};
+double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// Validates the visual factor list of one window and lays its landmarks out: groups by start frame (tile aligned), inside a
-// group longer tracks first, ties in ABI order (a stable counting sort over (start, m) bins).
-bool scan_window(const gfbe_window &win, int w, WinScan &sc) {
-  const int L = win.n_feature, K = win.vis.n_factor;
-  sc.L = L; sc.K = K;
-  auto fail = [&](const std::string &m) { sc.err = "window " + std::to_string(w) + ": " + m; return false; };
-  if (L > 0 && !win.para_Feature) return fail("para_Feature is null");
-  if (K > 0 && (!win.vis.feature_index || !win.vis.imu_i || !win.vis.imu_j || !win.vis.pts_i || !win.vis.pts_j || !win.vis.vel_i ||
-                !win.vis.vel_j || !win.vis.td_i || !win.vis.td_j)) return fail("null visual factor array");
-  sc.lstart.assign(L, 255); sc.lm.assign(L, 0);
-  std::vector<unsigned short> mask(L, 0);
-  int pair_cnt[NPAIR];
-  for (int p = 0; p < NPAIR; p++) pair_cnt[p] = 0;
-  for (int k = 0; k < K; k++) {
-    const int l = win.vis.feature_index[k], i = win.vis.imu_i[k], j = win.vis.imu_j[k];
-    if (l < 0 || l >= L || i < 0 || j <= i || j > win.frame_count) return fail("bad visual factor " + std::to_string(k));
-    if (sc.lstart[l] == 255) sc.lstart[l] = (unsigned char)i;
-    if (sc.lstart[l] != i) return fail("visual factors of one landmark must share imu_i");
-    const unsigned short bit = (unsigned short)(1u << (j - i - 1));
-    if (mask[l] & bit) return fail("two visual factors of one landmark on the same frame");
-    mask[l] |= bit; sc.lm[l]++;
-    pair_cnt[i * NF + j]++;
-  }
-  int bin_cnt[NF][MAXOBS + 1];
-  for (int s = 0; s < NF; s++) for (int m = 0; m <= MAXOBS; m++) bin_cnt[s][m] = 0;
-  for (int l = 0; l < L; l++) {
-    if (sc.lstart[l] == 255) sc.lstart[l] = 0;
-    const int m = sc.lm[l];
-    if (m > MAXOBS) return fail("landmark with more than 10 factors");
-    if (mask[l] != (unsigned short)((1u << m) - 1)) return fail("landmark track must be contiguous from start_frame (feature_per_frame order)");
-    bin_cnt[sc.lstart[l]][m]++;
-  }
-  int bin_base[NF][MAXOBS + 1];
-  int slots = 0;
-  for (int s = 0; s < NF; s++) {
-    sc.sf_tile_begin[s] = slots / LM_TILE;
-    int in_group = 0;
-    for (int m = MAXOBS; m >= 0; m--) { bin_base[s][m] = slots + in_group; in_group += bin_cnt[s][m]; }
-    slots += (in_group + LM_TILE - 1) / LM_TILE * LM_TILE;
-  }
-  sc.sf_tile_begin[NF] = slots / LM_TILE;
-  sc.slots = slots; sc.n_tiles = slots / LM_TILE;
-  sc.slot_rel.resize(L);
-  for (int l = 0; l < L; l++) sc.slot_rel[l] = bin_base[sc.lstart[l]][sc.lm[l]]++;
-  int run = 0;
-  for (int p = 0; p < NPAIR; p++) { sc.pair_begin[p] = run; run += pair_cnt[p]; }
-  sc.pair_begin[NPAIR] = run;
-  return true;
-}
-
-// Upper bound of the tangent size of the prior a marginalisation of this window can return (MarginalizationInfo::n): the
-// blocks the marginalisation set touches (k_marg builds the same table on the device) minus the dropped ones.
-int prior_out_bound(const gfbe_window &win, const int *pair_begin, bool old) {
-  bool touched[GFBE_BLK_COUNT];
-  for (int q = 0; q < GFBE_BLK_COUNT; q++) touched[q] = false;
-  const gfbe_prior *pr = (win.prior && win.prior->valid && win.prior->n > 0) ? win.prior : nullptr;
-  if (pr) for (int q = 0; q < pr->n_blocks; q++) touched[pr->block_id[q]] = true;
-  if (!old) return pr ? pr->n : 0;
-  for (int k = 0; k < win.n_imu; k++) if (win.imu_frame[k] == 0) touched[0] = touched[GFBE_BLK_SB0] = touched[1] = touched[GFBE_BLK_SB0 + 1] = true;
-  for (int k = 0; k < win.n_wheel; k++)
-    if (win.wheel_frame[k] == 0) touched[0] = touched[1] = touched[GFBE_BLK_EX_WHEEL] = touched[GFBE_BLK_SX] = touched[GFBE_BLK_SY] = touched[GFBE_BLK_SW] = touched[GFBE_BLK_TD_WHEEL] = true;
-  if (win.use_plane && win.frame_count > 0) touched[0] = touched[GFBE_BLK_EX_WHEEL] = touched[GFBE_BLK_PLANE_R] = touched[GFBE_BLK_PLANE_Z] = true;
-  if (win.gnss_ready) {
-    touched[0] = touched[GFBE_BLK_SB0] = touched[1] = touched[GFBE_BLK_SB0 + 1] = touched[GFBE_BLK_YAW_ENU] = touched[GFBE_BLK_ANC_ECEF] = true;
-    for (int k = 0; k < 4; k++) touched[GFBE_BLK_RCV_DT0 + 4 + k] = true;
-    touched[GFBE_BLK_RCV_DDT0 + 1] = true;
-  }
-  if (pair_begin) { for (int j = 1; j < NF; j++) if (pair_begin[j + 1] > pair_begin[j]) touched[0] = touched[j] = touched[GFBE_BLK_EX_CAM] = touched[GFBE_BLK_TD] = true; }
-  else for (int q = 0; q < NF; q++) touched[q] = touched[GFBE_BLK_EX_CAM] = touched[GFBE_BLK_TD] = true;   // (table-fed: pair counts live on the device)
-  int n = 0;
-  for (int q = 0; q < GFBE_BLK_COUNT; q++) if (touched[q] && q != 0 && q != GFBE_BLK_SB0) n += blk_lsize(q);
-  return std::min(n, (int)ND);
-}
-}  // namespace
-
-// tabs != nullptr: the visual factors of window w come from table tab0 + w of the device-resident feature tables
-// (wins[w]->vis, n_feature, para_Feature, feature_const are ignored); the landmark arrays are then filled on the device.
-// The call returns when the windows are packed into pinned memory and the copy + preparation kernels are enqueued on the
-// context's copy stream: the caller's buffers are free again, gfbe_batch_solve waits for the batch's `ev_up`.
-static gfbe_status upload_one(gfbe_ctx *c, int32_t B, const gfbe_window *const *wins, gfbe_batch **out, gfbe_ftab *tabs = nullptr,
-                              int tab0 = 0) {
-  if (!c || !wins || !out || B <= 0) return GFBE_BAD_INPUT;
-  if (c->device < 0 || !c->stream) { c->err = "HIP device context required (no CPU fallback)"; return GFBE_NO_DEVICE; }
-  const bool dbg_t = diag_getenv("GFBE_DEBUG_UPLOAD") != nullptr && diag_getenv("GFBE_DEBUG_UPLOAD")[0] != 0;   // phase times of the upload on stderr (tools/diag_e2e_latency.py)
-  auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  HIPCHK(c, hipSetDevice(c->device));
-  const double T0 = now();
-  for (int w = 0; w < B; w++) {
-    const gfbe_window *win = wins[w];
-    if (!win) { c->err = "window " + std::to_string(w) + ": null pointer"; return GFBE_BAD_INPUT; }
-    if (win->frame_count < 0 || win->frame_count > GFBE_WINDOW_SIZE || win->n_imu < 0 || win->n_imu > MAX_IMU || win->n_wheel < 0 || win->n_wheel > MAX_WHEEL ||
-        (!tabs && (win->n_feature < 0 || win->vis.n_factor < 0)) || (win->n_imu > 0 && (!win->imu || !win->imu_frame)) ||
-        (win->n_wheel > 0 && (!win->wheel || !win->wheel_frame))) {
-      c->err = "window " + std::to_string(w) + ": bad sizes"; return GFBE_BAD_INPUT;
-    }
-  }
-  if (c->allreduce && c->opt.max_solver_time_in_seconds > 0.0) {
-    // (every rank would stop on its own clock: the replicated dense state would diverge between the ranks)
-    c->err = "max_solver_time_in_seconds is not available with landmark sharding (gfbe_set_allreduce)"; return GFBE_BAD_INPUT;
-  }
+// Phase 1: the batch object, its events, and the stream the upload runs on.
+gfbe_status upload_prologue(gfbe_ctx *c, int32_t B, gfbe_ftab *tabs, gfbe_batch **out, hipStream_t *us_out) {
   gfbe_batch *b = new gfbe_batch();
   *out = b;
   BatchDev &d = b->d;
   std::memset(&d, 0, sizeof d);
   d.B = B;
   d.opt = c->opt;
+  d.test_fail_chol_iter = c->opt.test_fail_chol_iter;   // (test hook of the mu-retry path, 0 in production: gfbe_options)
   for (hipEvent_t *e : {&b->ev_up, &b->ev_done, &b->ev_dl}) {
     if (!c->sync_event_pool.empty()) { *e = c->sync_event_pool.back(); c->sync_event_pool.pop_back(); }
     else if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) { c->err = "hipEventCreate (batch) failed"; return GFBE_DEVICE_ERROR; }
@@ -728,169 +616,38 @@ static gfbe_status upload_one(gfbe_ctx *c, int32_t B, const gfbe_window *const *
   // (round 5: every batch below 32 windows — its upload is two kernels now (k_ingest_small reads the pinned staging buffer itself), ~40 us
   //  that would hide behind nothing, and the hop from the copy stream to the main stream cost 11 us of a single window's call)
   hipStream_t us = B < DENSE_SPLIT_MIN_B ? c->stream : c->copy;
+  *us_out = us;
   if (tabs && us != c->stream && tabs->ev_ops) HIPCHK(c, hipStreamWaitEvent(us, tabs->ev_ops, 0));
   // (a SMALL table-fed upload right behind a large one from the same tables — no table operation in between, so nobody has
   //  waited for ev_read — rewrites the tables' shared histogram / layout / id scratch on the main stream while the large batch's pack
   //  kernel may still read them on the copy stream: the main stream waits for the last reader first. The flag stays set: the next table
   //  operation still orders itself behind that reader through ft_ready.)
   if (tabs && us == c->stream && tabs->read_pending && tabs->ev_read) HIPCHK(c, hipStreamWaitEvent(us, tabs->ev_read, 0));
-  b->slot_of.resize(B);
-  b->L.resize(B);
-  b->anchor_only.assign(B, 0);
-  b->up_win_bytes.assign(B, 0.0);
-  std::vector<WinScan> scan(B);
-  std::vector<int> tcounts, tlayout;     // table source: per window [L, K, bins], layout table for the pack kernel
-  // ---- pass 1 (parallel over windows): validate the factor lists, lay the landmarks out
-  if (tabs) {
-    if (tab0 < 0 || tab0 + B > tabs->d.W) { c->err = "gfbe_batch_upload_tables: more windows than tables"; return GFBE_BAD_INPUT; }
-    int *dcounts = tabs->d.hist + (size_t)tab0 * (FT_BINS + 2);
-    launch_ftab_count(tabs->d, tabs->cur, tab0, B, dcounts, us);
-    tcounts.resize((size_t)B * (FT_BINS + 2));
-    // (through the tables' pinned staging mirror when it is large enough: a pageable device-to-host copy is staged by the runtime)
-    const bool pinned = tabs->stage_h && sizeof(int) * tcounts.size() <= tabs->stage_cap;
-    HIPCHK(c, hipMemcpyAsync(pinned ? (void *)tabs->stage_h : (void *)tcounts.data(), dcounts, sizeof(int) * tcounts.size(), hipMemcpyDeviceToHost, us));
-    HIPCHK(c, hipStreamSynchronize(us));
-    if (pinned) std::memcpy(tcounts.data(), tabs->stage_h, sizeof(int) * tcounts.size());
-    tlayout.assign((size_t)B * FT_LAY_STRIDE, 0);
-    for (int w = 0; w < B; w++) {   // layout from the per-bin counts: groups by start frame (tile aligned), longer tracks first inside a group
-      WinScan &sc = scan[w];
-      const int *cnt = &tcounts[(size_t)w * (FT_BINS + 2) + 2];
-      int *lay = &tlayout[(size_t)w * FT_LAY_STRIDE];
-      sc.L = tcounts[(size_t)w * (FT_BINS + 2)]; sc.K = tcounts[(size_t)w * (FT_BINS + 2) + 1];
-      if (sc.L < 0 || sc.K < 0) { c->err = "window " + std::to_string(w) + ": bad sizes"; return GFBE_BAD_INPUT; }
-      int slots = 0;
-      for (int s = 0; s < NF; s++) {
-        sc.sf_tile_begin[s] = slots / LM_TILE;
-        lay[FT_LAY_GRP + s] = slots;
-        int in_group = 0;
-        for (int m = MAXOBS; m >= 3; m--) { lay[FT_LAY_BIN + s * 8 + (m - 3)] = slots + in_group; in_group += cnt[s * 8 + (m - 3)]; }
-        slots += (in_group + LM_TILE - 1) / LM_TILE * LM_TILE;
-      }
-      sc.sf_tile_begin[NF] = slots / LM_TILE;
-      sc.slots = slots; sc.n_tiles = slots / LM_TILE;
-      // factors of pair (s, s+1+k) = landmarks of start frame s with more than k factors
-      int pair_cnt[NPAIR];
-      for (int p = 0; p < NPAIR; p++) pair_cnt[p] = 0;
-      for (int s = 0; s < NF; s++)
-        for (int k = 0; k < MAXOBS && s + 1 + k < NF; k++)
-          for (int m = std::max(k + 1, 3); m <= MAXOBS; m++) pair_cnt[s * NF + s + 1 + k] += cnt[s * 8 + (m - 3)];
-      int run = 0;
-      for (int p = 0; p < NPAIR; p++) { sc.pair_begin[p] = run; run += pair_cnt[p]; }
-      sc.pair_begin[NPAIR] = run;
-      std::memcpy(&lay[FT_LAY_PAIR], sc.pair_begin, sizeof(int) * (NPAIR + 1));
-    }
-  } else {
-    std::atomic<int> bad(-1);
-    const auto t_scan0 = std::chrono::steady_clock::now();
-    host_parallel(c, B, [&](int w) { if (!scan_window(*wins[w], w, scan[w])) { int e = -1; bad.compare_exchange_strong(e, w); } }, true);
-    c->host_ms[0] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_scan0).count();
-    if (bad.load() >= 0) { c->err = scan[bad.load()].err; return GFBE_BAD_INPUT; }
-  }
-  // ---- serial: offsets of every window in the batch-wide arrays
-  std::vector<WinDesc> desc_tmp(B);   // (only the offset fields are set here; the fill pass completes the descriptors)
-  std::vector<int> tile_start;
-  std::vector<int> feat_off(B + 1, 0);
-  std::vector<long long> j0_off(B + 1, 0);
-  int tot_n0 = 0;
-  int max_sf_tiles = 0;
-  int tot_lm = 0, tot_rec = 0, max_tiles = 0, n_imu_tot = 0, n_wheel_tot = 0, tot_lio = 0, pn_max = 0, tot_gnss = 0, any_gnss = 0, gnss_dims = 0, gnss_max = 0, marg_nmax = 0;
-  double algo_bytes = 0.0;
-  for (int w = 0; w < B; w++) {
-    const gfbe_window &win = *wins[w];
-    const WinScan &sc = scan[w];
-    WinDesc &ds = desc_tmp[w];
-    std::memset(&ds, 0, sizeof ds);
-    ds.L = sc.L; ds.K = sc.K; ds.frame_count = win.frame_count;
-    ds.lm_off = tot_lm; ds.lm_slots = sc.slots; ds.n_tiles = sc.n_tiles; ds.tile_off = (int)tile_start.size();
-    ds.rec_off = tot_rec;
-    ds.vel_off = tot_n0;
-    tot_n0 += tabs ? 0 : sc.pair_begin[NF];      // (records of the pairs (0, j): pair index i * NF + j, i-major)
-    for (int s = 0; s < NF; s++) for (int t = sc.sf_tile_begin[s]; t < sc.sf_tile_begin[s + 1]; t++) tile_start.push_back(s);
-    if (tabs) tlayout[(size_t)w * FT_LAY_STRIDE] = tot_lm;
-    tot_lm += sc.slots; tot_rec += sc.K; max_tiles = std::max(max_tiles, sc.n_tiles);
-    for (int s = 0; s < NF; s++) max_sf_tiles = std::max(max_sf_tiles, sc.sf_tile_begin[s + 1] - sc.sf_tile_begin[s]);
-    ds.imu_off = n_imu_tot; ds.wheel_off = n_wheel_tot; ds.lio_off = tot_lio;
-    n_imu_tot += win.n_imu; n_wheel_tot += win.n_wheel; tot_lio += win.lio.n > 0 ? win.lio.n : 0;
-    if (win.gnss_ready) {
-      if (win.n_gnss < 0 || (win.n_gnss > 0 && !win.gnss_obs)) { c->err = "window " + std::to_string(w) + ": gnss_ready without observations array"; return GFBE_BAD_INPUT; }
-      for (int k = 0; k < win.n_gnss; k++) {
-        const gfbe_gnss_obs &o = win.gnss_obs[k];
-        if (o.frame < 0 || o.frame > GFBE_WINDOW_SIZE || o.lower_idx < 0 || o.lower_idx >= GFBE_WINDOW_SIZE || (o.lower_idx != o.frame && o.lower_idx != o.frame - 1) ||
-            o.sys_idx < 0 || o.sys_idx > 3 || !(o.pr_uura > 0.0) || !(o.dp_uura > 0.0)) {
-          c->err = "window " + std::to_string(w) + ": GNSS observation " + std::to_string(k) + " has an index or a deviation out of range"; return GFBE_BAD_INPUT;
-        }
-      }
-      ds.gnss_ready = 1; ds.n_gnss = win.n_gnss; ds.gnss_off = tot_gnss;
-      tot_gnss += win.n_gnss; any_gnss = 1; gnss_max = std::max(gnss_max, win.n_gnss);
-    }
-    b->L[w] = sc.L;
-    feat_off[w + 1] = feat_off[w] + sc.L;
-    // MARGIN_SECOND_NEW with an INVALID last_marginalization_info that still lists Pose[WINDOW_SIZE-1] (estimator.cpp:3600, 3622-3632):
-    // the reference marginalises a PoseAnchorFactor on Pose[0] with drop set {Pose[0]} — six dims dropped, nothing kept — and ends
-    // with a valid, empty MarginalizationInfo. Nothing to compute: gfbe_batch_download hands back exactly that.
-    if (win.prior && !win.prior->valid && win.frame_count == GFBE_WINDOW_SIZE && win.prior->n_blocks > 0 && win.prior->n_blocks <= GFBE_MAX_PRIOR_BLOCKS)
-      for (int q = 0; q < win.prior->n_blocks; q++) if (win.prior->block_id[q] == GFBE_BLK_POSE0 + GFBE_WINDOW_SIZE - 1) b->anchor_only[w] = 1;
-    if (win.prior && win.prior->valid && win.prior->n > 0) {
-      const gfbe_prior &pr = *win.prior;
-      if (pr.n > ND || pr.n_blocks < 0 || pr.n_blocks > GFBE_MAX_PRIOR_BLOCKS || !pr.J0 || !pr.r0) { c->err = "window " + std::to_string(w) + ": prior too large or without J0 / r0"; return GFBE_BAD_INPUT; }
-      bool seen[GFBE_BLK_COUNT];
-      for (int q = 0; q < GFBE_BLK_COUNT; q++) seen[q] = false;
-      int xo = 0;
-      for (int q = 0; q < pr.n_blocks; q++) {
-        const int id = pr.block_id[q];
-        if (id < 0 || id >= GFBE_BLK_COUNT || pr.block_size[q] != blk_gsize(id) || seen[id] || pr.block_idx[q] < 0 || pr.block_idx[q] + blk_lsize(id) > pr.n) {
-          c->err = "window " + std::to_string(w) + ": prior block table inconsistent (id, size, duplicate or offset out of range)"; return GFBE_BAD_INPUT;
-        }
-        seen[id] = true; xo += pr.block_size[q];
-        if (id >= GFBE_BLK_ANC_ECEF) gnss_dims = 1;
-      }
-      if (xo > (int)PRIOR_X0) { c->err = "prior x0 too large"; return GFBE_BAD_INPUT; }
-      pn_max = std::max(pn_max, pr.n);
-    }
-    const int nb = std::max(prior_out_bound(win, tabs ? nullptr : sc.pair_begin, true), prior_out_bound(win, nullptr, false));
-    j0_off[w + 1] = j0_off[w] + (long long)nb * nb;
-    marg_nmax = std::max(marg_nmax, nb);
-    algo_bytes += 108.0 * sc.K;   // 12 f64 + 3 i32 per visual residual block, J never re-read by the host
-  }
-  d.tot_lm = tot_lm; d.max_tiles = max_tiles; d.tot_rec = tot_rec; d.tot_lio = tot_lio; d.max_sf_tiles = max_sf_tiles;
-  d.rank = c->rank; d.world = c->world; d.sharded = c->allreduce ? 1 : 0;
-  d.schur_groups = B >= DENSE_SPLIT_MIN_B ? SCHUR_GROUPS : (c->allreduce ? NF : 2 * NF);
-  d.test_fail_chol_iter = c->opt.test_fail_chol_iter;   // (test hook of the mu-retry path, 0 in production: gfbe_options)
-  b->algo_bytes_lin = algo_bytes;
-  for (int w = 0; w < B; w++) if (!wins[w]->ex_cam_const || !wins[w]->td_const) d.vis_full = 1;
-  // Host-fed batches that hold td and the camera extrinsic constant everywhere: the observations cross PCIe already shifted to the
-  // window's td (two doubles per factor instead of five: k_expand would apply the same shift, projectionTwoFrameOneCamFactor.cpp:
-  // 60-61, before anything reads them); velocity and td of an observation travel only for the landmarks that start in frame 0 — the
-  // marginalisation's td / extrinsic columns are the only readers (estimator.cpp:3498-3531 takes the factors with imu_i == 0).
-  // 378 -> ~200 KB of the 630 KB a 2000-landmark window uploads. (Not for gfbe_eval_factors: its records carry every td column.)
-  d.obs_compact = (!tabs && !d.vis_full && !c->want_records) ? 1 : 0;
-  for (int w = 0; w < B; w++) if (wins[w]->use_plane || wins[w]->use_anchor) d.any_plane = 1;
-  for (int w = 0; w < B; w++) if (wins[w]->prior && wins[w]->prior->valid) d.prior_n_max = std::max(d.prior_n_max, (int)wins[w]->prior->n);
-  d.any_gnss = any_gnss; d.tot_gnss = tot_gnss; d.gnss_max_obs = gnss_max; d.marg_nmax = marg_nmax;
-  d.nu = (any_gnss || gnss_dims) ? (int)ND : (int)NC;       // a batch without GNSS blocks never touches the last 59 tangent dims
-  d.solve_big = d.nu > NC;                                  // (decided per batch: k_solve / k_solve_chain hold the 187 core dims only)
-  if (diag_getenv("GFBE_VIS_FULL")) d.vis_full = 1;   // (diagnostics build only: force the 20-column panel)
-  // speculative linearisation (gfbe_options.speculative_linearization): every batch with landmarks gets a second set of the
-  // linearisation's outputs (round 6: also with an all-reduce hook — the landmark-sharded solve: the candidate's pass linearises its own
-  // tiles, the ranks' candidate costs travel as before; one evaluation pass less per iteration there too. The number of collectives per
-  // iteration stays: DESIGN.md section 7)
-  d.spec = (c->opt.speculative_linearization && max_tiles > 0) ? 1 : 0;
-  // k_linschur (gfbe_options.merge_lin_schur): throughput batches on the 7 x 7 panel, every tile on this rank
-  d.linschur = (c->opt.merge_lin_schur && B >= DENSE_SPLIT_MIN_B && !d.vis_full && !c->allreduce && max_tiles > 0) ? 1 : 0;
-  const size_t TL = tot_lm;
-  const size_t pj_row = (size_t)pn_max * pn_max;   // J0 of the priors travels compactly: rows of pn_max^2 doubles, spread into the ND^2 slots on the device
-  const double T1 = now();
-  // ---- allocation sequence (dry pass, then the real one)
+  return GFBE_OK;
+}
+
+// Phase 2 (table-fed only): the per-window [L, K, bins] landmark counts of tables [tab0, tab0 + B), counted on the device.
+gfbe_status fetch_table_counts(gfbe_ctx *c, gfbe_ftab *tabs, int tab0, int32_t B, hipStream_t us, std::vector<int> &tcounts) {
+  if (tab0 < 0 || tab0 + B > tabs->d.W) { c->err = "gfbe_batch_upload_tables: more windows than tables"; return GFBE_BAD_INPUT; }
+  int *dcounts = tabs->d.hist + (size_t)tab0 * (FT_BINS + 2);
+  launch_ftab_count(tabs->d, tabs->cur, tab0, B, dcounts, us);
+  tcounts.resize((size_t)B * (FT_BINS + 2));
+  // (through the tables' pinned staging mirror when it is large enough: a pageable device-to-host copy is staged by the runtime)
+  const bool pinned = tabs->stage_h && sizeof(int) * tcounts.size() <= tabs->stage_cap;
+  HIPCHK(c, hipMemcpyAsync(pinned ? (void *)tabs->stage_h : (void *)tcounts.data(), dcounts, sizeof(int) * tcounts.size(), hipMemcpyDeviceToHost, us));
+  HIPCHK(c, hipStreamSynchronize(us));
+  if (pinned) std::memcpy(tcounts.data(), tabs->stage_h, sizeof(int) * tcounts.size());
+  return GFBE_OK;
+}
+
+// Phase 4: the slab and the pinned mirror of its upload region. Two passes over one allocation sequence (dev_alloc above); the upload
+// region comes first (upload_region, gfbe_upload.h), `dev` / `host` receive its pointers over the slab / the pinned buffer.
+gfbe_status carve_batch(gfbe_ctx *c, gfbe_batch *b, const UploadPlan &p, const char *poison_env, UploadMirror *dev, UploadMirror *host) {
+  BatchDev &d = b->d;
+  const int B = p.B, max_tiles = p.max_tiles, tot_rec = p.tot_rec, tot_gnss = p.tot_gnss, n_imu_tot = p.n_imu_tot, n_wheel_tot = p.n_wheel_tot;
+  const size_t TL = p.tot_lm;
+  const bool tabs = p.table_fed;
   gfbe_status st;
-  WinDesc *h_desc = nullptr; int *h_lm_info = nullptr, *h_lm_abi = nullptr, *h_tile_start = nullptr, *h_feat_off = nullptr;
-  long long *h_j0_off = nullptr;
-  double *h_fvel = nullptr;
-  double *h_lm_pts = nullptr, *h_lam0 = nullptr, *h_fobs = nullptr, *h_x0 = nullptr, *h_lio = nullptr, *h_pr0 = nullptr, *h_px0 = nullptr, *h_pJ0 = nullptr;
-  gfbe_imu_preint *h_imu = nullptr; gfbe_wheel_preint *h_wheel = nullptr;
-  gfbe_gnss_obs *h_gnss = nullptr;
-  double *d_pJ0c = nullptr;
-  const bool want_rec = c->want_records;
-  const char *poison_env = diag_getenv("GFBE_POISON_UNCLEARED");   // (test hook of the diagnostics build, see the enqueue below; read per upload)
   for (int pass = 0; pass < 2; pass++) {
     b->dry = pass == 0;
     if (pass == 1) {
@@ -909,17 +666,15 @@ static gfbe_status upload_one(gfbe_ctx *c, int32_t B, const gfbe_window *const *
       b->up_h = pin_acquire(c, b->up_bytes, &b->up_cap);
       if (!b->up_h) { c->err = "hipHostMalloc(upload staging) failed"; return GFBE_DEVICE_ERROR; }
     }
-#define UP(field, host, n) if ((st = up_alloc(c, b, &d.field, &host, (size_t)(n))) != GFBE_OK) return st
 #define AL(field, n) do { const size_t o_ = b->slab_off; if ((st = dev_alloc(c, b, &d.field, (size_t)(n))) != GFBE_OK) return st; \
                           if (!b->dry && poison_env) b->poison_list.push_back({#field, o_, b->slab_off - o_}); } while (0)
     // -- upload region
-    UP(desc, h_desc, B); UP(tile_start, h_tile_start, tile_start.size()); UP(x0, h_x0, (size_t)B * NA);
-    UP(imu, h_imu, n_imu_tot); UP(wheel, h_wheel, n_wheel_tot); UP(lio, h_lio, (size_t)tot_lio * 8);
-    UP(prior_r0, h_pr0, (size_t)B * ND); UP(prior_x0, h_px0, (size_t)B * PRIOR_X0);
-    UP(dl_feat_off, h_feat_off, B + 1); UP(dl_j0_off, h_j0_off, B + 1);
-    UP(gnss_obs, h_gnss, std::max(tot_gnss, 1));
-    if ((st = up_alloc(c, b, &d_pJ0c, &h_pJ0, (size_t)B * pj_row)) != GFBE_OK) return st;
-    if (!tabs) { UP(lm_info, h_lm_info, TL); UP(lm_abi, h_lm_abi, TL); UP(lm_pts, h_lm_pts, (size_t)6 * TL); UP(lam0, h_lam0, TL); UP(fobs, h_fobs, (size_t)tot_rec * (d.obs_compact ? 2 : 5)); UP(fvel, h_fvel, d.obs_compact ? (size_t)std::max(tot_n0, 1) * 3 : 1); }
+    if (b->dry) b->slab_bytes = b->up_bytes = upload_region(p, nullptr).bytes;
+    else {
+      *dev = upload_region(p, b->slab); *host = upload_region(p, b->up_h);
+      point_upload_region(*dev, d);
+      b->slab_off = dev->bytes;
+    }
     const size_t up_end = b->dry ? b->slab_bytes : b->slab_off;
     // -- arrays the kernels expect zeroed at the start (rows past a track's length, partials of absent factors, ...)
     if (tabs) { AL(lm_info, TL); AL(lm_abi, TL); AL(lm_pts, (size_t)6 * TL); AL(lam0, TL); d.fobs = nullptr; d.fvel = nullptr; }
@@ -927,7 +682,7 @@ static gfbe_status upload_one(gfbe_ctx *c, int32_t B, const gfbe_window *const *
     AL(raw_imu, (size_t)MAX_IMU * (15 + 450) * 4 * ((B + 3) / 4)); AL(raw_wheel, (size_t)MAX_WHEEL * (6 + 132) * 4 * ((B + 3) / 4));   // [factor][window / 4][value][window % 4]
     AL(zero, 16); AL(vis_H, (size_t)B * NV * (NV + 1));
     d.vs_blocks = d.vis_full ? (int)VS_BLOCKS : 1;
-    if (B < DENSE_SPLIT_MIN_B && !c->allreduce) { AL(vis_Hs, (size_t)B * d.vs_blocks * NV * (NV + 1)); } else d.vis_Hs = nullptr;
+    if (B < DENSE_SPLIT_MIN_B && !d.sharded) { AL(vis_Hs, (size_t)B * d.vs_blocks * NV * (NV + 1)); } else d.vis_Hs = nullptr;
     AL(ctl, B);
     AL(lam, 2 * TL); AL(lm_Hll, TL); AL(lm_gl, TL); AL(lm_hC, (size_t)HC * TL);
     AL(lm_sl, TL); AL(lm_yl, TL); AL(lm_vl, TL); AL(lm_sw, TL);
@@ -980,7 +735,7 @@ static gfbe_status upload_one(gfbe_ctx *c, int32_t B, const gfbe_window *const *
       b->slab_n = nH + ng + nE + ne + nx;
     }
     AL(dbg_imu, (size_t)B * MAX_IMU * 15 * 31); AL(dbg_wheel, (size_t)B * MAX_WHEEL * 6 * 23); AL(dbg_prior, (size_t)B * ND);
-    AL(rec, want_rec ? (size_t)tot_rec * REC : 1); AL(mV, (size_t)B * ND * ND);
+    AL(rec, p.cx.want_records ? (size_t)tot_rec * REC : 1); AL(mV, (size_t)B * ND * ND);
     AL(vis_contrib, B < DENSE_SPLIT_MIN_B ? (size_t)B * std::max(max_tiles, 1) * MAXOBS * 16 * LM_TILE : 1);
     d.solve_scratch_stride = d.solve_big ? (size_t)BIG_LD * BIG_LD : solve_chain_scratch_doubles();
     AL(solveY, d.solve_big ? 1 : (size_t)B * solve_chain_scratch_doubles());
@@ -988,228 +743,61 @@ static gfbe_status upload_one(gfbe_ctx *c, int32_t B, const gfbe_window *const *
     AL(gnss_J, (size_t)std::max(tot_gnss, 1) * 36); AL(gnss_r, (size_t)std::max(tot_gnss, 1) * 2);
     if (d.spec) { AL(gnss_J2, (size_t)std::max(tot_gnss, 1) * 36); AL(gnss_r2, (size_t)std::max(tot_gnss, 1) * 2); AL(gnss_cost2, (size_t)B * 2); }
     else { d.gnss_J2 = d.gnss_r2 = d.gnss_cost2 = nullptr; }
-    AL(gnss_cost, (size_t)B * 2); AL(gnss_marg, any_gnss ? (size_t)B * GN_MPART : 1);
-    AL(dl_fix, (size_t)B * DL_FIX); AL(dl_feat, feat_off[B]); AL(dl_J0, (size_t)j0_off[B]);
+    AL(gnss_cost, (size_t)B * 2); AL(gnss_marg, d.any_gnss ? (size_t)B * GN_MPART : 1);
+    AL(dl_fix, (size_t)B * DL_FIX); AL(dl_feat, p.feat_off[B]); AL(dl_J0, (size_t)p.j0_off[B]);
     if (!b->dry) { b->up_end = up_end; b->zero_end = zero_end; }
-#undef UP
 #undef AL
   }
   // download staging: [dl_fix | dl_feat | dl_J0] are contiguous at the end of the slab -> one device-to-host copy
-  b->dl_bytes = (size_t)((char *)(d.dl_J0 + j0_off[B]) - (char *)d.dl_fix);
-  b->feat_off = feat_off; b->j0_off = j0_off;
-  const double T2 = now();
-  // ---- pass 2 (parallel over windows): fill the pinned mirror of the upload region
-  std::memcpy(h_tile_start, tile_start.data(), sizeof(int) * tile_start.size());
-  std::memcpy(h_feat_off, feat_off.data(), sizeof(int) * (B + 1));
-  std::memcpy(h_j0_off, j0_off.data(), sizeof(long long) * (B + 1));
-  std::atomic<int> bad(-1);
-  std::vector<std::string> errs(B);
-  const auto t_fill0 = std::chrono::steady_clock::now();
-  host_parallel(c, B, [&](int w) {
-    const gfbe_window &win = *wins[w];
-    const WinScan &sc = scan[w];
-    WinDesc &ds = h_desc[w];
-    ds = desc_tmp[w];
-    auto fail = [&](const char *m) { errs[w] = "window " + std::to_string(w) + ": " + m; int e = -1; bad.compare_exchange_strong(e, w); };
-    std::memcpy(ds.sf_tile_begin, sc.sf_tile_begin, sizeof ds.sf_tile_begin);
-    std::memcpy(ds.pair_begin, sc.pair_begin, sizeof ds.pair_begin);
-    double bytes = sizeof(WinDesc) + sizeof(double) * NA;
-    if (!tabs) {
-      // landmark scalars: padding slots first (valid = 0, abi -1, lambda 1), then the landmarks
-      const int o = ds.lm_off;
-      for (int q = 0; q < sc.slots; q++) { h_lm_info[o + q] = 0; h_lm_abi[o + q] = -1; h_lam0[o + q] = 1.0; }
-      for (int r = 0; r < 6; r++) std::memset(h_lm_pts + r * TL + o, 0, sizeof(double) * sc.slots);
-      for (int l = 0; l < sc.L; l++) {
-        const int slot = o + sc.slot_rel[l];
-        const bool is_const = win.feature_const && win.feature_const[l];
-        h_lm_info[slot] = sc.lstart[l] | (sc.lm[l] << 8) | ((is_const ? 1 : 0) << 16) | (1 << 24);
-        h_lm_abi[slot] = l;
-        h_lam0[slot] = win.para_Feature[l];
-      }
-      const bool compact = d.obs_compact != 0;
-      double *fo = h_fobs + (size_t)ds.rec_off * (compact ? 2 : 5), *fv = compact ? h_fvel + (size_t)ds.vel_off * 3 : nullptr;
-      const double tdw = win.state.para_Td;
-      for (int k = 0; k < sc.K; k++) {
-        const int l = win.vis.feature_index[k], i = win.vis.imu_i[k], j = win.vis.imu_j[k];
-        const int rel = sc.slot_rel[l];
-        const int rec = sc.pair_begin[i * NF + j] + (rel - sc.sf_tile_begin[i] * LM_TILE);
-        if (compact) {
-          // p' = p - (td - td_obs) v: k_expand's fused multiply-add (a correctly rounded std::fma is the same number; an observation
-          // stamped with the window's td — the usual case — is not touched)
-          const double dtj = tdw - win.vis.td_j[k];
-          double *f = fo + (size_t)rec * 2;
-          f[0] = dtj == 0.0 ? win.vis.pts_j[3 * k] : std::fma(-dtj, win.vis.vel_j[2 * k], win.vis.pts_j[3 * k]);
-          f[1] = dtj == 0.0 ? win.vis.pts_j[3 * k + 1] : std::fma(-dtj, win.vis.vel_j[2 * k + 1], win.vis.pts_j[3 * k + 1]);
-          if (i == 0) { double *v = fv + (size_t)rec * 3; v[0] = win.vis.vel_j[2 * k]; v[1] = win.vis.vel_j[2 * k + 1]; v[2] = win.vis.td_j[k]; }
-        } else {
-          double *f = fo + (size_t)rec * 5;
-          f[0] = win.vis.pts_j[3 * k]; f[1] = win.vis.pts_j[3 * k + 1]; f[2] = win.vis.vel_j[2 * k]; f[3] = win.vis.vel_j[2 * k + 1]; f[4] = win.vis.td_j[k];
-        }
-        if (j == i + 1) {   // the landmark's first observation travels with its first factor
-          const size_t slot = (size_t)o + rel;
-          h_lm_pts[0 * TL + slot] = win.vis.pts_i[3 * k]; h_lm_pts[1 * TL + slot] = win.vis.pts_i[3 * k + 1]; h_lm_pts[2 * TL + slot] = win.vis.pts_i[3 * k + 2];
-          h_lm_pts[3 * TL + slot] = win.vis.vel_i[2 * k]; h_lm_pts[4 * TL + slot] = win.vis.vel_i[2 * k + 1]; h_lm_pts[5 * TL + slot] = win.vis.td_i[k];
-        }
-      }
-      b->slot_of[w].resize(sc.L);
-      for (int l = 0; l < sc.L; l++) b->slot_of[w][l] = o + sc.slot_rel[l];
-      bytes += (double)sc.slots * (4 + 4 + 8 + 48) + (compact ? 16.0 * sc.K + 24.0 * sc.pair_begin[NF] : 40.0 * sc.K);
-    }
-    // dense state
-    std::memcpy(h_x0 + (size_t)w * NA, &win.state, sizeof(double) * NA);
-    // inertial factors
-    for (int q = 0; q < NF; q++) ds.imu_of_frame[q] = ds.wheel_of_frame[q] = -1;
-    ds.n_imu = win.n_imu;
-    for (int k = 0; k < win.n_imu; k++) {
-      if (win.imu_frame[k] < 0 || win.imu_frame[k] >= win.frame_count) return fail("bad imu_frame");
-      h_imu[ds.imu_off + k] = win.imu[k]; ds.imu_frame[k] = win.imu_frame[k]; ds.imu_of_frame[win.imu_frame[k]] = k;
-    }
-    ds.n_wheel = win.n_wheel;
-    for (int k = 0; k < win.n_wheel; k++) {
-      if (win.wheel_frame[k] < 0 || win.wheel_frame[k] >= win.frame_count) return fail("bad wheel_frame");
-      h_wheel[ds.wheel_off + k] = win.wheel[k]; ds.wheel_frame[k] = win.wheel_frame[k]; ds.wheel_of_frame[win.wheel_frame[k]] = k;
-    }
-    bytes += sizeof(gfbe_imu_preint) * win.n_imu + sizeof(gfbe_wheel_preint) * win.n_wheel;
-    // LiDAR factors on one pose
-    ds.lio_n = win.lio.n > 0 ? win.lio.n : 0; ds.lio_frame = win.lio.frame;
-    ds.lio_sqrt_info = win.lio.sqrt_info; ds.lio_huber = win.lio.huber_delta;
-    if (ds.lio_n > 0) {
-      if (win.lio.frame < 0 || win.lio.frame > win.frame_count || !win.lio.pts || !win.lio.normals || !win.lio.offsets) return fail("bad lio block");
-      double *lo = h_lio + (size_t)ds.lio_off * 8;
-      for (int k = 0; k < ds.lio_n; k++) {
-        for (int q = 0; q < 3; q++) { lo[8 * k + q] = win.lio.pts[3 * k + q]; lo[8 * k + 3 + q] = win.lio.normals[3 * k + q]; }
-        lo[8 * k + 6] = win.lio.offsets[k];
-        lo[8 * k + 7] = win.lio.weights ? win.lio.weights[k] : 1.0;
-      }
-      bytes += 64.0 * ds.lio_n;
-    }
-    // prior
-    bool used[GFBE_BLK_COUNT];
-    for (int q = 0; q < GFBE_BLK_COUNT; q++) used[q] = false;
-    if (ds.lio_n > 0) used[ds.lio_frame] = true;
-    for (int q = 0; q < ND; q++) ds.prior_map[q] = -1;
-    std::memset(h_pr0 + (size_t)w * ND, 0, sizeof(double) * ND);
-    std::memset(h_px0 + (size_t)w * PRIOR_X0, 0, sizeof(double) * PRIOR_X0);
-    if (pj_row) std::memset(h_pJ0 + (size_t)w * pj_row, 0, sizeof(double) * pj_row);
-    if (win.prior && win.prior->valid && win.prior->n > 0) {
-      const gfbe_prior &pr = *win.prior;   // (validated in the serial pass)
-      ds.prior_n = pr.n; ds.prior_nblk = pr.n_blocks;
-      int xo = 0;
-      for (int q = 0; q < pr.n_blocks; q++) {
-        const int id = pr.block_id[q];
-        ds.prior_blk_id[q] = id; ds.prior_blk_size[q] = pr.block_size[q]; ds.prior_blk_idx[q] = pr.block_idx[q];
-        ds.prior_x0_off[q] = xo; xo += pr.block_size[q];
-        used[id] = true;
-        for (int k = 0; k < blk_lsize(id); k++) ds.prior_map[blk_tan(id) + k] = pr.block_idx[q] + k;
-      }
-      std::memcpy(h_px0 + (size_t)w * PRIOR_X0, pr.x0, sizeof(double) * xo);
-      std::memcpy(h_pJ0 + (size_t)w * pj_row, pr.J0, sizeof(double) * pr.n * pr.n);
-      std::memcpy(h_pr0 + (size_t)w * ND, pr.r0, sizeof(double) * pr.n);
-      bytes += 8.0 * ((double)pr.n * pr.n + pr.n + xo);
-    }
-    // reduced program: blocks touched by a residual and not constant (Ceres drops the rest)
-    for (int k = 0; k < win.n_imu; k++) { const int i = win.imu_frame[k]; used[i] = used[GFBE_BLK_SB0 + i] = used[i + 1] = used[GFBE_BLK_SB0 + i + 1] = true; }
-    for (int k = 0; k < win.n_wheel; k++) {
-      const int i = win.wheel_frame[k];
-      used[i] = used[i + 1] = used[GFBE_BLK_EX_WHEEL] = used[GFBE_BLK_SX] = used[GFBE_BLK_SY] = used[GFBE_BLK_SW] = used[GFBE_BLK_TD_WHEEL] = true;
-    }
-    for (int p = 0; p < NPAIR; p++) if (sc.pair_begin[p + 1] > sc.pair_begin[p]) { used[p / NF] = used[p % NF] = used[GFBE_BLK_EX_CAM] = used[GFBE_BLK_TD] = true; }
-    // optional in-window factors: PlaneFactor on every pose i < frame_count (estimator.cpp:3214-3220), PoseAnchorFactor on Pose[0]
-    ds.n_plane = win.use_plane ? std::min(win.frame_count, (int)MAX_PLANE) : 0;
-    ds.use_anchor = win.use_anchor ? 1 : 0;
-    for (int q = 0; q < 3; q++) ds.plane_noise_inv[q] = win.plane_noise_inv[q];
-    for (int q = 0; q < 7; q++) ds.anchor_pose[q] = win.anchor_pose[q];
-    ds.anchor_sqrt_info = win.anchor_sqrt_info;
-    for (int i = 0; i < ds.n_plane; i++) used[i] = true;
-    if (ds.n_plane > 0) used[GFBE_BLK_EX_WHEEL] = used[GFBE_BLK_PLANE_R] = used[GFBE_BLK_PLANE_Z] = true;
-    if (ds.use_anchor) used[0] = true;
-    // GNSS (estimator.cpp:2965-3002, 3239-3291): the observations sorted by frame (stable: the reference's insertion order is
-    // frame-major already), the lowspeed gate from the window's velocities, the blocks the factors touch
-    if (ds.gnss_ready) {
-      int cnt[NF + 1];
-      for (int q = 0; q <= NF; q++) cnt[q] = 0;
-      for (int k = 0; k < win.n_gnss; k++) cnt[win.gnss_obs[k].frame + 1]++;
-      for (int q = 0; q < NF; q++) cnt[q + 1] += cnt[q];
-      for (int q = 0; q <= NF; q++) ds.gnss_frame_begin[q] = cnt[q];
-      for (int k = 0; k < win.n_gnss; k++) h_gnss[ds.gnss_off + cnt[win.gnss_obs[k].frame]++] = win.gnss_obs[k];
-      ds.gnss_has_iono = win.gnss_iono ? 1 : 0;
-      for (int q = 0; q < 8; q++) ds.gnss_iono[q] = win.gnss_iono ? win.gnss_iono[q] : 0.0;
-      for (int q = 0; q < GFBE_WINDOW_SIZE; q++) ds.gnss_frame_dt[q] = win.gnss_frame_dt[q];
-      ds.gnss_ddt_weight = win.gnss_ddt_weight;
-      double ax = 0.0, ay = 0.0;
-      for (int i = 0; i <= GFBE_WINDOW_SIZE; i++) { ax += std::fabs(win.state.para_SpeedBias[i][0]); ay += std::fabs(win.state.para_SpeedBias[i][1]); }
-      ax /= GFBE_WINDOW_SIZE + 1; ay /= GFBE_WINDOW_SIZE + 1;
-      ds.gnss_factors = !(std::sqrt(ax * ax + ay * ay) < 0.3);
-      if (ds.gnss_factors) {
-        for (int k = 0; k < win.n_gnss; k++) {
-          const gfbe_gnss_obs &o = win.gnss_obs[k];
-          used[o.lower_idx] = used[GFBE_BLK_SB0 + o.lower_idx] = used[o.lower_idx + 1] = used[GFBE_BLK_SB0 + o.lower_idx + 1] = true;
-          used[GFBE_BLK_YAW_ENU] = used[GFBE_BLK_ANC_ECEF] = true;
-        }
-        for (int q = GFBE_BLK_RCV_DT0; q < GFBE_BLK_COUNT; q++) used[q] = true;     // DtDdtFactor / DdtSmoothFactor chains
-      }
-      bytes += sizeof(gfbe_gnss_obs) * win.n_gnss;
-    }
-    for (int q = 0; q < GFBE_BLK_COUNT; q++) {
-      bool cst;
-      if (q < GFBE_BLK_SB0) cst = win.pose_const[q] || q > win.frame_count;
-      else if (q < GFBE_BLK_EX_CAM) cst = win.sb_const[q - GFBE_BLK_SB0] || (q - GFBE_BLK_SB0) > win.frame_count;
-      else if (q == GFBE_BLK_EX_CAM) cst = win.ex_cam_const;
-      else if (q == GFBE_BLK_EX_WHEEL) cst = win.ex_wheel_const;
-      else if (q == GFBE_BLK_TD) cst = win.td_const;
-      else if (q == GFBE_BLK_TD_WHEEL) cst = win.td_wheel_const;
-      else if (q == GFBE_BLK_PLANE_R || q == GFBE_BLK_PLANE_Z) cst = win.plane_const;
-      else if (q == GFBE_BLK_YAW_ENU) cst = win.gnss_ready != 0;         // estimator.cpp:2991
-      else if (q == GFBE_BLK_ANC_ECEF || q >= GFBE_BLK_RCV_DT0) cst = false;
-      else cst = win.ix_wheel_const;
-      ds.blk_free[q] = used[q] && !cst;
-      if (ds.blk_free[q]) for (int k = 0; k < blk_lsize(q); k++) ds.act[blk_tan(q) + k] = 1;
-    }
-    ds.act[T_PLR + 3] = 0;   // the plane quaternion's 4th slot only exists in the prior (three tangent dims in the solve)
-    std::memcpy(ds.ex_cam_mask, win.ex_cam_mask, 6);
-    std::memcpy(ds.ex_wheel_mask, win.ex_wheel_mask, 6);
-    b->up_win_bytes[w] = bytes;
-  }, true);
-  c->host_ms[0] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_fill0).count();
-  if (bad.load() >= 0) { c->err = errs[bad.load()]; return GFBE_BAD_INPUT; }
-  // k_solve_chain eliminates the speed-bias blocks as a chain: IMUFactor couples SpeedBias[k] with its neighbours only, and the
-  // priors the reference builds keep SpeedBias[0] alone (estimator.cpp:3400-3433, 3600-3632). A prior with any other speed-bias
-  // block breaks that structure: such a batch takes the monolithic factorisation (gfbe_options.solve_kernel = 1 forces it).
-  {
-    int ntile = 1, mono = c->opt.solve_kernel == 1;
-    for (int w = 0; w < B; w++) {
-      const WinDesc &ds = h_desc[w];
-      ntile = std::max(ntile, solve_chain_tiles(ds.act));
-      for (int q = 0; q < ds.prior_nblk; q++) if (ds.prior_blk_id[q] > GFBE_BLK_SB0 && ds.prior_blk_id[q] < GFBE_BLK_EX_CAM) mono = 1;
-    }
-    d.solve_ntile = ntile; d.solve_mono = mono;
-    {   // (round 6) a batch with GNSS dims: the chain kernel with nine tile columns when every window's dense part fits and the priors keep the chain's structure
-      int n_dense_max = 0;
-      for (int w = 0; w < B; w++) {
-        int nd = 0;
-        for (int a = 0; a < ND; a++) if (h_desc[w].act[a] && !(a >= T_SB(0) && a < T_SB(0) + 9 * NF)) nd++;
-        n_dense_max = std::max(n_dense_max, nd);
-      }
-      d.solve_wide = d.solve_big && !mono && c->opt.solve_kernel != 4 && solve_chain_wide_fits(n_dense_max);
-    }
-    // the chain kernel of the batch: the twisted one (both ends at once, eight waves, one workgroup per CU) where a window's latency
-    // counts — below DENSE_SPLIT_MIN_B windows, like the rest of the small-batch kernel set —, the classic one for throughput
-    // (a dense part of six tile columns — a free camera extrinsic — does not fit its LDS layout: the classic kernel whatever was asked)
-    d.solve_tw = (c->opt.solve_kernel == 3 || (c->opt.solve_kernel != 2 && B < DENSE_SPLIT_MIN_B)) && solve_chain_tw_fits(ntile);
-    // the assembly table of the context: the compact one unless a prior couples a speed-bias block other than SpeedBias[0] (entries
-    // outside the set it lists) or the batch carries GNSS dims
-    bool prior_sb = false;
-    for (int w = 0; w < B && !prior_sb; w++)
-      for (int q = 0; q < h_desc[w].prior_nblk; q++) if (h_desc[w].prior_blk_id[q] > GFBE_BLK_SB0 && h_desc[w].prior_blk_id[q] < GFBE_BLK_EX_CAM) prior_sb = true;
-    // (GFBE_ASM_FULL, diagnostics build only: the full table for every batch — tests/test_gpu_solve_kernels.py compares the two entry by entry)
-    const bool compact = !prior_sb && d.nu == NC && c->asm_compact_n > 0 && !diag_getenv("GFBE_ASM_FULL");
-    d.asm_tab = compact ? c->asm_compact : c->asm_full;
-    d.asm_legacy = diag_getenv("GFBE_ASM_LEGACY") ? 1 : 0;      // (diagnostics build only: diag_getenv is nullptr in the product)
-    d.asm_n = compact ? c->asm_compact_n : d.nu * (d.nu + 1) / 2;
+  b->dl_bytes = (size_t)((char *)(d.dl_J0 + p.j0_off[B]) - (char *)d.dl_fix);
+  return GFBE_OK;
+}
+
+// Phase 6: the solve kernels and the assembly table of the batch, from the packed descriptors.
+// k_solve_chain eliminates the speed-bias blocks as a chain: IMUFactor couples SpeedBias[k] with its neighbours only, and the
+// priors the reference builds keep SpeedBias[0] alone (estimator.cpp:3400-3433, 3600-3632). A prior with any other speed-bias
+// block breaks that structure: such a batch takes the monolithic factorisation (gfbe_options.solve_kernel = 1 forces it).
+void choose_solve_kernels(const gfbe_ctx *c, BatchDev &d, const WinDesc *h_desc) {
+  const int B = d.B;
+  int ntile = 1, mono = c->opt.solve_kernel == 1;
+  for (int w = 0; w < B; w++) {
+    const WinDesc &ds = h_desc[w];
+    ntile = std::max(ntile, solve_chain_tiles(ds.act));
+    for (int q = 0; q < ds.prior_nblk; q++) if (ds.prior_blk_id[q] > GFBE_BLK_SB0 && ds.prior_blk_id[q] < GFBE_BLK_EX_CAM) mono = 1;
   }
-  const double T3 = now();
-  // ---- enqueue: clear what must start as zero, ONE host-to-device copy, then the preparation kernels
-  // (a small batch: all of it in one kernel that reads the pinned staging buffer across PCIe itself — k_ingest_small)
+  d.solve_ntile = ntile; d.solve_mono = mono;
+  {   // (round 6) a batch with GNSS dims: the chain kernel with nine tile columns when every window's dense part fits and the priors keep the chain's structure
+    int n_dense_max = 0;
+    for (int w = 0; w < B; w++) {
+      int nd = 0;
+      for (int a = 0; a < ND; a++) if (h_desc[w].act[a] && !(a >= T_SB(0) && a < T_SB(0) + 9 * NF)) nd++;
+      n_dense_max = std::max(n_dense_max, nd);
+    }
+    d.solve_wide = d.solve_big && !mono && c->opt.solve_kernel != 4 && solve_chain_wide_fits(n_dense_max);
+  }
+  // the chain kernel of the batch: the twisted one (both ends at once, eight waves, one workgroup per CU) where a window's latency
+  // counts — below DENSE_SPLIT_MIN_B windows, like the rest of the small-batch kernel set —, the classic one for throughput
+  // (a dense part of six tile columns — a free camera extrinsic — does not fit its LDS layout: the classic kernel whatever was asked)
+  d.solve_tw = (c->opt.solve_kernel == 3 || (c->opt.solve_kernel != 2 && B < DENSE_SPLIT_MIN_B)) && solve_chain_tw_fits(ntile);
+  // the assembly table of the context: the compact one unless a prior couples a speed-bias block other than SpeedBias[0] (entries
+  // outside the set it lists) or the batch carries GNSS dims
+  bool prior_sb = false;
+  for (int w = 0; w < B && !prior_sb; w++)
+    for (int q = 0; q < h_desc[w].prior_nblk; q++) if (h_desc[w].prior_blk_id[q] > GFBE_BLK_SB0 && h_desc[w].prior_blk_id[q] < GFBE_BLK_EX_CAM) prior_sb = true;
+  // (GFBE_ASM_FULL, diagnostics build only: the full table for every batch — tests/test_gpu_solve_kernels.py compares the two entry by entry)
+  const bool compact = !prior_sb && d.nu == NC && c->asm_compact_n > 0 && !diag_getenv("GFBE_ASM_FULL");
+  d.asm_tab = compact ? c->asm_compact : c->asm_full;
+  d.asm_legacy = diag_getenv("GFBE_ASM_LEGACY") ? 1 : 0;      // (diagnostics build only: diag_getenv is nullptr in the product)
+  d.asm_n = compact ? c->asm_compact_n : d.nu * (d.nu + 1) / 2;
+}
+
+// Phase 7: clear what must start as zero, ONE host-to-device copy, then the preparation kernels
+// (a small batch: all of it in one kernel that reads the pinned staging buffer across PCIe itself — k_ingest_small)
+gfbe_status enqueue_upload(gfbe_ctx *c, gfbe_batch *b, const UploadPlan &p, const UploadMirror &dev, const UploadMirror &host, const char *poison_env,
+                           gfbe_ftab *tabs, int tab0, hipStream_t us) {
+  BatchDev &d = b->d;
+  const int B = d.B;
+  const size_t pj_row = p.pj_row();
   const bool ingest = B < DENSE_SPLIT_MIN_B && (b->up_end % 16) == 0 && ((b->zero_end - b->up_end) % 16) == 0;
   // (test hook, tests/test_gpu_uncleared.py: the part of the slab that is NOT cleared filled with NaN bit patterns — a kernel that
   //  uses what nobody wrote poisons its results instead of finding the previous batch's numbers there)
@@ -1224,24 +812,24 @@ static gfbe_status upload_one(gfbe_ctx *c, int32_t B, const gfbe_window *const *
     static_assert((sizeof(double) * ND * ND) % 16 == 0, "k_ingest_small clears H in 16-byte units");
     launch_ingest_small(b->up_h, b->slab, b->up_end, b->slab + b->up_end, b->zero_end > b->up_end ? b->zero_end - b->up_end : 0,
                         d.H, clearH ? sizeof(double) * (size_t)B * ND * ND : 0,
-                        pj_row > 0 ? (const double *)h_pJ0 : nullptr, d.prior_J0, pj_row > 0 ? B : 0, pj_row,
+                        pj_row > 0 ? (const double *)host.pJ0c : nullptr, d.prior_J0, pj_row > 0 ? B : 0, pj_row,
                         (size_t)ND * ND, us);
   } else {
-  if (b->zero_end > b->up_end) HIPCHK(c, hipMemsetAsync(b->slab + b->up_end, 0, b->zero_end - b->up_end, us));
-  // the compact assembly table writes only the entries of H some factor can reach: the others are read (as the zeros they are) by
-  // the solve kernels and must start as zeros — H is not part of the cleared region (the full table writes every entry)
-  if (d.asm_tab == c->asm_compact) HIPCHK(c, hipMemsetAsync(d.H, 0, sizeof(double) * (size_t)B * ND * ND, us));
-  HIPCHK(c, hipMemcpyAsync(b->slab, b->up_h, b->up_end, hipMemcpyHostToDevice, us));
-  if (pj_row > 0)
-    HIPCHK(c, hipMemcpy2DAsync(d.prior_J0, sizeof(double) * ND * ND, d_pJ0c, sizeof(double) * pj_row, sizeof(double) * pj_row, B, hipMemcpyDeviceToDevice, us));
+    if (b->zero_end > b->up_end) HIPCHK(c, hipMemsetAsync(b->slab + b->up_end, 0, b->zero_end - b->up_end, us));
+    // the compact assembly table writes only the entries of H some factor can reach: the others are read (as the zeros they are) by
+    // the solve kernels and must start as zeros — H is not part of the cleared region (the full table writes every entry)
+    if (d.asm_tab == c->asm_compact) HIPCHK(c, hipMemsetAsync(d.H, 0, sizeof(double) * (size_t)B * ND * ND, us));
+    HIPCHK(c, hipMemcpyAsync(b->slab, b->up_h, b->up_end, hipMemcpyHostToDevice, us));
+    if (pj_row > 0)
+      HIPCHK(c, hipMemcpy2DAsync(d.prior_J0, sizeof(double) * ND * ND, dev.pJ0c, sizeof(double) * pj_row, sizeof(double) * pj_row, B, hipMemcpyDeviceToDevice, us));
   }
   if (tabs) {   // landmark arrays straight from the device-resident tables (layout table and slot map live in the tables' own scratch)
     int *dlay = tabs->d.layout + (size_t)tab0 * FT_LAY_STRIDE, *dslot = tabs->d.ids_scratch + (size_t)tab0 * tabs->d.F;
     // (the layout table travels from a pinned buffer the batch keeps: nobody waits for the copy)
-    b->lay_h = pin_acquire(c, sizeof(int) * tlayout.size(), &b->lay_cap);
+    b->lay_h = pin_acquire(c, sizeof(int) * p.tlayout.size(), &b->lay_cap);
     if (!b->lay_h) { c->err = "hipHostMalloc(layout staging) failed"; return GFBE_DEVICE_ERROR; }
-    std::memcpy(b->lay_h, tlayout.data(), sizeof(int) * tlayout.size());
-    HIPCHK(c, hipMemcpyAsync(dlay, b->lay_h, sizeof(int) * tlayout.size(), hipMemcpyHostToDevice, us));
+    std::memcpy(b->lay_h, p.tlayout.data(), sizeof(int) * p.tlayout.size());
+    HIPCHK(c, hipMemcpyAsync(dlay, b->lay_h, sizeof(int) * p.tlayout.size(), hipMemcpyHostToDevice, us));
     launch_ftab_pack(tabs->d, tabs->cur, tab0, B, d, dlay, dslot, us);
     if (tabs->ev_read && us != c->stream) { HIPCHK(c, hipEventRecord(tabs->ev_read, us)); tabs->read_pending = true; }
     // (and the other way round: a small upload reads the shared scratch on the MAIN stream; a large one that follows it waits for ev_ops
@@ -1254,18 +842,65 @@ static gfbe_status upload_one(gfbe_ctx *c, int32_t B, const gfbe_window *const *
   else launch_prep(d, us);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(b->ev_up, us));
+  return GFBE_OK;
+}
+}  // namespace
+
+// tabs != nullptr: the visual factors of window w come from table tab0 + w of the device-resident feature tables
+// (wins[w]->vis, n_feature, para_Feature, feature_const are ignored); the landmark arrays are then filled on the device.
+// The call returns when the windows are packed into pinned memory and the copy + preparation kernels are enqueued on the
+// context's copy stream: the caller's buffers are free again, gfbe_batch_solve waits for the batch's `ev_up`.
+static gfbe_status upload_one(gfbe_ctx *c, int32_t B, const gfbe_window *const *wins, gfbe_batch **out, gfbe_ftab *tabs = nullptr,
+                              int tab0 = 0) {
+  if (!c || !wins || !out || B <= 0) return GFBE_BAD_INPUT;
+  if (c->device < 0 || !c->stream) { c->err = "HIP device context required (no CPU fallback)"; return GFBE_NO_DEVICE; }
+  const bool dbg_t = diag_getenv("GFBE_DEBUG_UPLOAD") != nullptr && diag_getenv("GFBE_DEBUG_UPLOAD")[0] != 0;   // phase times of the upload on stderr (tools/diag_e2e_latency.py)
+  const char *poison_env = diag_getenv("GFBE_POISON_UNCLEARED");   // (test hook of the diagnostics build, see enqueue_upload; read per upload)
+  HIPCHK(c, hipSetDevice(c->device));
+  const double T0 = now_ms();
+  hipStream_t us = nullptr;
+  gfbe_status st = upload_prologue(c, B, tabs, out, &us);
+  if (st != GFBE_OK) return st;
+  gfbe_batch *b = *out;
+  std::vector<int> tcounts;     // table source: per window [L, K, bins]
+  if (tabs && (st = fetch_table_counts(c, tabs, tab0, B, us, tcounts)) != GFBE_OK) return st;
+  // the packing passes (scan and fill) run on the context's host threads and add themselves up in gfbe_host_times
+  auto for_each_window = [c](int n, const std::function<void(int)> &fn) {
+    const auto t0 = std::chrono::steady_clock::now();
+    host_parallel(c, n, fn, true);
+    c->host_ms[0] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  };
+  UploadPlan plan;
+  const UploadContext cx = {c->allreduce != nullptr, c->want_records, c->rank, c->world};
+  if ((st = plan_upload(c->opt, cx, B, wins, tabs ? tcounts.data() : nullptr, for_each_window, plan, c->err)) != GFBE_OK) return st;
+  plan_to_batch(plan, b->d);
+  b->algo_bytes_lin = plan.algo_bytes;
+  b->L.resize(B);
+  for (int w = 0; w < B; w++) b->L[w] = plan.scan[w].L;
+  b->anchor_only = plan.anchor_only; b->feat_off = plan.feat_off; b->j0_off = plan.j0_off;
+  b->slot_of.resize(B);
+  b->up_win_bytes.assign(B, 0.0);
+  const double T1 = now_ms();
+  UploadMirror dev, host;
+  if ((st = carve_batch(c, b, plan, poison_env, &dev, &host)) != GFBE_OK) return st;
+  const double T2 = now_ms();
+  pack_batch_tables(plan, host);
+  for_each_window(B, [&](int w) { b->up_win_bytes[w] = pack_window(plan, w, *wins[w], host, b->slot_of[w]); });
+  choose_solve_kernels(c, b->d, host.desc);
+  const double T3 = now_ms();
+  if ((st = enqueue_upload(c, b, plan, dev, host, poison_env, tabs, tab0, us)) != GFBE_OK) return st;
   if (dbg_t) {
     (void)hipStreamSynchronize(us);
     fprintf(stderr, "upload: scan %.3f ms, layout + staging %.3f ms, fill %.3f ms, copy + prep %.3f ms (slab %.1f MB, upload %.2f MB, cleared %.1f MB)\n",
-            T1 - T0, T2 - T1, T3 - T2, now() - T3, b->slab_bytes / 1048576.0, b->up_end / 1048576.0, (b->zero_end - b->up_end) / 1048576.0);
+            T1 - T0, T2 - T1, T3 - T2, now_ms() - T3, b->slab_bytes / 1048576.0, b->up_end / 1048576.0, (b->zero_end - b->up_end) / 1048576.0);
   }
   return GFBE_OK;
 }
 
 extern "C" void gfbe_batch_free(gfbe_ctx *c, gfbe_batch *b);
 
-// Batches of >= BATCH_SPLIT_MIN_B windows become `split_batch` parts (default two halves) solved side by side, each on
-// its own pair of streams: a chain a -> a->second -> ...; part k + 1 runs on part k's `lane2`.
+// Batches of >= BATCH_SPLIT_MIN_B windows become `split_batch` parts (default: four parts from 2048 windows, one below) solved side
+// by side, each on its own pair of streams: a chain a -> a->second -> ...; part k + 1 runs on part k's `lane2`.
 static gfbe_status make_lane(gfbe_ctx *c, gfbe_batch *a) {
   if (!c->lane_pool.empty()) {
     const gfbe_ctx::LaneSet l = c->lane_pool.back();

@@ -398,7 +398,7 @@ def trim_to_frame_count(snap, fc):
 
 
 def layout_counts(snap):
-    """{(start frame, number of factors): landmarks} of a window as scan_window (gfbe_host.cpp) bins them: a landmark without factors
+    """{(start frame, number of factors): landmarks} of a window as scan_window (gfbe_upload.h) bins them: a landmark without factors
     counts for start frame 0 with 0 factors."""
     L = len(snap["para_feature"])
     m = np.bincount(np.asarray(snap["vis_feature_index"], int), minlength=L)

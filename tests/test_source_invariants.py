@@ -40,8 +40,11 @@ def test_lin_view_swaps_every_second_set_member():
 
 def test_host_points_every_second_set_member_into_the_slab():
     host = _read("gfbe_host.cpp")
+    carve = host[host.index("gfbe_status carve_batch("):]
+    carve = carve[:carve.index("#undef AL")]
     for name in _second_set_members():
         assert re.search(r"\bd\.%s\s*=" % name, host), "gfbe_host.cpp never sets BatchDev::" + name
+        assert re.search(r"\bAL\(%s\s*," % name, carve), "carve_batch (gfbe_host.cpp) never carves BatchDev::" + name + " from the slab"
 
 
 def test_options_default_and_binding_agree_on_the_speculative_pass():

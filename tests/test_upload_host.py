@@ -1,0 +1,522 @@
+"""The host half of a batch upload (csrc/gfbe_upload.h: plan_upload, upload_region, pack_window) without a GPU: compiled for the host by
+tests/upload_host_shim.cpp, fed windows through the ctypes structs of abi.py, and checked — exact integers, bit-equal doubles — against
+the windows themselves and against independent numpy restatements of the layout rule, the free-block table and prior_out_bound.
+tests/upload_host_main.cpp runs the same code under the address and undefined-behaviour sanitizers as a stand-alone program."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from _gfbe_import import gf
+
+abi, synth = gf.abi, gf.synth
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "ground-fusion2_amd", "csrc")
+BUILD = os.path.join(ROOT, "tests", "_build")
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+DEPS = [os.path.join(CSRC, "gfbe_upload.h"), os.path.join(CSRC, "gfbe_device.h"), os.path.join(ROOT, "include", "gfbe.h")]
+NF, MAXOBS, NPAIR, ND, NA, PRIOR_X0 = 11, 10, 121, 246, 259, abi.PRIOR_X0_CAP
+INFO = ("tot_lm", "tot_rec", "tot_n0", "n_imu_tot", "n_wheel_tot", "tot_lio", "tot_gnss", "gnss_max", "pn_max", "marg_nmax", "max_tiles", "max_sf_tiles",
+        "vis_full", "obs_compact", "any_plane", "prior_n_max", "any_gnss", "nu", "solve_big", "spec", "linschur", "schur_groups", "up_bytes", "n_tile_start")
+DESC = ("lm_off", "rec_off", "vel_off", "tile_off", "imu_off", "wheel_off", "lio_off", "lio_n", "gnss_off", "n_gnss", "gnss_factors", "prior_n", "n_plane",
+        "use_anchor")
+PI = C.POINTER(C.c_int)
+
+
+def _build(src, out, extra):
+    if not os.path.exists(HIPCC):
+        pytest.fail("hipcc not available: the upload's host half cannot be built")
+    deps = [src] + DEPS
+    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+        os.makedirs(BUILD, exist_ok=True)
+        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O2", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(ROOT, "include")] + extra + ["-o", out, src],
+                       check=True)
+    return out
+
+
+@pytest.fixture(scope="module")
+def shim():
+    lib = C.CDLL(_build(os.path.join(ROOT, "tests", "upload_host_shim.cpp"), os.path.join(BUILD, "libupload_host_shim.so"), ["-fPIC", "-shared"]))
+    lib.uh_pack.restype = C.c_void_p
+    lib.uh_array.restype = C.c_void_p
+    lib.uh_array.argtypes = [C.c_void_p, C.c_char_p]
+    lib.uh_free.argtypes = [C.c_void_p]
+    assert lib.uh_sizes(0) == 88 and lib.uh_sizes(2) == 64 and lib.uh_sizes(3) == C.sizeof(abi.GnssObs)
+    return lib
+
+
+# ---- windows --------------------------------------------------------------------------------------------------------------------
+_SCN = synth.Scenario(seed=11, n_landmarks=40, use_wheel=True)
+_BASE = _SCN.window(0)
+
+
+def window(tracks, seed=0, frame_count=10, td=0.0, **over):
+    """A window of the synthetic run whose landmarks are `tracks` = [(start frame, factors)], factors landmark-major with every second
+    observation stamped with another td than the window's."""
+    rng = np.random.default_rng(seed)
+    snap = dict(_BASE)
+    idx, ii, jj = [], [], []
+    for l, (s, m) in enumerate(tracks):
+        for k in range(1, m + 1):
+            idx.append(l); ii.append(s); jj.append(s + k)
+    K = len(idx)
+    pts_i = rng.normal(0, 0.3, (len(tracks), 3))
+    snap.update(vis_feature_index=np.array(idx, np.int32), vis_imu_i=np.array(ii, np.int32), vis_imu_j=np.array(jj, np.int32),
+                vis_pts_i=pts_i[idx] if K else np.zeros((0, 3)), vis_pts_j=rng.normal(0, 0.3, (K, 3)), vis_vel_i=rng.normal(0, 0.1, (K, 2)),
+                vis_vel_j=rng.normal(0, 0.1, (K, 2)), vis_td_i=np.full(K, td), vis_td_j=np.where(np.arange(K) % 2 == 0, td, td + 0.003),
+                para_feature=rng.uniform(0.1, 1.0, len(tracks)), feature_const=(np.arange(len(tracks)) % 5 == 0).astype(np.uint8))
+    snap["td"] = td
+    snap["frame_count"] = frame_count
+    n = min(frame_count, 10)
+    snap["imu"], snap["imu_frame"] = _BASE["imu"][:n], np.arange(n, dtype=np.int32)
+    snap["wheel"], snap["wheel_frame"] = _BASE["wheel"][:n], np.arange(n, dtype=np.int32)
+    snap.update(over)
+    return snap
+
+
+def prior(blocks, seed=0):
+    rng = np.random.default_rng(seed)
+    sizes = [abi.block_global_size(b) for b in blocks]
+    loc = [abi.block_local_size(b) for b in blocks]
+    n = sum(loc)
+    return dict(valid=1, n=n, block_id=blocks, block_size=sizes, block_idx=np.concatenate([[0], np.cumsum(loc)[:-1]]).astype(int), x0=rng.normal(0, 1, sum(sizes)),
+                J0=rng.normal(0, 1, (n, n)), r0=rng.normal(0, 1, n))
+
+
+def gnss(frames, seed=0):
+    rng = np.random.default_rng(seed)
+    obs = [dict(sv_pos=rng.normal(0, 2e7, 3), sv_vel=rng.normal(0, 3e3, 3), svdt=1e-5 * k, svddt=0.0, tgd=0.0, pr_uura=1.0 + k, dp_uura=2.0, psr=2.2e7 + k,
+                dopp=100.0 + k, wavelength=0.19, ratio=0.5, doy=100.0, tow=1000.0 + k, frame=f, lower_idx=max(f - 1, 0), sys_idx=k % 4)
+           for k, f in enumerate(frames)]
+    return dict(obs=obs, iono=np.arange(8.0), frame_dt=np.full(10, 0.1), ddt_weight=50.0)
+
+
+def lio(n, seed=0, frame=10):
+    rng = np.random.default_rng(seed)
+    return dict(frame=frame, pts=rng.normal(0, 3, (n, 3)), normals=rng.normal(0, 1, (n, 3)), offsets=rng.normal(0, 1, n), weights=None, sqrt_info=20.0, huber_delta=0.5)
+
+
+MIX = [(s, m) for s in range(8) for m in range(3, 11 - s) for _ in range(3)]
+CASES = {
+    "no_landmarks": window([]),
+    "one_landmark": window([(0, 3)]),
+    "tile_edge_64": window([(2, 3)] * 64, seed=1),
+    "tile_edge_65": window([(2, 3)] * 65 + [(0, 4)] * 3, seed=2),
+    "ten_and_zero_factors": window([(0, 10), (0, 0), (3, 1), (0, 10), (1, 9)], seed=3),
+    "short_window": window([(s, m) for s in range(4) for m in range(1, 7 - s)], seed=4, frame_count=6),
+    "no_prior": window(MIX, seed=5),
+    "prior_small": window(MIX[:50], seed=6, prior=prior([abi.BLK_SB0, 1, 2], 1)),
+    "prior_large": window(MIX[:70], seed=7, prior=prior([abi.BLK_SB0] + list(range(1, 11)) + [abi.BLK_EX_WHEEL, abi.BLK_EX_CAM, abi.BLK_TD], 2)),
+    "prior_other_speed_bias": window(MIX[:30], seed=8, prior=prior([abi.BLK_SB0, abi.BLK_SB0 + 2, 1, 3], 3)),
+    "gnss_unordered": window(MIX[:40], seed=9, gnss=gnss([3, 0, 10, 3, 1, 0, 7, 10, 2, 3]), gnss_state=dict(
+        rcv_dt=np.zeros((11, 4)), rcv_ddt=np.zeros(11), yaw_enu_local=0.1, anc_ecef=np.array([1.0, 2.0, 3.0]))),
+    "td_free": window(MIX[:60], seed=10, td=0.002, td_const=0),
+    "lio_unweighted": window(MIX[:20], seed=11, lio=lio(37)),
+    "plane_anchor": window(MIX[:20], seed=12, plane=dict(noise_inv=[10.0, 20.0, 30.0], const=0), anchor=dict(pose=np.arange(7.0), sqrt_info=120.0)),
+}
+BATCHES = [[k] for k in CASES] + [[k for k in CASES if k != "td_free"], list(CASES)]
+
+
+class Packed:
+    def __init__(self, lib, snaps, tcounts=None, allreduce=0, want_records=0, opt=None):
+        self.lib, self.snaps = lib, snaps
+        self.holders = [abi.WindowHolder(s) for s in snaps]
+        B = len(snaps)
+        arr = (C.POINTER(abi.Window) * B)(*[C.pointer(h.c) for h in self.holders])
+        if opt is None:
+            opt = abi.Options()
+            lib.uh_default_options(C.byref(opt))
+        st, err = C.c_int(-1), C.create_string_buffer(512)
+        tc = None if tcounts is None else np.ascontiguousarray(tcounts, np.int32).ctypes.data_as(PI)
+        self.h = C.c_void_p(lib.uh_pack(C.byref(opt), allreduce, want_records, B, arr, tc, C.byref(st), err, 512))
+        self.status, self.err = st.value, err.value.decode()
+        if self.h:
+            v = (C.c_longlong * len(INFO))()
+            lib.uh_info(self.h, v)
+            self.info = dict(zip(INFO, v))
+
+    def array(self, name, dtype, n):
+        p = self.lib.uh_array(self.h, name.encode())
+        assert p, name
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), (n,))
+
+    def scan(self, w):
+        head, sf, pb = (C.c_int * 4)(), (C.c_int * 12)(), (C.c_int * 122)()
+        L = self.holders[w].c.n_feature
+        rel = (C.c_int * max(L, 1))()
+        self.lib.uh_scan(self.h, w, head, sf, pb, rel)
+        return dict(L=head[0], K=head[1], slots=head[2], n_tiles=head[3], sf_tile_begin=np.array(sf), pair_begin=np.array(pb), slot_rel=np.array(rel)[:L])
+
+    def desc(self, w):
+        head, act, free, gfb, pm = (C.c_int * len(DESC))(), (C.c_ubyte * ND)(), (C.c_ubyte * 88)(), (C.c_int * 12)(), (C.c_int * ND)()
+        self.lib.uh_desc(self.h, w, head, act, free, gfb, pm)
+        d = dict(zip(DESC, head))
+        d.update(act=np.array(act), blk_free=np.array(free), gnss_frame_begin=np.array(gfb), prior_map=np.array(pm))
+        return d
+
+    def close(self):
+        self.lib.uh_free(self.h)
+
+
+@pytest.fixture(scope="module", params=range(len(BATCHES)), ids=["+".join(b) if len(b) == 1 else "mixed%d" % len(b) for b in BATCHES])
+def packed(request, shim):
+    p = Packed(shim, [CASES[k] for k in BATCHES[request.param]])
+    assert p.status == abi.OK, p.err
+    yield p
+    p.close()
+
+
+# ---- independent restatements ---------------------------------------------------------------------------------------------------
+def np_layout(bins):
+    """bins {(start, m): landmarks} -> first slot of every bin, sf_tile_begin, slots: groups by start frame, tile aligned, longer tracks first."""
+    base, sf, slots = {}, [], 0
+    for s in range(NF):
+        sf.append(slots // 64)
+        for m in range(MAXOBS, -1, -1):
+            base[(s, m)] = slots
+            slots += bins.get((s, m), 0)
+        slots = -(-slots // 64) * 64
+    return base, np.array(sf + [slots // 64]), slots
+
+
+def np_tracks(snap):
+    L = len(snap["para_feature"])
+    start, m = np.zeros(L, int), np.zeros(L, int)
+    for l, i in zip(snap["vis_feature_index"], snap["vis_imu_i"]):
+        start[l] = i
+        m[l] += 1
+    return start, m
+
+
+def np_used(snap, pair_present):
+    fc = snap["frame_count"]
+    used = np.zeros(abi.BLK_COUNT, bool)
+    pr = snap.get("prior")
+    if pr is not None and pr["valid"] and pr["n"] > 0:
+        used[list(pr["block_id"])] = True
+    for i in snap["imu_frame"]:
+        used[[i, i + 1, abi.BLK_SB0 + i, abi.BLK_SB0 + i + 1]] = True
+    for i in snap["wheel_frame"]:
+        used[[i, i + 1, abi.BLK_EX_WHEEL, abi.BLK_SX, abi.BLK_SY, abi.BLK_SW, abi.BLK_TD_WHEEL]] = True
+    for (i, j) in pair_present:
+        used[[i, j, abi.BLK_EX_CAM, abi.BLK_TD]] = True
+    if snap.get("lio") is not None:
+        used[snap["lio"]["frame"]] = True
+    if snap.get("plane") is not None:
+        used[list(range(min(fc, 10))) + [abi.BLK_EX_WHEEL, abi.BLK_PLANE_R, abi.BLK_PLANE_Z]] = True
+    if snap.get("anchor") is not None:
+        used[0] = True
+    gn = snap.get("gnss")
+    if gn is not None:
+        v = np.abs(np.asarray(snap["speed_bias"]).reshape(11, 9)[:, :2]).mean(axis=0)
+        if not np.hypot(v[0], v[1]) < 0.3:
+            for o in gn["obs"]:
+                k = o["lower_idx"]
+                used[[k, k + 1, abi.BLK_SB0 + k, abi.BLK_SB0 + k + 1, abi.BLK_YAW_ENU, abi.BLK_ANC_ECEF]] = True
+            used[abi.BLK_RCV_DT0:] = True
+    return used
+
+
+def np_block_table(snap, pair_present):
+    fc = snap["frame_count"]
+    cst = np.zeros(abi.BLK_COUNT, bool)
+    for q in range(11):
+        cst[q] = bool(np.asarray(snap.get("pose_const", np.zeros(11)))[q]) or q > fc
+        cst[abi.BLK_SB0 + q] = bool(np.asarray(snap.get("sb_const", np.zeros(11)))[q]) or q > fc
+    cst[abi.BLK_EX_CAM], cst[abi.BLK_EX_WHEEL], cst[abi.BLK_TD], cst[abi.BLK_TD_WHEEL] = snap["ex_cam_const"], snap["ex_wheel_const"], snap["td_const"], snap["td_wheel_const"]
+    cst[[abi.BLK_SX, abi.BLK_SY, abi.BLK_SW]] = snap["ix_wheel_const"]
+    cst[[abi.BLK_PLANE_R, abi.BLK_PLANE_Z]] = bool((snap.get("plane") or {}).get("const", 0))
+    cst[abi.BLK_YAW_ENU] = snap.get("gnss") is not None
+    free = np_used(snap, pair_present) & ~cst
+    act = np.zeros(ND, np.uint8)
+    for q in np.nonzero(free)[0]:
+        act[abi.block_tangent_offset(q):abi.block_tangent_offset(q) + abi.block_local_size(q)] = 1
+    act[182 + 3] = 0
+    return free.astype(np.uint8), act
+
+
+def np_prior_out_bound(snap, pairs0):
+    """max over MARGIN_OLD / MARGIN_SECOND_NEW of the tangent size of the prior the window can return; pairs0: frames j with a factor (0, j)."""
+    pr = snap.get("prior")
+    pr = pr if pr is not None and pr["valid"] and pr["n"] > 0 else None
+    t = set(pr["block_id"]) if pr else set()
+    if 0 in list(snap["imu_frame"]):
+        t |= {0, 1, abi.BLK_SB0, abi.BLK_SB0 + 1}
+    if 0 in list(snap["wheel_frame"]):
+        t |= {0, 1, abi.BLK_EX_WHEEL, abi.BLK_SX, abi.BLK_SY, abi.BLK_SW, abi.BLK_TD_WHEEL}
+    if snap.get("plane") is not None and snap["frame_count"] > 0:
+        t |= {0, abi.BLK_EX_WHEEL, abi.BLK_PLANE_R, abi.BLK_PLANE_Z}
+    if snap.get("gnss") is not None:
+        t |= {0, 1, abi.BLK_SB0, abi.BLK_SB0 + 1, abi.BLK_YAW_ENU, abi.BLK_ANC_ECEF, abi.BLK_RCV_DDT0 + 1} | {abi.BLK_RCV_DT0 + 4 + k for k in range(4)}
+    for j in pairs0:
+        t |= {0, j, abi.BLK_EX_CAM, abi.BLK_TD}
+    old = min(sum(abi.block_local_size(q) for q in t if q not in (0, abi.BLK_SB0)), ND)
+    return max(old, pr["n"] if pr else 0)
+
+
+# ---- the checks -----------------------------------------------------------------------------------------------------------------
+def test_round_trip_of_landmarks_and_observations(packed):
+    info = packed.info
+    TL, compact = info["tot_lm"], info["obs_compact"]
+    assert compact == (0 if any(not s["td_const"] for s in packed.snaps) else 1) and info["vis_full"] == 1 - compact
+    lm_info, lm_abi, lam0 = packed.array("lm_info", np.int32, max(TL, 1)), packed.array("lm_abi", np.int32, max(TL, 1)), packed.array("lam0", np.float64, max(TL, 1))
+    lm_pts = packed.array("lm_pts", np.float64, max(6 * TL, 1))
+    fobs = packed.array("fobs", np.float64, max(info["tot_rec"] * (2 if compact else 5), 1))
+    fvel = packed.array("fvel", np.float64, max(info["tot_n0"], 1) * 3 if compact else 1)
+    tot_lm = tot_rec = tot_n0 = 0
+    for w, snap in enumerate(packed.snaps):
+        sc, ds = packed.scan(w), packed.desc(w)
+        assert (ds["lm_off"], ds["rec_off"], ds["vel_off"]) == (tot_lm, tot_rec, tot_n0)
+        start, m = np_tracks(snap)
+        bins = {}
+        for s_, m_ in zip(start, m):
+            bins[(s_, m_)] = bins.get((s_, m_), 0) + 1
+        base, sf, slots = np_layout(bins)
+        assert sc["slots"] == slots and sc["n_tiles"] == slots // 64 and np.array_equal(sc["sf_tile_begin"], sf)
+        want_rel = np.zeros(len(m), int)
+        for l in range(len(m)):     # ties in ABI order
+            want_rel[l] = base[(start[l], m[l])]
+            base[(start[l], m[l])] += 1
+        assert np.array_equal(sc["slot_rel"], want_rel)
+        o = ds["lm_off"]
+        seen = np.zeros(slots, bool)
+        for l in range(len(m)):
+            q = o + sc["slot_rel"][l]
+            seen[sc["slot_rel"][l]] = True
+            assert lm_info[q] == start[l] | (m[l] << 8) | (int(snap["feature_const"][l]) << 16) | (1 << 24)
+            assert lm_abi[q] == l and lam0[q] == snap["para_feature"][l]
+        pad = o + np.nonzero(~seen)[0]
+        assert not lm_info[pad].any() and (lm_abi[pad] == -1).all() and (lam0[pad] == 1.0).all()
+        for r in range(6):
+            assert not lm_pts[r * TL + pad].any()
+        pair_cnt = np.zeros(NPAIR, int)
+        np.add.at(pair_cnt, snap["vis_imu_i"] * NF + snap["vis_imu_j"], 1)
+        assert np.array_equal(sc["pair_begin"], np.concatenate([[0], np.cumsum(pair_cnt)]))
+        td = snap["td"]
+        for k in range(len(snap["vis_feature_index"])):
+            l, i, j = snap["vis_feature_index"][k], snap["vis_imu_i"][k], snap["vis_imu_j"][k]
+            rec = sc["pair_begin"][i * NF + j] + (sc["slot_rel"][l] - sc["sf_tile_begin"][i] * 64)
+            pj, vj, tdj = snap["vis_pts_j"][k], snap["vis_vel_j"][k], snap["vis_td_j"][k]
+            if compact:
+                dt = td - tdj
+                want = [pj[0], pj[1]] if dt == 0.0 else [np_fma(-dt, vj[0], pj[0]), np_fma(-dt, vj[1], pj[1])]
+                assert fobs[2 * (tot_rec + rec):2 * (tot_rec + rec) + 2].tolist() == want
+                if i == 0:
+                    assert fvel[3 * (tot_n0 + rec):3 * (tot_n0 + rec) + 3].tolist() == [vj[0], vj[1], tdj]
+            else:
+                assert fobs[5 * (tot_rec + rec):5 * (tot_rec + rec) + 5].tolist() == [pj[0], pj[1], vj[0], vj[1], tdj]
+            if j == i + 1:
+                q = o + sc["slot_rel"][l]
+                assert [lm_pts[r * TL + q] for r in range(6)] == list(snap["vis_pts_i"][k]) + list(snap["vis_vel_i"][k]) + [snap["vis_td_i"][k]]
+        tot_lm += slots
+        tot_rec += sc["K"]
+        tot_n0 += int(sc["pair_begin"][NF])
+    assert (info["tot_lm"], info["tot_rec"], info["tot_n0"]) == (tot_lm, tot_rec, tot_n0)
+    assert info["up_bytes"] % 256 == 0
+
+
+def np_fma(a, b, c):
+    """a * b + c rounded once: the exact rational, then one correctly rounded conversion."""
+    from fractions import Fraction
+    return float(Fraction(float(a)) * Fraction(float(b)) + Fraction(float(c)))
+
+
+def test_table_fed_layout_agrees_with_the_host_scan(packed, shim):
+    for w, snap in enumerate(packed.snaps):
+        start, m = np_tracks(snap)
+        if len(m) and m.min() < 3:
+            continue        # (the tables hold landmarks with at least four observations)
+        counts = np.zeros(2 + 88, np.int32)
+        counts[0], counts[1] = len(m), m.sum()
+        for s_, m_ in zip(start, m):
+            counts[2 + s_ * 8 + (m_ - 3)] += 1
+        head, sf, pb, lay = (C.c_int * 4)(), (C.c_int * 12)(), (C.c_int * 122)(), (C.c_int * shim.uh_sizes(1))()
+        shim.uh_table_layout(counts.ctypes.data_as(PI), head, sf, pb, lay)
+        sc = packed.scan(w)
+        assert (head[2], head[3]) == (sc["slots"], sc["n_tiles"])
+        assert np.array_equal(np.array(sf), sc["sf_tile_begin"]) and np.array_equal(np.array(pb), sc["pair_begin"])
+        assert np.array_equal(np.array(lay)[1 + 88:1 + 88 + NF], sc["sf_tile_begin"][:NF] * 64)
+
+
+def test_table_fed_batch_packs_the_same_dense_half(shim):
+    names = ["no_prior", "prior_small", "lio_unweighted"]
+    snaps = [CASES[k] for k in names]
+    host = Packed(shim, snaps)
+    tc = np.zeros((len(snaps), 90), np.int32)
+    for w, snap in enumerate(snaps):
+        start, m = np_tracks(snap)
+        tc[w, 0], tc[w, 1] = len(m), m.sum()
+        np.add.at(tc[w], 2 + start * 8 + (m - 3), 1)
+    tab = Packed(shim, snaps, tcounts=tc)
+    assert tab.status == abi.OK and tab.info["obs_compact"] == 0 and tab.info["tot_n0"] == 0
+    assert not shim.uh_array(tab.h, b"lm_info") and not shim.uh_array(tab.h, b"fobs")
+    for k in ("tot_lm", "tot_rec", "max_tiles", "max_sf_tiles", "pn_max", "tot_lio"):
+        assert tab.info[k] == host.info[k], k
+    for w in range(len(snaps)):
+        a, b = host.desc(w), tab.desc(w)
+        assert np.array_equal(a["act"], b["act"]) and np.array_equal(a["blk_free"], b["blk_free"]) and a["lm_off"] == b["lm_off"]
+    # (pair counts live on the device: the bound of a table-fed window takes every pose)
+    j0t, j0h = tab.array("dl_j0_off", np.int64, len(snaps) + 1), host.array("dl_j0_off", np.int64, len(snaps) + 1)
+    assert (np.diff(j0t) >= np.diff(j0h)).all()
+    bad = tc.copy()
+    bad[1, 0] = -1
+    r = Packed(shim, snaps, tcounts=bad)
+    assert (r.status, r.err) == (abi.BAD_INPUT, "window 1: bad sizes")
+    host.close(); tab.close()
+
+
+def test_block_tables_and_dense_arrays(packed):
+    info, B = packed.info, len(packed.snaps)
+    x0 = packed.array("x0", np.float64, B * NA)
+    pn = info["pn_max"]
+    assert pn == max([s["prior"]["n"] for s in packed.snaps if s.get("prior") is not None] or [0]) == info["prior_n_max"]
+    pJ = packed.array("pJ0c", np.float64, max(B * pn * pn, 1))
+    r0, px0 = packed.array("prior_r0", np.float64, B * ND), packed.array("prior_x0", np.float64, B * PRIOR_X0)
+    liorows = packed.array("lio", np.float64, max(info["tot_lio"] * 8, 1))
+    gobs = packed.array("gnss_obs", np.uint8, max(info["tot_gnss"], 1) * C.sizeof(abi.GnssObs))
+    assert info["nu"] == (ND if any(s.get("gnss") is not None for s in packed.snaps) else 187) and info["solve_big"] == (info["nu"] > 187)
+    assert info["any_plane"] == any(s.get("plane") is not None or s.get("anchor") is not None for s in packed.snaps)
+    assert info["schur_groups"] == 22 and info["spec"] == (info["max_tiles"] > 0) and info["linschur"] == 0
+    for w, snap in enumerate(packed.snaps):
+        ds, hold = packed.desc(w), packed.holders[w]
+        pairs = sorted(set(zip(snap["vis_imu_i"].tolist(), snap["vis_imu_j"].tolist())))
+        free, act = np_block_table(snap, pairs)
+        assert np.array_equal(ds["blk_free"], free), np.nonzero(ds["blk_free"] != free)
+        assert np.array_equal(ds["act"], act)
+        assert x0[w * NA:(w + 1) * NA].tobytes() == bytes(hold.c.state)
+        pr = snap.get("prior")
+        want_map = np.full(ND, -1)
+        if pr is not None:
+            n = pr["n"]
+            assert ds["prior_n"] == n
+            assert np.array_equal(pJ[w * pn * pn:w * pn * pn + n * n], pr["J0"].ravel()) and not pJ[w * pn * pn + n * n:(w + 1) * pn * pn].any()
+            assert np.array_equal(r0[w * ND:w * ND + n], pr["r0"]) and not r0[w * ND + n:(w + 1) * ND].any()
+            assert np.array_equal(px0[w * PRIOR_X0:w * PRIOR_X0 + len(pr["x0"])], pr["x0"])
+            for bid, bidx in zip(pr["block_id"], pr["block_idx"]):
+                t = abi.block_tangent_offset(bid)
+                want_map[t:t + abi.block_local_size(bid)] = bidx + np.arange(abi.block_local_size(bid))
+        else:
+            assert ds["prior_n"] == 0 and not r0[w * ND:(w + 1) * ND].any() and not pJ[w * pn * pn:(w + 1) * pn * pn].any()
+        assert np.array_equal(ds["prior_map"], want_map)
+        if snap.get("lio") is not None:
+            li = snap["lio"]
+            rows = liorows[8 * ds["lio_off"]:8 * (ds["lio_off"] + ds["lio_n"])].reshape(-1, 8)
+            assert ds["lio_n"] == len(li["pts"]) and np.array_equal(rows[:, :3], li["pts"]) and np.array_equal(rows[:, 3:6], li["normals"])
+            assert np.array_equal(rows[:, 6], li["offsets"]) and (rows[:, 7] == 1.0).all()
+        if snap.get("gnss") is not None:
+            frames = np.array([o["frame"] for o in snap["gnss"]["obs"]])
+            order = np.argsort(frames, kind="stable")
+            assert np.array_equal(ds["gnss_frame_begin"], np.concatenate([[0], np.cumsum(np.bincount(frames, minlength=NF))]))
+            sz = C.sizeof(abi.GnssObs)
+            src = bytes(hold.gnss_obs)
+            for k, q in enumerate(order):
+                assert gobs[(ds["gnss_off"] + k) * sz:(ds["gnss_off"] + k + 1) * sz].tobytes() == src[q * sz:(q + 1) * sz]
+        assert ds["n_plane"] == (min(snap["frame_count"], 10) if snap.get("plane") is not None else 0) and ds["use_anchor"] == (snap.get("anchor") is not None)
+
+
+def test_j0_offsets_and_prior_out_bound(packed, shim):
+    B = len(packed.snaps)
+    j0, fo = packed.array("dl_j0_off", np.int64, B + 1), packed.array("dl_feat_off", np.int32, B + 1)
+    assert j0[0] == 0 and fo[0] == 0
+    nmax = 0
+    for w, snap in enumerate(packed.snaps):
+        pairs0 = sorted(set(j for i, j in zip(snap["vis_imu_i"].tolist(), snap["vis_imu_j"].tolist()) if i == 0))
+        nb = np_prior_out_bound(snap, pairs0)
+        assert j0[w + 1] - j0[w] == nb * nb, (w, nb)
+        assert fo[w + 1] - fo[w] == len(snap["para_feature"])
+        nmax = max(nmax, nb)
+        pb = packed.scan(w)["pair_begin"].astype(np.int32)
+        assert nb == max(shim.uh_prior_out_bound(C.byref(packed.holders[w].c), pb.ctypes.data_as(PI), 1), shim.uh_prior_out_bound(C.byref(packed.holders[w].c), None, 0))
+    assert packed.info["marg_nmax"] == nmax
+    ts = packed.array("tile_start", np.int32, max(packed.info["n_tile_start"], 1))
+    want = [s for w in range(B) for s in range(NF) for _ in range(packed.scan(w)["sf_tile_begin"][s + 1] - packed.scan(w)["sf_tile_begin"][s])]
+    assert ts[:len(want)].tolist() == want and packed.info["n_tile_start"] == len(want)
+
+
+def _with(snap, **kw):
+    s = dict(snap)
+    s.update(kw)
+    return s
+
+
+def _refusals():
+    """(message, snapshot, edit of the WindowHolder or None): windows with exactly one defect."""
+    ok = CASES["one_landmark"]          # landmark 0: start 0, factors (0, 1) (0, 2) (0, 3)
+    pr = prior([abi.BLK_SB0, 1], 0)
+    gn = dict(gnss=gnss([0, 1]), gnss_state=CASES["gnss_unordered"]["gnss_state"])
+    nullp, nulli = C.POINTER(C.c_double)(), C.POINTER(C.c_int32)()
+    J = lambda *v: np.array(v, np.int32)
+    return [
+        ("bad sizes", ok, lambda h: setattr(h.c, "frame_count", 11)),
+        ("bad sizes", ok, lambda h: setattr(h.c, "n_imu", 11)),
+        ("bad sizes", ok, lambda h: setattr(h.c, "n_feature", -1)),
+        ("bad sizes", ok, lambda h: setattr(h.c, "imu_frame", nulli)),
+        ("para_Feature is null", ok, lambda h: setattr(h.c, "para_Feature", nullp)),
+        ("null visual factor array", ok, lambda h: setattr(h.c.vis, "td_j", nullp)),
+        ("bad visual factor 1", _with(ok, vis_imu_j=J(1, 11, 3)), None),
+        ("visual factors of one landmark must share imu_i", _with(ok, vis_imu_i=J(0, 1, 0)), None),
+        ("two visual factors of one landmark on the same frame", _with(ok, vis_imu_j=J(1, 2, 2)), None),
+        ("landmark track must be contiguous from start_frame (feature_per_frame order)", _with(ok, vis_imu_j=J(1, 2, 4)), None),
+        ("bad imu_frame", ok, lambda h: _own_frames(h, "imu_frame").__setitem__(3, 10)),
+        ("bad wheel_frame", ok, lambda h: _own_frames(h, "wheel_frame").__setitem__(0, -1)),
+        ("bad lio block", _with(ok, lio=lio(5)), lambda h: setattr(h.c.lio, "frame", 11)),
+        ("bad lio block", _with(ok, lio=lio(5)), lambda h: setattr(h.c.lio, "normals", nullp)),
+        ("gnss_ready without observations array", _with(ok, **gn), lambda h: setattr(h.c, "gnss_obs", C.POINTER(abi.GnssObs)())),
+        ("GNSS observation 1 has an index or a deviation out of range", _with(ok, **gn), lambda h: setattr(h.gnss_obs[1], "lower_idx", 3)),
+        ("GNSS observation 1 has an index or a deviation out of range", _with(ok, **gn), lambda h: setattr(h.gnss_obs[1], "pr_uura", float("nan"))),
+        ("prior too large or without J0 / r0", _with(ok, prior=pr), lambda h: setattr(h.prior.c, "n", 247)),
+        ("prior too large or without J0 / r0", _with(ok, prior=pr), lambda h: setattr(h.prior.c, "r0", nullp)),
+        ("prior block table inconsistent (id, size, duplicate or offset out of range)", _with(ok, prior=pr), lambda h: h.prior.c.block_id.__setitem__(1, abi.BLK_SB0)),
+        ("prior block table inconsistent (id, size, duplicate or offset out of range)", _with(ok, prior=pr), lambda h: h.prior.c.block_idx.__setitem__(1, 10)),
+    ]
+
+
+def _own_frames(h, name):
+    """The holder's frame list as a copy of its own (the snapshots share the arrays)."""
+    a = getattr(h, name).copy()
+    setattr(h, name, a)
+    setattr(h.c, name, a.ctypes.data_as(C.POINTER(C.c_int32)))
+    return a
+
+
+def _refused(shim, holders, allreduce=0, opt=None, null_last=False):
+    ptrs = [C.pointer(h.c) for h in holders] + ([C.POINTER(abi.Window)()] if null_last else [])
+    arr = (C.POINTER(abi.Window) * len(ptrs))(*ptrs)
+    if opt is None:
+        opt = abi.Options()
+        shim.uh_default_options(C.byref(opt))
+    st, err = C.c_int(-1), C.create_string_buffer(512)
+    h = shim.uh_pack(C.byref(opt), allreduce, 0, len(ptrs), arr, None, C.byref(st), err, 512)
+    assert not h
+    return st.value, err.value.decode()
+
+
+def test_every_refusal_keeps_its_status_and_message(shim):
+    """Every message plan_upload and scan_window can give, behind a sound window 0. Two guards have no input that reaches them and are
+    not here: "landmark with more than 10 factors" (eleven factors of one landmark need two on one frame, refused before) and "prior x0
+    too large" (32 distinct blocks of the right sizes hold at most 203 of the 208 doubles)."""
+    good = CASES["no_landmarks"]
+    seen = set()
+    for msg, snap, edit in _refusals():
+        holders = [abi.WindowHolder(good), abi.WindowHolder(snap)]
+        if edit is not None:
+            edit(holders[1])
+        assert _refused(shim, holders) == (abi.BAD_INPUT, "window 1: " + msg), msg
+        seen.add(msg)
+    assert len(seen) == 14
+    assert _refused(shim, [abi.WindowHolder(good)], null_last=True) == (abi.BAD_INPUT, "window 1: null pointer")
+    opt = abi.Options()
+    shim.uh_default_options(C.byref(opt))
+    opt.max_solver_time_in_seconds = 0.04
+    assert _refused(shim, [abi.WindowHolder(good)], allreduce=1, opt=opt) == (
+        abi.BAD_INPUT, "max_solver_time_in_seconds is not available with landmark sharding (gfbe_set_allreduce)")
+
+
+def test_sanitized_stand_alone_program():
+    exe = _build(os.path.join(ROOT, "tests", "upload_host_main.cpp"), os.path.join(BUILD, "upload_host_main"), ["-g", "-Xarch_host", "-fsanitize=address,undefined",
+                                                                                                                "-Xarch_host", "-fno-sanitize-recover=undefined"])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "upload_host_main: ok" in r.stdout
