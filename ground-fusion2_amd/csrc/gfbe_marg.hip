@@ -180,8 +180,8 @@ __device__ void jacobi_eig(double *G, double *V, int n, int ld, double *lam, int
 //   are only recorded —, compaction of the surviving poles, M3b rotations applied to the rows, M4 one secular root per thread (the
 //   "middle way" rational iteration from the nearer pole, safeguarded by bisection: ~5 iterations; the root is kept as origin pole +
 //   offset, so that every difference d_j - lambda_i is formed without cancellation), M5 zhat, M6 norms, M7 the vectors into Vt
-//   (block-diagonal, transposed), M8 Q <- Q V in place, a WAVE per row (the row's old entries are read from LDS by all lanes before the
-//   wave overwrites them).
+//   (block-diagonal, transposed), M8 Q <- Q V in place, a 4 x 4 register tile of (rows, roots) per thread, whole row-tiles per pass
+//   (a pass forms all its tiles, block barrier, then writes them: it reads and writes only the rows of Q it owns).
 // Q: n x n (row stride ld): on return column j = eigenvector j of T (unsorted), lam (= wk[0 .. n)) its eigenvalue. Vt: n x n scratch.
 // dd / ee are not changed. wk: 12 n doubles. Everything in LDS. A numpy prototype of exactly this structure (scratch-free of LAPACK)
 // reaches 3e-15 |T| in residual and orthogonality on random, graded (1e16-conditioned), split, clustered and Wilkinson matrices
@@ -298,6 +298,8 @@ __device__ __forceinline__ void dc_secular_root8(const int i, const int k, const
   }
   o_out = o; mu_out = mu;
 }
+// blockDim.x >= (n + 3) / 4 is required: M8 gives a pass blockDim / nt4 whole row-tiles and would not advance with none (k_marg, the
+// only caller: the static_assert next to MARG_LDS_N).
 __device__ void tridiag_dc(mlds_double *Q, mlds_double *Vt, const int n, const int ld, const mlds_double *dd, const mlds_double *ee, mlds_double *wk, double *stamp = nullptr) {
   // (diagnostics build: time per phase, summed over the levels, into stamp[13 ..]: leaves, M1+M2, M3, M3b+M4, M5, M6, M7, M8)
   double ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -524,12 +526,18 @@ __device__ void tridiag_dc(mlds_double *Q, mlds_double *Vt, const int n, const i
     __syncthreads();
     DCSTAMP(6);
     // ---- M8: Q <- Q V on the columns of the surviving poles, in place: a 4 x 4 tile of (rows, roots) per thread in registers — a merge
-    // starts at a multiple of four, so no tile straddles two merges —, sixteen products per eight LDS loads; every tile is formed before
-    // any is written (a block barrier in between). (A wave per row with the products along its lanes: 94 us summed over the levels.)
+    // starts at a multiple of four, so no tile straddles two merges —, sixteen products per eight LDS loads. A tile of row-tile ty reads
+    // the rows 4 ty .. 4 ty + 3 of Q at every surviving column and writes the same rows, so all tiles of a row-tile are formed before
+    // any of them is written (the block barrier below) — and a pass takes WHOLE row-tiles, rpp = blockDim / nt4 of them: what a later
+    // pass reads, no earlier pass has written. (Passes of blockDim consecutive tiles split a row-tile between two passes once
+    // nt4^2 > blockDim — n = 89, 90 on the 512 threads of a throughput batch —, and the second pass then read rows the first had already
+    // overwritten: eigenvectors finite and wrong.) One pass whenever nt4^2 <= blockDim: the 86-dim prior on 512 threads, every in-LDS
+    // size on 1024; a tile's arithmetic does not depend on the pass it runs in, so the bits are those of the one-pass schedule
+    // everywhere. (A wave per row with the products along its lanes: 94 us summed over the levels.)
     {
-      const int nt4 = (n + 3) >> 2;
-      for (int e0 = 0; e0 < nt4 * nt4; e0 += nt) {
-        const int e = e0 + t;
+      const int nt4 = (n + 3) >> 2, rpp = nt / nt4;      // row-tiles per pass (>= 1: the static_assert next to MARG_LDS_N)
+      for (int ty0 = 0; ty0 < nt4; ty0 += rpp) {
+        const int tyl = t / nt4, e = (tyl < rpp && ty0 + tyl < nt4) ? (ty0 + tyl) * nt4 + (t - tyl * nt4) : nt4 * nt4;
         double acc[4][4];
 #pragma unroll
         for (int x = 0; x < 4; x++)
@@ -1032,6 +1040,8 @@ __device__ __forceinline__ int ldlt_registers(LoadA loadA, LoadB loadB, double *
 #define MARG_SQRT_PENDING (-1000000)
 #define MARG_LDS_N 90   // A' up to this size is eigen-decomposed entirely inside LDS (2 n^2 doubles + the 14 n of tridiag_ql_eig's scratch)
 #define MARG_LDS_DOUBLES (2 * MARG_LDS_N * MARG_LDS_N + 14 * MARG_LDS_N)
+static_assert((MARG_LDS_N + 3) / 4 <= GFBE_MARG_TP_THREADS && GFBE_MARG_TP_THREADS <= MARG_THREADS,
+              "tridiag_dc M8: the smallest workgroup of k_marg holds at least one whole row-tile (nt4 tiles) of the largest in-LDS prior");
 
 __global__ __launch_bounds__(MARG_THREADS) void k_marg(BatchDev d, int flag) {
   const int w = blockIdx.x;

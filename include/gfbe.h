@@ -248,7 +248,15 @@ typedef struct gfbe_options {
    *      tridiagonalisation + divide & conquer since round 6 — takes 0.64 ms of a 1.72 ms call. Default.
    *   The two square roots carry the same information J0^T J0, J0^T r0; they do NOT share the prior's constant term |r0|^2 (the
    *   smallest kept eigenvalues of A' amplify b'): a caller that logs costs sees a constant offset between the modes (and between
-   *   mode 0 and the reference's own Eigen build), never a different step. */
+   *   mode 0 and the reference's own Eigen build), never a different step.
+   *   Batch independence of the new prior: a window's J0, r0 do not depend IN BITS on the batch it is solved in as long as the batch
+   *   stays inside one kernel set — fewer than 32 windows (k_marg on 1024 threads, k_marg_ldlt<4>) or 32 and more (512 threads,
+   *   k_marg_ldlt_tp). Across the two sets the same window gets a prior that differs in its last bits, in both modes: measured
+   *   against an extended-precision model (tests/test_gpu_prior.py, priors of 71 .. 177 dims), J0^T J0 of the two sets agrees to
+   *   1.7e-5 u |A| for the LDL^T kernels and 1.4e-3 u |A| for the eigen path (MARGIN_SECOND_NEW: 0.14 / 12 u |A|; u = 2^-53, |A| the
+   *   largest entry of the un-reduced information; each set is within 7 u |A| of the model), and the number of non-zero rows is
+   *   the same whenever no eigenvalue / pivot of A' lies near marg_eps. A pivot within rounding (~64 u |A|) of marg_eps can be kept
+   *   by one set and dropped by the other. */
   int32_t marg_sqrt;
   /* 1: gfbe_batch_solve replays its fixed kernel sequence as a hipGraph from the third call on a batch (first
    * call eager, second captured); 0 (default): eager launches — on ROCm 7.2 / MI355X the replay measured 2.50 vs

@@ -8,6 +8,7 @@ from _gfbe_import import gf
 abi, synth = gf.abi, gf.synth
 
 from normal_equations_np import T_POSE, T_EX, T_TD, T_SB, T_EXW, T_SX, T_SY, T_SW, T_TDW, numpy_normal_equations      # noqa: E402,F401
+from prior_np import numpy_pivoted_ldlt_sqrt      # noqa: E402,F401
 
 
 def free_all(snap):
@@ -189,29 +190,6 @@ def test_marginalize_old_against_numpy_schur(oracle):
             want = [snap["td"] if bid_old == 27 else snap["td_wheel"]]
         np.testing.assert_array_equal(prior["x0"][off:off + size], np.asarray(want, float))
         off += size
-
-
-def numpy_pivoted_ldlt_sqrt(Ap, bp, eps=1e-8):
-    """Independent statement of the product's default square root: diagonally pivoted LDL^T with pivots > eps,
-    written as successive Schur complements on index sets (no in-place elimination loops like the C++ ones)."""
-    n = len(bp)
-    M, rhs = 0.5 * (Ap + Ap.T), bp.copy()
-    left = list(range(n))
-    J0, r0 = np.zeros((n, n)), np.zeros(n)
-    for k in range(n):
-        dg = np.array([M[i, i] for i in left])
-        p = left[int(np.argmax(dg))]
-        if not M[p, p] > eps:
-            break
-        d = M[p, p]
-        col = np.zeros(n)
-        col[left] = M[left, p] / d
-        J0[k] = np.sqrt(d) * col
-        r0[k] = rhs[p] / np.sqrt(d)
-        left.remove(p)
-        M[np.ix_(left, left)] -= d * np.outer(col[left], col[left])
-        rhs[left] -= col[left] * (r0[k] * np.sqrt(d))
-    return J0, r0
 
 
 def test_ldlt_square_root_mode_of_the_oracle(oracle):
