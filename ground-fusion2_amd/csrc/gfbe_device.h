@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "../../include/gfbe.h"
@@ -208,8 +209,28 @@ struct WinCtl {
                                          // window's mu — an accepted step's new mu is known to the pass that linearises its candidate — and forms them itself otherwise)
 };
 
-// ---- batch: all device pointers ----------------------------------------------------------------
-struct BatchDev {
+// ---- the outputs of one linearisation ----------------------------------------------------------
+// Everything a linearisation writes and the kernels up to the next one read. A batch holds the set twice when the candidate's pass
+// linearises (BatchDev::spec, BatchDev::lin2); lin_view puts the current one in the places of the first. Pointers to double only: the
+// host's carve (carve_slab, gfbe_upload.h) and the tests walk a set as sizeof(LinSet) / sizeof(double *) slots.
+struct LinSet {
+  double *lm_Hll, *lm_gl;     // [tot_lm]
+  double *lm_hC;              // [HC][tot_lm]
+  double *lm_hP;              // [MAXOBS][6][tot_lm]
+  double *lm_sw;              // [tot_lm] sqrt of the landmark's weight in the Schur term at the current linearisation (k_vis<0> -> k_schur)
+  double *vis_part;           // [B][max_tiles][MAXOBS][VP_STRIDE]  X^T X of the 64 factors of one tile at one step, X = [J | r]
+  double *schur_part;         // [B][schur_groups][SCHUR_STRIDE]  sum over the landmarks of one group of start frames (the second set's is its own only with
+                              // k_linschur<SPEC> — the landmark elimination of the candidate's linearisation —, the first set's otherwise)
+  double *imu_part, *wheel_part;     // [B][MAX_IMU][IMU_PART], [B][MAX_WHEEL][WHEEL_PART]
+  double *plane_part, *anchor_part;  // [B][MAX_PLANE][PLANE_PART], [B][ANCHOR_PART]   (only read for windows with n_plane / use_anchor)
+  double *prior_g;            // [B][ND + 2]  J0^T r, cost
+  double *lio_part;           // [B][LIOW_WGS][LIOW_PART]
+  double *gnss_J, *gnss_r;          // [tot_gnss][36], [tot_gnss][2]
+  double *gnss_cost;                // [B][2]  cost of the GNSS factors at the linearisation point / at the candidate
+};
+
+// ---- batch: all device pointers (the first set of the linearisation's outputs is its base: d.lm_hP, d.imu_part, ...) ------------
+struct BatchDev : LinSet {
   int B;
   int tot_lm;                 // total padded landmark slots
   int max_tiles;              // max n_tiles over windows
@@ -234,11 +255,7 @@ struct BatchDev {
   double *fobs;               // [tot_rec][5] host upload only: pjx pjy vjx vjy td_j of every factor in record (pair-major) order; k_expand
                               // scatters them into lm_obs / lm_rec (the ELL rows never cross PCIe: 40 B per factor instead of ~100)
   double *lam0, *lam;         // [tot_lm], [2][tot_lm]
-  double *lm_Hll, *lm_gl;     // [tot_lm]
-  double *lm_hC;              // [HC][tot_lm]
-  double *lm_hP;              // [MAXOBS][6][tot_lm]
   double *lm_sl, *lm_yl, *lm_vl;   // Jacobi scale, GN component, Cauchy direction component
-  double *lm_sw;              // [tot_lm] sqrt of the landmark's weight in the Schur term at the current linearisation (k_vis<0> -> k_schur)
   // visual block-CSR records, pair-major: [tot_rec][REC]
   double *rec;
   int tot_rec;
@@ -249,23 +266,18 @@ struct BatchDev {
   double *prior_J0, *prior_r0, *prior_x0, *prior_H;   // [B][ND*ND], [B][ND], [B][PRIOR_X0], [B][ND*ND]
   // partial results
   double *pair_part;          // [B][NF][VP_STRIDE]   marginalisation: X^T X of the pose pairs (0, j), slot j (sum of vis_part over the tiles of start frame 0)
-  double *vis_part;           // [B][max_tiles][MAXOBS][VP_STRIDE]  X^T X of the 64 factors of one tile at one step, X = [J | r]
-  double *schur_part;         // [B][schur_groups][SCHUR_STRIDE]  sum over the landmarks of one group of start frames
-  double *schur_part2;        // the second set's (k_linschur<SPEC>: the landmark elimination of the candidate's linearisation; nullptr without it)
   int linschur;               // throughput batch with constant extrinsic / td, not sharded: k_linschur (evaluation + landmark elimination in one
                               // launch) in the place of k_vis<0, false> + k_schur (gfbe_options.merge_lin_schur)
   int schur_groups;           // SCHUR_GROUPS for throughput batches; small batches: 2 NF (two workgroups per start frame), NF when sharded
-  double *imu_part, *wheel_part;     // [B][MAX_IMU][IMU_PART], [B][MAX_WHEEL][WHEEL_PART]
-  double *plane_part, *anchor_part;  // [B][MAX_PLANE][PLANE_PART], [B][ANCHOR_PART]   (only read for windows with n_plane / use_anchor)
   int any_plane;                     // some window of the batch has plane or anchor factors (else their workgroups are not launched)
   int prior_n_max;                   // largest prior dimension of the batch (k_prior_tp stages J0 in LDS when it fits)
-  double *prior_g;            // [B][ND + 2]  J0^T r, cost
   // ---- speculative linearisation (small batches, gfbe_options.speculative_linearization): the pass that evaluates the candidate of an
   // iteration LINEARISES there — into the second set of the linearisation's outputs below; k_accept's tail flips WinCtl::lb when the
   // step is accepted, and the next iteration starts at the Schur elimination (lin_view: the set WinCtl::lb names). A rejected step
   // leaves the current set alone, exactly what DoglegStrategy's reuse needs.
   int spec;
-  double *lm_Hll2, *lm_gl2, *lm_hC2, *lm_hP2, *lm_sw2, *vis_part2, *imu_part2, *wheel_part2, *plane_part2, *anchor_part2, *prior_g2, *lio_part2, *gnss_J2, *gnss_r2, *gnss_cost2;
+  LinSet lin2;                // (all null without spec)
+  __host__ __device__ const LinSet &lin_set(int k) const { return k ? lin2 : *this; }   // 0: the batch's own, 1: lin2
   // ---- landmark sharding over ranks (gfbe_set_allreduce): tile t of a window belongs to rank t % world.
   int rank, world;
   int sharded;                      // an all-reduce hook is installed (gfbe_set_allreduce): the launch sequence with the exchange blocks, also for world == 1
@@ -293,13 +305,10 @@ struct BatchDev {
   double *dense_cand;         // [B][4] dense-factor candidate cost, |x-xc|^2, |xc|^2
   int tot_lio;                // LiDAR factors of the whole batch (0: the kernels are not launched)
   double *lio;                // [tot_lio][8]  p(3) n(3) offset weight
-  double *lio_part;           // [B][LIOW_WGS][LIOW_PART]
   // assembled system
   // GNSS inside the solve (gfbe_gnss_solve.hip): observations, their residuals / Jacobians at the current linearisation, costs
   int any_gnss, tot_gnss, gnss_max_obs;   // some window has gnss_ready; observations of the whole batch / of its largest window
   gfbe_gnss_obs *gnss_obs;          // [tot_gnss]
-  double *gnss_J, *gnss_r;          // [tot_gnss][36], [tot_gnss][2]
-  double *gnss_cost;                // [B][2]  cost of the GNSS factors at the linearisation point / at the candidate
   double *gnss_marg;                // [B][GN_MPART]  the frame-0 GNSS factors of MARGIN_OLD at the re-anchored state (cost < 0: none)
   int solve_big;                    // some window has active GNSS dims: the batch takes k_solve_big (factor in global memory, n <= 246)
   double *solveS;                   // k_solve_big: [B][BIG_LD * BIG_LD] scaled system / its factor
@@ -335,6 +344,17 @@ struct BatchDev {
   int *dl_feat_off;           // [B + 1]
   long long *dl_j0_off;       // [B + 1]
 };
+static_assert(std::is_trivially_copyable<BatchDev>::value, "BatchDev is cleared with memset and passed to the kernels by value");
+
+// Speculative linearisation (BatchDev::spec): the batch seen with set `lb` of the linearisation's outputs in the places of the first
+// set — the kernels between two linearisations index d.lm_hP, d.imu_part, ... as before. lb = 0 (and every batch without the
+// second set): the batch itself.
+__host__ __device__ __forceinline__ BatchDev lin_view(const BatchDev &d, const int lb) {
+  BatchDev v = d;
+  if (d.spec && lb) static_cast<LinSet &>(v) = d.lin2;
+  return v;
+}
+
 enum { DL_CTL = (sizeof(WinCtl) + 7) / 8, DL_META = (4 + 3 * GFBE_MAX_PRIOR_BLOCKS + 1) / 2,
        DL_OFF_X = DL_CTL, DL_OFF_META = DL_OFF_X + NA, DL_OFF_X0 = DL_OFF_META + DL_META, DL_OFF_R0 = DL_OFF_X0 + GFBE_NFRAMES * 16 + 32,
        DL_FIX = DL_OFF_R0 + ND };

@@ -188,19 +188,16 @@ struct Lane { hipStream_t s, aux; hipEvent_t fork, join; };
 
 struct gfbe_batch {
   BatchDev d;
-  // every device array of the batch is carved from ONE slab: a dry pass over the allocation sequence adds up the sizes,
-  // the slab comes from the context's cache (or hipMalloc), the second pass hands out the pointers
+  // every device array of the batch is carved from ONE slab (carve_slab, gfbe_upload.h)
   char *slab = nullptr;
-  size_t slab_bytes = 0, slab_off = 0;
-  bool dry = false;
+  size_t slab_bytes = 0;
   std::vector<std::vector<int>> slot_of;   // per window: ABI landmark -> global slot (host-fed batches)
   std::vector<int> L;
   std::vector<unsigned char> anchor_only;      // window: MARGIN_SECOND_NEW meets an invalid prior that lists Pose[WINDOW_SIZE-1] (estimator.cpp:3622-3632)
   // upload region [0, up_end) of the slab = the pinned mirror up_h; [up_end, zero_end) is cleared; the rest is written before read
   char *up_h = nullptr;
-  size_t up_cap = 0, up_bytes = 0, up_end = 0, zero_end = 0;
-  struct PoisonEntry { const char *name; size_t off, bytes; };
-  std::vector<PoisonEntry> poison_list;     // (GFBE_POISON_UNCLEARED test hook: the slab's arrays by name)
+  size_t up_cap = 0, up_end = 0, zero_end = 0;
+  std::vector<gfd::SlabArray> arrays;       // the slab's arrays by name (GFBE_POISON_UNCLEARED test hook)
   // results: [dl_fix | dl_feat | dl_J0] at the end of the slab -> dl_h (pinned) in one copy
   char *dl_h = nullptr;
   char *lay_h = nullptr;                   // table-fed batches: the pinned source of the layout table's copy
@@ -213,7 +210,6 @@ struct gfbe_batch {
   int last_flag = GFBE_MARGIN_NONE;
   bool fetched = false;                    // dl_h holds the results of the last solve
   double algo_bytes_lin = 0.0;             // algorithmic bytes of one visual linearisation of the batch
-  size_t slab_n = 0;                       // doubles of the [H | g | E | eg | xa] slab
   // the launch sequence of one optimization() is fixed (no host decision inside): captured once per margin flag
   // into a hipGraph (second call) and replayed afterwards
   hipGraphExec_t graph[3] = {nullptr, nullptr, nullptr};
@@ -482,20 +478,6 @@ void prof_collect(gfbe_ctx *c) {
   }
 }
 
-// Two passes over one allocation sequence: the dry pass adds up the sizes, the slab comes from the context's cache (or
-// hipMalloc), the second pass hands out the pointers. The arrays the host fills come FIRST ("upload region"): they have a
-// mirror at the same offsets in one pinned host buffer, the packing threads write straight into that mirror, and the whole
-// region crosses PCIe as ONE hipMemcpyAsync. Only the arrays the kernels expect zeroed are cleared (one hipMemsetAsync).
-// (the upload region's part of the sequence is upload_region, gfbe_upload.h: the same sizes over the slab and over the mirror)
-template <typename T>
-gfbe_status dev_alloc(gfbe_ctx *c, gfbe_batch *b, T **p, size_t n) {
-  const size_t bytes = slab_bytes_of<T>(n);
-  if (b->dry) { b->slab_bytes += bytes; *p = nullptr; return GFBE_OK; }
-  if (b->slab_off + bytes > b->slab_bytes) { c->err = "batch slab overrun"; return GFBE_DEVICE_ERROR; }
-  *p = (T *)(b->slab + b->slab_off);
-  b->slab_off += bytes;
-  return GFBE_OK;
-}
 // the smallest cached slab that fits (and is not more than twice too large), else a new one
 gfbe_status slab_acquire(gfbe_ctx *c, gfbe_batch *b) {
   int best = -1;
@@ -640,116 +622,30 @@ gfbe_status fetch_table_counts(gfbe_ctx *c, gfbe_ftab *tabs, int tab0, int32_t B
   return GFBE_OK;
 }
 
-// Phase 4: the slab and the pinned mirror of its upload region. Two passes over one allocation sequence (dev_alloc above); the upload
-// region comes first (upload_region, gfbe_upload.h), `dev` / `host` receive its pointers over the slab / the pinned buffer.
-gfbe_status carve_batch(gfbe_ctx *c, gfbe_batch *b, const UploadPlan &p, const char *poison_env, UploadMirror *dev, UploadMirror *host) {
+// Phase 4: the slab and the pinned mirror of its upload region. The allocation sequence is carve_slab (gfbe_upload.h): a dry pass for the
+// size, the slab, then the pass that hands out the pointers; `dev` / `host` receive the upload region over the slab / the pinned buffer.
+gfbe_status carve_batch(gfbe_ctx *c, gfbe_batch *b, const UploadPlan &p, UploadMirror *dev, UploadMirror *host) {
   BatchDev &d = b->d;
-  const int B = p.B, max_tiles = p.max_tiles, tot_rec = p.tot_rec, tot_gnss = p.tot_gnss, n_imu_tot = p.n_imu_tot, n_wheel_tot = p.n_wheel_tot;
-  const size_t TL = p.tot_lm;
-  const bool tabs = p.table_fed;
+  const size_t chain = solve_chain_scratch_doubles(), pack = d.sharded ? sys_pack_doubles_host(d.nu, d.world) : 0;
   gfbe_status st;
-  for (int pass = 0; pass < 2; pass++) {
-    b->dry = pass == 0;
-    if (pass == 1) {
-      st = slab_acquire(c, b);
-      if (st != GFBE_OK && d.spec) {
-        // (the second set of the linearisation's outputs is ~1 MB per 2k-landmark window — a batch that fitted the device
-        //  before the option existed must still fit: size the slab again without it; the note travels with the batch's create note)
-        d.spec = 0;
-        c->err.clear();
-        c->note = "speculative_linearization switched off for a batch: its second set of outputs did not fit the device";
-        b->slab_bytes = 0; b->up_bytes = 0; b->slab_off = 0;
-        pass = -1;
-        continue;
-      }
-      if (st != GFBE_OK) return st;
-      b->up_h = pin_acquire(c, b->up_bytes, &b->up_cap);
-      if (!b->up_h) { c->err = "hipHostMalloc(upload staging) failed"; return GFBE_DEVICE_ERROR; }
-    }
-#define AL(field, n) do { const size_t o_ = b->slab_off; if ((st = dev_alloc(c, b, &d.field, (size_t)(n))) != GFBE_OK) return st; \
-                          if (!b->dry && poison_env) b->poison_list.push_back({#field, o_, b->slab_off - o_}); } while (0)
-    // -- upload region
-    if (b->dry) b->slab_bytes = b->up_bytes = upload_region(p, nullptr).bytes;
-    else {
-      *dev = upload_region(p, b->slab); *host = upload_region(p, b->up_h);
-      point_upload_region(*dev, d);
-      b->slab_off = dev->bytes;
-    }
-    const size_t up_end = b->dry ? b->slab_bytes : b->slab_off;
-    // -- arrays the kernels expect zeroed at the start (rows past a track's length, partials of absent factors, ...)
-    if (tabs) { AL(lm_info, TL); AL(lm_abi, TL); AL(lm_pts, (size_t)6 * TL); AL(lam0, TL); d.fobs = nullptr; d.fvel = nullptr; }
-    AL(lio_part, (size_t)B * LIOW_WGS * LIOW_PART);
-    AL(raw_imu, (size_t)MAX_IMU * (15 + 450) * 4 * ((B + 3) / 4)); AL(raw_wheel, (size_t)MAX_WHEEL * (6 + 132) * 4 * ((B + 3) / 4));   // [factor][window / 4][value][window % 4]
-    AL(zero, 16); AL(vis_H, (size_t)B * NV * (NV + 1));
-    d.vs_blocks = d.vis_full ? (int)VS_BLOCKS : 1;
-    if (B < DENSE_SPLIT_MIN_B && !d.sharded) { AL(vis_Hs, (size_t)B * d.vs_blocks * NV * (NV + 1)); } else d.vis_Hs = nullptr;
-    AL(ctl, B);
-    AL(lam, 2 * TL); AL(lm_Hll, TL); AL(lm_gl, TL); AL(lm_hC, (size_t)HC * TL);
-    AL(lm_sl, TL); AL(lm_yl, TL); AL(lm_vl, TL); AL(lm_sw, TL);
-    AL(imu_sqrt, (size_t)n_imu_tot * 225); AL(wheel_sqrt, (size_t)n_wheel_tot * 36);
-    AL(pair_part, (size_t)B * NF * VP_STRIDE); AL(schur_part, (size_t)B * d.schur_groups * SCHUR_STRIDE);
-    AL(imu_part, (size_t)B * MAX_IMU * IMU_PART); AL(wheel_part, (size_t)B * MAX_WHEEL * WHEEL_PART);
-    AL(plane_part, d.any_plane ? (size_t)B * MAX_PLANE * PLANE_PART : 1); AL(anchor_part, d.any_plane ? (size_t)B * ANCHOR_PART : 1);
-    AL(prior_g, (size_t)B * (ND + 2));
-    if (d.spec) {   // the second set (BatchDev::spec), cleared like the first
-      AL(lm_Hll2, TL); AL(lm_gl2, TL); AL(lm_hC2, (size_t)HC * TL); AL(lm_sw2, TL);
-      AL(imu_part2, (size_t)B * MAX_IMU * IMU_PART); AL(wheel_part2, (size_t)B * MAX_WHEEL * WHEEL_PART);
-      AL(plane_part2, d.any_plane ? (size_t)B * MAX_PLANE * PLANE_PART : 1); AL(anchor_part2, d.any_plane ? (size_t)B * ANCHOR_PART : 1);
-      AL(prior_g2, (size_t)B * (ND + 2)); AL(lio_part2, (size_t)B * LIOW_WGS * LIOW_PART);
-      if (d.linschur) { AL(schur_part2, (size_t)B * d.schur_groups * SCHUR_STRIDE); } else d.schur_part2 = nullptr;
-    } else {
-      d.schur_part2 = nullptr;
-      d.lm_Hll2 = d.lm_gl2 = d.lm_hC2 = d.lm_sw2 = d.imu_part2 = d.wheel_part2 = d.plane_part2 = d.anchor_part2 = d.prior_g2 = d.lio_part2 = nullptr;
-    }
-    AL(tile_cost, (size_t)B * std::max(max_tiles, 1)); AL(tile_cand, (size_t)B * std::max(max_tiles, 1) * 4);
-    AL(tile_cnt, B < DENSE_SPLIT_MIN_B ? (size_t)B * std::max(max_tiles, 1) : 1);
-    AL(win_cnt, B < DENSE_SPLIT_MIN_B ? (size_t)B * 2 : 1);
-    AL(tile_gram, (size_t)B * std::max(max_tiles, 1) * 8); AL(dense_cand, (size_t)B * 4);
-    AL(xb, (size_t)B * d.world * XCHG); AL(xc, (size_t)B * d.world * XCHG);
-    if (d.sharded) { AL(Er, (size_t)B * (NV * NV + NV)); AL(sys_pack, (size_t)B * sys_pack_doubles_host(d.nu, d.world)); } else { d.Er = nullptr; d.sys_pack = nullptr; }
-    AL(sp, (size_t)B * ND); AL(Dp, (size_t)B * ND); AL(gts, (size_t)B * ND); AL(vp, (size_t)B * ND);
-    AL(yp, (size_t)B * ND); AL(step, (size_t)B * ND);
-    AL(timing, (size_t)(B + 1) * 32);   // (+ one block for the phase stamps of a diagnostics build)
-    AL(mmeta, (size_t)B * (4 + 3 * GFBE_MAX_PRIOR_BLOCKS)); AL(mx0, (size_t)B * PRIOR_X0);
-    const size_t zero_end = b->dry ? b->slab_bytes : b->slab_off;
-    // -- written before they are read: no clearing (block-CSR records only exist for the inspection API)
-    AL(prior_J0, (size_t)B * ND * ND);     // (the n x n prior block arrives by copy; nothing reads past it)
-    AL(lm_obs, (size_t)MAXOBS * 5 * TL); AL(lm_rec, (size_t)MAXOBS * TL);   // (k_expand / k_ftab_pack write the rows of a track; the evaluation uses a row only below the track's length: 0.9 of the 2.8 MB per window that used to be cleared)
-    AL(lm_hP, (size_t)MAXOBS * 6 * TL);    // (k_vis writes the rows below a track's length, k_schur masks the others per landmark: 1.0 MB per window)
-    AL(vis_part, (size_t)B * std::max(max_tiles, 1) * MAXOBS * VP_STRIDE);   // (a tile's steps below its longest track are written by k_vis, the others never read)
-    // (the second set: the solve's linearisation only — its 7 x 7 partials take VPY_STRIDE doubles per step when no window frees the extrinsic / td)
-    if (d.spec) { AL(lm_hP2, (size_t)MAXOBS * 6 * TL); AL(vis_part2, (size_t)B * std::max(max_tiles, 1) * MAXOBS * (d.vis_full ? (size_t)VP_STRIDE : (size_t)VPY_STRIDE)); }
-    else { d.lm_hP2 = nullptr; d.vis_part2 = nullptr; }
-    AL(mA, (size_t)B * ND * ND); AL(mb, (size_t)B * ND); AL(mJ0, (size_t)B * ND * ND); AL(mr0, (size_t)B * ND);   // (k_marg / k_marg_ldlt write what they and k_gather read)
-    AL(x, (size_t)B * 2 * NA); AL(xout, (size_t)B * NA);                 // (k_reset / k_reanchor write them before anything reads)
-    AL(pc, (size_t)B * 3 * NPAIR * PAIR_CONST_DOUBLES);                   // (written by the kernels that produce a state)
-    AL(prior_H, (size_t)B * ND * ND);      // (k_prep writes the n x n block k_assemble reads)
-    // (k_assemble writes every entry of H (lower triangle) its table lists, g, E, eg it owns, k_visblock the exchange row: no clearing
-    //  here — a batch on the compact table clears H once at upload, below)
-    // the partial reduced system [H | g | E | eg | xa] is one slab: a single all-reduce per linearisation when the
-    // landmarks are sharded over ranks
-    {
-      const size_t nH = (size_t)B * ND * ND, ng = (size_t)B * ND, nE = (size_t)B * NV * NV, ne = (size_t)B * NV, nx = (size_t)B * d.world * XCHG;
-      AL(H, nH + ng + nE + ne + nx);
-      if (!b->dry) { d.g = d.H + nH; d.E = d.g + ng; d.eg = d.E + nE; d.xa = d.eg + ne; }
-      b->slab_n = nH + ng + nE + ne + nx;
-    }
-    AL(dbg_imu, (size_t)B * MAX_IMU * 15 * 31); AL(dbg_wheel, (size_t)B * MAX_WHEEL * 6 * 23); AL(dbg_prior, (size_t)B * ND);
-    AL(rec, p.cx.want_records ? (size_t)tot_rec * REC : 1); AL(mV, (size_t)B * ND * ND);
-    AL(vis_contrib, B < DENSE_SPLIT_MIN_B ? (size_t)B * std::max(max_tiles, 1) * MAXOBS * 16 * LM_TILE : 1);
-    d.solve_scratch_stride = d.solve_big ? (size_t)BIG_LD * BIG_LD : solve_chain_scratch_doubles();
-    AL(solveY, d.solve_big ? 1 : (size_t)B * solve_chain_scratch_doubles());
-    AL(solveS, d.solve_big ? (size_t)B * BIG_LD * BIG_LD : 1);
-    AL(gnss_J, (size_t)std::max(tot_gnss, 1) * 36); AL(gnss_r, (size_t)std::max(tot_gnss, 1) * 2);
-    if (d.spec) { AL(gnss_J2, (size_t)std::max(tot_gnss, 1) * 36); AL(gnss_r2, (size_t)std::max(tot_gnss, 1) * 2); AL(gnss_cost2, (size_t)B * 2); }
-    else { d.gnss_J2 = d.gnss_r2 = d.gnss_cost2 = nullptr; }
-    AL(gnss_cost, (size_t)B * 2); AL(gnss_marg, d.any_gnss ? (size_t)B * GN_MPART : 1);
-    AL(dl_fix, (size_t)B * DL_FIX); AL(dl_feat, p.feat_off[B]); AL(dl_J0, (size_t)p.j0_off[B]);
-    if (!b->dry) { b->up_end = up_end; b->zero_end = zero_end; }
-#undef AL
+  for (;;) {
+    b->slab_bytes = carve_slab(p, d, nullptr, chain, pack).bytes;
+    if ((st = slab_acquire(c, b)) == GFBE_OK) break;
+    if (!d.spec) return st;
+    // (the second set of the linearisation's outputs is ~1 MB per 2k-landmark window — a batch that fitted the device
+    //  before the option existed must still fit: size the slab again without it; the note travels with the batch's create note)
+    d.spec = 0;
+    c->err.clear();
+    c->note = "speculative_linearization switched off for a batch: its second set of outputs did not fit the device";
   }
+  b->up_h = pin_acquire(c, upload_region(p, nullptr).bytes, &b->up_cap);
+  if (!b->up_h) { c->err = "hipHostMalloc(upload staging) failed"; return GFBE_DEVICE_ERROR; }
+  SlabLayout lay = carve_slab(p, d, b->slab, chain, pack);
+  if (lay.bytes > b->slab_bytes) { c->err = "batch slab overrun"; return GFBE_DEVICE_ERROR; }
+  *dev = lay.up; *host = upload_region(p, b->up_h);
+  b->up_end = lay.up_end; b->zero_end = lay.zero_end; b->arrays = std::move(lay.arrays);
   // download staging: [dl_fix | dl_feat | dl_J0] are contiguous at the end of the slab -> one device-to-host copy
-  b->dl_bytes = (size_t)((char *)(d.dl_J0 + p.j0_off[B]) - (char *)d.dl_fix);
+  b->dl_bytes = (size_t)((char *)(d.dl_J0 + p.j0_off[p.B]) - (char *)d.dl_fix);
   return GFBE_OK;
 }
 
@@ -804,8 +700,8 @@ gfbe_status enqueue_upload(gfbe_ctx *c, gfbe_batch *b, const UploadPlan &p, cons
   //  GFBE_POISON_UNCLEARED=1: all of it; =<array name>: that array alone. Ahead of BOTH upload paths (the hook used to
   //  switch k_ingest_small off, so the shipped single-window upload's cleared ranges were never tested under poison).
   if (poison_env)
-    for (const auto &pl : b->poison_list)
-      if (pl.off >= b->zero_end && (!strcmp(poison_env, "1") || !strcmp(poison_env, "clean") || !strcmp(poison_env, pl.name)))
+    for (const auto &pl : b->arrays)
+      if (pl.off >= b->zero_end && (!strcmp(poison_env, "1") || !strcmp(poison_env, "clean") || pl.name == poison_env))
         HIPCHK(c, hipMemsetAsync(b->slab + pl.off, strcmp(poison_env, "clean") ? 0xFF : 0, pl.bytes, us));   // ("clean": zeros, for a scan that poisons one array at a time)
   if (ingest) {
     const bool clearH = d.asm_tab == c->asm_compact;
@@ -882,7 +778,7 @@ static gfbe_status upload_one(gfbe_ctx *c, int32_t B, const gfbe_window *const *
   b->up_win_bytes.assign(B, 0.0);
   const double T1 = now_ms();
   UploadMirror dev, host;
-  if ((st = carve_batch(c, b, plan, poison_env, &dev, &host)) != GFBE_OK) return st;
+  if ((st = carve_batch(c, b, plan, &dev, &host)) != GFBE_OK) return st;
   const double T2 = now_ms();
   pack_batch_tables(plan, host);
   for_each_window(B, [&](int w) { b->up_win_bytes[w] = pack_window(plan, w, *wins[w], host, b->slot_of[w]); });

@@ -1505,8 +1505,8 @@ __device__ __forceinline__ void dense_tp_factor(const BatchDev &d, int mode, int
   if (act == 0) return;
   // (BatchDev::spec: the set of outputs of the window this linearisation goes to — lin_view's selection for the two arrays written here)
   const int lset = (d.spec && mode == 0) ? (spec ? 1 - d.ctl[w].lb : d.ctl[w].lb) : 0;
-  double *part = IMU ? (lset ? d.imu_part2 : d.imu_part) + ((size_t)w * MAX_IMU + f) * IMU_PART
-                     : (lset ? d.wheel_part2 : d.wheel_part) + ((size_t)w * MAX_WHEEL + f) * WHEEL_PART;
+  double *part = IMU ? d.lin_set(lset).imu_part + ((size_t)w * MAX_IMU + f) * IMU_PART
+                     : d.lin_set(lset).wheel_part + ((size_t)w * MAX_WHEEL + f) * WHEEL_PART;
   if (act == 2) { if (mode == 1 && lane == 0) part[K::PART - 1] = 0.0; return; }
   const double *Xw = X + wv * 512, *Sw = St + wv * 256;
   double sa[NK], xb[NK];
@@ -1561,7 +1561,7 @@ __global__ __launch_bounds__(256) void k_prior_tp(BatchDev d, int mode, int lds_
   const WinCtl &c = d.ctl[w];
   if (!dense_pass_active(c, mode, spec)) return;
   // (BatchDev::spec: the set of outputs this linearisation goes to, as lin_view selects it)
-  double *pg = ((d.spec && mode == 0 && (spec ? 1 - c.lb : c.lb)) ? d.prior_g2 : d.prior_g) + (size_t)w * (ND + 2);
+  double *pg = d.lin_set(d.spec && mode == 0 && (spec ? 1 - c.lb : c.lb)).prior_g + (size_t)w * (ND + 2);
   const int n = ds.prior_n;
   if (n == 0) { if (t == 0) { pg[ND] = 0.0; pg[ND + 1] = 0.0; } return; }
   double *dx = psm, *rp = psm + ND, *pp = psm + 2 * ND, *sJ = psm + 6 * ND;
@@ -2005,7 +2005,7 @@ __global__ __launch_bounds__(256, GFBE_SCHUR_WGS) void k_schur(BatchDev d0, int 
 // tolerance like every other pair of kernel sets (tests/test_gpu_linschur.py).
 // d_k still goes to lm_hP (one write, one read by k_lm_step; the slow E rebuild of a mu retry reads it too) — see WRITE_D.
 // SPEC: the linearisation at the candidate, into the other set of outputs (vis_body's SPEC); the Schur partial then belongs to that set
-// too (schur_part2, lin_view). gate_mu (not SPEC; batches with the second set): the launch in front of every later iteration — only
+// too (lin2.schur_part, lin_view). gate_mu (not SPEC; batches with the second set): the launch in front of every later iteration — only
 // the windows whose current set was formed with another mu than the window's (after TrustRegionMinimizer::HandleInvalidStep: mu x 10
 // on the same linearisation) are evaluated again; k_visasm records the mu of a set that is about to be solved (WinCtl::sw_mu).
 // MEASURED SLOWER than the two kernels (profiles/r6_linschur_ab.txt; gfbe_options.merge_lin_schur is 0 by default): neither kernel

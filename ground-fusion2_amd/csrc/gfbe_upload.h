@@ -1,13 +1,13 @@
 // gfbe_upload.h — the host arithmetic of a batch upload, free of HIP calls: validation and landmark layout of the windows (plan_upload),
-// the layout of the upload region (upload_region) and the packing of one window into it (pack_window). gfbe_host.cpp runs these between
-// its HIP calls (upload_one); tests/upload_host_shim.cpp and tests/upload_host_main.cpp run them against plain heap buffers.
+// the allocation sequence of the batch's slab (carve_slab: the upload region — upload_region —, the cleared arrays, the rest; both sets of the
+// linearisation's outputs through one pair of helpers) and the packing of one window into the upload region (pack_window). gfbe_host.cpp
+// runs these between its HIP calls (upload_one); tests/upload_host_shim.cpp and tests/upload_host_main.cpp run them against plain heap buffers.
 #pragma once
 #include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstring>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "gfbe_device.h"
@@ -285,6 +285,9 @@ inline void plan_to_batch(const UploadPlan &p, BatchDev &d) {
 // bytes an array of n elements takes in the slab
 template <typename T>
 inline size_t slab_bytes_of(size_t n) { return (std::max<size_t>(n, 1) * sizeof(T) + 255) & ~(size_t)255; }
+// the next array of an allocation sequence over `base` (nullptr: sizes only)
+template <typename T>
+inline void slab_take(char *base, size_t &off, T *&ptr, size_t n) { ptr = base ? (T *)(base + off) : nullptr; off += slab_bytes_of<T>(n); }
 
 struct UploadMirror {
   WinDesc *desc; int *tile_start; double *x0;
@@ -301,11 +304,7 @@ inline UploadMirror upload_region(const UploadPlan &p, char *base) {
   UploadMirror m;
   std::memset(&m, 0, sizeof m);
   size_t off = 0;
-  auto up = [&](auto *&ptr, size_t n) {
-    typedef typename std::remove_reference<decltype(*ptr)>::type T;
-    ptr = base ? (T *)(base + off) : nullptr;
-    off += slab_bytes_of<T>(n);
-  };
+  auto up = [&](auto *&ptr, size_t n) { slab_take(base, off, ptr, n); };
   const size_t B = p.B, TL = p.tot_lm;
   up(m.desc, B); up(m.tile_start, p.tile_start.size()); up(m.x0, B * NA);
   up(m.imu, p.n_imu_tot); up(m.wheel, p.n_wheel_tot); up(m.lio, (size_t)p.tot_lio * 8);
@@ -326,6 +325,103 @@ inline void point_upload_region(const UploadMirror &m, BatchDev &d) {
   d.prior_r0 = m.prior_r0; d.prior_x0 = m.prior_x0; d.dl_feat_off = m.dl_feat_off; d.dl_j0_off = m.dl_j0_off; d.gnss_obs = m.gnss_obs;
   if (m.lm_info) { d.lm_info = m.lm_info; d.lm_abi = m.lm_abi; d.lm_pts = m.lm_pts; d.lam0 = m.lam0; d.fobs = m.fobs; d.fvel = m.fvel; }
 }
+// ---- the slab: every device array of a batch, carved from ONE allocation. Two passes over one allocation sequence (carve_slab): a dry
+// pass over no base adds up the sizes, the slab comes from the context's cache (or hipMalloc), the second pass hands out the pointers.
+// The arrays the host fills come FIRST ("upload region", upload_region above): they have a mirror at the same offsets in one pinned
+// host buffer, the packing threads write straight into that mirror, and the whole region crosses PCIe as ONE hipMemcpyAsync. Then the
+// arrays the kernels expect zeroed — only they are cleared (one hipMemsetAsync) —, then the ones that are written before they are read.
+struct SlabArray { std::string name; size_t off, bytes; };
+struct SlabLayout {
+  // the whole slab; [0, up_end) upload region, [up_end, zero_end) cleared, the rest written before read; doubles of the [H | g | E | eg | xa] slab
+  size_t bytes = 0, up_end = 0, zero_end = 0, slab_n = 0;
+  UploadMirror up;                              // the upload region over the base
+  std::vector<SlabArray> arrays;                // every array behind the upload region, by name (the second set's: lm_hP2, vis_part2, ...)
+};
+// One set of the linearisation's outputs (LinSet), once per set, through the carver `al(pointer, name, elements)` of carve_slab: the
+// members that start as zeros ...
+template <class Carver>
+void carve_lin_cleared(Carver &al, const BatchDev &d, LinSet &s, const std::string &sfx, bool own_schur) {
+  const size_t B = d.B, TL = d.tot_lm;
+  al(s.lm_Hll, "lm_Hll" + sfx, TL); al(s.lm_gl, "lm_gl" + sfx, TL); al(s.lm_hC, "lm_hC" + sfx, (size_t)HC * TL); al(s.lm_sw, "lm_sw" + sfx, TL);
+  if (own_schur) al(s.schur_part, "schur_part" + sfx, B * d.schur_groups * SCHUR_STRIDE); else s.schur_part = d.schur_part;
+  al(s.imu_part, "imu_part" + sfx, B * MAX_IMU * IMU_PART); al(s.wheel_part, "wheel_part" + sfx, B * MAX_WHEEL * WHEEL_PART);
+  al(s.plane_part, "plane_part" + sfx, d.any_plane ? B * MAX_PLANE * PLANE_PART : 1); al(s.anchor_part, "anchor_part" + sfx, d.any_plane ? B * ANCHOR_PART : 1);
+  al(s.prior_g, "prior_g" + sfx, B * (ND + 2)); al(s.lio_part, "lio_part" + sfx, B * LIOW_WGS * LIOW_PART);
+}
+// ... and the members that are written before they are read. vis_stride: doubles per (tile, observation step) slot of vis_part.
+template <class Carver>
+void carve_lin_written(Carver &al, const BatchDev &d, LinSet &s, const std::string &sfx, size_t vis_stride) {
+  const size_t B = d.B, TL = d.tot_lm, ng = std::max(d.tot_gnss, 1);
+  al(s.lm_hP, "lm_hP" + sfx, (size_t)MAXOBS * 6 * TL);    // (k_vis writes the rows below a track's length, k_schur masks the others per landmark: 1.0 MB per window)
+  al(s.vis_part, "vis_part" + sfx, B * std::max(d.max_tiles, 1) * MAXOBS * vis_stride);   // (a tile's steps below its longest track are written by k_vis, the others never read)
+  al(s.gnss_J, "gnss_J" + sfx, ng * 36); al(s.gnss_r, "gnss_r" + sfx, ng * 2); al(s.gnss_cost, "gnss_cost" + sfx, B * 2);
+}
+
+// The allocation sequence of the whole slab over `base` (nullptr: sizes only, every pointer null). d: the batch as plan_to_batch left
+// it (d.spec may have been taken back since: a slab that did not fit); receives the pointers, vs_blocks and solve_scratch_stride.
+// chain_scratch_doubles = solve_chain_scratch_doubles(), sys_pack_doubles = sys_pack_doubles_host(nu, world) (sharded batches): the
+// two sizes the kernels' translation units own.
+inline SlabLayout carve_slab(const UploadPlan &p, BatchDev &d, char *base, size_t chain_scratch_doubles, size_t sys_pack_doubles) {
+  SlabLayout lay;
+  const size_t B = p.B, TL = p.tot_lm, tiles = std::max(p.max_tiles, 1);
+  const bool small = p.B < DENSE_SPLIT_MIN_B;
+  // -- upload region
+  lay.up = upload_region(p, base);
+  if (base) point_upload_region(lay.up, d);
+  size_t off = lay.up_end = lay.up.bytes;
+  auto al = [&](auto *&ptr, const std::string &name, size_t n) { const size_t o = off; slab_take(base, off, ptr, n); lay.arrays.push_back({name, o, off - o}); };
+  // -- arrays the kernels expect zeroed at the start (rows past a track's length, partials of absent factors, ...)
+  if (p.table_fed) { al(d.lm_info, "lm_info", TL); al(d.lm_abi, "lm_abi", TL); al(d.lm_pts, "lm_pts", 6 * TL); al(d.lam0, "lam0", TL); d.fobs = nullptr; d.fvel = nullptr; }
+  al(d.raw_imu, "raw_imu", (size_t)MAX_IMU * (15 + 450) * 4 * ((B + 3) / 4)); al(d.raw_wheel, "raw_wheel", (size_t)MAX_WHEEL * (6 + 132) * 4 * ((B + 3) / 4));   // [factor][window / 4][value][window % 4]
+  al(d.zero, "zero", 16); al(d.vis_H, "vis_H", B * NV * (NV + 1));
+  d.vs_blocks = d.vis_full ? (int)VS_BLOCKS : 1;
+  if (small && !d.sharded) al(d.vis_Hs, "vis_Hs", B * d.vs_blocks * NV * (NV + 1)); else d.vis_Hs = nullptr;
+  al(d.ctl, "ctl", B);
+  al(d.lam, "lam", 2 * TL); al(d.lm_sl, "lm_sl", TL); al(d.lm_yl, "lm_yl", TL); al(d.lm_vl, "lm_vl", TL);
+  al(d.imu_sqrt, "imu_sqrt", (size_t)p.n_imu_tot * 225); al(d.wheel_sqrt, "wheel_sqrt", (size_t)p.n_wheel_tot * 36);
+  al(d.pair_part, "pair_part", B * NF * VP_STRIDE);
+  carve_lin_cleared(al, d, d, "", true);
+  // (the second set, cleared like the first; its Schur partial is its own where the candidate's pass eliminates the landmarks too)
+  if (d.spec) carve_lin_cleared(al, d, d.lin2, "2", d.linschur != 0); else d.lin2 = LinSet{};
+  al(d.tile_cost, "tile_cost", B * tiles); al(d.tile_cand, "tile_cand", B * tiles * 4);
+  al(d.tile_cnt, "tile_cnt", small ? B * tiles : 1); al(d.win_cnt, "win_cnt", small ? B * 2 : 1);
+  al(d.tile_gram, "tile_gram", B * tiles * 8); al(d.dense_cand, "dense_cand", B * 4);
+  al(d.xb, "xb", B * d.world * XCHG); al(d.xc, "xc", B * d.world * XCHG);
+  if (d.sharded) { al(d.Er, "Er", B * (NV * NV + NV)); al(d.sys_pack, "sys_pack", B * sys_pack_doubles); } else { d.Er = nullptr; d.sys_pack = nullptr; }
+  al(d.sp, "sp", B * ND); al(d.Dp, "Dp", B * ND); al(d.gts, "gts", B * ND); al(d.vp, "vp", B * ND); al(d.yp, "yp", B * ND); al(d.step, "step", B * ND);
+  al(d.timing, "timing", (B + 1) * 32);   // (+ one block for the phase stamps of a diagnostics build)
+  al(d.mmeta, "mmeta", B * (4 + 3 * GFBE_MAX_PRIOR_BLOCKS)); al(d.mx0, "mx0", B * PRIOR_X0);
+  lay.zero_end = off;
+  // -- written before they are read: no clearing (block-CSR records only exist for the inspection API)
+  al(d.prior_J0, "prior_J0", B * ND * ND);     // (the n x n prior block arrives by copy; nothing reads past it)
+  al(d.lm_obs, "lm_obs", (size_t)MAXOBS * 5 * TL); al(d.lm_rec, "lm_rec", (size_t)MAXOBS * TL);   // (k_expand / k_ftab_pack write the rows of a track; the evaluation uses a row only below the track's length: 0.9 of the 2.8 MB per window that used to be cleared)
+  carve_lin_written(al, d, d, "", VP_STRIDE);
+  // (the second set: the solve's linearisation only — its 7 x 7 partials take VPY_STRIDE doubles per step when no window frees the extrinsic / td)
+  if (d.spec) carve_lin_written(al, d, d.lin2, "2", d.vis_full ? (size_t)VP_STRIDE : (size_t)VPY_STRIDE);
+  al(d.mA, "mA", B * ND * ND); al(d.mb, "mb", B * ND); al(d.mJ0, "mJ0", B * ND * ND); al(d.mr0, "mr0", B * ND);   // (k_marg / k_marg_ldlt write what they and k_gather read)
+  al(d.x, "x", B * 2 * NA); al(d.xout, "xout", B * NA);                 // (k_reset / k_reanchor write them before anything reads)
+  al(d.pc, "pc", B * 3 * NPAIR * PAIR_CONST_DOUBLES);                   // (written by the kernels that produce a state)
+  al(d.prior_H, "prior_H", B * ND * ND);      // (k_prep writes the n x n block k_assemble reads)
+  // (k_assemble writes every entry of H (lower triangle) its table lists, g, E, eg it owns, k_visblock the exchange row: no clearing
+  //  here — a batch on the compact table clears H once at upload)
+  // the partial reduced system [H | g | E | eg | xa] is one slab: a single all-reduce per linearisation when the
+  // landmarks are sharded over ranks
+  const size_t nH = B * ND * ND, ng = B * ND, nE = B * NV * NV, ne = B * NV;
+  al(d.H, "H", lay.slab_n = nH + ng + nE + ne + B * d.world * XCHG);
+  if (base) { d.g = d.H + nH; d.E = d.g + ng; d.eg = d.E + nE; d.xa = d.eg + ne; }
+  al(d.dbg_imu, "dbg_imu", B * MAX_IMU * 15 * 31); al(d.dbg_wheel, "dbg_wheel", B * MAX_WHEEL * 6 * 23); al(d.dbg_prior, "dbg_prior", B * ND);
+  al(d.rec, "rec", p.cx.want_records ? (size_t)p.tot_rec * REC : 1); al(d.mV, "mV", B * ND * ND);
+  al(d.vis_contrib, "vis_contrib", small ? B * tiles * MAXOBS * 16 * LM_TILE : 1);
+  d.solve_scratch_stride = d.solve_big ? (size_t)BIG_LD * BIG_LD : chain_scratch_doubles;
+  al(d.solveY, "solveY", d.solve_big ? 1 : B * chain_scratch_doubles);
+  al(d.solveS, "solveS", d.solve_big ? B * BIG_LD * BIG_LD : 1);
+  al(d.gnss_marg, "gnss_marg", d.any_gnss ? B * GN_MPART : 1);
+  // (the results last and contiguous: [dl_fix | dl_feat | dl_J0] leave in one device-to-host copy)
+  al(d.dl_fix, "dl_fix", B * DL_FIX); al(d.dl_feat, "dl_feat", p.feat_off[B]); al(d.dl_J0, "dl_J0", (size_t)p.j0_off[B]);
+  lay.bytes = off;
+  return lay;
+}
+
 // the batch-wide tables of the region (once per batch, before the windows are packed)
 inline void pack_batch_tables(const UploadPlan &p, const UploadMirror &m) {
   if (!p.tile_start.empty()) std::memcpy(m.tile_start, p.tile_start.data(), sizeof(int) * p.tile_start.size());   // (no landmarks: data() may be null)

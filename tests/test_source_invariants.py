@@ -1,9 +1,8 @@
 """Source-level invariants of the product's host / device headers that no runtime test on a CPU box can see (no GPU here).
 
-Speculative linearisation keeps a SECOND set of the linearisation's outputs (BatchDev members named `<first>2`, csrc/gfbe_device.h);
-the kernels between two linearisations see the current set through lin_view (csrc/gfbe_devutil.h), which must swap every one of them,
-and gfbe_host.cpp must point every one of them into the slab. A member added to one place and not the others would read a stale or
-null array only in windows whose step was accepted — these checks fail first.
+Speculative linearisation keeps a SECOND set of the linearisation's outputs: BatchDev::lin2, a LinSet like the batch's own
+(csrc/gfbe_device.h). That every member of it is carved from the slab and swapped by lin_view is checked by RUNNING carve_slab and
+lin_view (tests/test_upload_host.py); what stays here is that no hand-kept `<member>2` twin of a LinSet member comes back.
 """
 import os
 import re
@@ -16,35 +15,20 @@ def _read(name):
         return f.read()
 
 
-def _second_set_members():
+def _lin_set_members():
     dev = _read("gfbe_device.h")
-    body = dev[dev.index("struct BatchDev"):]
-    body = body[:body.index("\n};")]
-    names = re.findall(r"\*\s*([A-Za-z_][A-Za-z_0-9]*2)\b", body)
-    members = set(re.findall(r"\*\s*([A-Za-z_][A-Za-z_0-9]*)\b", body))
-    return sorted(n for n in set(names) if n[:-1] in members)
+    body = dev[dev.index("struct LinSet {"):]
+    body = re.sub(r"//[^\n]*", "", body[:body.index("\n};")])
+    return sorted(set(re.findall(r"\*\s*([A-Za-z_][A-Za-z_0-9]*)\b", body)))
 
 
-def test_second_set_is_declared():
-    second = _second_set_members()
-    assert len(second) >= 15 and "lm_hP2" in second and "gnss_cost2" in second, second
-
-
-def test_lin_view_swaps_every_second_set_member():
-    util = _read("gfbe_devutil.h")
-    view = util[util.index("BatchDev lin_view("):]
-    view = view[:view.index("return v;")]
-    for name in _second_set_members():
-        assert re.search(r"v\.%s\s*=\s*d\.%s\s*;" % (name[:-1], name), view), "lin_view does not swap " + name
-
-
-def test_host_points_every_second_set_member_into_the_slab():
-    host = _read("gfbe_host.cpp")
-    carve = host[host.index("gfbe_status carve_batch("):]
-    carve = carve[:carve.index("#undef AL")]
-    for name in _second_set_members():
-        assert re.search(r"\bd\.%s\s*=" % name, host), "gfbe_host.cpp never sets BatchDev::" + name
-        assert re.search(r"\bAL\(%s\s*," % name, carve), "carve_batch (gfbe_host.cpp) never carves BatchDev::" + name + " from the slab"
+def test_no_second_set_member_is_kept_by_hand():
+    members = _lin_set_members()
+    assert len(members) >= 16 and "lm_hP" in members and "gnss_cost" in members and "schur_part" in members, members
+    for name in ("gfbe_device.h", "gfbe_host.cpp"):
+        text = re.sub(r"//[^\n]*", "", _read(name))
+        for m in members:
+            assert not re.search(r"(?<![A-Za-z_0-9\"])%s2\b" % m, text), "%s declares or assigns %s2" % (name, m)
 
 
 def test_options_default_and_binding_agree_on_the_speculative_pass():

@@ -1,6 +1,8 @@
 """The host half of a batch upload (csrc/gfbe_upload.h: plan_upload, upload_region, pack_window) without a GPU: compiled for the host by
 tests/upload_host_shim.cpp, fed windows through the ctypes structs of abi.py, and checked — exact integers, bit-equal doubles — against
 the windows themselves and against independent numpy restatements of the layout rule, the free-block table and prior_out_bound.
+The slab's allocation sequence (carve_slab) and lin_view (csrc/gfbe_device.h) run here too: both sets of the linearisation's outputs are
+walked as the pointer slots of a LinSet, so a member added to the struct is covered without anybody naming it.
 tests/upload_host_main.cpp runs the same code under the address and undefined-behaviour sanitizers as a stand-alone program."""
 import ctypes as C
 import os
@@ -43,6 +45,11 @@ def shim():
     lib.uh_array.restype = C.c_void_p
     lib.uh_array.argtypes = [C.c_void_p, C.c_char_p]
     lib.uh_free.argtypes = [C.c_void_p]
+    lib.uh_carve.restype = C.c_void_p
+    lib.uh_carve.argtypes = [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong]
+    lib.uh_carve_free.argtypes = [C.c_void_p]
+    for f in (lib.uh_carve_info, lib.uh_carve_array, lib.uh_carve_slots, lib.uh_carve_upload, lib.uh_lin_view):
+        f.argtypes = None
     assert lib.uh_sizes(0) == 88 and lib.uh_sizes(2) == 64 and lib.uh_sizes(3) == C.sizeof(abi.GnssObs)
     return lib
 
@@ -512,6 +519,203 @@ def test_every_refusal_keeps_its_status_and_message(shim):
     opt.max_solver_time_in_seconds = 0.04
     assert _refused(shim, [abi.WindowHolder(good)], allreduce=1, opt=opt) == (
         abi.BAD_INPUT, "max_solver_time_in_seconds is not available with landmark sharding (gfbe_set_allreduce)")
+
+
+# ---- the slab's allocation sequence and lin_view ----------------------------------------------------------------------------------
+CARVE = ("dry_bytes", "dry_up_end", "dry_zero_end", "bytes", "up_end", "zero_end", "slab_n", "dry_slab_n", "n_arrays", "dry_n_arrays", "slots", "spec",
+         "linschur", "vis_full", "H", "g", "E", "eg", "xa", "vs_blocks", "solve_scratch_stride", "VP_STRIDE", "VPY_STRIDE")
+CHAIN, PACK = 96 * 104, 12345       # (stand-ins for the two sizes the kernels' translation units own: any numbers do)
+
+
+def _opt(shim, **kw):
+    opt = abi.Options()
+    shim.uh_default_options(C.byref(opt))
+    for k, v in kw.items():
+        setattr(opt, k, v)
+    return opt
+
+
+def _many(n, **over):
+    return [window(MIX[:20 + 3 * (w % 7)], seed=20 + w, **(over if w == 5 else {})) for w in range(n)]
+
+
+PLANS = {
+    "one_window": lambda shim: dict(snaps=[CASES["no_prior"]]),
+    "33_windows": lambda shim: dict(snaps=_many(33)),
+    "33_windows_linschur": lambda shim: dict(snaps=_many(33), opt=_opt(shim, merge_lin_schur=1)),
+    "33_windows_vis_full": lambda shim: dict(snaps=_many(33, ex_cam_const=0)),
+    "no_landmarks": lambda shim: dict(snaps=[CASES["no_landmarks"]]),
+    "gnss": lambda shim: dict(snaps=[CASES["gnss_unordered"]]),
+    "plane_anchor": lambda shim: dict(snaps=[CASES["plane_anchor"]]),
+    "lidar": lambda shim: dict(snaps=[CASES["lio_unweighted"]]),
+    "allreduce": lambda shim: dict(snaps=[CASES["no_prior"], CASES["prior_small"], CASES["tile_edge_65"]], allreduce=1),
+}
+
+
+class Carved:
+    def __init__(self, lib, packed_h, spec_off=0):
+        self.lib = lib
+        self.h = C.c_void_p(lib.uh_carve(packed_h, spec_off, CHAIN, PACK))
+        v = (C.c_longlong * len(CARVE))()
+        lib.uh_carve_info(self.h, v)
+        self.info = dict(zip(CARVE, v))
+        self.arrays, self.dry_arrays = self._arrays(0, self.info["n_arrays"]), self._arrays(1, self.info["dry_n_arrays"])
+        self.by_off = {off: (name, nbytes) for name, off, nbytes in self.arrays}
+        self.set = [self._slots(0), self._slots(1)]
+
+    def _arrays(self, dry, n):
+        out, name, off, nb = [], C.create_string_buffer(64), C.c_longlong(), C.c_longlong()
+        for k in range(n):
+            self.lib.uh_carve_array(self.h, dry, k, name, 64, C.byref(off), C.byref(nb))
+            out.append((name.value.decode(), off.value, nb.value))
+        return out
+
+    def _slots(self, k):
+        v = (C.c_longlong * self.info["slots"])()
+        self.lib.uh_carve_slots(self.h, k, v)
+        return list(v)
+
+    def view(self, lb, spec=-1):
+        lay = (C.c_int * 3)()
+        n = self.lib.uh_lin_view(self.h, lb, spec, None, None, lay)
+        d, v = (C.c_ubyte * n)(), (C.c_ubyte * n)()
+        self.lib.uh_lin_view(self.h, lb, spec, d, v, lay)
+        return bytes(d), bytes(v), tuple(lay)
+
+    def close(self):
+        self.lib.uh_carve_free(self.h)
+
+
+@pytest.fixture(scope="module")
+def carved_plans(shim):
+    """Every plan of PLANS, carved with the second set and with BatchDev::spec taken back: [(name, packed, on, off)]."""
+    out = []
+    for name in PLANS:
+        kw = PLANS[name](shim)
+        p = Packed(shim, kw.pop("snaps"), **kw)
+        assert p.status == abi.OK, p.err
+        out.append((name, p, Carved(shim, p.h), Carved(shim, p.h, spec_off=1)))
+    yield out
+    for _, p, on, off in out:
+        on.close(); off.close(); p.close()
+
+
+def _every_plan(check):
+    """The test that runs `check` on every carved plan (one test, not one per plan: a failure names the plan)."""
+    def test(carved_plans, shim):
+        assert [c[0] for c in carved_plans] == list(PLANS) and len(PLANS) == 9
+        for carved in carved_plans:
+            try:
+                check(carved, shim)
+            except AssertionError as e:
+                raise AssertionError("plan %s: %s" % (carved[0], e)) from e
+    test.__doc__ = check.__doc__
+    return test
+
+
+def _plans_cover_the_paths_of_the_carve(carved, shim):
+    name, p, on, off = carved
+    want = dict(spec=name != "no_landmarks", linschur=name == "33_windows_linschur", vis_full=name == "33_windows_vis_full")
+    assert {k: bool(on.info[k]) for k in want} == want and not off.info["spec"]
+    assert p.info["spec"] == on.info["spec"] and p.info["linschur"] == on.info["linschur"]
+    assert (p.info["nu"] == ND) == (name == "gnss") and bool(p.info["any_plane"]) == (name == "plane_anchor") and (p.info["tot_lio"] > 0) == (name == "lidar")
+    assert on.info["vs_blocks"] == (20 if on.info["vis_full"] else 1)
+    assert on.info["solve_scratch_stride"] == (272 * 272 if name == "gnss" else CHAIN)
+    assert ("sys_pack" in [a[0] for a in on.arrays]) == (name == "allreduce")
+
+
+def _both_sets_are_carved_slot_by_slot(carved, shim):
+    """Was test_source_invariants: the second set is declared (>= 15 members, lm_hP and gnss_cost among them) and the host sets and carves
+    every member — here: every slot of a LinSet, whatever its name."""
+    _, p, on, off = carved
+    assert on.info["slots"] >= 16
+    for c in (on, off):
+        first, second = c.set
+        assert all(0 <= o < c.info["bytes"] for o in first), first
+        names = [c.by_off[o][0] for o in first]
+        assert len(set(names)) == len(names) and "lm_hP" in names and "gnss_cost" in names and "schur_part" in names
+        if not c.info["spec"]:
+            assert second == [-1] * len(first)
+            continue
+        assert all(0 <= o < c.info["bytes"] for o in second), second
+        for k, (a, b) in enumerate(zip(first, second)):
+            (na, sa), (nb, sb) = c.by_off[a], c.by_off[b]
+            if na == "schur_part" and not c.info["linschur"]:
+                assert b == a                   # the one permitted alias: the second set names the first set's Schur partial
+                continue
+            assert nb == na + "2" and b != a, (na, nb)
+            if na == "vis_part" and not c.info["vis_full"]:
+                cells = len(p.snaps) * max(p.info["max_tiles"], 1) * MAXOBS      # VP_STRIDE : VPY_STRIDE doubles per (tile, step), each array rounded up to 256 B
+                assert (sa, sb) == tuple(-(-cells * c.info[k] * 8 // 256) * 256 for k in ("VP_STRIDE", "VPY_STRIDE")) and (c.info["VP_STRIDE"], c.info["VPY_STRIDE"]) == (336, 32)
+            else:
+                assert sa == sb, (na, sa, sb)
+            assert (a < c.info["zero_end"]) == (b < c.info["zero_end"]), na
+        if c.info["linschur"]:
+            assert "schur_part2" in [c.by_off[o][0] for o in second]
+    if on.info["spec"]:
+        own = sum(on.by_off[b][1] for a, b in zip(*on.set) if b != a)
+        assert on.info["bytes"] - off.info["bytes"] == own > 0
+        assert (on.info["up_end"], on.info["zero_end"] - off.info["zero_end"]) == (off.info["up_end"], sum(on.by_off[b][1] for a, b in zip(*on.set) if b != a and b < on.info["zero_end"]))
+    else:
+        assert on.arrays == off.arrays and on.info == off.info
+
+
+def _slab_arrays_are_disjoint_and_in_their_regions(carved, shim):
+    _, p, on, off = carved
+    for c in (on, off):
+        i = c.info
+        assert (i["dry_bytes"], i["dry_up_end"], i["dry_zero_end"], i["dry_slab_n"]) == (i["bytes"], i["up_end"], i["zero_end"], i["slab_n"])
+        assert c.dry_arrays == c.arrays
+        assert i["up_end"] == p.info["up_bytes"] <= i["zero_end"] <= i["bytes"]
+        end = i["up_end"]
+        for name, o, nb in sorted(c.arrays, key=lambda a: a[1]):
+            assert o == end and nb > 0 and nb % 256 == 0, name       # back to back: pairwise disjoint, nothing between the regions
+            assert o >= i["zero_end"] or o + nb <= i["zero_end"], name
+            end = o + nb
+        assert end == i["bytes"]
+        assert len(set(a[0] for a in c.arrays)) == len(c.arrays)
+        # the one permitted overlap: [H | g | E | eg | xa] is one allocation
+        B, (h0, hb) = len(p.snaps), [(o, nb) for name, o, nb in c.arrays if name == "H"][0]
+        world = 1
+        assert [i[k] - h0 for k in ("H", "g", "E", "eg", "xa")] == list(8 * np.cumsum([0, B * ND * ND, B * ND, B * 73 * 73, B * 73]))
+        assert i["slab_n"] == B * (ND * ND + ND + 73 * 73 + 73 + world * 8) and i["slab_n"] * 8 <= hb < i["slab_n"] * 8 + 256
+        assert h0 >= i["zero_end"]
+        assert [a[0] for a in c.arrays][-3:] == ["dl_fix", "dl_feat", "dl_J0"]      # the results leave in one copy
+
+
+def _upload_region_of_the_slab_is_upload_region(carved, shim):
+    _, _, on, off = carved
+    for c in (on, off):
+        got, want = (C.c_longlong * 32)(), (C.c_longlong * 32)()
+        n = shim.uh_carve_upload(c.h, got, want)
+        assert n >= 17 and list(got)[:n] == list(want)[:n] and want[0] == 0
+
+
+def _lin_view_swaps_the_whole_set_and_nothing_else(carved, shim):
+    """Was test_source_invariants: lin_view swaps every member of the second set."""
+    _, _, on, off = carved
+    d, v, (o1, o2, n) = on.view(1)
+    assert o1 + n <= o2 and n == 8 * on.info["slots"]
+    if on.info["spec"]:
+        assert v[o1:o1 + n] == d[o2:o2 + n] and d[o1:o1 + n] != d[o2:o2 + n]
+        assert v[:o1] + v[o1 + n:] == d[:o1] + d[o1 + n:]
+        d, v, _ = on.view(1, spec=0)
+        assert v == d
+    else:
+        assert v == d
+    d, v, _ = on.view(0)
+    assert v == d
+    d, v, _ = off.view(1)
+    assert v == d
+    d, v, _ = off.view(1, spec=1)       # (a view never looks at the pointers: with the flag set it is the — empty — second set)
+    assert v[o1:o1 + n] == d[o2:o2 + n] == bytes(n)
+
+
+test_plans_cover_the_paths_of_the_carve = _every_plan(_plans_cover_the_paths_of_the_carve)
+test_both_sets_are_carved_slot_by_slot = _every_plan(_both_sets_are_carved_slot_by_slot)
+test_slab_arrays_are_disjoint_and_in_their_regions = _every_plan(_slab_arrays_are_disjoint_and_in_their_regions)
+test_upload_region_of_the_slab_is_upload_region = _every_plan(_upload_region_of_the_slab_is_upload_region)
+test_lin_view_swaps_the_whole_set_and_nothing_else = _every_plan(_lin_view_swaps_the_whole_set_and_nothing_else)
 
 
 def test_sanitized_stand_alone_program():

@@ -1,7 +1,8 @@
 // TEST INFRASTRUCTURE. The host half of a batch upload (csrc/gfbe_upload.h) as a stand-alone program for the address and undefined-
 // behaviour sanitizers (tests/test_upload_host.py::test_sanitized_stand_alone_program builds it with -fsanitize=address,undefined and
 // runs it): a handful of windows built here, planned and packed into heap buffers of exactly the planned size — a wrong index in the
-// packing is a heap overrun the sanitizer reports. No HIP call, no GPU.
+// packing is a heap overrun the sanitizer reports. Every plan's slab is carved too (carve_slab), dry and over a heap buffer of exactly the
+// dry pass's size, and the first and last byte of every array it lists are written. No HIP call, no GPU.
 #include "../ground-fusion2_amd/csrc/gfbe_upload.h"
 
 #include <cstdio>
@@ -81,6 +82,35 @@ struct Win {
 int failures = 0;
 #define CHECK(cond) do { if (!(cond)) { printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); failures++; } } while (0)
 
+// the slab of a plan, with the second set of the linearisation's outputs (where the plan has one) or without it
+void carve(const UploadPlan &plan, int with_spec) {
+  BatchDev d;
+  std::memset(&d, 0, sizeof d);
+  d.B = plan.B;
+  plan_to_batch(plan, d);
+  if (!with_spec) d.spec = 0;
+  const size_t chain = 96 * 104, pack = 4321;     // (stand-ins for the sizes the kernels' translation units own)
+  const SlabLayout dry = carve_slab(plan, d, nullptr, chain, pack);
+  CHECK(d.lm_hP == nullptr && d.lin2.gnss_cost == nullptr && d.dl_J0 == nullptr);
+  std::unique_ptr<char[]> buf(new char[dry.bytes]);
+  const SlabLayout lay = carve_slab(plan, d, buf.get(), chain, pack);
+  CHECK(lay.bytes == dry.bytes && lay.up_end == dry.up_end && lay.zero_end == dry.zero_end && lay.arrays.size() == dry.arrays.size());
+  CHECK(lay.up_end == upload_region(plan, nullptr).bytes && lay.up_end <= lay.zero_end && lay.zero_end <= lay.bytes);
+  for (const SlabArray &a : lay.arrays) {
+    CHECK(a.off >= lay.up_end && a.bytes > 0 && a.off + a.bytes <= lay.bytes);
+    buf[a.off] = 1; buf[a.off + a.bytes - 1] = 2;
+  }
+  double *const *s0 = (double *const *)&d.lin_set(0), *const *s1 = (double *const *)&d.lin_set(1);
+  for (size_t k = 0; k < sizeof(LinSet) / sizeof(double *); k++) {
+    CHECK(s0[k] != nullptr && (s1[k] != nullptr) == (d.spec != 0));
+    *(char *)s0[k] = 3;
+    if (s1[k]) *(char *)s1[k] = 4;
+  }
+  const BatchDev v = lin_view(d, 1);
+  CHECK(v.lm_hP == (d.spec ? d.lin2.lm_hP : d.lm_hP) && v.gnss_cost == (d.spec ? d.lin2.gnss_cost : d.gnss_cost) && v.lam == d.lam);
+  d.g[0] = 1.0; d.xa[(size_t)plan.B * d.world * XCHG - 1] = 2.0;      // the ends of the [H | g | E | eg | xa] slab's parts
+}
+
 // plan + pack into heap buffers of exactly the planned size; returns the status
 gfbe_status run(const std::vector<Win *> &set, const int *tcounts, std::string &err) {
   gfbe_options opt;
@@ -104,6 +134,7 @@ gfbe_status run(const std::vector<Win *> &set, const int *tcounts, std::string &
     if (!tcounts) for (int l = 0; l < plan.scan[w].L; l++) CHECK(m.lm_abi[slot_of[l]] == l);
   }
   CHECK(m.dl_feat_off[wins.size()] == plan.feat_off.back());
+  carve(plan, 1); carve(plan, 0);
   return GFBE_OK;
 }
 }  // namespace

@@ -1,5 +1,6 @@
 // TEST INFRASTRUCTURE. The host half of a batch upload (csrc/gfbe_upload.h) behind a C interface for tests/test_upload_host.py: plan B
-// windows, lay the upload region out in a malloc'ed buffer of exactly the planned size, pack every window into it. No HIP call.
+// windows, lay the upload region out in a malloc'ed buffer of exactly the planned size, pack every window into it; carve the whole slab of
+// the plan (carve_slab) into another one and look at a batch through lin_view. No HIP call.
 #include "../ground-fusion2_amd/csrc/gfbe_upload.h"
 
 #include <cstdio>
@@ -14,6 +15,16 @@ struct Packed {
   std::vector<std::vector<int>> slot_of;
   std::vector<double> win_bytes;
 };
+// the slab of a plan: the dry pass, then the real one over a malloc'ed buffer of the dry pass's size
+struct Carved {
+  BatchDev d;
+  SlabLayout dry, real;
+  UploadMirror alone;       // what upload_region alone returns over the same buffer
+  char *buf = nullptr;
+};
+enum { LIN_SLOTS = sizeof(LinSet) / sizeof(double *) };
+static_assert(sizeof(LinSet) == LIN_SLOTS * sizeof(double *), "a LinSet is pointer slots and nothing else");
+long long rel(const Carved *c, const void *q) { return q ? (long long)((const char *)q - c->buf) : -1; }
 }  // namespace
 
 extern "C" {
@@ -77,6 +88,67 @@ void *uh_array(void *hp, const char *name) {
   for (const auto &t : tab) if (!strcmp(t.n, name)) return t.p;
   return nullptr;
 }
+// ---- the slab of the plan. spec_off: with BatchDev::spec taken back (what carve_batch does when the slab does not fit); chain / pack: the two
+// sizes the kernels' translation units own
+void *uh_carve(void *hp, int spec_off, long long chain, long long pack) {
+  const UploadPlan &p = ((Packed *)hp)->plan;
+  Carved *c = new Carved();
+  std::memset(&c->d, 0, sizeof c->d);
+  c->d.B = p.B;
+  plan_to_batch(p, c->d);
+  if (spec_off) c->d.spec = 0;
+  c->dry = carve_slab(p, c->d, nullptr, (size_t)chain, (size_t)pack);
+  c->buf = (char *)malloc(c->dry.bytes);
+  c->real = carve_slab(p, c->d, c->buf, (size_t)chain, (size_t)pack);
+  c->alone = upload_region(p, c->buf);
+  return c;
+}
+void uh_carve_free(void *cp) { Carved *c = (Carved *)cp; if (c) { free(c->buf); delete c; } }
+// in the order of tests/test_upload_host.py::CARVE
+void uh_carve_info(void *cp, long long *out) {
+  const Carved *c = (const Carved *)cp;
+  const BatchDev &d = c->d;
+  const long long v[] = {(long long)c->dry.bytes, (long long)c->dry.up_end, (long long)c->dry.zero_end, (long long)c->real.bytes, (long long)c->real.up_end,
+                         (long long)c->real.zero_end, (long long)c->real.slab_n, (long long)c->dry.slab_n, (long long)c->real.arrays.size(),
+                         (long long)c->dry.arrays.size(), LIN_SLOTS, d.spec, d.linschur, d.vis_full, rel(c, d.H), rel(c, d.g), rel(c, d.E), rel(c, d.eg),
+                         rel(c, d.xa), d.vs_blocks, (long long)d.solve_scratch_stride, VP_STRIDE, VPY_STRIDE};
+  for (size_t k = 0; k < sizeof v / sizeof v[0]; k++) out[k] = v[k];
+}
+void uh_carve_array(void *cp, int dry, int k, char *name, int cap, long long *off, long long *bytes) {
+  const SlabArray &a = (dry ? ((Carved *)cp)->dry : ((Carved *)cp)->real).arrays[k];
+  snprintf(name, cap, "%s", a.name.c_str());
+  *off = (long long)a.off; *bytes = (long long)a.bytes;
+}
+// the slots of set `set` (0: the batch's own, 1: lin2) as offsets into the buffer, -1 for a null slot
+void uh_carve_slots(void *cp, int set, long long *out) {
+  const Carved *c = (const Carved *)cp;
+  double *const *slot = (double *const *)&c->d.lin_set(set);
+  for (int k = 0; k < LIN_SLOTS; k++) out[k] = rel(c, slot[k]);
+}
+// the upload region's pointers of the carved batch, then what upload_region alone gives for the same members (offsets, -1: null)
+int uh_carve_upload(void *cp, long long *got, long long *want) {
+  const Carved *c = (const Carved *)cp;
+  const BatchDev &d = c->d;
+  const UploadMirror &m = c->alone, &u = c->real.up;
+  const void *g[] = {d.desc, d.tile_start, d.x0, d.imu, d.wheel, d.lio, d.prior_r0, d.prior_x0, d.dl_feat_off, d.dl_j0_off, d.gnss_obs, u.pJ0c,
+                     m.lm_info ? d.lm_info : nullptr, m.lm_info ? d.lm_abi : nullptr, m.lm_info ? d.lm_pts : nullptr, m.lm_info ? d.lam0 : nullptr, d.fobs, d.fvel};
+  const void *w[] = {m.desc, m.tile_start, m.x0, m.imu, m.wheel, m.lio, m.prior_r0, m.prior_x0, m.dl_feat_off, m.dl_j0_off, m.gnss_obs, m.pJ0c,
+                     m.lm_info, m.lm_abi, m.lm_pts, m.lam0, m.fobs, m.fvel};
+  const int n = (int)(sizeof g / sizeof g[0]);
+  for (int k = 0; k < n; k++) { got[k] = rel(c, g[k]); want[k] = rel(c, w[k]); }
+  return u.bytes == m.bytes ? n : -1;
+}
+// lin_view(d, lb) of the carved batch, with BatchDev::spec as it is (spec < 0) or set to `spec`: the bytes of the batch it was called on and of
+// the view. Returns sizeof(BatchDev); lay = offsets of the first set and of lin2 inside it, sizeof(LinSet).
+int uh_lin_view(void *cp, int lb, int spec, unsigned char *of_d, unsigned char *of_view, int *lay) {
+  BatchDev d = ((Carved *)cp)->d;
+  if (spec >= 0) d.spec = spec;
+  const BatchDev v = lin_view(d, lb);
+  if (of_d) { std::memcpy(of_d, &d, sizeof d); std::memcpy(of_view, &v, sizeof v); }
+  lay[0] = (int)((const char *)static_cast<const LinSet *>(&d) - (const char *)&d); lay[1] = (int)((const char *)&d.lin2 - (const char *)&d); lay[2] = (int)sizeof(LinSet);
+  return (int)sizeof d;
+}
+
 // the table-fed entry of the layout rule on one window's [L, K, bins] counts
 void uh_table_layout(const int *counts, int *head, int *sf_tile_begin, int *pair_begin, int *lay) {
   WinScan sc;
