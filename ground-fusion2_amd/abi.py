@@ -1359,7 +1359,8 @@ class VoxelMap:
             if not hasattr(self.opt, k):
                 raise TypeError("gfbe_vmap_options has no field %r" % k)
             setattr(self.opt, k, v)
-        for name in ("create", "add_points", "erase_far", "size", "download", "upload", "associate", "linearize", "localizability", "register", "add_scan"):
+        for name in ("create", "add_points", "erase_far", "size", "download", "upload", "associate", "linearize", "localizability", "register", "add_scan",
+                     "register_scan", "add_scan_handle"):
             self._f(name).restype = c_i
         self._f("destroy").restype = None
         self._f("linearize").argtypes = [C.c_void_p, C.c_void_p, c_i, c_d, PD, PD, PD, PD, PD, PD, PD]
@@ -1478,3 +1479,114 @@ class VoxelMap:
         out = np.zeros((n, 3)) if want_world else None
         self._check(self._f("add_scan")(self.ctx, self.h, int(ct), n, _pd(raw), _pd(al), _pd(pb), _pd(pe), int(min_num_points), _pd(out) if want_world else None), "add_scan")
         return out
+
+    def register_scan_raw(self, ct, scan, pose_begin, pose_end=None, prev_translation=None, prev_rotation=None, frame_init=False, **options):
+        """gfbe_vmap_register_scan on the KEYPOINTS of `scan` (abi.Scan): (status, pose_begin, pose_end, summary dict)."""
+        o = vreg_default_options(self.lib, self.prefix)
+        for k, v in options.items():
+            if not hasattr(o, k):
+                raise TypeError("gfbe_vreg_options has no field %r" % k)
+            setattr(o, k, v)
+        pb = _f64(pose_begin)
+        pe = _f64(pose_end if pose_end is not None else pose_begin)
+        pt = _pd(_f64(prev_translation)) if prev_translation is not None else None
+        pr = _pd(_f64(prev_rotation)) if prev_rotation is not None else None
+        ob, oe, sm = np.full(7, np.nan), np.full(7, np.nan), VregSummary()
+        rc = self._f("register_scan")(self.ctx, self.h, C.byref(o), int(ct), scan.h, _pd(pb), _pd(pe), pt, pr, int(bool(frame_init)), _pd(ob), _pd(oe), C.byref(sm))
+        return rc, ob, oe, vreg_summary_to_dict(sm)
+
+    def register_scan(self, ct, scan, pose_begin, pose_end=None, prev_translation=None, prev_rotation=None, frame_init=False, **options):
+        rc, ob, oe, sm = self.register_scan_raw(ct, scan, pose_begin, pose_end, prev_translation, prev_rotation, frame_init, **options)
+        self._check(rc, "register_scan")
+        return ob, oe, sm
+
+    def add_scan_handle_raw(self, ct, scan, pose_begin, pose_end=None, min_num_points=0):
+        pb = _f64(pose_begin)
+        pe = _f64(pose_end if pose_end is not None else pose_begin)
+        return self._f("add_scan_handle")(self.ctx, self.h, int(ct), scan.h, _pd(pb), _pd(pe), int(min_num_points))
+
+    def add_scan_handle(self, ct, scan, pose_begin, pose_end=None, min_num_points=0):
+        """gfbe_vmap_add_scan on the POINTS of `scan` (abi.Scan); nothing crosses to the host."""
+        self._check(self.add_scan_handle_raw(ct, scan, pose_begin, pose_end, min_num_points), "add_scan_handle")
+
+
+# ---------------------------------------------------------------------------------------------
+# A LiDAR scan held on the device (gfbe_scan_*): subSampleFrame, Undistort, transformPoint + gridSampling
+# ---------------------------------------------------------------------------------------------
+class Scan:
+    """A device-resident scan behind `lib` (prefix gfbe_, ctx = gfbe_ctx*) of up to `capacity` points. The *_raw methods return the
+    status; the others raise."""
+
+    def __init__(self, lib, prefix, ctx, capacity=1 << 16):
+        self.lib, self.prefix, self.ctx, self.cap = lib, prefix, ctx, capacity
+        self.h = C.c_void_p()
+        for name in ("create", "upload", "subsample", "undistort", "keypoints", "size", "download"):
+            self._f(name).restype = c_i
+        self._f("destroy").restype = None
+        self._f("subsample").argtypes = [C.c_void_p, C.c_void_p, c_d]
+        self._f("keypoints").argtypes = [C.c_void_p, C.c_void_p, c_i, PD, PD, c_d, C.POINTER(c_i)]
+        self._check(self._f("create")(self.ctx, int(capacity), C.byref(self.h)), "create")
+
+    def _f(self, name):
+        return getattr(self.lib, self.prefix + "scan_" + name)
+
+    def _check(self, rc, what):
+        if rc != OK:
+            raise RuntimeError("%sscan_%s failed with status %d" % (self.prefix, what, rc))
+
+    def close(self):
+        if self.h:
+            self._f("destroy")(self.ctx, self.h)
+            self.h = C.c_void_p()
+
+    def upload_raw(self, raw_pts, alpha, timestamp=None, til=None):
+        raw = _f64(raw_pts).reshape(-1, 3)
+        n = len(raw)
+        al = _f64(alpha if alpha is not None else np.zeros(n))
+        ts = _f64(timestamp) if timestamp is not None else None
+        tl = _f64(til) if til is not None else None
+        assert len(al) == n and (ts is None or len(ts) == n)
+        return self._f("upload")(self.ctx, self.h, n, _pd(raw), _pd(al), _pd(ts) if ts is not None else None, _pd(tl) if tl is not None else None)
+
+    def upload(self, raw_pts, alpha, timestamp=None, til=None):
+        self._check(self.upload_raw(raw_pts, alpha, timestamp, til), "upload")
+
+    def subsample_raw(self, size_voxel):
+        return self._f("subsample")(self.ctx, self.h, float(size_voxel))
+
+    def subsample(self, size_voxel):
+        self._check(self.subsample_raw(size_voxel), "subsample")
+
+    def undistort_raw(self, state_time, state_pose):
+        t, p = _f64(state_time), _f64(state_pose).reshape(-1, 7)
+        assert len(t) == len(p)
+        return self._f("undistort")(self.ctx, self.h, len(t), _pd(t), _pd(p))
+
+    def undistort(self, state_time, state_pose):
+        self._check(self.undistort_raw(state_time, state_pose), "undistort")
+
+    def keypoints_raw(self, ct, pose_begin, pose_end, size_voxel):
+        pb = _f64(pose_begin)
+        pe = _f64(pose_end if pose_end is not None else pose_begin)
+        n = c_i(-1)
+        return self._f("keypoints")(self.ctx, self.h, int(ct), _pd(pb), _pd(pe), float(size_voxel), C.byref(n)), n.value
+
+    def keypoints(self, ct, pose_begin, pose_end=None, size_voxel=0.2):
+        """transformPoint + gridSampling at the poses; returns the keypoint count (waits)."""
+        rc, n = self.keypoints_raw(ct, pose_begin, pose_end, size_voxel)
+        self._check(rc, "keypoints")
+        return n
+
+    def size(self):
+        """dict(n_points, n_keypoints, n_skipped)."""
+        v = (c_i * 3)()
+        self._check(self._f("size")(self.ctx, self.h, C.byref(v, 0), C.byref(v, 4), C.byref(v, 8)), "size")
+        return dict(n_points=v[0], n_keypoints=v[1], n_skipped=v[2])
+
+    def download(self, which=0):
+        """which 0: the points, 1: the keypoints: dict(src [n] index in the uploaded cloud, pts [n, 3], alpha [n], timestamp [n])."""
+        sz = self.size()
+        n = sz["n_keypoints"] if which else sz["n_points"]
+        src, pts, al, ts = np.zeros(n, np.int32), np.zeros((n, 3)), np.zeros(n), np.zeros(n)
+        self._check(self._f("download")(self.ctx, self.h, int(which), _pi(src), _pd(pts), _pd(al), _pd(ts)), "download")
+        return dict(src=src, pts=pts, alpha=al, timestamp=ts)

@@ -41,6 +41,8 @@ EXPORTS = [
     "gfbe_vmap_default_options", "gfbe_vmap_create", "gfbe_vmap_destroy", "gfbe_vmap_add_points", "gfbe_vmap_erase_far", "gfbe_vmap_size",
     "gfbe_vmap_download", "gfbe_vmap_upload", "gfbe_vmap_associate", "gfbe_vmap_linearize", "gfbe_vmap_localizability",
     "gfbe_vreg_default_options", "gfbe_vmap_register", "gfbe_vmap_add_scan",
+    "gfbe_scan_create", "gfbe_scan_destroy", "gfbe_scan_upload", "gfbe_scan_subsample", "gfbe_scan_undistort", "gfbe_scan_keypoints",
+    "gfbe_scan_size", "gfbe_scan_download", "gfbe_vmap_register_scan", "gfbe_vmap_add_scan_handle",
 ]
 
 
@@ -237,6 +239,14 @@ class Backend(abi.CApi):
         association of addSurfCostFactor, gfbe_vmap_*). options: fields of gfbe_vmap_options."""
         try:
             return abi.VoxelMap(self.lib, "gfbe_", self.ctx, voxel_capacity, **options)
+        except RuntimeError as e:
+            raise BackendError("%s: %s" % (e, self._err()))
+
+    def scan(self, capacity=1 << 16):
+        """A device-resident LiDAR scan (abi.Scan: subSampleFrame, Undistort, transformPoint + gridSampling, gfbe_scan_*) for
+        VoxelMap.register_scan / add_scan_handle."""
+        try:
+            return abi.Scan(self.lib, "gfbe_", self.ctx, capacity)
         except RuntimeError as e:
             raise BackendError("%s: %s" % (e, self._err()))
 

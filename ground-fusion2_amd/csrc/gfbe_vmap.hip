@@ -44,36 +44,6 @@ namespace {
 
 constexpr int VM_THREADS = 1024;
 
-__device__ __forceinline__ unsigned long long vm_load_key(const unsigned long long *p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// slot of `key`, or -1 (bounded by the table size: a probe sequence always meets a free slot, the bound only guards a corrupted table)
-__device__ __forceinline__ int vm_find(const VmDev &V, unsigned long long key) {
-  int h = (int)(vmap_hash(key) & (unsigned long long)V.mask);
-  for (int probe = 0; probe <= V.mask; probe++) {
-    const unsigned long long k = V.keys[h];
-    if (k == key) return h;
-    if (k == VM_EMPTY) return -1;
-    h = (h + 1) & V.mask;
-  }
-  return -1;
-}
-// slot of `key`, claiming a free one when absent (*fresh); -1 only for a full table, which the capacity rule excludes
-__device__ __forceinline__ int vm_claim(const VmDev &V, unsigned long long key, bool *fresh) {
-  int h = (int)(vmap_hash(key) & (unsigned long long)V.mask);
-  *fresh = false;
-  for (int probe = 0; probe <= V.mask; probe++) {
-    unsigned long long k = vm_load_key(V.keys + h);
-    if (k == VM_EMPTY) {
-      k = atomicCAS(V.keys + h, (unsigned long long)VM_EMPTY, key);
-      if (k == VM_EMPTY) { *fresh = true; return h; }
-    }
-    if (k == key) return h;
-    h = (h + 1) & V.mask;
-  }
-  return -1;
-}
-
 __global__ __launch_bounds__(256) void k_vm_keys(int n, const double *pts, double size, unsigned long long *key, int *idx) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
@@ -85,10 +55,7 @@ __global__ __launch_bounds__(256) void k_vm_keys(int n, const double *pts, doubl
 __global__ __launch_bounds__(256) void k_vm_world(int n, int ct, const double *raw, const double *alpha, const double *pb, const double *pe, double *out) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const Qx qb = {pb[3], pb[4], pb[5], pb[6]}, qe = {pe[3], pe[4], pe[5], pe[6]};
-  double R[9], pw[3];
-  lio_world_point(ct, qb, qe, pb, pe, ct ? alpha[i] : 0.0, raw + 3 * (size_t)i, R, pw);
-  for (int a = 0; a < 3; a++) out[3 * (size_t)i + a] = pw[a];
+  lio_world_store(i, ct, raw, alpha, pb, pe, out);
 }
 // per sorted position: an out-of-range point; the head of a run whose voxel would be created
 __global__ __launch_bounds__(256) void k_vm_probe(VmDev V, int n, const unsigned long long *skey, int min_num_points, int *isnew, int *skip) {
@@ -518,14 +485,26 @@ gfbe_status gfbe_vmap_add_points(gfbe_ctx *c, gfbe_vmap *m, int32_t n, const dou
   return GFBE_OK;
 }
 
-// transformKeypoints (lidarodom.cpp:509-532) on the device, then the add_points pipeline on the device buffer
+// transformKeypoints (lidarodom.cpp:509-532) on the device, then the add_points pipeline on the device buffer: the body on a scan
+// already on the device (draw [n][3], dal [n], the poses dpb / dpe [7]; n > 0 known to the host)
+static gfbe_status vm_add_scan_device(gfbe_ctx *c, gfbe_vmap *m, int ct, int n, const double *draw, const double *dal, const double *dpb, const double *dpe,
+                                      int min_num_points, const AddScratch &a, double *pts_world_out) {
+  hipStream_t s = ctx_stream(c);
+  const size_t N = (size_t)n;
+  gfbe_status st;
+  hipLaunchKernelGGL(k_vm_world, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, n, ct ? 1 : 0, draw, dal, dpb, dpe, a.world);
+  if ((st = vm_add_device(c, m, n, a.world, min_num_points, a.key, a.skey, a.idx, a.sidx, a.isnew, a.skip, a.added, a.tmp_bytes)) != GFBE_OK) return st;
+  if (pts_world_out) VM_CHECK(c, hipMemcpyAsync(pts_world_out, a.world, sizeof(double) * 3 * N, hipMemcpyDeviceToHost, s));
+  return GFBE_OK;
+}
+
+// the staging front of the host-fed call
 gfbe_status gfbe_vmap_add_scan(gfbe_ctx *c, gfbe_vmap *m, int32_t ct, int32_t n, const double *raw_pts, const double *alpha, const double *pose_begin,
                                const double *pose_end, int32_t min_num_points, double *pts_world_out) {
   gfbe_status st = vm_ready(c, m);
   if (st != GFBE_OK) return st;
   if (n < 0 || !pose_begin || (n > 0 && !raw_pts) || (ct && (!pose_end || (n > 0 && !alpha)))) return GFBE_BAD_INPUT;
   if (n == 0) return GFBE_OK;
-  hipStream_t s = ctx_stream(c);
   m->gen++;
   const size_t N = (size_t)n;
   AddScratch a;
@@ -535,9 +514,30 @@ gfbe_status gfbe_vmap_add_scan(gfbe_ctx *c, gfbe_vmap *m, int32_t ct, int32_t n,
     const double *draw = sg.up(raw_pts, 3 * N), *dal = sg.up(ct ? alpha : nullptr, N), *dpb = sg.up(pose_begin, 7), *dpe = sg.up(pose_end ? pose_end : pose_begin, 7);
     if (!sg.ok) { ctx_set_error(c, "gfbe_vmap_add_scan: staging allocation failed"); return GFBE_DEVICE_ERROR; }
     sg.flush();
-    hipLaunchKernelGGL(k_vm_world, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, n, ct ? 1 : 0, draw, dal, dpb, dpe, a.world);
-    if ((st = vm_add_device(c, m, n, a.world, min_num_points, a.key, a.skey, a.idx, a.sidx, a.isnew, a.skip, a.added, a.tmp_bytes)) != GFBE_OK) return st;
-    if (pts_world_out) VM_CHECK(c, hipMemcpyAsync(pts_world_out, a.world, sizeof(double) * 3 * N, hipMemcpyDeviceToHost, s));
+    if ((st = vm_add_scan_device(c, m, ct, n, draw, dal, dpb, dpe, min_num_points, a, pts_world_out)) != GFBE_OK) return st;
+  }
+  VM_CHECK(c, hipGetLastError());
+  return GFBE_OK;
+}
+
+// the same body on the POINTS of a scan handle: only the two poses are staged, nobody waits
+gfbe_status gfbe_vmap_add_scan_handle(gfbe_ctx *c, gfbe_vmap *m, int32_t ct, gfbe_scan *scan, const double *pose_begin, const double *pose_end,
+                                      int32_t min_num_points) {
+  gfbe_status st = vm_ready(c, m);
+  if (st != GFBE_OK) return st;
+  if (!scan || !pose_begin || (ct && !pose_end)) return GFBE_BAD_INPUT;
+  ScanView sv;
+  if ((st = scan_points_view(c, scan, "gfbe_vmap_add_scan_handle", &sv)) != GFBE_OK) return st;
+  if (sv.n == 0) return GFBE_OK;
+  m->gen++;
+  AddScratch a;
+  if ((st = vm_add_scratch(c, m, sv.n, true, &a)) != GFBE_OK) return st;
+  {
+    Staged sg(c, m, 2048, /*defer=*/true);
+    const double *dpb = sg.up(pose_begin, 7), *dpe = sg.up(pose_end ? pose_end : pose_begin, 7);
+    if (!sg.ok) { ctx_set_error(c, "gfbe_vmap_add_scan_handle: staging allocation failed"); return GFBE_DEVICE_ERROR; }
+    sg.flush();
+    if ((st = vm_add_scan_device(c, m, ct, sv.n, sv.pts, sv.alpha, dpb, dpe, min_num_points, a, nullptr)) != GFBE_OK) return st;
   }
   VM_CHECK(c, hipGetLastError());
   return GFBE_OK;

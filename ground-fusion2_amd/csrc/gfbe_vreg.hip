@@ -319,18 +319,22 @@ void gfbe_vreg_default_options(gfbe_vreg_options *o) {
   o->thres_translation_norm = 0.01; o->thres_orientation_norm = 0.1;
 }
 
-gfbe_status gfbe_vmap_register(gfbe_ctx *c, gfbe_vmap *m, const gfbe_vreg_options *opt, int32_t ct, int32_t n, const double *raw_pts, const double *alpha,
-                               const double *pose_begin, const double *pose_end, const double *prev_translation, const double *prev_rotation, int32_t frame_init,
-                               double *pose_begin_out, double *pose_end_out, gfbe_vreg_summary *summary) {
+// what both fronts check before they stage anything: the context, the options, the map
+static gfbe_status vr_front(gfbe_ctx *c, gfbe_vmap *m, const gfbe_vreg_options *opt, gfbe_vreg_options *o) {
   if (!c) return GFBE_BAD_INPUT;
-  gfbe_vreg_options o;
-  if (opt) { if (opt->struct_size != (int32_t)sizeof(gfbe_vreg_options)) return GFBE_BAD_INPUT; o = *opt; }
-  else gfbe_vreg_default_options(&o);
+  if (opt) { if (opt->struct_size != (int32_t)sizeof(gfbe_vreg_options)) return GFBE_BAD_INPUT; *o = *opt; }
+  else gfbe_vreg_default_options(o);
   if (ctx_device(c) < 0) return GFBE_NO_DEVICE;
   if (!m) return GFBE_BAD_INPUT;
-  if (!vr_options_ok(&o)) { ctx_set_error(c, "gfbe_vmap_register: an option is outside its admitted range"); return GFBE_BAD_INPUT; }
-  if (n < 0 || !pose_begin || !pose_begin_out || (n > 0 && !raw_pts) || (ct && (!pose_end || !pose_end_out || (n > 0 && !alpha)))) return GFBE_BAD_INPUT;
-  ct = ct ? 1 : 0;
+  if (!vr_options_ok(o)) { ctx_set_error(c, "gfbe_vmap_register: an option is outside its admitted range"); return GFBE_BAD_INPUT; }
+  return GFBE_OK;
+}
+
+// The body: the loop on n keypoints already on the device (draw [n][3], dal [n]; n known to the host). sg: the map's staging chunk
+// with whatever the front put into it, not yet flushed; the state and the partials go behind it, one copy up, one wait.
+static gfbe_status vr_run(gfbe_ctx *c, gfbe_vmap *m, const gfbe_vreg_options &o, int ct, int n, Staged &sg, const double *draw, const double *dal,
+                          const double *pose_begin, const double *pose_end, const double *prev_translation, const double *prev_rotation, int32_t frame_init,
+                          double *pose_begin_out, double *pose_end_out, gfbe_vreg_summary *summary) {
   hipStream_t s = ctx_stream(c);
   m->assoc_valid = false;
   VrOpt O;
@@ -343,15 +347,12 @@ gfbe_status gfbe_vmap_register(gfbe_ctx *c, gfbe_vmap *m, const gfbe_vreg_option
   // grids by the bound of the residual count (the count itself is known only on the device)
   const long long bound = std::max<long long>(1, std::min<long long>((long long)n * m->opt.num_closest_neighbors, m->opt.max_num_residuals));
   const int G = (int)std::min<long long>(VR_MAXG, (bound + VR_THREADS - 1) / VR_THREADS);
-  const size_t N = (size_t)std::max(n, 1);
   VrState hs;
   std::memset(&hs, 0, sizeof hs);
   std::memcpy(hs.x, pose_begin, sizeof(double) * 7);
   std::memcpy(hs.x + 7, pose_end ? pose_end : pose_begin, sizeof(double) * 7);
   gfbe_status st = GFBE_OK;
   {
-    Staged sg(c, m, N * 32 + sizeof(VrState) + sizeof(double) * VR_MAXG * VrDim<1>::PART + 8192);
-    const double *draw = sg.up(raw_pts, 3 * (size_t)n), *dal = sg.up(ct ? alpha : nullptr, (size_t)n);
     VrState *dS = sg.up(&hs, 1);
     double *dpart = sg.up<double>(nullptr, (size_t)VR_MAXG * VrDim<1>::PART);
     if (!sg.ok) { ctx_set_error(c, "gfbe_vmap_register: staging allocation failed"); return GFBE_DEVICE_ERROR; }
@@ -395,6 +396,36 @@ gfbe_status gfbe_vmap_register(gfbe_ctx *c, gfbe_vmap *m, const gfbe_vreg_option
   }
   if (hs.failed) { ctx_set_error(c, "gfbe_vmap_register: the inner solve produced no usable step"); return GFBE_NUMERICAL_FAILURE; }
   return GFBE_OK;
+}
+
+// the staging front of the host-fed call: the keypoints go up with the state
+gfbe_status gfbe_vmap_register(gfbe_ctx *c, gfbe_vmap *m, const gfbe_vreg_options *opt, int32_t ct, int32_t n, const double *raw_pts, const double *alpha,
+                               const double *pose_begin, const double *pose_end, const double *prev_translation, const double *prev_rotation, int32_t frame_init,
+                               double *pose_begin_out, double *pose_end_out, gfbe_vreg_summary *summary) {
+  gfbe_vreg_options o;
+  const gfbe_status st = vr_front(c, m, opt, &o);
+  if (st != GFBE_OK) return st;
+  if (n < 0 || !pose_begin || !pose_begin_out || (n > 0 && !raw_pts) || (ct && (!pose_end || !pose_end_out || (n > 0 && !alpha)))) return GFBE_BAD_INPUT;
+  ct = ct ? 1 : 0;
+  const size_t N = (size_t)std::max(n, 1);
+  Staged sg(c, m, N * 32 + sizeof(VrState) + sizeof(double) * VR_MAXG * VrDim<1>::PART + 8192);
+  const double *draw = sg.up(raw_pts, 3 * (size_t)n), *dal = sg.up(ct ? alpha : nullptr, (size_t)n);
+  return vr_run(c, m, o, ct, n, sg, draw, dal, pose_begin, pose_end, prev_translation, prev_rotation, frame_init, pose_begin_out, pose_end_out, summary);
+}
+
+// the same body on the KEYPOINTS of a scan handle: only the state goes up
+gfbe_status gfbe_vmap_register_scan(gfbe_ctx *c, gfbe_vmap *m, const gfbe_vreg_options *opt, int32_t ct, gfbe_scan *scan, const double *pose_begin,
+                                    const double *pose_end, const double *prev_translation, const double *prev_rotation, int32_t frame_init,
+                                    double *pose_begin_out, double *pose_end_out, gfbe_vreg_summary *summary) {
+  gfbe_vreg_options o;
+  gfbe_status st = vr_front(c, m, opt, &o);
+  if (st != GFBE_OK) return st;
+  if (!scan || !pose_begin || !pose_begin_out || (ct && (!pose_end || !pose_end_out))) return GFBE_BAD_INPUT;
+  ScanView sv;
+  if ((st = scan_keypoints_view(c, scan, "gfbe_vmap_register_scan", &sv)) != GFBE_OK) return st;
+  ct = ct ? 1 : 0;
+  Staged sg(c, m, sizeof(VrState) + sizeof(double) * VR_MAXG * VrDim<1>::PART + 8192);
+  return vr_run(c, m, o, ct, sv.n, sg, sv.pts, sv.alpha, pose_begin, pose_end, prev_translation, prev_rotation, frame_init, pose_begin_out, pose_end_out, summary);
 }
 
 }  // extern "C"

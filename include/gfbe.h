@@ -609,7 +609,7 @@ gfbe_status gfbe_vmap_localizability(gfbe_ctx *ctx, gfbe_vmap *map, double *sv, 
 
 /* ------------------------------------------------------------------------------------------
  * f4c Scan-to-map registration loop on the device: one call of lidarodom::optimize from the head of its ICP loop to the
- *     loop's end (lio/src/liw/lio/lidarodom.cpp:534-748; gridSampling in front of the loop stays with the caller):
+ *     loop's end (lio/src/liw/lio/lidarodom.cpp:534-748; gridSampling in front of the loop: the caller's, or f4d's):
  *       the ICP loop, exit test           lidarodom.cpp:534-748      gfbe_vmap_register
  *       addSurfCostFactor                 :929-1071                  (gfbe_vmap_associate's kernels, at the current poses)
  *       point-to-plane factors            lidarFactor.cpp:18-120     (the rows of gfbe_lio_linearize) under HuberLoss(0.5)
@@ -663,6 +663,75 @@ gfbe_status gfbe_vmap_register(gfbe_ctx *ctx, gfbe_vmap *map, const gfbe_vreg_op
 gfbe_status gfbe_vmap_add_scan(gfbe_ctx *ctx, gfbe_vmap *map, int32_t ct, int32_t n, const double *raw_pts,
                                const double *alpha, const double *pose_begin, const double *pose_end,
                                int32_t min_num_points, double *pts_world_out /* [n][3], may be NULL */);
+
+/* ------------------------------------------------------------------------------------------
+ * f4d Device-resident LiDAR scan: what the reference does on the host between the driver's cloud and lidarodom::optimize,
+ *     and the hand-over of the result to the registration and the map update (paths under lio/src/):
+ *       subSampleFrame            apps/main_eskf.cpp:56-64, common/utility.cpp:34-54             gfbe_scan_subsample
+ *       Undistort / PoseInterp    liw/lio/lidarodom.cpp:1578-1600, common/math_utils.h:530-585    gfbe_scan_undistort
+ *       transformPoint            lidarodom.cpp:1301-1304, common/utility.cpp:91-111              gfbe_scan_keypoints
+ *       gridSampling              lidarodom.cpp:503-505, common/utility.cpp:56-71                 gfbe_scan_keypoints
+ *       optimize on the keypoints :534-748                                                        gfbe_vmap_register_scan
+ *       map_incremental           :758, :1167-1266                                                gfbe_vmap_add_scan_handle
+ *     Conventions of gfbe_vmap / gfbe_ltab: operations run in order on the context's stream; without a GPU every entry
+ *     point returns GFBE_NO_DEVICE; a bad argument returns GFBE_BAD_INPUT with gfbe_last_error set and the handle
+ *     untouched. Points are held in the IMU frame: til [t | q(x,y,z,w)] at upload applies T_IL once (NULL: identity, what
+ *     every other LiDAR entry point assumes), so the T_IL^-1 .. T_IL sandwich of Undistort disappears.
+ *     Voxel key (subsample on the held points, keypoints on the WORLD points): (short)(p / size_voxel) per axis, truncated
+ *     toward zero, as gfbe_vmap; a point with |p / size| >= 32767 on an axis or a NaN coordinate is dropped and counted
+ *     in n_skipped (the reference's cast is undefined there). size_voxel must be finite and > 0.
+ *     One point per voxel: the kept SET is the reference's ("first pushed" = the LOWEST input index); the ORDER is
+ *     ascending input index, where the reference has the iteration order of its unordered_map (a deliberate deviation).
+ *     No result depends on the order workgroups ran in or on the layout of a table.
+ *     Undistort, the time rule (PoseInterp restated): a stamp q behind the last state time gives Ti = T_end (inside and
+ *     outside the reference's 0.5 s allowance: it leaves Ti = T_end when it returns false); otherwise the first k with
+ *     t_k < q && t_k+1 >= q; when there is none (q <= t_0) segment 0 with s = (q - t_0) / (t_1 - t_0) as it comes out
+ *     (s <= 0: extrapolation, the reference's arithmetic); |t_k+1 - t_k| < 1e-6: Ti = T_k; n_states == 1: every point gets
+ *     T_end (the reference dereferences end()). Ti = (slerp(q_k, s, q_k+1) normalised, p_k (1 - s) + p_k+1 s); the new
+ *     point is T_end^-1 Ti p. State quaternions must be unit.
+ *     A LiDAR frame has TWO host waits with the handle: gfbe_scan_keypoints (the counts) and gfbe_vmap_register_scan.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct gfbe_scan gfbe_scan;
+/* GFBE_BAD_INPUT: point_capacity outside 1 .. 2^21. */
+gfbe_status gfbe_scan_create(gfbe_ctx *ctx, int32_t point_capacity, gfbe_scan **out);
+void gfbe_scan_destroy(gfbe_ctx *ctx, gfbe_scan *scan);
+/* The cloud as CloudConvert leaves it: raw_pts [n][3], alpha [n], timestamp [n] or NULL (then gfbe_scan_undistort is
+ * refused; downloads give 0), til [7] or NULL. Replaces the handle's contents and clears the keypoints and n_skipped.
+ * n > point_capacity: GFBE_BAD_INPUT. Returns without waiting when the arrays fit a staging slot. */
+gfbe_status gfbe_scan_upload(gfbe_ctx *ctx, gfbe_scan *scan, int32_t n, const double *raw_pts, const double *alpha,
+                             const double *timestamp, const double *til);
+/* subSampleFrame: keeps, per voxel of size_voxel, the point of LOWEST input index; survivors stay in ascending input
+ * index. Clears the keypoints; returns without waiting. */
+gfbe_status gfbe_scan_subsample(gfbe_ctx *ctx, gfbe_scan *scan, double size_voxel);
+/* Undistort: n_states (1 .. 512) nominal states, state_time [n_states] finite and ascending, state_pose [n_states][7];
+ * T_end = the last state. Clears the keypoints; returns without waiting. */
+gfbe_status gfbe_scan_undistort(gfbe_ctx *ctx, gfbe_scan *scan, int32_t n_states, const double *state_time,
+                                const double *state_pose);
+/* transformPoint + gridSampling: world points at (ct, pose_begin, pose_end) exactly as gfbe_vmap_add_scan forms them
+ * (bit-identical to its pts_world_out), then one keypoint per voxel of size_voxel of the WORLD point (lowest index,
+ * ascending index order). The points stay as they are. Waits; writes the keypoint count (n_keypoints may be NULL). */
+gfbe_status gfbe_scan_keypoints(gfbe_ctx *ctx, gfbe_scan *scan, int32_t ct, const double *pose_begin,
+                                const double *pose_end, double size_voxel, int32_t *n_keypoints);
+/* any output may be NULL; waits. n_keypoints: 0 until gfbe_scan_keypoints ran on the scan as it is now. n_skipped: points
+ * dropped by gfbe_scan_subsample since the upload + points without a voxel in the last gfbe_scan_keypoints. */
+gfbe_status gfbe_scan_size(gfbe_ctx *ctx, gfbe_scan *scan, int32_t *n_points, int32_t *n_keypoints, int32_t *n_skipped);
+/* which 0: the points, 1: the keypoints (their IMU-frame point, not the world point). src = index in the uploaded
+ * cloud; any output may be NULL; waits. */
+gfbe_status gfbe_scan_download(gfbe_ctx *ctx, gfbe_scan *scan, int32_t which, int32_t *src, double *pts, double *alpha,
+                               double *timestamp);
+/* gfbe_vmap_register on the handle's KEYPOINTS (points + alpha in keypoint order; max_num_residuals cuts in that order), no
+ * geometry through the host: the same kernels in the same order on the same values as the host-fed call on the downloaded
+ * keypoints, bit-identical outputs. GFBE_BAD_INPUT also: no gfbe_scan_keypoints since the last upload / subsample /
+ * undistort; a handle of another context. */
+gfbe_status gfbe_vmap_register_scan(gfbe_ctx *ctx, gfbe_vmap *map, const gfbe_vreg_options *opt, int32_t ct, gfbe_scan *scan,
+                                    const double *pose_begin, const double *pose_end, const double *prev_translation,
+                                    const double *prev_rotation, int32_t frame_init, double *pose_begin_out,
+                                    double *pose_end_out, gfbe_vreg_summary *summary);
+/* gfbe_vmap_add_scan on the handle's POINTS (lidarodom.cpp:758 + map_incremental); returns without waiting (when the
+ * point count changed since the host last read it — a subsample without a later gfbe_scan_keypoints / _size — it is read
+ * back first). */
+gfbe_status gfbe_vmap_add_scan_handle(gfbe_ctx *ctx, gfbe_vmap *map, int32_t ct, gfbe_scan *scan, const double *pose_begin,
+                                      const double *pose_end, int32_t min_num_points);
 
 /* ------------------------------------------------------------------------------------------
  * f2  Optional in-window factors. PlaneFactor and PoseAnchorFactor run INSIDE
