@@ -765,6 +765,67 @@ def pg_plus(x, d6):
 
 
 # ---------------------------------------------------------------------------------------------
+# f3b: loop-closure pose graph of dense_map, 4-DoF (gfbe_lc4_*; the model is tests/lc4_np.py, there is no oracle row)
+# ---------------------------------------------------------------------------------------------
+LC4_MAX_LOOPS = 64
+
+
+class Lc4Options(C.Structure):
+    _fields_ = [("struct_size", c_i), ("max_num_iterations", c_i), ("span", c_i), ("reserved", c_i), ("huber_delta", c_d), ("loop_yaw_div", c_d)]
+
+
+class LoopGraph:
+    """Keyframes t [n,3], ypr [n,3] (degrees); see include/gfbe.h f3b."""
+
+    def __init__(self, lib, prefix, ctx):
+        self.lib, self.prefix, self.ctx = lib, prefix, ctx
+        PO = C.POINTER(Lc4Options)
+        f = getattr(lib, prefix + "lc4_default_options")
+        f.restype, f.argtypes = None, [PO]
+        f = getattr(lib, prefix + "lc4_eval")
+        f.restype, f.argtypes = c_i, [C.c_void_p, PO, c_i, PD, PD, c_i, PI, PI, PU8, PD, PD, PD, PD]
+        f = getattr(lib, prefix + "lc4_solve")
+        f.restype, f.argtypes = c_i, [C.c_void_p, PO, c_i, PD, PD, PI, PU8, c_i, PI, PI, PD, PD, PD, PD, C.POINTER(Summary)]
+
+    def options(self, **kw):
+        o = Lc4Options()
+        getattr(self.lib, self.prefix + "lc4_default_options")(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+
+    def eval_rc(self, t, ypr, edge_i, edge_j, kind, meas, opt=None):
+        t, ypr, meas = _f64(t).reshape(-1, 3), _f64(ypr).reshape(-1, 3), _f64(meas).reshape(-1, 6)
+        ei, ej, kd = _i32(edge_i), _i32(edge_j), _u8(kind)
+        E = len(ei)
+        r, J, cost = np.zeros((E, 4)), np.zeros((E, 4, 8)), np.zeros(1)
+        rc = getattr(self.lib, self.prefix + "lc4_eval")(self.ctx, C.byref(opt) if opt is not None else None, len(t), _pd(t), _pd(ypr), E, _pi(ei), _pi(ej),
+                                                        kd.ctypes.data_as(PU8), _pd(meas), _pd(r), _pd(J), _pd(cost))
+        return rc, dict(r=r, J=J, cost=float(cost[0]))
+
+    def eval(self, *a, **kw):
+        rc, out = self.eval_rc(*a, **kw)
+        if rc != OK:
+            raise RuntimeError("%slc4_eval failed with status %d" % (self.prefix, rc))
+        return out
+
+    def solve_rc(self, t, ypr, sequence, fixed, loop_i, loop_c, loop_meas, opt=None):
+        t, ypr, lm = _f64(t).reshape(-1, 3), _f64(ypr).reshape(-1, 3), _f64(loop_meas).reshape(-1, 4)
+        seq, fx, li, lc = _i32(sequence), _u8(fixed), _i32(loop_i), _i32(loop_c)
+        n = len(t)
+        t_out, yaw_out, drift, sm = np.full((n, 3), np.nan), np.full(n, np.nan), np.full(4, np.nan), Summary()
+        rc = getattr(self.lib, self.prefix + "lc4_solve")(self.ctx, C.byref(opt) if opt is not None else None, n, _pd(t), _pd(ypr), _pi(seq), fx.ctypes.data_as(PU8),
+                                                         len(li), _pi(li), _pi(lc), _pd(lm), _pd(t_out), _pd(yaw_out), _pd(drift), C.byref(sm))
+        return rc, dict(t=t_out, yaw=yaw_out, drift=drift, summary=summary_to_dict(sm), status=rc)
+
+    def solve(self, *a, **kw):
+        rc, out = self.solve_rc(*a, **kw)
+        if rc not in (OK, NO_CONVERGENCE):
+            raise RuntimeError("%slc4_solve failed with status %d" % (self.prefix, rc))
+        return out
+
+
+# ---------------------------------------------------------------------------------------------
 # f4: LIO point-to-plane factors (gfbe_lio_linearize / gfo_lio_linearize)
 # ---------------------------------------------------------------------------------------------
 def lio_linearize(lib, prefix, ctx, ct, pts, normals, offsets, alpha, weights, sqrt_info, pose_begin, pose_end=None, blocks=True):

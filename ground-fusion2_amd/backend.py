@@ -43,6 +43,7 @@ EXPORTS = [
     "gfbe_vreg_default_options", "gfbe_vmap_register", "gfbe_vmap_add_scan",
     "gfbe_scan_create", "gfbe_scan_destroy", "gfbe_scan_upload", "gfbe_scan_subsample", "gfbe_scan_undistort", "gfbe_scan_keypoints",
     "gfbe_scan_size", "gfbe_scan_download", "gfbe_vmap_register_scan", "gfbe_vmap_add_scan_handle",
+    "gfbe_lc4_default_options", "gfbe_lc4_eval", "gfbe_lc4_solve",
 ]
 
 

@@ -517,3 +517,69 @@ def lidar_block(scn, k0, n=2000, seed=0, noise=0.02, sqrt_info=20.0, huber_delta
     offs = -(nrm * pw).sum(axis=1) + err
     return dict(frame=frame, pts=pts, normals=nrm, offsets=offs, weights=rng.uniform(0.5, 1.0, n), sqrt_info=sqrt_info,
                 huber_delta=huber_delta)
+
+
+def _wrap_deg(a):
+    return (np.asarray(a, float) + 180.0) % 360.0 - 180.0
+
+
+def loop_graph(n=200, n_loop=8, seed=0, laps=2, yaw0=0.0, yaw_bias=0.02, scale_err=0.01, n_fixed_sequence=0, loop_into_first=False,
+               loop_same_block=False, meas_noise=1e-3, throw=0.0):
+    """A planar figure-of-eight driven `laps` times, for the loop-closure pose graph (gfbe_lc4_solve): n keyframes with the VIO's drifted
+    poses (a yaw bias per keyframe in degrees, a scale error on the travelled distance), small non-zero pitch and roll, and n_loop
+    loop edges (loop_c < loop_i, one per loop_i) that join a keyframe of a later lap to the one at the same place one lap earlier, with
+    the true relative translation and yaw plus meas_noise. yaw0 turns the whole course (yaw0 = 140 puts headings on both sides of
+    +-180). n_fixed_sequence > 0: the first keyframes form sequence 0 (fixed), the rest sequence 1. loop_into_first: the first loop edge
+    goes into keyframe 0 (constant); loop_same_block: one more loop edge whose two ends lie in one group of four keyframes (replaces the
+    last). throw: the VIO poses after the first are displaced by normal noise of this size (metres / tens of degrees): a start far off.
+    Returns dict(t, ypr, sequence, fixed, loop_i, loop_c, loop_meas, true_t, true_yaw)."""
+    rng = np.random.default_rng(20251019 + seed)
+    s = np.linspace(0.0, 2 * np.pi * laps, n, endpoint=False)
+    A = 10.0
+    true_t = np.stack([A * np.sin(s), A * np.sin(s) * np.cos(s), 0.2 * np.sin(2 * s)], axis=1)
+    vel = np.stack([np.cos(s), np.cos(2 * s)], axis=1)
+    true_yaw = _wrap_deg(np.rad2deg(np.arctan2(vel[:, 1], vel[:, 0])) + yaw0)
+    c0, s0 = np.cos(np.deg2rad(yaw0)), np.sin(np.deg2rad(yaw0))
+    true_t[:, :2] = true_t[:, :2] @ np.array([[c0, s0], [-s0, c0]])
+    pitch, roll = rng.normal(0, 2.0, n), rng.normal(0, 2.0, n)
+    # the VIO: truth's relative motion in the yaw frame, with a bias on the yaw increment and a scale error on the translation
+    t, yaw = np.zeros((n, 3)), np.zeros(n)
+    t[0], yaw[0] = true_t[0], true_yaw[0]
+    for i in range(1, n):
+        a = np.deg2rad(true_yaw[i - 1])
+        d = true_t[i] - true_t[i - 1]
+        body = np.array([np.cos(a) * d[0] + np.sin(a) * d[1], -np.sin(a) * d[0] + np.cos(a) * d[1], d[2]]) * (1.0 + scale_err)
+        b = np.deg2rad(yaw[i - 1])
+        t[i] = t[i - 1] + np.array([np.cos(b) * body[0] - np.sin(b) * body[1], np.sin(b) * body[0] + np.cos(b) * body[1], body[2]])
+        yaw[i] = _wrap_deg(yaw[i - 1] + _wrap_deg(true_yaw[i] - true_yaw[i - 1]) + yaw_bias)
+    if throw > 0.0:
+        t[1:] += rng.normal(0, throw, (n - 1, 3))
+        yaw[1:] = _wrap_deg(yaw[1:] + rng.normal(0, 10.0 * throw, n - 1))
+    ypr = np.stack([yaw, pitch, roll], axis=1)
+    per = n // laps
+    cand = np.arange(max(per, 1), n)
+    loop_i = np.sort(rng.choice(cand, size=min(n_loop, len(cand)), replace=False)) if n_loop and len(cand) else np.zeros(0, int)
+    if n_loop and len(loop_i) < n_loop:      # small graphs: any later keyframe, joined to an earlier one
+        loop_i = np.sort(rng.choice(np.arange(1, n), size=min(n_loop, n - 1), replace=False))
+    loop_c = np.array([i - per if i - per >= 0 and per > 0 and laps > 1 and i >= per else int(rng.integers(0, i)) for i in loop_i], int)
+    if loop_into_first and len(loop_i):
+        loop_c[0] = 0
+    if loop_same_block and len(loop_i):
+        taken = set(loop_i[:-1].tolist())
+        i = next(k for k in range(n - 1, 0, -1) if k % 4 == 3 and k not in taken)
+        loop_i[-1], loop_c[-1] = i, i - 2
+        order = np.argsort(loop_i)
+        loop_i, loop_c = loop_i[order], loop_c[order]
+    meas = np.zeros((len(loop_i), 4))
+    for l, (i, c) in enumerate(zip(loop_i, loop_c)):
+        R = rz(np.deg2rad(true_yaw[c])) @ ry(np.deg2rad(pitch[c])) @ rx(np.deg2rad(roll[c]))
+        meas[l, :3] = R.T @ (true_t[i] - true_t[c]) + rng.normal(0, meas_noise, 3)
+        meas[l, 3] = _wrap_deg(true_yaw[i] - true_yaw[c]) + rng.normal(0, 10 * meas_noise)
+    sequence = np.ones(n, np.int32)
+    fixed = np.zeros(n, np.uint8)
+    fixed[0] = 1
+    if n_fixed_sequence > 0:
+        sequence[:n_fixed_sequence] = 0
+        fixed[:n_fixed_sequence] = 1
+    return dict(t=t, ypr=ypr, sequence=sequence, fixed=fixed, loop_i=loop_i.astype(np.int32), loop_c=loop_c.astype(np.int32), loop_meas=meas,
+                true_t=true_t, true_yaw=true_yaw)

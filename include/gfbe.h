@@ -520,6 +520,47 @@ gfbe_status gfbe_pg_solve(gfbe_ctx *ctx, int32_t n_poses, const double *pose_in,
                           gfbe_summary *summary);
 
 /* ------------------------------------------------------------------------------------------
+ * f3b loop-closure pose graph of dense_map, the 4-DoF solve that runs on VIO input:
+ *       PoseGraph::optimize4DoF             dense_map/src/pose_graph.cpp:529-705 (options :558-566)
+ *       FourDOFError / FourDOFWeightError   dense_map/src/pose_graph.h:199-288 (automatic differentiation in the
+ *                                           reference; analytic tangent Jacobians here)
+ * A keyframe is t(3) and ypr(3) in DEGREES (Utility::R2ypr's order); the solve moves yaw and t, pitch and roll are frozen
+ * into the factors. Tangent of a pose: [yaw, t_x, t_y, t_z]; yaw moves by NormalizeAngle(yaw + delta), a single wrap.
+ * gfbe_lc4_eval: an explicit edge list (edge_i, edge_j), kind 0 = FourDOFError, 1 = FourDOFWeightError under HuberLoss,
+ * meas [n_edges][6] = t_x t_y t_z relative_yaw pitch_i roll_i. Returns r [n_edges][4], J [n_edges][4][8] (columns yaw_i
+ * t_i(3) yaw_j t_j(3); kind 1 through the corrector) and the cost with the loss. Any output pointer may be NULL.
+ * gfbe_lc4_solve: the graph optimize4DoF builds. t / ypr [n][3] are the VIO poses: the starting point AND the source of
+ * the sequence measurements — for every i and k = 1 .. span with sequence[i] == sequence[i - k] an edge (i - k, i) with
+ * relative_t = R(ypr_{i-k})^T (t_i - t_{i-k}), relative_yaw = yaw_i - yaw_{i-k} (not normalised), formed by the library.
+ * fixed[i] != 0: the pose is constant (the caller sets it for the earliest looped keyframe and for sequence 0). Loop edges
+ * (loop_c[l], loop_i[l]) with loop_c < loop_i, at most one per loop_i, loop_meas [n_loop][4] = relative t, relative yaw
+ * (pitch and roll of the connected pose come from ypr). At most GFBE_LC4_MAX_LOOPS loop edges. Solver = what ceres::Solve
+ * does with the reference's options: Levenberg-Marquardt, Jacobi scaling, Ceres 1.14 defaults; the normal equations are
+ * block-tridiagonal in 16 x 16 super-blocks of four poses plus a rank-4 term per loop edge, solved exactly (parallel block
+ * cyclic reduction with the loop columns as right-hand sides, then the 4 n_loop capacitance system).
+ * Outputs: t_out [n][3], yaw_out [n], drift[4] = yaw_drift, t_drift of the last keyframe (:674-681; may be NULL), summary
+ * as gfbe_pg_solve fills it. GFBE_BAD_INPUT with nothing written for n_loop > GFBE_LC4_MAX_LOOPS, an index out of range,
+ * loop_c >= loop_i, two loops on one loop_i or an options struct of another size; GFBE_NO_DEVICE without a GPU.
+ * ------------------------------------------------------------------------------------------ */
+#define GFBE_LC4_MAX_LOOPS 64
+typedef struct gfbe_lc4_options {
+  int32_t struct_size;          /* sizeof(gfbe_lc4_options), written by gfbe_lc4_default_options */
+  int32_t max_num_iterations;   /* 5 (pose_graph.cpp:563); at most 15 are run */
+  int32_t span;                 /* 4 (:606): sequence edges reach this many keyframes back, 1 .. 4 */
+  int32_t reserved;
+  double huber_delta;           /* 0.1 (:566), loop edges only */
+  double loop_yaw_div;          /* 10.0 (pose_graph.h:271) */
+} gfbe_lc4_options;
+void gfbe_lc4_default_options(gfbe_lc4_options *opt);
+gfbe_status gfbe_lc4_eval(gfbe_ctx *ctx, const gfbe_lc4_options *opt /* NULL: defaults */, int32_t n_poses, const double *t,
+                          const double *ypr, int32_t n_edges, const int32_t *edge_i, const int32_t *edge_j,
+                          const uint8_t *kind, const double *meas, double *r, double *J, double *cost);
+gfbe_status gfbe_lc4_solve(gfbe_ctx *ctx, const gfbe_lc4_options *opt /* NULL: defaults */, int32_t n_poses, const double *t,
+                           const double *ypr, const int32_t *sequence, const uint8_t *fixed, int32_t n_loop,
+                           const int32_t *loop_i, const int32_t *loop_c, const double *loop_meas, double *t_out,
+                           double *yaw_out, double *drift, gfbe_summary *summary);
+
+/* ------------------------------------------------------------------------------------------
  * f4  LIO scan residuals (BASELINE configs[4]): point-to-plane factors of the LiDAR
  *     odometry, evaluated and reduced to normal equations on the device (the voxel neighbour search that produces
  *     the planes runs on the device too: the voxel map section below, gfbe_vmap_associate / gfbe_vmap_linearize):
