@@ -6,7 +6,7 @@ The product is csrc/libgfbe.so (hand-written HIP for gfx950 behind the C ABI of 
 this package is the thin ctypes binding + synthetic-input generator. There is NO CPU fallback:
 every compute entry point raises if the HIP library or a GPU is missing.
 """
-from . import abi, synth, synth_line, synth_scan, dist, stream  # noqa: F401
+from . import abi, synth, synth_line, synth_scan, synth_dmap, dist, stream  # noqa: F401
 from . import backend  # noqa: F401
 from .backend import Backend, BackendError, lib_path, build_native, WindowSet, DownloadBuffers, strip_visual  # noqa: F401
 

@@ -1651,3 +1651,116 @@ class Scan:
         src, pts, al, ts = np.zeros(n, np.int32), np.zeros((n, 3)), np.zeros(n), np.zeros(n)
         self._check(self._f("download")(self.ctx, self.h, int(which), _pi(src), _pd(pts), _pd(al), _pd(ts)), "download")
         return dict(src=src, pts=pts, alpha=al, timestamp=ts)
+
+
+# ---------------------------------------------------------------------------------------------
+# f3c: the dense RGB-D map of dense_map held on the device (gfbe_dmap_*; the model is tests/dmap_np.py)
+# ---------------------------------------------------------------------------------------------
+PF = C.POINTER(C.c_float)
+DMAP_COUNTS = ("n_keyframes", "n_stored", "n_cloud", "n_voxels", "n_skipped", "n_gated", "n_refused", "n_fast")
+
+
+class DmapOptions(C.Structure):
+    _fields_ = [("struct_size", c_i), ("add_cap", c_i), ("rebuild_cap", c_i), ("filter_min_neighbors", c_i), ("resolution", c_d), ("origin", c_d),
+                ("z_min", c_d), ("z_max", c_d), ("ex_cam", c_d * 7), ("filter_radius", c_d)]
+
+
+def dmap_default_options(lib, prefix="gfbe_"):
+    o = DmapOptions()
+    f = getattr(lib, prefix + "dmap_default_options")
+    f.restype = None
+    f(C.byref(o))
+    return o
+
+
+def _f32(a):
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+class DenseMap:
+    """The dense map behind `lib` (prefix gfbe_, ctx = gfbe_ctx*): addKeyFrame's capped insert, updatePath's rebuild and the radius
+    filter of dense_map/src/pose_graph.cpp on up to `point_capacity` stored points of `keyframe_capacity` keyframes. options: fields
+    of gfbe_dmap_options. The *_raw methods return the status; the others raise."""
+
+    def __init__(self, lib, prefix, ctx, point_capacity=1 << 16, keyframe_capacity=1024, **options):
+        self.lib, self.prefix, self.ctx = lib, prefix, ctx
+        self.h = C.c_void_p()
+        for name in ("create", "add_keyframe", "rebuild", "filter", "size", "download_cloud", "download_keyframe"):
+            self._f(name).restype = c_i
+        self._f("destroy").restype = None
+        self._f("create").argtypes = [C.c_void_p, c_i, c_i, C.POINTER(DmapOptions), C.POINTER(C.c_void_p)]
+        self._f("add_keyframe").argtypes = [C.c_void_p, C.c_void_p, PD, c_i, PF, PU8]
+        self._f("rebuild").argtypes = [C.c_void_p, C.c_void_p, c_i, PD]
+        self._f("filter").argtypes = [C.c_void_p, C.c_void_p, PU8, C.POINTER(c_i), PF, PU8]
+        self._f("size").argtypes = [C.c_void_p, C.c_void_p, C.POINTER(c_i)]
+        self._f("download_cloud").argtypes = [C.c_void_p, C.c_void_p, PF, PU8, C.POINTER(c_i), C.POINTER(c_i)]
+        self._f("download_keyframe").argtypes = [C.c_void_p, C.c_void_p, c_i, C.POINTER(c_i), PF, PU8]
+        self.opt = dmap_default_options(lib, prefix)
+        for k, v in options.items():
+            if k == "ex_cam":
+                self.opt.ex_cam = (c_d * 7)(*[float(x) for x in v])
+            else:
+                setattr(self.opt, k, v)
+        self._check(self._f("create")(self.ctx, int(point_capacity), int(keyframe_capacity), C.byref(self.opt), C.byref(self.h)), "create")
+
+    def _f(self, name):
+        return getattr(self.lib, self.prefix + "dmap_" + name)
+
+    def _check(self, rc, what):
+        if rc != OK:
+            raise RuntimeError("%sdmap_%s failed with status %d" % (self.prefix, what, rc))
+
+    def close(self):
+        if self.h:
+            self._f("destroy")(self.ctx, self.h)
+            self.h = C.c_void_p()
+
+    def add_keyframe_raw(self, pose7, pts_cam, rgb):
+        p, pts, col = _f64(pose7), _f32(pts_cam).reshape(-1, 3), _u8(rgb).reshape(-1, 3)
+        assert len(p) == 7 and len(pts) == len(col)
+        return self._f("add_keyframe")(self.ctx, self.h, _pd(p), len(pts), pts.ctypes.data_as(PF), col.ctypes.data_as(PU8))
+
+    def add_keyframe(self, pose7, pts_cam, rgb):
+        """addKeyFrame of one keyframe (returns without waiting for the device when the points fit a staging slot)."""
+        self._check(self.add_keyframe_raw(pose7, pts_cam, rgb), "add_keyframe")
+
+    def rebuild_raw(self, poses):
+        p = _f64(poses).reshape(-1, 7)
+        return self._f("rebuild")(self.ctx, self.h, len(p), _pd(p))
+
+    def rebuild(self, poses):
+        """updatePath's rebuild at the corrected poses [n_keyframes, 7] (returns without waiting)."""
+        self._check(self.rebuild_raw(poses), "rebuild")
+
+    def size(self):
+        """dict of DMAP_COUNTS (waits)."""
+        v = (c_i * len(DMAP_COUNTS))()
+        self._check(self._f("size")(self.ctx, self.h, v), "size")
+        return dict(zip(DMAP_COUNTS, list(v)))
+
+    def filter(self, compact=True):
+        """dict(keep [n_cloud] uint8, n_keep and, with compact, xyz [n_keep, 3] float32 / rgb [n_keep, 3] in cloud order)."""
+        n = self.size()["n_cloud"]
+        keep, nk = np.zeros(n, np.uint8), c_i(-1)
+        xyz, rgb = (np.zeros((n, 3), np.float32), np.zeros((n, 3), np.uint8)) if compact else (None, None)
+        self._check(self._f("filter")(self.ctx, self.h, keep.ctypes.data_as(PU8), C.byref(nk), xyz.ctypes.data_as(PF) if compact else None,
+                                      rgb.ctypes.data_as(PU8) if compact else None), "filter")
+        out = dict(keep=keep, n_keep=nk.value)
+        if compact:
+            out.update(xyz=xyz[:nk.value], rgb=rgb[:nk.value])
+        return out
+
+    def cloud(self):
+        """dict(xyz [n, 3] float32 world, rgb [n, 3], kf [n], src [n] pool index) in insertion order."""
+        n = self.size()["n_cloud"]
+        xyz, rgb, kf, src = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.uint8), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self._check(self._f("download_cloud")(self.ctx, self.h, xyz.ctypes.data_as(PF), rgb.ctypes.data_as(PU8), _pi(kf), _pi(src)), "download_cloud")
+        return dict(xyz=xyz, rgb=rgb, kf=kf, src=src)
+
+    def keyframe(self, k):
+        """dict(pts [n, 3] float32 camera frame, rgb [n, 3]): keyframe k's list as it is now."""
+        n = c_i(-1)
+        self._check(self._f("download_keyframe")(self.ctx, self.h, int(k), C.byref(n), None, None), "download_keyframe")
+        pts, rgb = np.zeros((n.value, 3), np.float32), np.zeros((n.value, 3), np.uint8)
+        self._check(self._f("download_keyframe")(self.ctx, self.h, int(k), C.byref(n), pts.ctypes.data_as(PF), rgb.ctypes.data_as(PU8)), "download_keyframe")
+        return dict(pts=pts, rgb=rgb)

@@ -44,6 +44,8 @@ EXPORTS = [
     "gfbe_scan_create", "gfbe_scan_destroy", "gfbe_scan_upload", "gfbe_scan_subsample", "gfbe_scan_undistort", "gfbe_scan_keypoints",
     "gfbe_scan_size", "gfbe_scan_download", "gfbe_vmap_register_scan", "gfbe_vmap_add_scan_handle",
     "gfbe_lc4_default_options", "gfbe_lc4_eval", "gfbe_lc4_solve",
+    "gfbe_dmap_default_options", "gfbe_dmap_create", "gfbe_dmap_destroy", "gfbe_dmap_add_keyframe", "gfbe_dmap_rebuild", "gfbe_dmap_filter",
+    "gfbe_dmap_size", "gfbe_dmap_download_cloud", "gfbe_dmap_download_keyframe",
 ]
 
 
@@ -248,6 +250,14 @@ class Backend(abi.CApi):
         VoxelMap.register_scan / add_scan_handle."""
         try:
             return abi.Scan(self.lib, "gfbe_", self.ctx, capacity)
+        except RuntimeError as e:
+            raise BackendError("%s: %s" % (e, self._err()))
+
+    def dense_map(self, point_capacity=1 << 16, keyframe_capacity=1024, **options):
+        """The dense RGB-D map of the loop-closure thread held on the device (abi.DenseMap: addKeyFrame's capped insert, updatePath's
+        rebuild at the corrected poses and the radius filter, gfbe_dmap_*). options: fields of gfbe_dmap_options."""
+        try:
+            return abi.DenseMap(self.lib, "gfbe_", self.ctx, point_capacity, keyframe_capacity, **options)
         except RuntimeError as e:
             raise BackendError("%s: %s" % (e, self._err()))
 

@@ -561,6 +561,79 @@ gfbe_status gfbe_lc4_solve(gfbe_ctx *ctx, const gfbe_lc4_options *opt /* NULL: d
                            double *yaw_out, double *drift, gfbe_summary *summary);
 
 /* ------------------------------------------------------------------------------------------
+ * f3c dense RGB-D map of dense_map, what the loop-closure thread does with the solved poses (paths under dense_map/src/):
+ *       addKeyFrame: gate, density < 3, the keyframe's list shrunk to the survivors   pose_graph.cpp:191-221   gfbe_dmap_add_keyframe
+ *       updatePath: the map cleared and rebuilt at the corrected poses, density < 5   :997-1032                gfbe_dmap_rebuild
+ *       RadiusOutlierRemoval 0.8 m / 10 neighbours, the published cloud               :228-239, :1041-1056     gfbe_dmap_filter
+ *     The handle holds the keyframes' camera-frame point lists (KeyFrame::point_rgbd: float xyz, uint8 rgb) in one pool, in
+ *     keyframe order then list order, the voxel table (key -> point count) and the cloud in insertion order (world float
+ *     xyz, rgb, keyframe index, pool index). Conventions of gfbe_scan: operations run in order on the context's stream,
+ *     every count lives in device memory and nothing but gfbe_dmap_size, the downloads and gfbe_dmap_filter waits for the
+ *     device (an insert whose arrays exceed a 64 KB staging slot, about 3 900 points, also waits); without a GPU every
+ *     entry point returns GFBE_NO_DEVICE; a bad argument returns GFBE_BAD_INPUT with gfbe_last_error set and the handle
+ *     untouched.
+ *     World point: pw = R(q) (R(q_ic) (double)p + t_ic) + P in FP64, quaternions x y z w and unit, products left to right
+ *     per row; the stored and keyed point is (float)pw. Gate (insert only): dropped when pw.z > z_max || pw.z < z_min on the
+ *     FP64 value; gated points leave the keyframe's list too. Voxel key per axis: floor(((double)pf - origin) / resolution)
+ *     of the float point, valid for 0 <= key < 2^21 (with the defaults the box -10000 .. 10971.52 m); a NaN point or one
+ *     outside the box is skipped and counted. PCL's octree key arithmetic is not part of the reference tree: this key is a
+ *     stated deviation.
+ *     Density cap: within one call the candidates are the call's points that pass the gate and have a key, in list order; a
+ *     candidate is kept iff base + rank < cap, base = the voxel's count before the call, rank = the number of earlier
+ *     candidates of this call in the same voxel; kept points raise the count. After a rebuild (cap 5) a voxel may hold 5,
+ *     and a later insert (cap 3) keeps nothing there, as in the reference. No result depends on the order workgroups ran in.
+ *     Capacity: an insert keeps, of the points it would keep, the first that fit the pool, and counts the rest in
+ *     n_refused; an insert that meets a full pool or a full keyframe table is refused whole, all n points counted
+ *     unexamined, and adds no keyframe. Never an out-of-bounds write. The table has the next power of two >= 2
+ *     point_capacity slots, so a claim cannot fail.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct gfbe_dmap gfbe_dmap;
+typedef struct gfbe_dmap_options {
+  int32_t struct_size;            /* sizeof(gfbe_dmap_options), written by gfbe_dmap_default_options */
+  int32_t add_cap;                /* 3 (pose_graph.cpp:212), 1 .. 8 */
+  int32_t rebuild_cap;            /* 5 (:1025), 1 .. 8 */
+  int32_t filter_min_neighbors;   /* 10 (:236): a point is kept with MORE than this many points within the radius, itself
+                                     counted. This is how PCL's RadiusOutlierRemoval is remembered (self counted, outlier
+                                     when k <= min_pts); PCL is not in the reference tree, so it cannot be checked here */
+  double resolution;              /* 0.01 (:29) */
+  double origin;                  /* -10000 (:1004; the constructor's box has y_min = -1000, :34: both whole voxels) */
+  double z_min, z_max;            /* -0.5, 2 (:201) */
+  double ex_cam[7];               /* t_ic, q_ic (x y z w, unit); default identity */
+  double filter_radius;           /* 0.8 (:234) */
+} gfbe_dmap_options;
+void gfbe_dmap_default_options(gfbe_dmap_options *opt);
+/* GFBE_BAD_INPUT: point_capacity outside 1 .. 2^26, keyframe_capacity outside 1 .. 2^24, caps outside 1 .. 8, an options
+ * struct of another size, non-finite options, a filter_radius too small for its coarse grid to cover the voxel box. */
+gfbe_status gfbe_dmap_create(gfbe_ctx *ctx, int32_t point_capacity, int32_t keyframe_capacity,
+                             const gfbe_dmap_options *opt /* NULL: defaults */, gfbe_dmap **out);
+void gfbe_dmap_destroy(gfbe_ctx *ctx, gfbe_dmap *map);
+/* addKeyFrame: a new keyframe at pose7 [t | q] with n points pts_cam [n][3], rgb [n][3]; cap = add_cap. The kept points are
+ * appended to the cloud and, camera-frame, to the pool as the keyframe's list, both in ascending input index.
+ * GFBE_BAD_INPUT: n < 0, n > point_capacity, a NULL array with n > 0, a non-finite pose. */
+gfbe_status gfbe_dmap_add_keyframe(gfbe_ctx *ctx, gfbe_dmap *map, const double *pose7, int32_t n, const float *pts_cam,
+                                   const uint8_t *rgb);
+/* updatePath: the table and the cloud are cleared; the candidates are all pool points in pool order at pose7
+ * [n_keyframes][7]; no gate; cap = rebuild_cap. The pool is not changed. GFBE_BAD_INPUT: n_keyframes is not the number of
+ * keyframes held, a non-finite pose. Returns without waiting. */
+gfbe_status gfbe_dmap_rebuild(gfbe_ctx *ctx, gfbe_dmap *map, int32_t n_keyframes, const double *pose7);
+/* keep [n_cloud] = 1 iff more than filter_min_neighbors cloud points, the point itself counted, have
+ * (dx dx + dy dy) + dz dz <= radius radius in FP64 on the float coordinates. xyz_out / rgb_out [n_cloud][3] (both or
+ * neither): the kept points compacted in cloud order, what pub_octree publishes. Any output may be NULL; waits. */
+gfbe_status gfbe_dmap_filter(gfbe_ctx *ctx, gfbe_dmap *map, uint8_t *keep, int32_t *n_keep, float *xyz_out,
+                             uint8_t *rgb_out);
+/* counts [GFBE_DMAP_N_COUNTS]: keyframes, stored points (the pool), cloud points, voxels, skipped (NaN or outside the
+ * box; inserts and rebuilds), gated, refused for capacity (the last three since the handle was made), and the points the
+ * last filter kept through its dense-cell fast path. Waits. */
+#define GFBE_DMAP_N_COUNTS 8
+gfbe_status gfbe_dmap_size(gfbe_ctx *ctx, gfbe_dmap *map, int32_t *counts);
+/* The cloud in insertion order: xyz [n_cloud][3], rgb [n_cloud][3], kf [n_cloud], src [n_cloud] (pool index). Any may be
+ * NULL; waits. */
+gfbe_status gfbe_dmap_download_cloud(gfbe_ctx *ctx, gfbe_dmap *map, float *xyz, uint8_t *rgb, int32_t *kf, int32_t *src);
+/* Keyframe k's list as it is now: *n, pts [n][3] camera frame, rgb [n][3] (pts / rgb NULL: the count only). Waits.
+ * GFBE_BAD_INPUT: no such keyframe. */
+gfbe_status gfbe_dmap_download_keyframe(gfbe_ctx *ctx, gfbe_dmap *map, int32_t k, int32_t *n, float *pts, uint8_t *rgb);
+
+/* ------------------------------------------------------------------------------------------
  * f4  LIO scan residuals (BASELINE configs[4]): point-to-plane factors of the LiDAR
  *     odometry, evaluated and reduced to normal equations on the device (the voxel neighbour search that produces
  *     the planes runs on the device too: the voxel map section below, gfbe_vmap_associate / gfbe_vmap_linearize):
