@@ -768,6 +768,7 @@ def pg_plus(x, d6):
 # f3b: loop-closure pose graph of dense_map, 4-DoF (gfbe_lc4_*; the model is tests/lc4_np.py, there is no oracle row)
 # ---------------------------------------------------------------------------------------------
 LC4_MAX_LOOPS = 64
+LC4_LONG_MAX_LOOPS = 512
 
 
 class Lc4Options(C.Structure):
@@ -784,8 +785,9 @@ class LoopGraph:
         f.restype, f.argtypes = None, [PO]
         f = getattr(lib, prefix + "lc4_eval")
         f.restype, f.argtypes = c_i, [C.c_void_p, PO, c_i, PD, PD, c_i, PI, PI, PU8, PD, PD, PD, PD]
-        f = getattr(lib, prefix + "lc4_solve")
-        f.restype, f.argtypes = c_i, [C.c_void_p, PO, c_i, PD, PD, PI, PU8, c_i, PI, PI, PD, PD, PD, PD, C.POINTER(Summary)]
+        for name in ("lc4_solve", "lc4_solve_long"):
+            f = getattr(lib, prefix + name)
+            f.restype, f.argtypes = c_i, [C.c_void_p, PO, c_i, PD, PD, PI, PU8, c_i, PI, PI, PD, PD, PD, PD, C.POINTER(Summary)]
 
     def options(self, **kw):
         o = Lc4Options()
@@ -809,19 +811,29 @@ class LoopGraph:
             raise RuntimeError("%slc4_eval failed with status %d" % (self.prefix, rc))
         return out
 
-    def solve_rc(self, t, ypr, sequence, fixed, loop_i, loop_c, loop_meas, opt=None):
+    def solve_rc(self, t, ypr, sequence, fixed, loop_i, loop_c, loop_meas, opt=None, entry="lc4_solve"):
         t, ypr, lm = _f64(t).reshape(-1, 3), _f64(ypr).reshape(-1, 3), _f64(loop_meas).reshape(-1, 4)
         seq, fx, li, lc = _i32(sequence), _u8(fixed), _i32(loop_i), _i32(loop_c)
         n = len(t)
         t_out, yaw_out, drift, sm = np.full((n, 3), np.nan), np.full(n, np.nan), np.full(4, np.nan), Summary()
-        rc = getattr(self.lib, self.prefix + "lc4_solve")(self.ctx, C.byref(opt) if opt is not None else None, n, _pd(t), _pd(ypr), _pi(seq), fx.ctypes.data_as(PU8),
-                                                         len(li), _pi(li), _pi(lc), _pd(lm), _pd(t_out), _pd(yaw_out), _pd(drift), C.byref(sm))
+        rc = getattr(self.lib, self.prefix + entry)(self.ctx, C.byref(opt) if opt is not None else None, n, _pd(t), _pd(ypr), _pi(seq), fx.ctypes.data_as(PU8),
+                                                   len(li), _pi(li), _pi(lc), _pd(lm), _pd(t_out), _pd(yaw_out), _pd(drift), C.byref(sm))
         return rc, dict(t=t_out, yaw=yaw_out, drift=drift, summary=summary_to_dict(sm), status=rc)
 
     def solve(self, *a, **kw):
         rc, out = self.solve_rc(*a, **kw)
         if rc not in (OK, NO_CONVERGENCE):
             raise RuntimeError("%slc4_solve failed with status %d" % (self.prefix, rc))
+        return out
+
+    def solve_long_rc(self, *a, **kw):
+        """gfbe_lc4_solve_long: up to LC4_LONG_MAX_LOOPS loop edges; arguments and result as solve_rc."""
+        return self.solve_rc(*a, entry="lc4_solve_long", **kw)
+
+    def solve_long(self, *a, **kw):
+        rc, out = self.solve_long_rc(*a, **kw)
+        if rc not in (OK, NO_CONVERGENCE):
+            raise RuntimeError("%slc4_solve_long failed with status %d" % (self.prefix, rc))
         return out
 
 

@@ -43,7 +43,7 @@ EXPORTS = [
     "gfbe_vreg_default_options", "gfbe_vmap_register", "gfbe_vmap_add_scan",
     "gfbe_scan_create", "gfbe_scan_destroy", "gfbe_scan_upload", "gfbe_scan_subsample", "gfbe_scan_undistort", "gfbe_scan_keypoints",
     "gfbe_scan_size", "gfbe_scan_download", "gfbe_vmap_register_scan", "gfbe_vmap_add_scan_handle",
-    "gfbe_lc4_default_options", "gfbe_lc4_eval", "gfbe_lc4_solve",
+    "gfbe_lc4_default_options", "gfbe_lc4_eval", "gfbe_lc4_solve", "gfbe_lc4_solve_long",
     "gfbe_dmap_default_options", "gfbe_dmap_create", "gfbe_dmap_destroy", "gfbe_dmap_add_keyframe", "gfbe_dmap_rebuild", "gfbe_dmap_filter",
     "gfbe_dmap_size", "gfbe_dmap_download_cloud", "gfbe_dmap_download_keyframe",
 ]

@@ -21,6 +21,7 @@
 namespace gfd {
 
 constexpr int LC4_MAX_LOOPS = 64;      // GFBE_LC4_MAX_LOOPS: the capacitance system stays within 16 tile columns
+constexpr int LC4_LONG_MAX_LOOPS = 512;      // GFBE_LC4_LONG_MAX_LOOPS: 128 tile columns, factorised across workgroups (gfbe_lc4_solve_long)
 constexpr int LC4_SB = 16;             // a super-block: four consecutive poses x four tangent dimensions
 constexpr int LC4_MAX_SPAN = 4;        // sequence edges reach at most four poses back: neighbours share or touch a super-block
 
@@ -113,9 +114,9 @@ struct Lc4Plan {
 
 LC4_HD inline size_t lc4_align32(size_t v) { return (v + 31) & ~(size_t)31; }
 
-// false for n < 1 or n_loop outside [0, LC4_MAX_LOOPS]
-LC4_HD inline bool lc4_plan(int n, int n_loop, Lc4Plan *p) {
-  if (n < 1 || n_loop < 0 || n_loop > LC4_MAX_LOOPS) return false;
+// false for n < 1 or n_loop outside [0, max_loops]
+LC4_HD inline bool lc4_plan_within(int n, int n_loop, int max_loops, Lc4Plan *p) {
+  if (n < 1 || n_loop < 0 || n_loop > max_loops) return false;
   p->n = n; p->n_loop = n_loop;
   p->M = (n + 3) / 4;
   p->rows = LC4_SB * p->M;
@@ -143,11 +144,29 @@ LC4_HD inline bool lc4_plan(int n, int n_loop, Lc4Plan *p) {
   p->total = at;
   return true;
 }
+// false for n < 1 or n_loop outside [0, LC4_MAX_LOOPS]
+LC4_HD inline bool lc4_plan(int n, int n_loop, Lc4Plan *p) { return lc4_plan_within(n, n_loop, LC4_MAX_LOOPS, p); }
 
-// Input validation of gfbe_lc4_solve (the GFBE_BAD_INPUT cases that need no device): 0 = fine, else which rule failed.
-inline int lc4_check_graph(int n, int n_loop, const int32_t *loop_i, const int32_t *loop_c, int span, uint8_t *has_loop /* [n], scratch */) {
+// The plan of gfbe_lc4_solve_long: the same carve up to LC4_LONG_MAX_LOOPS loop edges (off_Dinv holds the cap_ld / 16 pivot tiles'
+// inverses, 256 doubles each), and behind it the right-hand side v = U^T z_0 of the capacitance system, which the blocked
+// factorisation carries through its forward substitution. p.total includes it: 2 rows ld + 2 cap_ld^2 + 161 rows + 18 cap_ld doubles
+// (rounded up to 256-byte units); at n = 5000 with 512 loop edges 2 panels of 20 000 x 2064 and S, L of 2048 x 2048, 0.75 GB in all.
+struct Lc4LongPlan {
+  Lc4Plan p;
+  size_t off_v;      // [cap_ld]
+};
+LC4_HD inline bool lc4_long_plan(int n, int n_loop, Lc4LongPlan *q) {
+  if (!lc4_plan_within(n, n_loop, LC4_LONG_MAX_LOOPS, &q->p)) return false;
+  q->off_v = q->p.total;
+  q->p.total += lc4_align32((size_t)q->p.cap_ld);
+  return true;
+}
+
+// Input validation of gfbe_lc4_solve / gfbe_lc4_solve_long (the GFBE_BAD_INPUT cases that need no device): 0 = fine, else which rule
+// failed (2: more than max_loops loop edges).
+inline int lc4_check_graph_within(int n, int n_loop, int max_loops, const int32_t *loop_i, const int32_t *loop_c, int span, uint8_t *has_loop /* [n], scratch */) {
   if (n < 1) return 1;
-  if (n_loop < 0 || n_loop > LC4_MAX_LOOPS) return 2;
+  if (n_loop < 0 || n_loop > max_loops) return 2;
   if (span < 1 || span > LC4_MAX_SPAN) return 3;
   for (int i = 0; i < n; i++) has_loop[i] = 0;
   for (int l = 0; l < n_loop; l++) {
@@ -157,6 +176,12 @@ inline int lc4_check_graph(int n, int n_loop, const int32_t *loop_i, const int32
     has_loop[loop_i[l]] = 1;
   }
   return 0;
+}
+inline int lc4_check_graph(int n, int n_loop, const int32_t *loop_i, const int32_t *loop_c, int span, uint8_t *has_loop) {
+  return lc4_check_graph_within(n, n_loop, LC4_MAX_LOOPS, loop_i, loop_c, span, has_loop);
+}
+inline int lc4_long_check_graph(int n, int n_loop, const int32_t *loop_i, const int32_t *loop_c, int span, uint8_t *has_loop) {
+  return lc4_check_graph_within(n, n_loop, LC4_LONG_MAX_LOOPS, loop_i, loop_c, span, has_loop);
 }
 
 }  // namespace gfd

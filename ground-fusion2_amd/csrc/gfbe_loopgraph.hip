@@ -1,4 +1,4 @@
-// gfbe_loopgraph.hip — the loop-closure pose graph of dense_map on the device (gfbe_lc4_eval, gfbe_lc4_solve).
+// gfbe_loopgraph.hip — the loop-closure pose graph of dense_map on the device (gfbe_lc4_eval, gfbe_lc4_solve, gfbe_lc4_solve_long).
 //
 //   PoseGraph::optimize4DoF             dense_map/src/pose_graph.cpp:529-705 (options :558-566)
 //   FourDOFError, FourDOFWeightError    dense_map/src/pose_graph.h:199-288
@@ -11,7 +11,8 @@
 //                               multiplier against 16-column tiles of the panel (ping-pong in the context's scratch);
 //   S = I + U^T Z               gathered through U's 8 non-zeros per column, factorised by ONE workgroup as a block LDL^T in 16-wide
 //                               tiles through L2 (the pivot tile inverted as the super-blocks are, matrix cores for L_IP and the
-//                               trailing update), then y = z_0 - Z S^-1 U^T z_0.
+//                               trailing update), then y = z_0 - Z S^-1 U^T z_0. Beyond LC4_MAX_LOOPS loop edges
+//                               (gfbe_lc4_solve_long) the same factorisation runs across workgroups, one pivot step per launch pair.
 // Every sum runs in a fixed order (owner-computes linearisation, no atomics); the trust-region loop (the statements of k_pg_decide,
 // restated) lives in a device struct: the host enqueues max_num_iterations passes and waits once, every kernel returns at once when
 // `done` is set, nothing spins and no kernel waits on another workgroup. tests/lc4_np.py is the model, phase for phase.
@@ -20,6 +21,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "gfbe_device.h"
@@ -474,6 +476,116 @@ __global__ __launch_bounds__(256) void k_lc4_cap(Lc4Dev P, const Lc4State *st, c
   }
   if (t < N) w[t] = sv[t];
 }
+// ---- the capacitance system beyond LC4_MAX_LOOPS loop edges (gfbe_lc4_solve_long; N = cap_ld up to 2048, 128 tile columns): the
+// algorithm of k_lc4_cap spread over the device and ordered by launch boundaries alone — a gather, per pivot step p one launch for the
+// tile column (k_lc4_cap_panel) and one for the trailing update (k_lc4_cap_trail), then the substitution (k_lc4_cap_back). Within a
+// launch no workgroup reads what another one writes: the panel launch reads column p of S and writes column p of L, the trailing
+// launch reads those two columns and writes the columns behind them. Every tile is written by one wave per launch, by one fixed
+// sequence of operations, and every entry of S, L, D^-1 and v that is read was written in this pass.
+enum { LC4_GATHER_BLOCKS = 2048 };
+// S = I + U^T Z[:, 1:] and v = U^T z_0 (entry N N + a), element by element: the 8-term sum of k_lc4_cap in its order; padding = identity
+__global__ __launch_bounds__(256) void k_lc4_cap_gather(Lc4Dev P, const Lc4State *st, const double *Us, const double *Z, double *Sm, double *v) {
+  if (st->done) return;
+  const size_t N = (size_t)P.cap_ld, NN = N * N, total = NN + N;
+  const int c4 = 4 * P.L, ld = P.ld;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+    const bool vec = e >= NN;
+    const int a = vec ? (int)(e - NN) : (int)(e / N), b = vec ? -1 : (int)(e - (size_t)a * N);      // (b = -1: column 0 of Z)
+    double s = a == b ? 1.0 : 0.0;
+    if (a < c4 && b < c4) {
+      const int l = a >> 2;
+      for (int k = 0; k < 8; k++) {
+        const int row = 4 * (k < 4 ? P.loop_c[l] : P.loop_i[l]) + (k & 3);
+        s += Us[8 * (size_t)a + k] * Z[(size_t)row * ld + 1 + b];
+      }
+    }
+    if (vec) v[a] = s; else Sm[e] = s;
+  }
+}
+// pivot step p, the tile column: every workgroup inverts the pivot tile S_pp for itself (the same instructions on the same values),
+// workgroup 0 keeps D_p^-1; wave w of workgroup b takes tile row I = p + 1 + 4 b + w: L_Ip = S_Ip D_p^-1 on the matrix cores, and the
+// forward substitution rides along, v_I -= L_Ip v_p (v_p is final since the launch of step p - 1), one lane per row, columns in order
+__global__ __launch_bounds__(256) void k_lc4_cap_panel(int N, int p, const Lc4State *st, const double *Sm, double *Lb, double *Dinv, double *v, int *fail) {
+  __shared__ double W[16 * GJ_LD], sD[256], sL[4][16 * 17], svp[16];
+  if (st->done) return;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, lr = lane & 15, lk = lane >> 4, nt = N / 16;
+  if (t < 64) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) { const int e = t + 64 * j; W[(e >> 4) * GJ_LD + (e & 15)] = Sm[(size_t)(16 * p + (e >> 4)) * N + 16 * p + (e & 15)]; }
+  }
+  if (t < 16) svp[t] = v[16 * p + t];
+  gj_inverse16(W, t, fail);
+  gj_store(W, t, blockIdx.x == 0 ? Dinv + (size_t)p * 256 : nullptr, sD);
+  __syncthreads();
+  const int I = p + 1 + 4 * (int)blockIdx.x + wave;
+  if (I < nt) {
+    const dbl4 zero = {0.0, 0.0, 0.0, 0.0};
+    const dbl4 acc = mm16(Sm + (size_t)16 * I * N + 16 * p, N, sD, 16, zero, lr, lk, 1.0);
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      Lb[(size_t)(16 * I + lk + 4 * q) * N + 16 * p + lr] = acc[q];
+      sL[wave][(lk + 4 * q) * 17 + lr] = acc[q];
+    }
+  }
+  __syncthreads();
+  if (I < nt && lane < 16) {
+    double s = 0.0;
+    for (int k = 0; k < 16; k++) s += sL[wave][lane * 17 + k] * svp[k];
+    v[16 * I + lane] -= s;
+  }
+}
+// ... and the trailing update S_IJ -= L_Ip S_Jp^T of the lower triangle p < J <= I, one wave per tile: workgroup (x, y) takes row
+// I = p + 1 + x, its wave w column J = p + 1 + 4 y + w. The operands and the four matrix-core operations of k_lc4_cap.
+__global__ __launch_bounds__(256) void k_lc4_cap_trail(int N, int p, const Lc4State *st, double *Sm, const double *Lb) {
+  if (st->done) return;
+  const int t = threadIdx.x, lane = t & 63, lr = lane & 15, lk = lane >> 4;
+  const int I = p + 1 + (int)blockIdx.x, J = p + 1 + 4 * (int)blockIdx.y + (t >> 6);
+  if (J > I) return;
+  double *Cij = Sm + (size_t)16 * I * N + 16 * J;
+  const double *LI = Lb + (size_t)16 * I * N + 16 * p, *SJ = Sm + (size_t)16 * J * N + 16 * p;
+  dbl4 acc;
+  double va[4], vb[4];
+#pragma unroll
+  for (int q = 0; q < 4; q++) { acc[q] = Cij[(size_t)(lk + 4 * q) * N + lr]; va[q] = -LI[(size_t)lr * N + 4 * q + lk]; vb[q] = SJ[(size_t)lr * N + 4 * q + lk]; }
+#pragma unroll
+  for (int kk = 0; kk < 4; kk++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(va[kk], vb[kk], acc, 0, 0, 0);
+#pragma unroll
+  for (int q = 0; q < 4; q++) Cij[(size_t)(lk + 4 * q) * N + lr] = acc[q];
+}
+// w = L^-T D^-1 (L^-1 v): the forward part came with the panels; here the pivot tiles' inverses, one thread per row, and the backward
+// substitution with the vector in LDS (N <= 2048: 16 KB), one workgroup of 1024: once tile I of w is final every column c < 16 I takes
+// its share, w_c -= sum_k L[16 I + k][c] w[16 I + k] (k in order; a thread owns its columns, the rows of L are read coalesced)
+enum { LC4_BACK_THREADS = 1024, LC4_BACK_N = 16 * ((4 * LC4_LONG_MAX_LOOPS + 15) / 16) };
+__global__ __launch_bounds__(LC4_BACK_THREADS) void k_lc4_cap_back(int N, const Lc4State *st, const double *Lb, const double *Dinv, const double *v, double *w) {
+  __shared__ double sv[LC4_BACK_N];
+  if (st->done) return;
+  const int t = threadIdx.x, nt = N / 16;
+  for (int r = t; r < N; r += LC4_BACK_THREADS) sv[r] = v[r];
+  __syncthreads();
+  double z[LC4_BACK_N / LC4_BACK_THREADS];
+#pragma unroll
+  for (int j = 0; j < LC4_BACK_N / LC4_BACK_THREADS; j++) {
+    const int r = t + LC4_BACK_THREADS * j;
+    double s = 0.0;
+    if (r < N) for (int k = 0; k < 16; k++) s += Dinv[(size_t)(r >> 4) * 256 + (r & 15) * 16 + k] * sv[16 * (r >> 4) + k];
+    z[j] = s;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < LC4_BACK_N / LC4_BACK_THREADS; j++) { const int r = t + LC4_BACK_THREADS * j; if (r < N) sv[r] = z[j]; }
+  __syncthreads();
+  for (int I = nt - 1; I >= 1; I--) {
+    const double *LI = Lb + (size_t)16 * I * N;
+    for (int c = t; c < 16 * I; c += LC4_BACK_THREADS) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < 16; k++) s += LI[(size_t)k * N + c] * sv[16 * I + k];
+      sv[c] -= s;
+    }
+    __syncthreads();
+  }
+  for (int r = t; r < N; r += LC4_BACK_THREADS) w[r] = sv[r];
+}
 // y = z_0 - Z[:, 1:] w, one thread per row, the columns in order
 __global__ __launch_bounds__(256) void k_lc4_apply(int rows, int ld, int c4, const Lc4State *st, const double *Z, const double *w, double *y) {
   if (st->done) return;
@@ -700,21 +812,38 @@ gfbe_status gfbe_lc4_eval(gfbe_ctx *c, const gfbe_lc4_options *opt, int32_t n, c
   return GFBE_OK;
 }
 
-gfbe_status gfbe_lc4_solve(gfbe_ctx *c, const gfbe_lc4_options *opt, int32_t n, const double *t, const double *ypr, const int32_t *sequence, const uint8_t *fixed,
-                           int32_t n_loop, const int32_t *loop_i, const int32_t *loop_c, const double *loop_meas, double *t_out, double *yaw_out, double *drift,
-                           gfbe_summary *S_out) {
+}  // extern "C"
+
+namespace {
+
+// The body of gfbe_lc4_solve (max_loops = LC4_MAX_LOOPS) and gfbe_lc4_solve_long (LC4_LONG_MAX_LOOPS): one graph construction, one
+// pass structure. Up to LC4_MAX_LOOPS loop edges the capacitance system is k_lc4_cap's, beyond it the blocked kernels'.
+gfbe_status lc4_solve_body(const char *name, const char *limit_name, int max_loops, gfbe_ctx *c, const gfbe_lc4_options *opt, int32_t n, const double *t, const double *ypr,
+                           const int32_t *sequence, const uint8_t *fixed, int32_t n_loop, const int32_t *loop_i, const int32_t *loop_c, const double *loop_meas, double *t_out,
+                           double *yaw_out, double *drift, gfbe_summary *S_out) {
   gfbe_lc4_options o;
   if (!c) return GFBE_BAD_INPUT;
-  if (!options_ok(opt, &o)) { ctx_set_error(c, "gfbe_lc4_solve: gfbe_lc4_options of another size or out of range (ABI mismatch)"); return GFBE_BAD_INPUT; }
+  const std::string who(name);
+  if (!options_ok(opt, &o)) { ctx_set_error(c, (who + ": gfbe_lc4_options of another size or out of range (ABI mismatch)").c_str()); return GFBE_BAD_INPUT; }
   if (n < 1 || !t || !ypr || !sequence || !fixed || !t_out || !yaw_out || n_loop < 0 || (n_loop && (!loop_i || !loop_c || !loop_meas))) return GFBE_BAD_INPUT;
   Lc4Plan plan;
+  size_t off_v = 0;
+  const bool blocked = n_loop > LC4_MAX_LOOPS;
   std::vector<uint8_t> has_loop(n);
-  const int bad = lc4_check_graph(n, n_loop, loop_i, loop_c, o.span, has_loop.data());
-  if (bad || !lc4_plan(n, n_loop, &plan)) {
-    ctx_set_error(c, bad == 2 ? "gfbe_lc4_solve: more than GFBE_LC4_MAX_LOOPS loop edges" : "gfbe_lc4_solve: loop edges need 0 <= loop_c < loop_i < n, one per loop_i");
+  const int bad = lc4_check_graph_within(n, n_loop, max_loops, loop_i, loop_c, o.span, has_loop.data());
+  bool planned = false;
+  if (!bad && blocked) {
+    Lc4LongPlan lp;
+    planned = lc4_long_plan(n, n_loop, &lp);
+    if (planned) { plan = lp.p; off_v = lp.off_v; }
+  } else if (!bad) {
+    planned = lc4_plan(n, n_loop, &plan);
+  }
+  if (bad || !planned) {
+    ctx_set_error(c, (bad == 2 ? who + ": more than " + limit_name + " loop edges" : who + ": loop edges need 0 <= loop_c < loop_i < n, one per loop_i").c_str());
     return GFBE_BAD_INPUT;
   }
-  if (ctx_device(c) < 0) { ctx_set_error(c, "gfbe_lc4_solve: no device (no CPU fallback)"); return GFBE_NO_DEVICE; }
+  if (ctx_device(c) < 0) { ctx_set_error(c, (who + ": no device (no CPU fallback)").c_str()); return GFBE_NO_DEVICE; }
   const int max_it = std::min(o.max_num_iterations, 15);
   // the graph: sequence edges with their measurements (formed from the input poses), the loop edges that are kept, who is in the problem
   std::vector<unsigned char> emask(n, 0), free_(n, 0), loop_on(std::max(n_loop, 1), 0);
@@ -778,14 +907,14 @@ gfbe_status gfbe_lc4_solve(gfbe_ctx *c, const gfbe_lc4_options *opt, int32_t n, 
     Bs = buf.dev<double>((size_t)256 * M); As = buf.dev<double>((size_t)256 * M); Cs = buf.dev<double>((size_t)256 * M); Us = buf.dev<double>((size_t)32 * L);
     big = buf.dev<double>(plan.total);      // the plan's carve: panels, band sets, multipliers, capacitance, step
     xo = buf.pinned<double>((size_t)4 * n);
-    if (pass == 0 && !buf.commit(small_bytes)) { ctx_set_error(c, "gfbe_lc4_solve: device allocation failed"); return GFBE_DEVICE_ERROR; }
+    if (pass == 0 && !buf.commit(small_bytes)) { ctx_set_error(c, (who + ": device allocation failed").c_str()); return GFBE_DEVICE_ERROR; }
   }
   Q = {cost_i, cost_l, gabs, model_r, step2_i, xn2_i};
   double *panel[2] = {big + plan.off_panel[0], big + plan.off_panel[1]};
   double *band[2][4];
   for (int q = 0; q < 2; q++) for (int k = 0; k < 4; k++) band[q][k] = big + plan.off_band[q][k];
   double *alpha = big + plan.off_alpha, *gamma = big + plan.off_gamma, *Sm = big + plan.off_S, *Lb = big + plan.off_L, *Dinv = big + plan.off_Dinv,
-         *w = big + plan.off_w, *y = big + plan.off_y;
+         *w = big + plan.off_w, *y = big + plan.off_y, *vcap = big + off_v;      // (vcap: the blocked path only)
   const dim3 gr((rows + 255) / 256), b256(256);
   auto lin = [&](int cand) {
     hipLaunchKernelGGL(k_lc4_lin, gr, b256, 0, s, P, dst, S, cand, cost_i);
@@ -796,6 +925,8 @@ gfbe_status gfbe_lc4_solve(gfbe_ctx *c, const gfbe_lc4_options *opt, int32_t n, 
   decide(0);
   const dim3 gp(M, (plan.ntile + 3) / 4);
   const int fill_blocks = (int)std::min<size_t>(((size_t)rows * plan.ld + 255) / 256, 4096);
+  const int cap_nt = plan.cap_ld / LC4_SB;
+  const int gather_blocks = (int)std::min<size_t>(((size_t)plan.cap_ld * (plan.cap_ld + 1) + 255) / 256, LC4_GATHER_BLOCKS);
   // max_it passes, enqueued blindly: every kernel of a pass returns at once when the loop has ended
   for (int pass = 0; pass < max_it; pass++) {
     hipLaunchKernelGGL(k_lc4_scale, gr, b256, 0, s, P, dst, S, scale, g0, diag0, gabs);
@@ -812,7 +943,16 @@ gfbe_status gfbe_lc4_solve(gfbe_ctx *c, const gfbe_lc4_options *opt, int32_t n, 
     }
     double *Z = panel[1 - cur];
     hipLaunchKernelGGL(k_lc4_final, gp, b256, 0, s, plan.ld, plan.ntile, dst, band[cur][3], panel[cur], Z);
-    if (L) hipLaunchKernelGGL(k_lc4_cap, dim3(1), b256, 0, s, P, dst, Us, Z, Sm, Lb, Dinv, w, fail);
+    if (L && !blocked) hipLaunchKernelGGL(k_lc4_cap, dim3(1), b256, 0, s, P, dst, Us, Z, Sm, Lb, Dinv, w, fail);
+    if (blocked) {      // 2 + 2 cap_nt - 1 launches
+      hipLaunchKernelGGL(k_lc4_cap_gather, dim3(gather_blocks), b256, 0, s, P, dst, Us, Z, Sm, vcap);
+      for (int p = 0; p < cap_nt; p++) {
+        const int nrem = cap_nt - 1 - p;
+        hipLaunchKernelGGL(k_lc4_cap_panel, dim3(std::max(1, (nrem + 3) / 4)), b256, 0, s, plan.cap_ld, p, dst, Sm, Lb, Dinv, vcap, fail);
+        if (nrem) hipLaunchKernelGGL(k_lc4_cap_trail, dim3(nrem, (nrem + 3) / 4), b256, 0, s, plan.cap_ld, p, dst, Sm, Lb);
+      }
+      hipLaunchKernelGGL(k_lc4_cap_back, dim3(1), dim3(LC4_BACK_THREADS), 0, s, plan.cap_ld, dst, Lb, Dinv, vcap, w);
+    }
     hipLaunchKernelGGL(k_lc4_apply, gr, b256, 0, s, rows, plan.ld, 4 * L, dst, Z, w, y);
     hipLaunchKernelGGL(k_lc4_candidate, dim3((rows + L + 255) / 256), b256, 0, s, P, dst, S, Bs, As, Cs, gs, Us, y, scale, model_r, step2_i, xn2_i);
     decide(1);
@@ -821,7 +961,7 @@ gfbe_status gfbe_lc4_solve(gfbe_ctx *c, const gfbe_lc4_options *opt, int32_t n, 
   }
   Lc4State *hst = (Lc4State *)buf.result();
   hipLaunchKernelGGL(k_lc4_finish, dim3(std::min(256, (4 * n + 255) / 256)), b256, 0, s, n, dst, S, xo, hst);
-  if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) { ctx_set_error(c, "gfbe_lc4_solve: device error"); return GFBE_DEVICE_ERROR; }
+  if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) { ctx_set_error(c, (who + ": device error").c_str()); return GFBE_DEVICE_ERROR; }
   for (int i = 0; i < n; i++) {
     yaw_out[i] = xo[4 * (size_t)i];
     for (int k = 0; k < 3; k++) t_out[3 * (size_t)i + k] = xo[4 * (size_t)i + 1 + k];
@@ -841,6 +981,23 @@ gfbe_status gfbe_lc4_solve(gfbe_ctx *c, const gfbe_lc4_options *opt, int32_t n, 
   for (int q = 0; q < 16; q++) { sm.cost_history[q] = hst->cost_history[q]; sm.accepted[q] = (uint8_t)hst->accepted[q]; }
   if (S_out) *S_out = sm;
   return sm.status == GFBE_NUMERICAL_FAILURE ? GFBE_NUMERICAL_FAILURE : GFBE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+gfbe_status gfbe_lc4_solve(gfbe_ctx *c, const gfbe_lc4_options *opt, int32_t n, const double *t, const double *ypr, const int32_t *sequence, const uint8_t *fixed,
+                           int32_t n_loop, const int32_t *loop_i, const int32_t *loop_c, const double *loop_meas, double *t_out, double *yaw_out, double *drift,
+                           gfbe_summary *S_out) {
+  return lc4_solve_body("gfbe_lc4_solve", "GFBE_LC4_MAX_LOOPS", LC4_MAX_LOOPS, c, opt, n, t, ypr, sequence, fixed, n_loop, loop_i, loop_c, loop_meas, t_out, yaw_out, drift, S_out);
+}
+
+gfbe_status gfbe_lc4_solve_long(gfbe_ctx *c, const gfbe_lc4_options *opt, int32_t n, const double *t, const double *ypr, const int32_t *sequence, const uint8_t *fixed,
+                                int32_t n_loop, const int32_t *loop_i, const int32_t *loop_c, const double *loop_meas, double *t_out, double *yaw_out, double *drift,
+                                gfbe_summary *S_out) {
+  return lc4_solve_body("gfbe_lc4_solve_long", "GFBE_LC4_LONG_MAX_LOOPS", LC4_LONG_MAX_LOOPS, c, opt, n, t, ypr, sequence, fixed, n_loop, loop_i, loop_c, loop_meas, t_out, yaw_out,
+                        drift, S_out);
 }
 
 }  // extern "C"

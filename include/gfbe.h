@@ -541,8 +541,18 @@ gfbe_status gfbe_pg_solve(gfbe_ctx *ctx, int32_t n_poses, const double *pose_in,
  * Outputs: t_out [n][3], yaw_out [n], drift[4] = yaw_drift, t_drift of the last keyframe (:674-681; may be NULL), summary
  * as gfbe_pg_solve fills it. GFBE_BAD_INPUT with nothing written for n_loop > GFBE_LC4_MAX_LOOPS, an index out of range,
  * loop_c >= loop_i, two loops on one loop_i or an options struct of another size; GFBE_NO_DEVICE without a GPU.
+ * gfbe_lc4_solve_long: the same call for a long revisit, up to GFBE_LC4_LONG_MAX_LOOPS loop edges: the same arguments, graph,
+ * solver statements, outputs and failure contract (GFBE_BAD_INPUT with nothing written beyond GFBE_LC4_LONG_MAX_LOOPS). Up to
+ * GFBE_LC4_MAX_LOOPS loop edges it runs the code of gfbe_lc4_solve and returns its bits; beyond, the 4 n_loop capacitance system
+ * (up to 2048 x 2048, 128 tile columns) is factorised across the device, one pair of launches per 16-column pivot step.
+ * Device scratch of a call (grow-only, owned by the context), in doubles, with rows = 16 ceil(n / 4), ld = 16 ceil((1 + 4 n_loop) / 16)
+ * and cap_ld = 16 ceil(4 n_loop / 16):
+ *     2 rows ld  (the two panels)  +  2 cap_ld^2  (S and L)  +  about 330 rows + 140 n_loop + 18 cap_ld  (band sets, vectors)
+ * At n = 5000, n_loop = 512: 2 x 20 000 x 2064 + 2 x 2048^2 doubles = 0.73 GB for panels, S and L, 0.78 GB with the rest; a failed
+ * allocation is GFBE_DEVICE_ERROR.
  * ------------------------------------------------------------------------------------------ */
 #define GFBE_LC4_MAX_LOOPS 64
+#define GFBE_LC4_LONG_MAX_LOOPS 512
 typedef struct gfbe_lc4_options {
   int32_t struct_size;          /* sizeof(gfbe_lc4_options), written by gfbe_lc4_default_options */
   int32_t max_num_iterations;   /* 5 (pose_graph.cpp:563); at most 15 are run */
@@ -559,6 +569,10 @@ gfbe_status gfbe_lc4_solve(gfbe_ctx *ctx, const gfbe_lc4_options *opt /* NULL: d
                            const double *ypr, const int32_t *sequence, const uint8_t *fixed, int32_t n_loop,
                            const int32_t *loop_i, const int32_t *loop_c, const double *loop_meas, double *t_out,
                            double *yaw_out, double *drift, gfbe_summary *summary);
+gfbe_status gfbe_lc4_solve_long(gfbe_ctx *ctx, const gfbe_lc4_options *opt /* NULL: defaults */, int32_t n_poses, const double *t,
+                                const double *ypr, const int32_t *sequence, const uint8_t *fixed, int32_t n_loop,
+                                const int32_t *loop_i, const int32_t *loop_c, const double *loop_meas, double *t_out,
+                                double *yaw_out, double *drift, gfbe_summary *summary);
 
 /* ------------------------------------------------------------------------------------------
  * f3c dense RGB-D map of dense_map, what the loop-closure thread does with the solved poses (paths under dense_map/src/):
