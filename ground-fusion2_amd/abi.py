@@ -1776,3 +1776,139 @@ class DenseMap:
         pts, rgb = np.zeros((n.value, 3), np.float32), np.zeros((n.value, 3), np.uint8)
         self._check(self._f("download_keyframe")(self.ctx, self.h, int(k), C.byref(n), pts.ctypes.data_as(PF), rgb.ctypes.data_as(PU8)), "download_keyframe")
         return dict(pts=pts, rgb=rgb)
+
+
+# ---------------------------------------------------------------------------------------------
+# f3d: the loop database of dense_map held on the device (gfbe_ldb_*; the model is tests/ldb_np.py)
+# ---------------------------------------------------------------------------------------------
+PU64 = C.POINTER(C.c_uint64)
+LDB_COUNTS = ("n_keyframes", "n_descriptors", "n_bow", "n_refused")
+LDB_MAX_CHILDREN, LDB_MAX_RESULTS, LDB_MAX_KEYFRAME_DESCRIPTORS = 256, 16, 4096
+
+
+class LdbVocab(C.Structure):
+    _fields_ = [("k", c_i), ("L", c_i), ("scoring", c_i), ("weighting", c_i), ("n_nodes", c_i), ("n_words", c_i), ("node_id", C.POINTER(c_i)),
+                ("parent_id", C.POINTER(c_i)), ("weight", PD), ("descriptor", PU64), ("word_id", C.POINTER(c_i)), ("word_node", C.POINTER(c_i))]
+
+
+class LdbOptions(C.Structure):
+    _fields_ = [("struct_size", c_i), ("max_results", c_i), ("query_gap", c_i), ("min_loop_frame", c_i), ("max_keyframe_descriptors", c_i),
+                ("match_start", c_i), ("match_max", c_i), ("reserved", c_i), ("score_first", c_d), ("score_other", c_d)]
+
+
+def ldb_default_options(lib, prefix="gfbe_"):
+    o = LdbOptions()
+    f = getattr(lib, prefix + "ldb_default_options")
+    f.restype = None
+    f(C.byref(o))
+    return o
+
+
+def _u64(a, cols=4):
+    return np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, cols)
+
+
+class LdbVocabHolder:
+    """gfbe_ldb_vocab over numpy arrays kept alive: dict(k, L, scoring, weighting, node_id, parent_id, weight, descriptor [n, 4] uint64,
+    word_id, word_node) in the order of the vocabulary file."""
+
+    def __init__(self, voc):
+        self.node_id, self.parent_id = _i32(voc["node_id"]), _i32(voc["parent_id"])
+        self.weight, self.descriptor = _f64(voc["weight"]), _u64(voc["descriptor"])
+        self.word_id, self.word_node = _i32(voc["word_id"]), _i32(voc["word_node"])
+        self.c = LdbVocab(int(voc["k"]), int(voc["L"]), int(voc.get("scoring", 0)), int(voc.get("weighting", 0)), len(self.node_id), len(self.word_id),
+                          _pi(self.node_id), _pi(self.parent_id), _pd(self.weight), self.descriptor.ctypes.data_as(PU64), _pi(self.word_id), _pi(self.word_node))
+
+
+class LoopDatabase:
+    """The loop database behind `lib` (prefix gfbe_, ctx = gfbe_ctx*): detectLoop / addKeyFrameIntoVoc of dense_map/src/pose_graph.cpp and
+    searchByBRIEFDes of keyframe.cpp over a vocabulary `voc` (LdbVocabHolder or its dict). options: fields of gfbe_ldb_options. The *_raw
+    methods return the status; the others raise."""
+
+    def __init__(self, lib, prefix, ctx, voc, keyframe_capacity=1024, descriptor_capacity=1 << 20, **options):
+        self.lib, self.prefix, self.ctx = lib, prefix, ctx
+        self.h = C.c_void_p()
+        self.voc = voc if isinstance(voc, LdbVocabHolder) else LdbVocabHolder(voc)
+        PI = C.POINTER(c_i)
+        for name in ("create", "transform", "add_keyframe", "match", "size", "download_entry"):
+            self._f(name).restype = c_i
+        self._f("destroy").restype = None
+        self._f("create").argtypes = [C.c_void_p, C.POINTER(LdbVocab), c_i, C.c_int64, C.POINTER(LdbOptions), C.POINTER(C.c_void_p)]
+        self._f("destroy").argtypes = [C.c_void_p, C.c_void_p]
+        self._f("transform").argtypes = [C.c_void_p, C.c_void_p, c_i, PU64, PI, PI, PI, PD]
+        self._f("add_keyframe").argtypes = [C.c_void_p, C.c_void_p, c_i, PU64, PF, PF, c_i, PI, PI, PI, PI, PD]
+        self._f("match").argtypes = [C.c_void_p, C.c_void_p, c_i, c_i, PU64, PU8, PI, PI, PI, PI, PF, PF]
+        self._f("size").argtypes = [C.c_void_p, C.c_void_p, PI]
+        self._f("download_entry").argtypes = [C.c_void_p, C.c_void_p, c_i, PI, PI, PD, PI, PU64, PF, PF]
+        self.opt = ldb_default_options(lib, prefix)
+        for k, v in options.items():
+            setattr(self.opt, k, v)
+        self._check(self._f("create")(self.ctx, C.byref(self.voc.c), int(keyframe_capacity), int(descriptor_capacity), C.byref(self.opt), C.byref(self.h)), "create")
+
+    def _f(self, name):
+        return getattr(self.lib, self.prefix + "ldb_" + name)
+
+    def _check(self, rc, what):
+        if rc != OK:
+            raise RuntimeError("%sldb_%s failed with status %d" % (self.prefix, what, rc))
+
+    def close(self):
+        if self.h:
+            self._f("destroy")(self.ctx, self.h)
+            self.h = C.c_void_p()
+
+    def transform(self, desc):
+        """dict(word [n] the word of every descriptor, bow_word / bow_value the normalised BoW vector); no database change."""
+        d = _u64(desc)
+        word, nb, bw, bv = np.zeros(len(d), np.int32), c_i(-1), np.zeros(len(d), np.int32), np.zeros(len(d))
+        self._check(self._f("transform")(self.ctx, self.h, len(d), d.ctypes.data_as(PU64), _pi(word), C.byref(nb), _pi(bw), _pd(bv)), "transform")
+        return dict(word=word, bow_word=bw[:nb.value], bow_value=bv[:nb.value])
+
+    def add_keyframe_raw(self, desc, pts, pts_norm, detect_loop=True):
+        d, p, pn = _u64(desc), _f32(pts).reshape(-1, 2), _f32(pts_norm).reshape(-1, 2)
+        assert len(d) == len(p) == len(pn)
+        idx, loop, nr = c_i(-7), c_i(-7), c_i(-7)
+        rid, rs = np.full(LDB_MAX_RESULTS, -7, np.int32), np.zeros(LDB_MAX_RESULTS)
+        rc = self._f("add_keyframe")(self.ctx, self.h, len(d), d.ctypes.data_as(PU64), p.ctypes.data_as(PF), pn.ctypes.data_as(PF), int(bool(detect_loop)),
+                                     C.byref(idx), C.byref(loop), C.byref(nr), _pi(rid), _pd(rs))
+        n = max(nr.value, 0)
+        return rc, dict(index=idx.value, loop_index=loop.value, result_id=rid[:n].copy(), result_score=rs[:n].copy())
+
+    def add_keyframe(self, desc, pts, pts_norm, detect_loop=True):
+        """detectLoop (detect_loop, waits for the results) or addKeyFrameIntoVoc of one keyframe: dict(index (-1: refused), loop_index,
+        result_id, result_score)."""
+        rc, out = self.add_keyframe_raw(desc, pts, pts_norm, detect_loop)
+        self._check(rc, "add_keyframe")
+        return out
+
+    def match_raw(self, old_index, window_desc):
+        w = _u64(window_desc)
+        n = len(w)
+        st, bi, bd, nm = np.zeros(n, np.uint8), np.zeros(n, np.int32), np.zeros(n, np.int32), c_i(-7)
+        src, pt, ptn = np.zeros(n, np.int32), np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32)
+        rc = self._f("match")(self.ctx, self.h, int(old_index), n, w.ctypes.data_as(PU64), st.ctypes.data_as(PU8), _pi(bi), _pi(bd), C.byref(nm), _pi(src),
+                              pt.ctypes.data_as(PF), ptn.ctypes.data_as(PF))
+        m = max(nm.value, 0)
+        return rc, dict(status=st, best_index=bi, best_dist=bd, n_matched=nm.value, matched_src=src[:m], matched_pt=pt[:m], matched_pt_norm=ptn[:m])
+
+    def match(self, old_index, window_desc):
+        """searchByBRIEFDes + reduceVector of the window descriptors against held keyframe old_index (waits)."""
+        rc, out = self.match_raw(old_index, window_desc)
+        self._check(rc, "match")
+        return out
+
+    def size(self):
+        """dict of LDB_COUNTS (waits)."""
+        v = (c_i * len(LDB_COUNTS))()
+        self._check(self._f("size")(self.ctx, self.h, v), "size")
+        return dict(zip(LDB_COUNTS, list(v)))
+
+    def entry(self, e):
+        """dict(bow_word, bow_value, desc [n, 4] uint64, pts, pts_norm [n, 2]) of entry e as it is held."""
+        nb, nd = c_i(-1), c_i(-1)
+        self._check(self._f("download_entry")(self.ctx, self.h, int(e), C.byref(nb), None, None, C.byref(nd), None, None, None), "download_entry")
+        bw, bv = np.zeros(nb.value, np.int32), np.zeros(nb.value)
+        d, p, pn = np.zeros((nd.value, 4), np.uint64), np.zeros((nd.value, 2), np.float32), np.zeros((nd.value, 2), np.float32)
+        self._check(self._f("download_entry")(self.ctx, self.h, int(e), C.byref(nb), _pi(bw), _pd(bv), C.byref(nd), d.ctypes.data_as(PU64), p.ctypes.data_as(PF),
+                                              pn.ctypes.data_as(PF)), "download_entry")
+        return dict(bow_word=bw, bow_value=bv, desc=d, pts=p, pts_norm=pn)

@@ -46,6 +46,8 @@ EXPORTS = [
     "gfbe_lc4_default_options", "gfbe_lc4_eval", "gfbe_lc4_solve", "gfbe_lc4_solve_long",
     "gfbe_dmap_default_options", "gfbe_dmap_create", "gfbe_dmap_destroy", "gfbe_dmap_add_keyframe", "gfbe_dmap_rebuild", "gfbe_dmap_filter",
     "gfbe_dmap_size", "gfbe_dmap_download_cloud", "gfbe_dmap_download_keyframe",
+    "gfbe_ldb_default_options", "gfbe_ldb_create", "gfbe_ldb_destroy", "gfbe_ldb_transform", "gfbe_ldb_add_keyframe", "gfbe_ldb_match",
+    "gfbe_ldb_size", "gfbe_ldb_download_entry",
 ]
 
 
@@ -258,6 +260,14 @@ class Backend(abi.CApi):
         rebuild at the corrected poses and the radius filter, gfbe_dmap_*). options: fields of gfbe_dmap_options."""
         try:
             return abi.DenseMap(self.lib, "gfbe_", self.ctx, point_capacity, keyframe_capacity, **options)
+        except RuntimeError as e:
+            raise BackendError("%s: %s" % (e, self._err()))
+
+    def loop_database(self, voc, keyframe_capacity=1024, descriptor_capacity=1 << 20, **options):
+        """The loop database of the loop-closure thread held on the device (abi.LoopDatabase: detectLoop's vocabulary query and decision,
+        addKeyFrameIntoVoc and searchByBRIEFDes, gfbe_ldb_*). voc: abi.LdbVocabHolder or its dict; options: fields of gfbe_ldb_options."""
+        try:
+            return abi.LoopDatabase(self.lib, "gfbe_", self.ctx, voc, keyframe_capacity, descriptor_capacity, **options)
         except RuntimeError as e:
             raise BackendError("%s: %s" % (e, self._err()))
 

@@ -648,6 +648,118 @@ gfbe_status gfbe_dmap_download_cloud(gfbe_ctx *ctx, gfbe_dmap *map, float *xyz, 
 gfbe_status gfbe_dmap_download_keyframe(gfbe_ctx *ctx, gfbe_dmap *map, int32_t k, int32_t *n, float *pts, uint8_t *rgb);
 
 /* ------------------------------------------------------------------------------------------
+ * f3d loop database of dense_map: what produces the loop edges that gfbe_lc4_solve consumes (paths under dense_map/src/;
+ *     DBoW2 is vendored under ThirdParty/DBoW/):
+ *       detectLoop: BoW vector, query, add, the decision             pose_graph.cpp:432-512          gfbe_ldb_add_keyframe, detect_loop = 1
+ *       addKeyFrameIntoVoc: add without a query                      :514-527                        gfbe_ldb_add_keyframe, detect_loop = 0
+ *       searchByBRIEFDes / searchInAera / HammingDis, reduceVector   keyframe.cpp:194-244, 571-576, 374-380   gfbe_ldb_match
+ *     PnPRANSAC (cv::solvePnPRansac) and the loop_info arithmetic behind it stay with the caller.
+ *     A descriptor is uint64_t [4], the four blocks loadBin hands to boost::dynamic_bitset (TemplatedVocabulary.h:1541); pts /
+ *     pts_norm are float [n][2] (keypoints[i].pt, keypoints_norm[i].pt). Conventions of gfbe_dmap: operations run in order on
+ *     the context's stream, the counts live in device memory, without a GPU every entry point returns GFBE_NO_DEVICE, a bad
+ *     argument returns GFBE_BAD_INPUT with gfbe_last_error set and the handle untouched.
+ *     Every rule below is an integer operation or an IEEE FP64 addition, subtraction, fabs, comparison or division in a stated
+ *     order (no multiply-add), and the device returns the bits of a sequential FP64 walk: word ids, BoW values, scores, result
+ *     order, loop_index and every match output. No result depends on the order workgroups ran in or on what the scratch or
+ *     the pools held before.
+ *     1 Descent (TemplatedVocabulary.h:1217-1258): from the root, among the node's children in file order take the one with
+ *       the smallest Hamming distance, a later child only with a strictly smaller distance; stop at a leaf (isLeaf, :1253,
+ *       wherever it sits: trees need not be balanced, a node may have fewer than k children). Result: the leaf's word id, weight.
+ *     2 BoW vector (:1065-1121, BowVector.cpp:34-84): a word met c times has the value ((w + w) + w) + ..., c - 1 additions, not
+ *       c w; words with w <= 0 are dropped; norm = the sum of fabs(value) in ascending word id from 0.0; every value is divided
+ *       by the norm when it is > 0.
+ *     3 Query (TemplatedDatabase.h:656-723): entry e takes part iff e < max_id || max_id == -1 || e == n_entries - 1, with
+ *       max_id = frame_index - query_gap and n_entries the count before this keyframe is added: the previous keyframe always
+ *       takes part, at frame_index == query_gap - 1 every entry does (max_id is -1), below that only the previous one. An
+ *       entry with no word in common is absent. raw = the sum over the common words in ascending word id of
+ *       (fabs(q - d) - fabs(q)) - fabs(d), from the first term. The results are the max_results smallest in (raw, id) order:
+ *       ascending raw, ties to the lower id (std::sort leaves ties open: a stated deviation). The
+ *       reported score is -raw / 2.0.
+ *     4 Decision (pose_graph.cpp:476-511): find_loop iff there is a result, score[0] > score_first and some i >= 1 has
+ *       score[i] > score_other. When find_loop && frame_index > min_loop_frame, loop_index starts as result 0's id, taken
+ *       unconditionally, and a later result replaces it only when its id is lower and its score is above score_other;
+ *       otherwise loop_index = -1. frame_index is the entry id: the count of keyframes held before the call (:98).
+ *     5 Add: the keyframe's BoW vector, descriptors and keypoints are appended to the handle's pools. n = 0 is a valid keyframe
+ *       with an empty vector. REFUSAL: a keyframe that does not fit keyframe_capacity or descriptor_capacity is refused whole:
+ *       the handle is unchanged, index_out = -1, loop_index = -1, no result, the call returns GFBE_OK and the keyframe is counted
+ *       in n_refused. From then on the caller's keyframe indices and the database's part ways: the caller has to size the pools.
+ *     6 Match (keyframe.cpp:194-244): per window descriptor best = match_start, index = -1; over the old keyframe's descriptors in
+ *       order a strictly smaller distance wins, so a distance of match_start or more never does; status = 1 iff index != -1 &&
+ *       best < match_max. matched_src = the window indices with status 1, ascending (reduceVector); matched_pt / matched_pt_norm
+ *       = the old keyframe's pt / pt_norm at their best indices. The caller reduces its own point_3d, point_id and the rest with
+ *       matched_src and compares n_matched with MIN_LOOP_NUM (25, keyframe.h:29) before its PnP.
+ *     Vocabulary: plain arrays in the order of the vocabulary file as loadBin reads it (TemplatedVocabulary.h:1509-1561); the
+ *     children of a node are its nodes in file order (push_back, :1538), which decides ties. Accepted: scoring 0 (L1) with
+ *     weighting 0 (TF-IDF) or 1 (TF), one code path once the weights are read (:1081-1093, mustNormalize true). Checked on the
+ *     host, GFBE_BAD_INPUT otherwise: node ids 1 .. n_nodes each once; a parent is the root (0) or an earlier-defined id; every
+ *     leaf has exactly one word and every word a leaf, word ids 0 .. n_words - 1 each once; finite non-negative weights; at
+ *     most GFBE_LDB_MAX_CHILDREN children per node (256: the child position is the low byte of the descent's packed key); depth
+ *     at most 16; 1 <= k <= GFBE_LDB_MAX_CHILDREN and 1 <= L <= 16 (neither bounds the tree beyond that).
+ * ------------------------------------------------------------------------------------------ */
+#define GFBE_LDB_MAX_CHILDREN 256
+#define GFBE_LDB_MAX_RESULTS 16
+#define GFBE_LDB_MAX_KEYFRAME_DESCRIPTORS 4096
+typedef struct gfbe_ldb gfbe_ldb;
+typedef struct gfbe_ldb_vocab {
+  int32_t k, L;                   /* branching factor and depth levels of the file's header */
+  int32_t scoring, weighting;     /* ScoringType (0 = L1_NORM), WeightingType (0 = TF_IDF, 1 = TF) */
+  int32_t n_nodes;                /* without the root */
+  int32_t n_words;
+  const int32_t *node_id;         /* [n_nodes] */
+  const int32_t *parent_id;       /* [n_nodes], 0 = the root */
+  const double *weight;           /* [n_nodes] */
+  const uint64_t *descriptor;     /* [n_nodes][4] */
+  const int32_t *word_id;         /* [n_words] */
+  const int32_t *word_node;       /* [n_words] node id of the word's leaf */
+} gfbe_ldb_vocab;
+typedef struct gfbe_ldb_options {
+  int32_t struct_size;                /* sizeof(gfbe_ldb_options), written by gfbe_ldb_default_options */
+  int32_t max_results;                /* 4 (pose_graph.cpp:447), 1 .. GFBE_LDB_MAX_RESULTS */
+  int32_t query_gap;                  /* 50 (:447): max_id = frame_index - query_gap, >= 0 */
+  int32_t min_loop_frame;             /* 50 (:500): a loop needs frame_index > min_loop_frame */
+  int32_t max_keyframe_descriptors;   /* 4096: descriptors of one keyframe, 1 .. GFBE_LDB_MAX_KEYFRAME_DESCRIPTORS */
+  int32_t match_start;                /* 128 (keyframe.cpp:202), 1 .. 257 */
+  int32_t match_max;                  /* 80 (:215), >= 0 */
+  int32_t reserved;
+  double score_first;                 /* 0.05 (pose_graph.cpp:476) */
+  double score_other;                 /* 0.015 (:480, :505) */
+} gfbe_ldb_options;
+void gfbe_ldb_default_options(gfbe_ldb_options *opt);
+/* The vocabulary is checked and copied to the device; the pools hold up to keyframe_capacity keyframes and descriptor_capacity
+ * descriptors (and as many BoW words). GFBE_BAD_INPUT: a vocabulary that fails a check above, keyframe_capacity outside
+ * 1 .. 2^24, descriptor_capacity outside 1 .. 2^26, an option outside its range or non-finite, an options struct of another size. */
+gfbe_status gfbe_ldb_create(gfbe_ctx *ctx, const gfbe_ldb_vocab *voc, int32_t keyframe_capacity, int64_t descriptor_capacity,
+                            const gfbe_ldb_options *opt /* NULL: defaults */, gfbe_ldb **out);
+void gfbe_ldb_destroy(gfbe_ctx *ctx, gfbe_ldb *db);
+/* Rules 1 and 2 on n descriptors without any change to the database: word_out [n] (the word of every descriptor, stopped words
+ * included), *n_bow, bow_word / bow_value [up to n] ascending. Any output may be NULL; waits.
+ * GFBE_BAD_INPUT: n < 0, n > max_keyframe_descriptors, desc NULL with n > 0. */
+gfbe_status gfbe_ldb_transform(gfbe_ctx *ctx, gfbe_ldb *db, int32_t n, const uint64_t *desc, int32_t *word_out, int32_t *n_bow,
+                               int32_t *bow_word, double *bow_value);
+/* Rules 1 to 5 for one keyframe. detect_loop = 1 is detectLoop: it waits once, for loop_index and the results: *n_results,
+ * result_id / result_score [max_results], best first. detect_loop = 0 is addKeyFrameIntoVoc: no query, loop_index = -1,
+ * *n_results = 0, and no wait unless the arrays exceed a 64 KB staging slot (about 1 190 descriptors). *index_out = the entry id
+ * of the keyframe, or -1 when it was refused (rule 5). Any output may be NULL.
+ * GFBE_BAD_INPUT: n < 0, n > max_keyframe_descriptors, a NULL input array with n > 0. */
+gfbe_status gfbe_ldb_add_keyframe(gfbe_ctx *ctx, gfbe_ldb *db, int32_t n, const uint64_t *desc, const float *pts,
+                                  const float *pts_norm, int32_t detect_loop, int32_t *index_out, int32_t *loop_index,
+                                  int32_t *n_results, int32_t *result_id, double *result_score);
+/* Rule 6 of n_window descriptors against held keyframe old_index: status [n_window], best_index / best_dist [n_window] for every
+ * window descriptor, *n_matched, matched_src [up to n_window], matched_pt / matched_pt_norm [up to n_window][2]. Any output may
+ * be NULL; waits once. GFBE_BAD_INPUT: old_index is not a held keyframe, n_window outside 0 .. 2^20, window_desc NULL with
+ * n_window > 0. */
+gfbe_status gfbe_ldb_match(gfbe_ctx *ctx, gfbe_ldb *db, int32_t old_index, int32_t n_window, const uint64_t *window_desc,
+                           uint8_t *status, int32_t *best_index, int32_t *best_dist, int32_t *n_matched, int32_t *matched_src,
+                           float *matched_pt, float *matched_pt_norm);
+/* counts [GFBE_LDB_N_COUNTS]: keyframes, descriptors, BoW words held, and the keyframes refused since the handle was made. Waits. */
+#define GFBE_LDB_N_COUNTS 4
+gfbe_status gfbe_ldb_size(gfbe_ctx *ctx, gfbe_ldb *db, int32_t *counts);
+/* Entry e as it is held: *n_bow, bow_word / bow_value [n_bow] ascending, *n_desc, desc [n_desc][4], pts / pts_norm [n_desc][2]
+ * (arrays NULL: the counts only). Waits. GFBE_BAD_INPUT: no such entry. */
+gfbe_status gfbe_ldb_download_entry(gfbe_ctx *ctx, gfbe_ldb *db, int32_t e, int32_t *n_bow, int32_t *bow_word, double *bow_value,
+                                    int32_t *n_desc, uint64_t *desc, float *pts, float *pts_norm);
+
+/* ------------------------------------------------------------------------------------------
  * f4  LIO scan residuals (BASELINE configs[4]): point-to-plane factors of the LiDAR
  *     odometry, evaluated and reduced to normal equations on the device (the voxel neighbour search that produces
  *     the planes runs on the device too: the voxel map section below, gfbe_vmap_associate / gfbe_vmap_linearize):
