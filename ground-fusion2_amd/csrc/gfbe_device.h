@@ -207,7 +207,12 @@ struct WinCtl {
   long long t_start, t_solved, t_marg;   // device wall clock (100 MHz ticks): k_reset, k_reanchor, end of the marginalisation (0: none)
   double sw_mu[2];                       // BatchDev::spec: the mu the weights lm_sw of set 0 / 1 were formed with (k_schur uses them when it is the
                                          // window's mu — an accepted step's new mu is known to the pass that linearises its candidate — and forms them itself otherwise)
+  double solve_dbg[8];                   // diagnostics (gfbe_debug_vector, which = 4): the dense solve's own mu, G2, N2, gy, vHv, vHy, yHy, grad_max of the last
+                                         // factorisation — copies, since k_step folds the landmark shares into the live fields and k_accept rewrites mu
 };
+// (one thread, beside the stores of the live fields: no extra launch)
+#define GFBE_SOLVE_DBG(c) do { (c).solve_dbg[0] = (c).mu; (c).solve_dbg[1] = (c).G2; (c).solve_dbg[2] = (c).N2; (c).solve_dbg[3] = (c).gy; \
+    (c).solve_dbg[4] = (c).vHv; (c).solve_dbg[5] = (c).vHy; (c).solve_dbg[6] = (c).yHy; (c).solve_dbg[7] = (c).grad_max; } while (0)
 
 // ---- the outputs of one linearisation ----------------------------------------------------------
 // Everything a linearisation writes and the kernels up to the next one read. A batch holds the set twice when the candidate's pass

@@ -1450,7 +1450,7 @@ extern "C" gfbe_status gfbe_debug_timing(gfbe_ctx *c, gfbe_batch *b, int32_t w, 
   return GFBE_OK;
 }
 extern "C" gfbe_status gfbe_debug_vector(gfbe_ctx *c, gfbe_batch *b, int32_t w, int32_t which, double *out) {
-  if (!c || !b || !out || which < 0 || (which > 3 && !(which >= 1000 && which < 1000 + ND) && !(which >= 2000 && which <= 2000 + NV))) return GFBE_BAD_INPUT;
+  if (!c || !b || !out || which < 0 || (which > 4 && !(which >= 1000 && which < 1000 + ND) && !(which >= 2000 && which <= 2000 + NV))) return GFBE_BAD_INPUT;
   int off = (!b->place.empty() && w >= 0 && w < (int)b->place.size()) ? b->place[w] : w;
   gfbe_batch *p = b;
   while (p && off >= p->d.B) { off -= p->d.B; p = p->second; }
@@ -1458,6 +1458,7 @@ extern "C" gfbe_status gfbe_debug_vector(gfbe_ctx *c, gfbe_batch *b, int32_t w, 
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (which >= 1000 && which < 1000 + ND) {           // row (which - 1000) of the assembled H (lower triangle valid)
     HIPCHK(c, hipMemcpy(out, p->d.H + (size_t)off * ND * ND + (size_t)(which - 1000) * ND, sizeof(double) * ND, hipMemcpyDeviceToHost));
+    for (int a = (which - 1000 < p->d.nu ? p->d.nu : 0); a < ND; a++) out[a] = 0.0;      // (dims the batch does not carry: no kernel writes them)
     return GFBE_OK;
   }
   if (which >= 2000 && which < 2000 + NV + 1) {       // row (which - 2000) of E (NV entries; row NV: eg)
@@ -1465,8 +1466,14 @@ extern "C" gfbe_status gfbe_debug_vector(gfbe_ctx *c, gfbe_batch *b, int32_t w, 
     HIPCHK(c, hipMemcpy(out, srcE, sizeof(double) * NV, hipMemcpyDeviceToHost));
     return GFBE_OK;
   }
+  if (which == 4) {                                   // the dense solve's scalars of the last factorisation (WinCtl::solve_dbg), zeros behind them
+    for (int a = 0; a < ND; a++) out[a] = 0.0;
+    HIPCHK(c, hipMemcpy(out, (const char *)(p->d.ctl + off) + offsetof(WinCtl, solve_dbg), sizeof(double) * 8, hipMemcpyDeviceToHost));
+    return GFBE_OK;
+  }
   const double *src = which == 0 ? p->d.yp : which == 1 ? p->d.vp : which == 2 ? p->d.sp : p->d.g;
   HIPCHK(c, hipMemcpy(out, src + (size_t)off * ND, sizeof(double) * ND, hipMemcpyDeviceToHost));
+  for (int a = p->d.nu; a < ND; a++) out[a] = which == 2 ? 1.0 : 0.0;      // (dims the batch does not carry: no kernel writes them)
   return GFBE_OK;
 }
 

@@ -250,6 +250,7 @@ __global__ __launch_bounds__(256) void k_reset(BatchDev d) {
       c.c1 = c.c2 = c.step_norm = c.model_change = 0; c.initial_cost = 0;
       for (int i = 0; i < 16; i++) { c.cost_history[i] = 0; c.accepted[i] = 0; }
       c.t_start = (long long)wall_clock64(); c.t_solved = 0; c.t_marg = 0; c.marg_ran = 0; c.lb = 0; c.sw_mu[0] = -1.0; c.sw_mu[1] = -1.0;
+      for (int i = 0; i < 8; i++) c.solve_dbg[i] = 0;
       d.ctl[w] = c;
     }
   }

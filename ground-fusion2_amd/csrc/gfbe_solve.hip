@@ -618,6 +618,7 @@ __global__ __launch_bounds__(SOLVE_THREADS, SOLVE_WAVES_PER_EU) void k_solve(Bat
     c.vHy = vrhs - mu * vDy + vEy;
     c.yHy = zz - mu * n2 + yEy;
     c.grad_max = gmax;
+    GFBE_SOLVE_DBG(c);
     c.x_norm = xn2;        // dense share; k_step adds the landmarks and takes the square root
     c.have_step = 2;       // "fresh linearisation" marker consumed by k_step
     c.lin_retry = 0;
@@ -1786,6 +1787,7 @@ if (!TW) {
     c.vHy = vrhs - mu * vDy + vEy;
     c.yHy = zz - mu * n2 + yEy;
     c.grad_max = s_keep[1];
+    GFBE_SOLVE_DBG(c);
     c.x_norm = s_keep[2];
     c.have_step = 2;
     c.lin_retry = 0;
@@ -2152,6 +2154,7 @@ __global__ __launch_bounds__(BIG_THREADS) void k_solve_big(BatchDev d, int retry
     c.vHy = vrhs - mu * vDy + vEy;
     c.yHy = s_zz - mu * n2 + yEy;
     c.grad_max = gmax;
+    GFBE_SOLVE_DBG(c);
     c.x_norm = xn2;
     c.have_step = 2;
     c.lin_retry = 0;

@@ -1384,7 +1384,14 @@ gfbe_status gfbe_debug_timing(gfbe_ctx *ctx, gfbe_batch *batch, int32_t w, doubl
  * Coordinates: H and g are unscaled, constant dims removed. E = sum_l w_l h_l h_l^T and eg = sum_l w_l h_l g_l with the UNSCALED pose
  * columns h_l = H_pl[l] of H and g; only the landmark side is Jacobi-scaled and mu-regularised, through the weight
  * w_l = s_l^2 / (s_l^2 H_ll + mu clamp(s_l^2 H_ll)), s_l = 1 / (1 + sqrt(H_ll)) fixed at iteration 0 (w_l = 0 for a constant landmark
- * and one without factors). The dense solve scales H - E afterwards. tests/test_gpu_normal_equations.py compares all four entry by entry. */
+ * and one without factors). The dense solve scales H - E afterwards. tests/test_gpu_normal_equations.py compares all four entry by entry.
+ * Dims the batch does not carry — the GNSS dims of a batch without a GNSS window, which no kernel of such a batch reads or writes — are
+ * reported like inactive dims: 0.0 in y, v, g and H, 1.0 in s.
+ * which = 4: the scalars of the dense solve of that linearisation, out[0..7] = mu of the factorisation that succeeded, G2 = sum gt^2 / D^2,
+ * N2 = sum D^2 y^2, gy = sum gt y, v^T Ht v, v^T Ht y, y^T Ht y (Ht = s H s, gt = s g, D^2 the clamped scaled diagonal) and max |g|: the
+ * DENSE shares as the solve kernel formed them, before the step kernel adds the landmarks' and before an accepted step changes mu
+ * (copies kept in the window's control block for this call; the mu is the factorisation's own, not the trust-region state's). The rest
+ * of out is zero. tests/test_gpu_solve_step.py holds y, s, v and these against an extended-precision restatement of the reduced system. */
 gfbe_status gfbe_debug_vector(gfbe_ctx *ctx, gfbe_batch *batch, int32_t w, int32_t which, double *out);
 
 /* Multi-GPU landmark sharding: when set, the library calls

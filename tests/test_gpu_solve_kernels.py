@@ -4,11 +4,16 @@ blocks from one end before the dense pose / extrinsic part, k_solve_chain_tw (3;
 both ends at once — two chain waves that meet in the middle block —, k_solve (1) factorises everything as one tiled matrix. Same
 Gauss-Newton step up to rounding — compared entry by entry through gfbe_debug_vector — on the window shapes that change the code
 path: five and six tile columns of the dense part, a window that is still filling up, no speed-bias blocks at all; and the structure
-check that hands a prior with a second speed-bias block to the monolithic kernel."""
+check that hands a prior with a second speed-bias block to the monolithic kernel.
+
+This module compares the kernels with EACH OTHER and whole solves with the oracle; a defect the kernels share, or one of relative size
+1e-8 in one of them, passes both. The accuracy of the step itself — its backward error on the system the device assembled, per kernel
+and launch shape, with the dogleg scalars — is pinned by tests/test_gpu_solve_step.py."""
 import numpy as np
 import pytest
 
 from _gfbe_import import gf
+from solve_step_cases import no_imu_window, partial_window
 from test_gpu_branches import all_free
 from test_gpu_parity import check_solve, window_with_prior
 
@@ -28,20 +33,8 @@ def _cases(oracle):
     first = scn.window(0)
     _, free = window_with_prior(oracle, 83, 400)
     free = all_free(free)                                    # camera extrinsic + td free: 83 dense dims = six tile columns
-    partial = dict(synth.Scenario(seed=84, n_landmarks=300, use_wheel=True).window(0))     # a window that is still filling up
-    fc = 6
-    keep = partial["vis_imu_j"] <= fc
-    for k in list(partial):
-        if k.startswith("vis_"):
-            partial[k] = partial[k][keep]
-    partial["frame_count"] = fc
-    for k in ("imu", "imu_frame", "wheel", "wheel_frame"):
-        partial[k] = partial[k][:fc]
-    no_imu = dict(synth.Scenario(seed=85, n_landmarks=300, use_wheel=True).window(0))
-    no_imu["imu"], no_imu["imu_frame"] = np.zeros((0, abi.IMU_DOUBLES)), np.zeros(0, np.int32)
-    pc = np.zeros(abi.NFRAMES, np.uint8)
-    pc[0] = 1
-    no_imu["pose_const"] = pc
+    partial = partial_window(seed=84, L=300, fc=6)           # a window that is still filling up
+    no_imu = no_imu_window(seed=85, L=300)
     return [("prior", with_prior), ("first", first), ("all_free", free), ("no_imu", no_imu), ("partial", partial)]
 
 
