@@ -89,3 +89,134 @@ def next_gnss_window(scn, tru, res, seed=81):
                              yaw_enu_local=g["yaw_enu_local"], anc_ecef=g["anc_ecef"])
     nxt["gnss"] = tru.block(1)
     return nxt
+
+
+# ---------------------------------------------------------------------------------------------------------------- windows of the normal-equation pins
+# Windows tests/test_gpu_gnss_normal_equations.py compares H and g of, entry by entry (60 landmarks each). Observations per frame 0..10:
+NE_COUNTS = {
+    "n8": [8] * 11,                                   # 88: staged in LDS, the work item of k_lin_small in the candidate pass
+    "clock_only": [0] * 11,                           # gnss_ready without one observation: the clock chains alone
+    "one_obs": [0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0],
+    "gaps": [8, 0, 8, 0, 0, 8, 0, 8, 0, 0, 8],        # empty frames between full ones, frame 10 among the full ones
+    "one_frame": [0, 0, 0, 0, 0, 30, 0, 0, 0, 0, 0],
+    "n256": [24] * 10 + [16],                         # GN_ITEM_MAX_OBS and one more: the launch of k_gnss in place of the work item
+    "n257": [24] * 10 + [17],
+    "n320": [30] * 10 + [20],                         # GN_LDS_OBS and one more: the sums from the global copy
+    "n321": [30] * 10 + [21],
+    "one_constellation": [6] * 11,
+    "const_frame": [8] * 11,                          # pose 4 and speed-bias 4 constant: their rows and columns are structural zeros
+    "anchor": [5] * 11,
+    "all_three": [7] * 11,                            # GNSS, PlaneFactors (free plane blocks) and the anchor
+    "lowspeed": [6] * 11,                             # no GNSS dim in the program
+    # pose 0 constant: the P_0 columns of the observations of frames 0 and 1 drop out, and the gauge fix behind a solve is the identity,
+    # so the state a solve hands back is the one its next linearisation ran at (the windows of the second-linearisation comparison)
+    "n8_hold0": [8] * 11,
+    "n257_hold0": [24] * 10 + [17],
+}
+NE_EXTRA = ("plane_free", "plane_const", "second", "plain")    # windows without GNSS with PlaneFactors (free / constant plane blocks); the window
+                                                               # that follows a GNSS window, with its ~95-dim prior; a window with none of it
+_ne_cache, _truth_cache = {}, {}
+
+
+def ne_case_names():
+    return [n for n in NE_COUNTS if n != "n257_hold0"] + list(NE_EXTRA) + ["n257_hold0"]      # (a case's place here is part of its seed)
+
+
+def _truth(seed, n_per_frame, L=60):
+    key = (seed, n_per_frame, L)
+    if key not in _truth_cache:
+        _truth_cache[key] = gnss_window(seed=seed, L=L, n_per_frame=n_per_frame)
+    return _truth_cache[key]
+
+
+def _with_plane(snap, seed, const):
+    rng = np.random.default_rng(seed)
+    q = synth.so3_exp(rng.normal(0, 0.01, 3))
+    q[2] = 0.0
+    snap["plane_R"] = q / np.linalg.norm(q)
+    snap["plane_Z"] = -float(snap["ex_pose_wheel"][2]) + 0.02
+    snap["plane"] = dict(noise_inv=[100.0, 100.0, 50.0], const=const)
+    return snap
+
+
+def ne_case(name, oracle=None):
+    """The window of case `name`. Deterministic; cached per process and never modified afterwards."""
+    if name in _ne_cache:
+        return _ne_cache[name]
+    seed = 8100 + ne_case_names().index(name)
+    if name in NE_COUNTS:
+        counts = NE_COUNTS[name]
+        per = max(max(counts), 1)
+        scn, tru, base = _truth(8100 if per > 8 else seed, 30 if per > 8 else per)      # (the large windows share one scenario's satellites)
+        snap = dict(base)
+        snap["gnss"] = dict(base["gnss"])
+        seen, obs = [0] * 11, []
+        for o in base["gnss"]["obs"]:                # frame-major; the first observation of a frame is the one on the other side of the keyframe
+            if seen[o["frame"]] < counts[o["frame"]]:
+                seen[o["frame"]] += 1
+                obs.append(dict(o))
+        assert seen == counts
+        if name == "one_constellation":              # every satellite of constellation 2: the measurement moves with the clock bias it now meets
+            for o in obs:
+                o["psr"] += tru.dt[o["frame"], 2] - tru.dt[o["frame"], o["sys_idx"]]
+                o["sys_idx"] = 2
+        snap["gnss"]["obs"] = obs
+        if name.endswith("_hold0"):
+            snap["pose_const"] = np.zeros(11, np.uint8)
+            snap["pose_const"][0] = 1
+        if name == "const_frame":
+            snap["pose_const"], snap["sb_const"] = np.zeros(11, np.uint8), np.zeros(11, np.uint8)
+            snap["pose_const"][4] = snap["sb_const"][4] = 1
+        if name in ("anchor", "all_three"):
+            snap["anchor"] = dict(pose=snap["pose"][0].copy(), sqrt_info=120.0)
+        if name == "all_three":
+            _with_plane(snap, seed, 0)
+        if name == "lowspeed":
+            snap["speed_bias"] = np.array(snap["speed_bias"], float).copy()
+            snap["speed_bias"][:, :2] *= 0.2
+    elif name in ("plane_free", "plane_const"):
+        snap = _with_plane(synth.Scenario(seed=seed, n_landmarks=60, use_wheel=True).window(0), seed, int(name == "plane_const"))
+    elif name == "plain":
+        snap = synth.Scenario(seed=seed, n_landmarks=60, use_wheel=True).window(0)
+    elif name == "second":
+        scn, tru, first = _truth(seed, 6)
+        snap = next_gnss_window(scn, tru, oracle.solve(first, abi.MARGIN_OLD), seed=seed)
+    else:
+        raise KeyError(name)
+    _ne_cache[name] = snap
+    return snap
+
+
+_ne_ref_cache = {}
+
+
+def ne_reference(name, oracle):
+    """(window, the oracle's per-factor blocks, the extended-precision reference system) of a case; cached per process, left unchanged."""
+    import normal_equations_np as ne
+    if name not in _ne_ref_cache:
+        snap = ne_case(name, oracle)
+        ev = oracle.eval_factors(snap, robustify=True)
+        _ne_ref_cache[name] = (snap, ev, ne.reference_system(snap, ev))
+    return _ne_ref_cache[name]
+
+
+def at_state(snap, res):
+    """The window `snap` at the state a solve left it in (res: one window's download). A solve hands every quaternion back through a
+    rotation matrix, in the canonical sign; the solve itself carries q (x) dq along, and the inertial factor's 2 vec(q) arithmetic is
+    not blind to the sign: each quaternion gets the sign that continues the window's own."""
+    out = dict(snap, para_feature=np.array(res["feature"], float))
+    for k, v in res["state"].items():
+        if k in snap or k == "gnss_state":
+            out[k] = v
+    pose = np.array(out["pose"], float)
+    flip = (pose[:, 3:] * np.asarray(snap["pose"], float)[:, 3:]).sum(axis=1) < 0
+    pose[flip, 3:] *= -1.0
+    out["pose"] = pose
+    for k in ("ex_pose", "ex_pose_wheel"):
+        q = np.array(out[k], float)
+        if q[3:] @ np.asarray(snap[k], float)[3:] < 0:
+            q[3:] *= -1.0
+        out[k] = q
+    if "gnss_state" not in snap:
+        out.pop("gnss_state", None)
+    return out

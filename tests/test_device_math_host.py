@@ -69,24 +69,7 @@ def test_device_gnss_math_matches_oracle(shim, oracle):
     """csrc/gfbe_gnss.h on the host against oracle/gfo_gnss.cpp: pseudo-ranges of 2.5e7 m in doubles, weights up to 250."""
     import gnss_cases as gc
 
-    class Shim:      # abi.gnss_eval drives any library exporting <prefix>gnss_eval with the C ABI's argument list
-        def __init__(self, lib):
-            self.lib = lib
-
-        def __getattr__(self, name):
-            assert name == "shim_gnss_eval"
-            f = self.lib.shim_gnss_eval
-
-            def call(ctx, n, arr, io, st, g, fdt, w, r, J, rc, rs, cost):
-                return f(n, arr, io, st, g, fdt, C.c_double(w), r, J, rc, rs)
-            return _Holder(call)
-
-    class _Holder:
-        def __init__(self, fn):
-            self.fn, self.restype, self.argtypes = fn, None, None
-
-        def __call__(self, *a):
-            return self.fn(*a)
+    from gnss_np import ShimLib as Shim      # abi.gnss_eval drives any library exporting <prefix>gnss_eval with the C ABI's argument list
 
     for seed, lat in [(11, 22.3), (12, -50.0), (13, 80.0)]:
         c = gc.gnss_case(seed, lat=lat)

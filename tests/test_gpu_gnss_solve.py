@@ -8,7 +8,10 @@ GNSS: check_solve's bounds are taken times GNSS_LOOSE = 10 here (measured on MI3
 relative, final cost 5e-11, poses 1e-11 m, clock biases 5e-9 m, anchor 4e-9 m: inside the plain bounds already); the priors'
 normal equations are compared on PRIOR_LOOSE = 300 (A' 1.3e-9 relative measured; b' — the marginal cost's gradient at a state the
 solve left before it had settled, cancelling numbers of the information's size — 1.5e-4 of its largest entry, plus what the difference of the
-linearisation points explains: check_prior). The receiver clock biases are metres (1e5 m in size), the anchor is ECEF metres."""
+linearisation points explains: check_prior). The receiver clock biases are metres (1e5 m in size), the anchor is ECEF metres.
+The 1e-5 and the x10 / x300 above describe WHOLE SOLVES. The factors themselves are held entry by entry to K u A bounds against an
+extended-precision model (tests/test_gpu_gnss.py: 1e-6 and less on a residual), and their share of H and g likewise
+(tests/test_gpu_gnss_normal_equations.py)."""
 import numpy as np
 import pytest
 
