@@ -397,20 +397,14 @@ class WindowHolder:
 
 
 def bind(lib, prefix):
-    """Attach argtypes/restype for the entry points shared by the product (gfbe_) and oracle (gfo_)."""
-    P = C.POINTER
-    f = getattr(lib, prefix + "build_visual_factors")
-    f.restype = c_i
-    f.argtypes = [P(FeatureList), c_i, PI, PI, PI, PD, PD, PD, PD, PD, PD, PD, PU8]
-    f = getattr(lib, prefix + "feature_count")
-    f.restype = c_i
-    f.argtypes = [P(FeatureList)]
-    f = getattr(lib, prefix + "visual_factor_count")
-    f.restype = c_i
-    f.argtypes = [P(FeatureList), c_i]
-    f = getattr(lib, prefix + "set_depth")
-    f.restype = None
-    f.argtypes = [P(FeatureList), PD, PD, PI]
+    """Types every entry point of signatures.TABLES[prefix] that `lib` exports (gfbe_: the product, gfo_: the oracle,
+    gfbe_rccl_: the all-reduce hook; any other prefix: the product's entry points under another name, as a test's host build has
+    them) and returns `lib`. Once per library and prefix: a second call changes nothing."""
+    from . import signatures      # (it imports the struct mirrors of this module)
+    done = vars(lib).setdefault("_bound_prefixes", set())
+    if prefix not in done:
+        signatures.declare(lib, prefix, signatures.TABLES.get(prefix, signatures.GFBE))
+        done.add(prefix)
     return lib
 
 
@@ -487,11 +481,9 @@ class CApi:
         npr = wh.prior.c.n if wh.prior is not None else 0
         out["prior_r"] = np.zeros(npr)
         cost = c_d(0.0)
-        f = self._fn("eval_factors")
-        f.restype = c_i
-        rc = f(self.head, C.byref(wh.c), int(robustify), _pd(out["vis_r"]), _pd(out["vis_J"]), _pd(out["imu_r"]),
-               _pd(out["imu_J"]), _pd(out["wheel_r"]), _pd(out["wheel_J"]),
-               _pd(out["prior_r"]) if npr else None, C.byref(cost))
+        rc = self._fn("eval_factors")(self.head, C.byref(wh.c), int(robustify), _pd(out["vis_r"]), _pd(out["vis_J"]), _pd(out["imu_r"]),
+                                      _pd(out["imu_J"]), _pd(out["wheel_r"]), _pd(out["wheel_J"]),
+                                      _pd(out["prior_r"]) if npr else None, C.byref(cost))
         self.check(rc, "eval_factors")
         out["cost"] = cost.value
         return out
@@ -513,9 +505,8 @@ class CApi:
         out = np.zeros((n, out_w))
         nz = _f64(noise)
         f = self._fn(name)
-        f.restype = c_i
         args = [n, _pi(off), _pd(samples), _pd(first), _pd(lin), _pd(nz), C.cast(out.ctypes.data, C.POINTER(rec_t))]
-        rc = f(*(([self.head] if self.prefix == "gfbe_" else []) + args))
+        rc = f(*([self.head] * (len(f.argtypes) - len(args)) + args))      # (the product's takes its context first, the oracle's nothing)
         self.check(rc, name)
         return out
 
@@ -538,25 +529,18 @@ class CApi:
         feat = np.zeros(wh.n_feature)
         pr = PriorHolder()
         sm = Summary()
-        f = self._fn("solve_window")
-        f.restype = c_i
-        rc = f(self.head, C.byref(wh.c), int(margin_flag), C.byref(st), _pd(feat), C.byref(pr.c), C.byref(sm))
+        rc = self._fn("solve_window")(self.head, C.byref(wh.c), int(margin_flag), C.byref(st), _pd(feat), C.byref(pr.c), C.byref(sm))
         self.check(rc, "solve_window")
         return dict(state=state_to_dict(st), feature=feat, prior=pr.to_dict() if pr.c.valid else None,
                     summary=summary_to_dict(sm), perf=summary_perf(sm), status=rc)
 
-
-def _solve_raw(self, wh, margin_flag=MARGIN_NONE):
-    """solve_window into outputs kept on the holder: the bare C call (latency measurements)."""
-    if not hasattr(wh, "_raw_out"):
-        wh._raw_out = (State(), np.zeros(max(wh.n_feature, 1)), PriorHolder(), Summary())
-    st, feat, pr, sm = wh._raw_out
-    f = self._fn("solve_window")
-    f.restype = c_i
-    return self.check(f(self.head, C.byref(wh.c), int(margin_flag), C.byref(st), _pd(feat), C.byref(pr.c), C.byref(sm)), "solve_window")
-
-
-CApi.solve_raw = _solve_raw
+    def solve_raw(self, wh, margin_flag=MARGIN_NONE):
+        """solve_window into outputs kept on the holder: the bare C call (latency measurements)."""
+        if not hasattr(wh, "_raw_out"):
+            wh._raw_out = (State(), np.zeros(max(wh.n_feature, 1)), PriorHolder(), Summary())
+        st, feat, pr, sm = wh._raw_out
+        return self.check(self._fn("solve_window")(self.head, C.byref(wh.c), int(margin_flag), C.byref(st), _pd(feat), C.byref(pr.c), C.byref(sm)),
+                          "solve_window")
 
 
 def summary_to_dict(sm):
@@ -595,38 +579,53 @@ def pose_rows(pose7):
     return out
 
 
-class FeatureTables:
-    """W feature tables behind `lib` (prefix gfbe_: device-resident, ctx = gfbe_ctx*; prefix gfo_: the CPU oracle,
-    ctx ignored). Per-table arguments are lists of length W."""
+def options_struct(lib, prefix, family, cls, fields=None):
+    """A `cls` as <prefix><family>default_options fills it, then `fields` (a dict; an array-valued field takes a sequence). A name
+    that is no field of the struct is refused."""
+    o = cls()
+    getattr(bind(lib, prefix), prefix + family + "default_options")(C.byref(o))
+    for k, v in (fields or {}).items():
+        if not hasattr(o, k):
+            raise TypeError("gfbe_%soptions has no field %r" % (family, k))
+        cur = getattr(o, k)
+        setattr(o, k, type(cur)(*[float(x) for x in v]) if isinstance(cur, C.Array) else v)
+    return o
 
-    def __init__(self, lib, prefix, ctx, n_tables=1, capacity=4096, options=None):
-        self.lib, self.prefix, self.ctx, self.W, self.cap = lib, prefix, ctx, n_tables, capacity
-        self.h = C.c_void_p()
-        for name in ("create", "add_frame", "remove_back_shift_depth", "remove_back", "remove_front", "remove_outlier",
-                     "remove_failures", "clear_depth", "set_depth", "get_depth_vector", "triangulate", "check_outliers",
-                     "size", "download"):
-            self._f(name).restype = c_i
-        self._f("destroy").restype = None
-        opt = None
-        if options is not None:
-            opt = FtabOptions()
-            self._f("default_options")(C.byref(opt))
-            for k, v in options.items():
-                setattr(opt, k, v)
-        self._check(self._f("create")(self.ctx, int(n_tables), int(capacity), C.byref(opt) if opt is not None else None,
-                                      C.byref(self.h)), "create")
+
+class Handle:
+    """Base of the classes that own one opaque handle `h` of a family of entry points <prefix><family>* behind `lib`."""
+    family = ""
+
+    def __init__(self, lib, prefix, ctx):
+        self.lib, self.prefix, self.ctx, self.h = bind(lib, prefix), prefix, ctx, C.c_void_p()
 
     def _f(self, name):
-        return getattr(self.lib, self.prefix + "ftab_" + name)
+        return getattr(self.lib, self.prefix + self.family + name)
 
     def _check(self, rc, what):
         if rc != OK:
-            raise RuntimeError("%sftab_%s failed with status %d" % (self.prefix, what, rc))
+            raise RuntimeError("%s%s%s failed with status %d" % (self.prefix, self.family, what, rc))
+
+    def _options(self, cls, fields=None, family=None):
+        return options_struct(self.lib, self.prefix, family or self.family, cls, fields)
 
     def close(self):
         if self.h:
             self._f("destroy")(self.ctx, self.h)
             self.h = C.c_void_p()
+
+
+class FeatureTables(Handle):
+    """W feature tables behind `lib` (prefix gfbe_: device-resident, ctx = gfbe_ctx*; prefix gfo_: the CPU oracle,
+    ctx ignored). Per-table arguments are lists of length W."""
+    family = "ftab_"
+
+    def __init__(self, lib, prefix, ctx, n_tables=1, capacity=4096, options=None):
+        Handle.__init__(self, lib, prefix, ctx)
+        self.W, self.cap = n_tables, capacity
+        opt = self._options(FtabOptions, options) if options is not None else None
+        self._check(self._f("create")(self.ctx, int(n_tables), int(capacity), C.byref(opt) if opt is not None else None,
+                                      C.byref(self.h)), "create")
 
     @staticmethod
     def _ragged(rows, dtype, width=None):
@@ -721,12 +720,7 @@ class PoseGraph:
     """Chain pose graph: poses [n,7] = t(3) q(wxyz); rel_i [m]; rel_meas [m,7]; fix_i [k]; fix_meas [k,4] = x y z var."""
 
     def __init__(self, lib, prefix, ctx):
-        self.lib, self.prefix, self.ctx = lib, prefix, ctx
-        for name in ("pg_eval", "pg_solve"):
-            f = getattr(lib, prefix + name)
-            f.restype = c_i
-        getattr(lib, prefix + "pg_eval").argtypes = [C.c_void_p, c_i, PD, c_i, PI, PD, c_d, c_d, c_i, PI, PD, c_d, PD, PD, PD, PD]
-        getattr(lib, prefix + "pg_solve").argtypes = [C.c_void_p, c_i, PD, c_i, PI, PD, c_d, c_d, c_i, PI, PD, c_d, c_i, PD, C.POINTER(Summary)]
+        self.lib, self.prefix, self.ctx = bind(lib, prefix), prefix, ctx
 
     def _args(self, g):
         pose = _f64(g["pose"]).reshape(-1, 7)
@@ -779,22 +773,10 @@ class LoopGraph:
     """Keyframes t [n,3], ypr [n,3] (degrees); see include/gfbe.h f3b."""
 
     def __init__(self, lib, prefix, ctx):
-        self.lib, self.prefix, self.ctx = lib, prefix, ctx
-        PO = C.POINTER(Lc4Options)
-        f = getattr(lib, prefix + "lc4_default_options")
-        f.restype, f.argtypes = None, [PO]
-        f = getattr(lib, prefix + "lc4_eval")
-        f.restype, f.argtypes = c_i, [C.c_void_p, PO, c_i, PD, PD, c_i, PI, PI, PU8, PD, PD, PD, PD]
-        for name in ("lc4_solve", "lc4_solve_long"):
-            f = getattr(lib, prefix + name)
-            f.restype, f.argtypes = c_i, [C.c_void_p, PO, c_i, PD, PD, PI, PU8, c_i, PI, PI, PD, PD, PD, PD, C.POINTER(Summary)]
+        self.lib, self.prefix, self.ctx = bind(lib, prefix), prefix, ctx
 
     def options(self, **kw):
-        o = Lc4Options()
-        getattr(self.lib, self.prefix + "lc4_default_options")(C.byref(o))
-        for k, v in kw.items():
-            setattr(o, k, v)
-        return o
+        return options_struct(self.lib, self.prefix, "lc4_", Lc4Options, kw)
 
     def eval_rc(self, t, ypr, edge_i, edge_j, kind, meas, opt=None):
         t, ypr, meas = _f64(t).reshape(-1, 3), _f64(ypr).reshape(-1, 3), _f64(meas).reshape(-1, 6)
@@ -851,9 +833,7 @@ def lio_linearize(lib, prefix, ctx, ct, pts, normals, offsets, alpha, weights, s
     pe = _f64(pose_end if pose_end is not None else pose_begin)
     r, J = (np.zeros(n), np.zeros((n, dn))) if blocks else (None, None)
     H, g, cost = np.zeros((dn, dn)), np.zeros(dn), np.zeros(1)
-    f = getattr(lib, prefix + "lio_linearize")
-    f.restype = c_i
-    f.argtypes = [C.c_void_p, c_i, c_i, PD, PD, PD, PD, PD, c_d, PD, PD, PD, PD, PD, PD, PD]
+    f = getattr(bind(lib, prefix), prefix + "lio_linearize")
     rc = f(ctx, int(ct), n, _pd(pts), _pd(normals), _pd(offsets), _pd(al), _pd(wg), float(sqrt_info), _pd(pb), _pd(pe),
            _pd(r) if blocks else None, _pd(J) if blocks else None, _pd(H), _pd(g), _pd(cost))
     if rc != OK:
@@ -869,9 +849,7 @@ def plane_eval(lib, prefix, ctx, pose, ex_wheel, plane_R, plane_Z, noise_inv):
     n = len(pose)
     ex, q, ni = _f64(ex_wheel), _f64(plane_R), _f64(noise_inv)
     r, J, cost = np.zeros((n, 3)), np.zeros((n, 3, 16)), np.zeros(1)
-    f = getattr(lib, prefix + "plane_eval")
-    f.restype = c_i
-    f.argtypes = [C.c_void_p, c_i, PD, PD, PD, c_d, PD, PD, PD, PD]
+    f = getattr(bind(lib, prefix), prefix + "plane_eval")
     rc = f(ctx, n, _pd(pose), _pd(ex), _pd(q), float(plane_Z), _pd(ni), _pd(r), _pd(J), _pd(cost))
     if rc != OK:
         raise RuntimeError("%splane_eval failed with status %d" % (prefix, rc))
@@ -882,9 +860,7 @@ def anchor_eval(lib, prefix, ctx, pose, anchor, sqrt_info=120.0):
     pose, anchor = _f64(pose).reshape(-1, 7), _f64(anchor).reshape(-1, 7)
     n = len(pose)
     r, J, cost = np.zeros((n, 6)), np.zeros((n, 6, 6)), np.zeros(1)
-    f = getattr(lib, prefix + "anchor_eval")
-    f.restype = c_i
-    f.argtypes = [C.c_void_p, c_i, PD, PD, c_d, PD, PD, PD]
+    f = getattr(bind(lib, prefix), prefix + "anchor_eval")
     rc = f(ctx, n, _pd(pose), _pd(anchor), float(sqrt_info), _pd(r), _pd(J), _pd(cost))
     if rc != OK:
         raise RuntimeError("%sanchor_eval failed with status %d" % (prefix, rc))
@@ -893,10 +869,7 @@ def anchor_eval(lib, prefix, ctx, pose, anchor, sqrt_info=120.0):
 
 def orientation_subset_plus(lib, prefix, q, delta, constant=(0, 0, 1)):
     q, d, m, out = _f64(q), _f64(delta), _u8(constant), np.zeros(4)
-    f = getattr(lib, prefix + "orientation_subset_plus")
-    f.restype = None
-    f.argtypes = [PD, PD, PU8, PD]
-    f(_pd(q), _pd(d), m.ctypes.data_as(PU8), _pd(out))
+    getattr(bind(lib, prefix), prefix + "orientation_subset_plus")(_pd(q), _pd(d), m.ctypes.data_as(PU8), _pd(out))
     return out
 
 
@@ -937,9 +910,7 @@ def gnss_eval(lib, prefix, ctx, obs, iono, pose, speed_bias, rcv_dt, rcv_ddt, ya
     assert fdt.shape == (WINDOW_SIZE,)
     io = _f64(iono) if iono is not None else None
     r, J, rc_, rs, cost = np.zeros((n, 2)), np.zeros((n, 2, 18)), np.zeros((4, WINDOW_SIZE)), np.zeros(WINDOW_SIZE), np.zeros(1)
-    f = getattr(lib, prefix + "gnss_eval")
-    f.restype = c_i
-    f.argtypes = [C.c_void_p, c_i, C.POINTER(GnssObs), PD, C.POINTER(State), C.POINTER(GnssState), PD, c_d, PD, PD, PD, PD, PD]
+    f = getattr(bind(lib, prefix), prefix + "gnss_eval")
     rc = f(ctx, n, arr, _pd(io) if io is not None else None, C.byref(st), C.byref(g), _pd(fdt), float(ddt_weight), _pd(r),
            _pd(J) if want_J else None, _pd(rc_), _pd(rs), _pd(cost))
     if rc != OK:
@@ -981,9 +952,7 @@ def line_eval(lib, prefix, ctx, pose, ex_cam, orth, obs, sqrt_info=400.0, robust
     n = len(pose)
     assert len(orth) == n and len(obs) == n
     r, Jp, Je, Jo, cost = np.zeros((n, 2)), np.zeros((n, 2, 7)), np.zeros((n, 2, 7)), np.zeros((n, 2, 4)), np.zeros(1)
-    f = getattr(lib, prefix + "line_eval")
-    f.restype = c_i
-    f.argtypes = [C.c_void_p, c_i, PD, PD, PD, PD, c_d, c_i, PD, PD, PD, PD, PD]
+    f = getattr(bind(lib, prefix), prefix + "line_eval")
     rc = f(ctx, n, _pd(pose), _pd(ex), _pd(orth), _pd(obs), float(sqrt_info), int(bool(robustify)), _pd(r), _pd(Jp), _pd(Je), _pd(Jo), _pd(cost))
     if rc != OK:
         raise RuntimeError("%sline_eval failed with status %d" % (prefix, rc))
@@ -999,9 +968,7 @@ def line_refine_raw(lib, prefix, ctx, holders, sqrt_info=400.0, cauchy_scale=1.0
     plk = np.zeros((n_lines, 6)) if plucker_out is None else plucker_out
     keep = np.zeros(n_lines, np.uint8) if keep_out is None else keep_out
     sums = (Summary * max(len(holders), 1))() if summary is None else summary
-    f = getattr(lib, prefix + "line_refine")
-    f.restype = c_i
-    f.argtypes = [C.c_void_p, c_i, C.POINTER(C.POINTER(LineWindow)), c_d, c_d, c_i, PD, PU8, C.POINTER(Summary)]
+    f = getattr(bind(lib, prefix), prefix + "line_refine")
     rc = f(ctx, len(holders), arr, float(sqrt_info), float(cauchy_scale), int(max_num_iterations), _pd(plk), keep.ctypes.data_as(PU8), sums)
     return rc, plk, keep, sums
 
@@ -1071,10 +1038,8 @@ def _line_reduced_split(bufs):
 def line_reduce_raw(lib, prefix, ctx, holders, mode, sqrt_info, huber_width, mu, red):
     """gfbe_line_reduce over prebuilt LineWindowHolders into the LineReduced `red`; returns the status."""
     arr = (C.POINTER(LineWindow) * max(len(holders), 1))(*[C.pointer(h.c) for h in holders])
-    f = getattr(lib, prefix + "line_reduce")
-    f.restype = c_i
-    f.argtypes = [C.c_void_p, c_i, C.POINTER(C.POINTER(LineWindow)), c_i, c_d, c_d, c_d, C.POINTER(LineReduced)]
-    return f(ctx, len(holders), arr, int(mode), float(sqrt_info), float(huber_width), float(mu), C.byref(red) if red is not None else None)
+    f = getattr(bind(lib, prefix), prefix + "line_reduce")
+    return f(ctx, len(holders), arr, int(mode), float(sqrt_info), float(huber_width), float(mu), _reduced_ptr(red))
 
 
 def line_reduce(lib, prefix, ctx, windows, mode=LINE_REDUCE_SOLVE, sqrt_info=400.0, huber_width=1.0, mu=0.0, want=LINE_REDUCE_KEYS):
@@ -1095,6 +1060,12 @@ def line_reduce(lib, prefix, ctx, windows, mode=LINE_REDUCE_SOLVE, sqrt_info=400
 class LineReducedV(C.Structure):
     """gfbe_line_reduced at its current size: LineReduced (the size before the member V, still admitted by the library) plus V."""
     _fields_ = LineReduced._fields_ + [("V", PD)]
+
+
+def _reduced_ptr(red):
+    """`red` (LineReduced or LineReducedV, told apart by struct_size: the library admits both; None: NULL) as the gfbe_line_reduced *
+    of the signatures."""
+    return C.cast(C.byref(red), C.POINTER(LineReducedV)) if red is not None else None
 
 
 LINE_RECORD_KEYS = ("Vinv", "bl", "W", "V", "failed")
@@ -1129,12 +1100,7 @@ def line_reduce_v(lib, prefix, ctx, windows, mode=LINE_REDUCE_SOLVE, sqrt_info=4
     holders = [w if isinstance(w, LineWindowHolder) else LineWindowHolder(w) for w in windows]
     want = tuple(want) + tuple(k for k in ("n_eligible",) if k not in want)
     bufs = line_reduced_buffers_v(len(holders), sum(h.n for h in holders), want)
-    red = line_reduced_struct_v(bufs)
-    arr = (C.POINTER(LineWindow) * max(len(holders), 1))(*[C.pointer(h.c) for h in holders])
-    f = getattr(lib, prefix + "line_reduce")
-    f.restype = c_i
-    f.argtypes = [C.c_void_p, c_i, C.POINTER(C.POINTER(LineWindow)), c_i, c_d, c_d, c_d, C.c_void_p]
-    rc = f(ctx, len(holders), arr, int(mode), float(sqrt_info), float(huber_width), float(mu), C.byref(red))
+    rc = line_reduce_raw(lib, prefix, ctx, holders, mode, sqrt_info, huber_width, mu, line_reduced_struct_v(bufs))
     if rc != OK:
         raise RuntimeError("%sline_reduce failed with status %d" % (prefix, rc))
     return _line_split(bufs, bufs["n_eligible"], LINE_RECORD_KEYS)
@@ -1172,10 +1138,8 @@ def line_step_raw(lib, prefix, ctx, holders, red, sqrt_info, huber_width, mu, y_
     """gfbe_line_step over prebuilt LineWindowHolders; red: LineReducedV over the records (or None), stepped: LineStepped (or None);
     y_p, v_p [W][72], rest [W][8], radius [W] float64 contiguous. Returns the status."""
     arr = (C.POINTER(LineWindow) * max(len(holders), 1))(*[C.pointer(h.c) for h in holders])
-    f = getattr(lib, prefix + "line_step")
-    f.restype = c_i
-    f.argtypes = [C.c_void_p, c_i, C.POINTER(C.POINTER(LineWindow)), C.c_void_p, c_d, c_d, c_d, PD, PD, PD, PD, C.c_void_p]
-    return f(ctx, len(holders), arr, C.byref(red) if red is not None else None, float(sqrt_info), float(huber_width), float(mu),
+    f = getattr(bind(lib, prefix), prefix + "line_step")
+    return f(ctx, len(holders), arr, _reduced_ptr(red), float(sqrt_info), float(huber_width), float(mu),
              _pd(y_p), _pd(v_p), _pd(rest), _pd(radius), C.byref(stepped) if stepped is not None else None)
 
 
@@ -1210,30 +1174,14 @@ def line_step(lib, prefix, ctx, windows, records, y_p, v_p, rest, radius, sqrt_i
 # ---------------------------------------------------------------------------------------------
 # Line feature tables (gfbe_ltab_*): FeatureManager::linefeature on the device
 # ---------------------------------------------------------------------------------------------
-class LineTables:
+class LineTables(Handle):
     """W device-resident line tables behind `lib` (prefix gfbe_, ctx = gfbe_ctx*). Per-table arguments are lists of length W."""
+    family = "ltab_"
 
     def __init__(self, lib, prefix, ctx, n_tables=1, capacity=1024):
-        self.lib, self.prefix, self.ctx, self.W, self.cap = lib, prefix, ctx, n_tables, capacity
-        self.h = C.c_void_p()
-        for name in ("create", "add_frame", "triangulate", "remove_back_shift", "remove_back", "remove_front", "refine", "size",
-                     "line_count", "download", "upload"):
-            self._f(name).restype = c_i
-        self._f("destroy").restype = None
-        self._f("refine").argtypes = [C.c_void_p, C.c_void_p, PD, PD, c_d, c_d, c_i, C.POINTER(Summary)]
+        Handle.__init__(self, lib, prefix, ctx)
+        self.W, self.cap = n_tables, capacity
         self._check(self._f("create")(self.ctx, int(n_tables), int(capacity), C.byref(self.h)), "create")
-
-    def _f(self, name):
-        return getattr(self.lib, self.prefix + "ltab_" + name)
-
-    def _check(self, rc, what):
-        if rc != OK:
-            raise RuntimeError("%sltab_%s failed with status %d" % (self.prefix, what, rc))
-
-    def close(self):
-        if self.h:
-            self._f("destroy")(self.ctx, self.h)
-            self.h = C.c_void_p()
 
     def add_frame(self, frame_count, ids, obs4):
         """ids[w]: ascending line ids; obs4[w]: [n, 4]. Returns counters [W, 2] = [tracked, new]."""
@@ -1275,11 +1223,8 @@ class LineTables:
 
     def reduce_raw(self, pose7, ex_cam, mode, sqrt_info, huber_width, mu, red):
         """gfbe_ltab_reduce on prepared arrays (pose7 [W][11][7], ex_cam [W][7], float64, contiguous) into the LineReduced `red`."""
-        f = self._f("reduce")
-        f.restype = c_i
-        f.argtypes = [C.c_void_p, C.c_void_p, c_i, PD, PD, c_d, c_d, c_d, C.c_void_p]      # (LineReduced or LineReducedV: both sizes are admitted)
-        return f(self.ctx, self.h, int(mode), _pd(pose7), _pd(ex_cam), float(sqrt_info), float(huber_width), float(mu),
-                 C.byref(red) if red is not None else None)
+        return self._f("reduce")(self.ctx, self.h, int(mode), _pd(pose7), _pd(ex_cam), float(sqrt_info), float(huber_width), float(mu),
+                                 _reduced_ptr(red))      # (LineReduced or LineReducedV: both sizes are admitted)
 
     def reduce(self, pose7, ex_cam, mode=LINE_REDUCE_SOLVE, sqrt_info=400.0, huber_width=1.0, mu=0.0, want=LINE_REDUCE_KEYS):
         """Reduced normal equations of the line factors of every table, read in place (abi.line_reduce's result per table)."""
@@ -1308,18 +1253,12 @@ class LineTables:
 
     def keep_records(self, on=True):
         """gfbe_ltab_keep_records: while on, a solve-mode reduce leaves its per-line records on the handle for step()."""
-        f = self._f("keep_records")
-        f.restype = c_i
-        f.argtypes = [C.c_void_p, C.c_void_p, c_i]
-        self._check(f(self.ctx, self.h, int(bool(on))), "keep_records")
+        self._check(self._f("keep_records")(self.ctx, self.h, int(bool(on))), "keep_records")
 
     def step_raw(self, pose7, ex_cam, sqrt_info, huber_width, y_p, v_p, rest, radius, stepped):
         """gfbe_ltab_step on prepared arrays (float64, contiguous) into the LineStepped `stepped`; returns the status."""
-        f = self._f("step")
-        f.restype = c_i
-        f.argtypes = [C.c_void_p, C.c_void_p, PD, PD, c_d, c_d, PD, PD, PD, PD, C.c_void_p]
-        return f(self.ctx, self.h, _pd(pose7), _pd(ex_cam), float(sqrt_info), float(huber_width), _pd(y_p), _pd(v_p), _pd(rest), _pd(radius),
-                 C.byref(stepped) if stepped is not None else None)
+        return self._f("step")(self.ctx, self.h, _pd(pose7), _pd(ex_cam), float(sqrt_info), float(huber_width), _pd(y_p), _pd(v_p), _pd(rest),
+                               _pd(radius), C.byref(stepped) if stepped is not None else None)
 
     def step(self, pose7, ex_cam, y_p, v_p, rest, radius, n_eligible, sqrt_info=400.0, huber_width=1.0, want=LINE_STEP_KEYS):
         """The step half on every table from the records the last solve-mode reduce kept (abi.line_step's result per table).
@@ -1336,10 +1275,7 @@ class LineTables:
     def commit(self, accept):
         """gfbe_ltab_commit: tables with accept[w] != 0 take the candidate lines of the last step()."""
         a = _u8(accept).reshape(self.W)
-        f = self._f("commit")
-        f.restype = c_i
-        f.argtypes = [C.c_void_p, C.c_void_p, PU8]
-        self._check(f(self.ctx, self.h, a.ctypes.data_as(PU8)), "commit")
+        self._check(self._f("commit")(self.ctx, self.h, a.ctypes.data_as(PU8)), "commit")
 
     def line_count(self):
         n = np.zeros(self.W, np.int32)
@@ -1382,11 +1318,7 @@ class VmapOptions(C.Structure):
 
 
 def vmap_default_options(lib, prefix="gfbe_"):
-    o = VmapOptions()
-    f = getattr(lib, prefix + "vmap_default_options")
-    f.restype = None
-    f(C.byref(o))
-    return o
+    return options_struct(lib, prefix, "vmap_", VmapOptions)
 
 
 class VregOptions(C.Structure):
@@ -1402,11 +1334,7 @@ class VregSummary(C.Structure):
 
 
 def vreg_default_options(lib, prefix="gfbe_"):
-    o = VregOptions()
-    f = getattr(lib, prefix + "vreg_default_options")
-    f.restype = None
-    f(C.byref(o))
-    return o
+    return options_struct(lib, prefix, "vreg_", VregOptions)
 
 
 def vreg_summary_to_dict(sm):
@@ -1420,36 +1348,16 @@ def vreg_summary_to_dict(sm):
     return d
 
 
-class VoxelMap:
+class VoxelMap(Handle):
     """A device-resident voxel map behind `lib` (prefix gfbe_, ctx = gfbe_ctx*). options: fields of gfbe_vmap_options."""
+    family = "vmap_"
     PI16 = C.POINTER(C.c_int16)
 
     def __init__(self, lib, prefix, ctx, voxel_capacity=1 << 16, **options):
-        self.lib, self.prefix, self.ctx, self.cap = lib, prefix, ctx, voxel_capacity
-        self.h = C.c_void_p()
-        self.opt = vmap_default_options(lib, prefix)
-        for k, v in options.items():
-            if not hasattr(self.opt, k):
-                raise TypeError("gfbe_vmap_options has no field %r" % k)
-            setattr(self.opt, k, v)
-        for name in ("create", "add_points", "erase_far", "size", "download", "upload", "associate", "linearize", "localizability", "register", "add_scan",
-                     "register_scan", "add_scan_handle"):
-            self._f(name).restype = c_i
-        self._f("destroy").restype = None
-        self._f("linearize").argtypes = [C.c_void_p, C.c_void_p, c_i, c_d, PD, PD, PD, PD, PD, PD, PD]
+        Handle.__init__(self, lib, prefix, ctx)
+        self.cap = voxel_capacity
+        self.opt = self._options(VmapOptions, options)
         self._check(self._f("create")(self.ctx, int(voxel_capacity), C.byref(self.opt), C.byref(self.h)), "create")
-
-    def _f(self, name):
-        return getattr(self.lib, self.prefix + "vmap_" + name)
-
-    def _check(self, rc, what):
-        if rc != OK:
-            raise RuntimeError("%svmap_%s failed with status %d" % (self.prefix, what, rc))
-
-    def close(self):
-        if self.h:
-            self._f("destroy")(self.ctx, self.h)
-            self.h = C.c_void_p()
 
     def add_points(self, pts_world, min_num_points=0):
         p = _f64(pts_world).reshape(-1, 3)
@@ -1462,7 +1370,7 @@ class VoxelMap:
     def size(self):
         """dict(n_voxels, n_points, n_skipped, overflow)."""
         v = (c_i * 4)()
-        self._check(self._f("size")(self.ctx, self.h, C.byref(v, 0), C.byref(v, 4), C.byref(v, 8), C.byref(v, 12)), "size")
+        self._check(self._f("size")(self.ctx, self.h, *[C.cast(C.byref(v, 4 * k), PI) for k in range(4)]), "size")
         return dict(n_voxels=v[0], n_points=v[1], n_skipped=v[2], overflow=v[3])
 
     def download(self):
@@ -1519,11 +1427,7 @@ class VoxelMap:
 
     def register_raw(self, ct, raw_pts, alpha, pose_begin, pose_end=None, prev_translation=None, prev_rotation=None, frame_init=False, **options):
         """gfbe_vmap_register: (status, pose_begin, pose_end, summary dict). options: fields of gfbe_vreg_options."""
-        o = vreg_default_options(self.lib, self.prefix)
-        for k, v in options.items():
-            if not hasattr(o, k):
-                raise TypeError("gfbe_vreg_options has no field %r" % k)
-            setattr(o, k, v)
+        o = self._options(VregOptions, options, "vreg_")
         raw = _f64(raw_pts).reshape(-1, 3)
         n = len(raw)
         al = _f64(alpha if alpha is not None else np.zeros(n))
@@ -1555,11 +1459,7 @@ class VoxelMap:
 
     def register_scan_raw(self, ct, scan, pose_begin, pose_end=None, prev_translation=None, prev_rotation=None, frame_init=False, **options):
         """gfbe_vmap_register_scan on the KEYPOINTS of `scan` (abi.Scan): (status, pose_begin, pose_end, summary dict)."""
-        o = vreg_default_options(self.lib, self.prefix)
-        for k, v in options.items():
-            if not hasattr(o, k):
-                raise TypeError("gfbe_vreg_options has no field %r" % k)
-            setattr(o, k, v)
+        o = self._options(VregOptions, options, "vreg_")
         pb = _f64(pose_begin)
         pe = _f64(pose_end if pose_end is not None else pose_begin)
         pt = _pd(_f64(prev_translation)) if prev_translation is not None else None
@@ -1586,31 +1486,15 @@ class VoxelMap:
 # ---------------------------------------------------------------------------------------------
 # A LiDAR scan held on the device (gfbe_scan_*): subSampleFrame, Undistort, transformPoint + gridSampling
 # ---------------------------------------------------------------------------------------------
-class Scan:
+class Scan(Handle):
     """A device-resident scan behind `lib` (prefix gfbe_, ctx = gfbe_ctx*) of up to `capacity` points. The *_raw methods return the
     status; the others raise."""
+    family = "scan_"
 
     def __init__(self, lib, prefix, ctx, capacity=1 << 16):
-        self.lib, self.prefix, self.ctx, self.cap = lib, prefix, ctx, capacity
-        self.h = C.c_void_p()
-        for name in ("create", "upload", "subsample", "undistort", "keypoints", "size", "download"):
-            self._f(name).restype = c_i
-        self._f("destroy").restype = None
-        self._f("subsample").argtypes = [C.c_void_p, C.c_void_p, c_d]
-        self._f("keypoints").argtypes = [C.c_void_p, C.c_void_p, c_i, PD, PD, c_d, C.POINTER(c_i)]
+        Handle.__init__(self, lib, prefix, ctx)
+        self.cap = capacity
         self._check(self._f("create")(self.ctx, int(capacity), C.byref(self.h)), "create")
-
-    def _f(self, name):
-        return getattr(self.lib, self.prefix + "scan_" + name)
-
-    def _check(self, rc, what):
-        if rc != OK:
-            raise RuntimeError("%sscan_%s failed with status %d" % (self.prefix, what, rc))
-
-    def close(self):
-        if self.h:
-            self._f("destroy")(self.ctx, self.h)
-            self.h = C.c_void_p()
 
     def upload_raw(self, raw_pts, alpha, timestamp=None, til=None):
         raw = _f64(raw_pts).reshape(-1, 3)
@@ -1653,7 +1537,7 @@ class Scan:
     def size(self):
         """dict(n_points, n_keypoints, n_skipped)."""
         v = (c_i * 3)()
-        self._check(self._f("size")(self.ctx, self.h, C.byref(v, 0), C.byref(v, 4), C.byref(v, 8)), "size")
+        self._check(self._f("size")(self.ctx, self.h, *[C.cast(C.byref(v, 4 * k), PI) for k in range(3)]), "size")
         return dict(n_points=v[0], n_keypoints=v[1], n_skipped=v[2])
 
     def download(self, which=0):
@@ -1678,54 +1562,23 @@ class DmapOptions(C.Structure):
 
 
 def dmap_default_options(lib, prefix="gfbe_"):
-    o = DmapOptions()
-    f = getattr(lib, prefix + "dmap_default_options")
-    f.restype = None
-    f(C.byref(o))
-    return o
+    return options_struct(lib, prefix, "dmap_", DmapOptions)
 
 
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
-class DenseMap:
+class DenseMap(Handle):
     """The dense map behind `lib` (prefix gfbe_, ctx = gfbe_ctx*): addKeyFrame's capped insert, updatePath's rebuild and the radius
     filter of dense_map/src/pose_graph.cpp on up to `point_capacity` stored points of `keyframe_capacity` keyframes. options: fields
     of gfbe_dmap_options. The *_raw methods return the status; the others raise."""
+    family = "dmap_"
 
     def __init__(self, lib, prefix, ctx, point_capacity=1 << 16, keyframe_capacity=1024, **options):
-        self.lib, self.prefix, self.ctx = lib, prefix, ctx
-        self.h = C.c_void_p()
-        for name in ("create", "add_keyframe", "rebuild", "filter", "size", "download_cloud", "download_keyframe"):
-            self._f(name).restype = c_i
-        self._f("destroy").restype = None
-        self._f("create").argtypes = [C.c_void_p, c_i, c_i, C.POINTER(DmapOptions), C.POINTER(C.c_void_p)]
-        self._f("add_keyframe").argtypes = [C.c_void_p, C.c_void_p, PD, c_i, PF, PU8]
-        self._f("rebuild").argtypes = [C.c_void_p, C.c_void_p, c_i, PD]
-        self._f("filter").argtypes = [C.c_void_p, C.c_void_p, PU8, C.POINTER(c_i), PF, PU8]
-        self._f("size").argtypes = [C.c_void_p, C.c_void_p, C.POINTER(c_i)]
-        self._f("download_cloud").argtypes = [C.c_void_p, C.c_void_p, PF, PU8, C.POINTER(c_i), C.POINTER(c_i)]
-        self._f("download_keyframe").argtypes = [C.c_void_p, C.c_void_p, c_i, C.POINTER(c_i), PF, PU8]
-        self.opt = dmap_default_options(lib, prefix)
-        for k, v in options.items():
-            if k == "ex_cam":
-                self.opt.ex_cam = (c_d * 7)(*[float(x) for x in v])
-            else:
-                setattr(self.opt, k, v)
+        Handle.__init__(self, lib, prefix, ctx)
+        self.opt = self._options(DmapOptions, options)
         self._check(self._f("create")(self.ctx, int(point_capacity), int(keyframe_capacity), C.byref(self.opt), C.byref(self.h)), "create")
-
-    def _f(self, name):
-        return getattr(self.lib, self.prefix + "dmap_" + name)
-
-    def _check(self, rc, what):
-        if rc != OK:
-            raise RuntimeError("%sdmap_%s failed with status %d" % (self.prefix, what, rc))
-
-    def close(self):
-        if self.h:
-            self._f("destroy")(self.ctx, self.h)
-            self.h = C.c_void_p()
 
     def add_keyframe_raw(self, pose7, pts_cam, rgb):
         p, pts, col = _f64(pose7), _f32(pts_cam).reshape(-1, 3), _u8(rgb).reshape(-1, 3)
@@ -1797,11 +1650,7 @@ class LdbOptions(C.Structure):
 
 
 def ldb_default_options(lib, prefix="gfbe_"):
-    o = LdbOptions()
-    f = getattr(lib, prefix + "ldb_default_options")
-    f.restype = None
-    f(C.byref(o))
-    return o
+    return options_struct(lib, prefix, "ldb_", LdbOptions)
 
 
 def _u64(a, cols=4):
@@ -1820,42 +1669,17 @@ class LdbVocabHolder:
                           _pi(self.node_id), _pi(self.parent_id), _pd(self.weight), self.descriptor.ctypes.data_as(PU64), _pi(self.word_id), _pi(self.word_node))
 
 
-class LoopDatabase:
+class LoopDatabase(Handle):
     """The loop database behind `lib` (prefix gfbe_, ctx = gfbe_ctx*): detectLoop / addKeyFrameIntoVoc of dense_map/src/pose_graph.cpp and
     searchByBRIEFDes of keyframe.cpp over a vocabulary `voc` (LdbVocabHolder or its dict). options: fields of gfbe_ldb_options. The *_raw
     methods return the status; the others raise."""
+    family = "ldb_"
 
     def __init__(self, lib, prefix, ctx, voc, keyframe_capacity=1024, descriptor_capacity=1 << 20, **options):
-        self.lib, self.prefix, self.ctx = lib, prefix, ctx
-        self.h = C.c_void_p()
+        Handle.__init__(self, lib, prefix, ctx)
         self.voc = voc if isinstance(voc, LdbVocabHolder) else LdbVocabHolder(voc)
-        PI = C.POINTER(c_i)
-        for name in ("create", "transform", "add_keyframe", "match", "size", "download_entry"):
-            self._f(name).restype = c_i
-        self._f("destroy").restype = None
-        self._f("create").argtypes = [C.c_void_p, C.POINTER(LdbVocab), c_i, C.c_int64, C.POINTER(LdbOptions), C.POINTER(C.c_void_p)]
-        self._f("destroy").argtypes = [C.c_void_p, C.c_void_p]
-        self._f("transform").argtypes = [C.c_void_p, C.c_void_p, c_i, PU64, PI, PI, PI, PD]
-        self._f("add_keyframe").argtypes = [C.c_void_p, C.c_void_p, c_i, PU64, PF, PF, c_i, PI, PI, PI, PI, PD]
-        self._f("match").argtypes = [C.c_void_p, C.c_void_p, c_i, c_i, PU64, PU8, PI, PI, PI, PI, PF, PF]
-        self._f("size").argtypes = [C.c_void_p, C.c_void_p, PI]
-        self._f("download_entry").argtypes = [C.c_void_p, C.c_void_p, c_i, PI, PI, PD, PI, PU64, PF, PF]
-        self.opt = ldb_default_options(lib, prefix)
-        for k, v in options.items():
-            setattr(self.opt, k, v)
+        self.opt = self._options(LdbOptions, options)
         self._check(self._f("create")(self.ctx, C.byref(self.voc.c), int(keyframe_capacity), int(descriptor_capacity), C.byref(self.opt), C.byref(self.h)), "create")
-
-    def _f(self, name):
-        return getattr(self.lib, self.prefix + "ldb_" + name)
-
-    def _check(self, rc, what):
-        if rc != OK:
-            raise RuntimeError("%sldb_%s failed with status %d" % (self.prefix, what, rc))
-
-    def close(self):
-        if self.h:
-            self._f("destroy")(self.ctx, self.h)
-            self.h = C.c_void_p()
 
     def transform(self, desc):
         """dict(word [n] the word of every descriptor, bow_word / bow_value the normalised BoW vector); no database change."""

@@ -11,44 +11,17 @@ import subprocess
 
 import numpy as np
 
-from . import abi
+from . import abi, signatures
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 # GFBE_LIB: an alternative build of the library (tools/diag_variants.py compares kernel variants built side by side)
 _SO = os.environ.get("GFBE_LIB") or os.path.join(_CSRC, "libgfbe.so")
 
-# Every symbol include/gfbe.h declares (checked by tests/test_abi.py on CPU).
-EXPORTS = [
-    "gfbe_default_options", "gfbe_options_size", "gfbe_create", "gfbe_destroy", "gfbe_last_error", "gfbe_create_note", "gfbe_host_times", "gfbe_version", "gfbe_set_stream",
-    "gfbe_feature_count", "gfbe_visual_factor_count", "gfbe_build_visual_factors", "gfbe_set_depth",
-    "gfbe_eval_factors", "gfbe_preintegrate_imu", "gfbe_preintegrate_wheel",
-    "gfbe_solve_window", "gfbe_solve_batch",
-    "gfbe_batch_upload", "gfbe_batch_solve", "gfbe_batch_download", "gfbe_batch_free",
-    "gfbe_profile_enable", "gfbe_profile_count", "gfbe_profile_get", "gfbe_profile_reset",
-    "gfbe_set_allreduce", "gfbe_debug_timing", "gfbe_debug_vector",
-    "gfbe_ftab_default_options", "gfbe_ftab_create", "gfbe_ftab_destroy", "gfbe_ftab_add_frame",
-    "gfbe_ftab_remove_back_shift_depth", "gfbe_ftab_remove_back", "gfbe_ftab_remove_front", "gfbe_ftab_remove_outlier",
-    "gfbe_ftab_remove_failures", "gfbe_ftab_clear_depth", "gfbe_ftab_set_depth", "gfbe_ftab_get_depth_vector",
-    "gfbe_ftab_triangulate", "gfbe_ftab_check_outliers", "gfbe_ftab_size", "gfbe_ftab_download", "gfbe_slide_window_state",
-    "gfbe_pg_eval", "gfbe_pg_solve", "gfbe_lio_linearize", "gfbe_batch_upload_tables", "gfbe_batch_feature_count",
-    "gfbe_plane_eval", "gfbe_anchor_eval", "gfbe_orientation_subset_plus", "gfbe_gnss_eval",
-    "gfbe_line_eval", "gfbe_line_refine", "gfbe_line_reduce", "gfbe_ltab_reduce",
-    "gfbe_line_step", "gfbe_ltab_keep_records", "gfbe_ltab_step", "gfbe_ltab_commit",
-    "gfbe_ltab_create", "gfbe_ltab_destroy", "gfbe_ltab_add_frame", "gfbe_ltab_triangulate", "gfbe_ltab_remove_back_shift",
-    "gfbe_ltab_remove_back", "gfbe_ltab_remove_front", "gfbe_ltab_refine", "gfbe_ltab_size", "gfbe_ltab_line_count",
-    "gfbe_ltab_download", "gfbe_ltab_upload",
-    "gfbe_vmap_default_options", "gfbe_vmap_create", "gfbe_vmap_destroy", "gfbe_vmap_add_points", "gfbe_vmap_erase_far", "gfbe_vmap_size",
-    "gfbe_vmap_download", "gfbe_vmap_upload", "gfbe_vmap_associate", "gfbe_vmap_linearize", "gfbe_vmap_localizability",
-    "gfbe_vreg_default_options", "gfbe_vmap_register", "gfbe_vmap_add_scan",
-    "gfbe_scan_create", "gfbe_scan_destroy", "gfbe_scan_upload", "gfbe_scan_subsample", "gfbe_scan_undistort", "gfbe_scan_keypoints",
-    "gfbe_scan_size", "gfbe_scan_download", "gfbe_vmap_register_scan", "gfbe_vmap_add_scan_handle",
-    "gfbe_lc4_default_options", "gfbe_lc4_eval", "gfbe_lc4_solve", "gfbe_lc4_solve_long",
-    "gfbe_dmap_default_options", "gfbe_dmap_create", "gfbe_dmap_destroy", "gfbe_dmap_add_keyframe", "gfbe_dmap_rebuild", "gfbe_dmap_filter",
-    "gfbe_dmap_size", "gfbe_dmap_download_cloud", "gfbe_dmap_download_keyframe",
-    "gfbe_ldb_default_options", "gfbe_ldb_create", "gfbe_ldb_destroy", "gfbe_ldb_transform", "gfbe_ldb_add_keyframe", "gfbe_ldb_match",
-    "gfbe_ldb_size", "gfbe_ldb_download_entry",
-]
+# Every symbol include/gfbe.h / include/gfbe_rccl.h declares: the keys of the signature tables (checked against the headers by
+# tests/test_abi.py on CPU).
+EXPORTS = ["gfbe_" + name for name in signatures.GFBE]
+RCCL_EXPORTS = ["gfbe_rccl_" + name for name in signatures.RCCL]
 
 
 class BackendError(RuntimeError):
@@ -111,8 +84,6 @@ def build_native(force=False, verbose=False, out=None, extra_flags=None, fp_cont
 
 
 _RCCL_SO = os.path.join(_CSRC, "libgfbe_rccl.so")
-RCCL_EXPORTS = ["gfbe_rccl_unique_id", "gfbe_rccl_create", "gfbe_rccl_destroy", "gfbe_rccl_allreduce", "gfbe_rccl_last_error", "gfbe_rccl_calls",
-                "gfbe_rccl_bytes", "gfbe_rccl_comm_count"]
 
 
 def build_rccl_hook(force=False, verbose=False):
@@ -140,23 +111,12 @@ class Backend(abi.CApi):
         self.lib = abi.bind(C.CDLL(_SO), "gfbe_")
         self.opt = options or abi.default_options()
         self.ctx = C.c_void_p()
-        self.lib.gfbe_create.restype = abi.c_i
-        self.lib.gfbe_last_error.restype = C.c_char_p
-        self.lib.gfbe_last_error.argtypes = [C.c_void_p]
-        self.lib.gfbe_version.restype = C.c_char_p
         rc = self.lib.gfbe_create(C.byref(self.ctx), int(device), C.byref(self.opt))
         if rc != abi.OK:
             raise BackendError("gfbe_create(device=%d) failed with status %d (%s)" % (device, rc, self._err()))
-        self.lib.gfbe_create_note.restype = C.c_char_p
-        self.lib.gfbe_create_note.argtypes = [C.c_void_p]
         self.create_note = (self.lib.gfbe_create_note(self.ctx) or b"").decode()   # (a remark, not an error: e.g. speculative_linearization switched off for a batch)
         self.head = self.ctx
         self.device = device
-        for name in ("batch_upload", "batch_solve", "batch_download", "solve_batch", "profile_enable",
-                     "profile_get", "set_stream", "set_allreduce", "eval_factors", "solve_window"):
-            getattr(self.lib, "gfbe_" + name).restype = abi.c_i
-        self.lib.gfbe_batch_free.restype = None
-        self.lib.gfbe_profile_count.restype = abi.c_i
         self._cb = None
 
     def _err(self):
@@ -169,6 +129,13 @@ class Backend(abi.CApi):
         if rc not in (abi.OK, abi.NO_CONVERGENCE):
             raise BackendError("gfbe_%s failed with status %d: %s" % (what, rc, self._err()))
         return rc
+
+    def _call(self, fn, *args, **kw):
+        """fn(lib, "gfbe_", ctx, ...) of abi.py; its RuntimeError becomes a BackendError that carries gfbe_last_error."""
+        try:
+            return fn(self.lib, "gfbe_", self.ctx, *args, **kw)
+        except RuntimeError as e:
+            raise BackendError("%s: %s" % (e, self._err()))
 
     def close(self):
         if self.ctx:
@@ -194,82 +161,52 @@ class Backend(abi.CApi):
     # ---- line landmarks (gfbe_line_eval / gfbe_line_refine)
     def line_eval(self, pose, ex_cam, orth, obs, sqrt_info=400.0, robustify=True):
         """lineProjectionFactor at n (pose, line, observation) triples: r [n][2], J_pose / J_ex [n][2][7], J_orth [n][2][4], cost."""
-        try:
-            return abi.line_eval(self.lib, "gfbe_", self.ctx, pose, ex_cam, orth, obs, sqrt_info, robustify)
-        except RuntimeError as e:
-            raise BackendError("%s: %s" % (e, self._err()))
+        return self._call(abi.line_eval, pose, ex_cam, orth, obs, sqrt_info, robustify)
 
     def line_refine(self, windows, sqrt_info=400.0, cauchy_scale=1.0, max_num_iterations=8):
         """onlyLineOpt() + removeLineOutlier() of each line window (dicts as synth_line.LineScenario makes them, or
         abi.LineWindowHolder): per window plucker [n][6] (ineligible lines unchanged), keep [n], summary."""
-        try:
-            return abi.line_refine(self.lib, "gfbe_", self.ctx, windows, sqrt_info, cauchy_scale, max_num_iterations)
-        except RuntimeError as e:
-            raise BackendError("%s: %s" % (e, self._err()))
+        return self._call(abi.line_refine, windows, sqrt_info, cauchy_scale, max_num_iterations)
 
     def line_reduce(self, windows, mode=abi.LINE_REDUCE_SOLVE, sqrt_info=400.0, huber_width=1.0, mu=0.0, want=abi.LINE_REDUCE_KEYS):
         """The line loops of optimizationwithLine() linearised and reduced onto the 72 pose / extrinsic dims (dims 0..71 of the dense
         block): per window H [72][72], g, U, bp, cost, n_eligible, n_failed and the per-line records Vinv, bl, W, failed. For device-
         resident tables: line_tables(...).reduce(...)."""
-        try:
-            return abi.line_reduce(self.lib, "gfbe_", self.ctx, windows, mode, sqrt_info, huber_width, mu, want)
-        except RuntimeError as e:
-            raise BackendError("%s: %s" % (e, self._err()))
+        return self._call(abi.line_reduce, windows, mode, sqrt_info, huber_width, mu, want)
 
     def line_reduce_v(self, windows, mode=abi.LINE_REDUCE_SOLVE, sqrt_info=400.0, huber_width=1.0, mu=0.0, want=abi.LINE_REDUCE_KEYS_V):
         """line_reduce with the record V (the lower triangle of V_l without mu) beside Vinv, bl, W, failed: what line_step takes."""
-        try:
-            return abi.line_reduce_v(self.lib, "gfbe_", self.ctx, windows, mode, sqrt_info, huber_width, mu, want)
-        except RuntimeError as e:
-            raise BackendError("%s: %s" % (e, self._err()))
+        return self._call(abi.line_reduce_v, windows, mode, sqrt_info, huber_width, mu, want)
 
     def line_step(self, windows, records, y_p, v_p, rest, radius, sqrt_info=400.0, huber_width=1.0, mu=0.0, want=abi.LINE_STEP_KEYS):
         """The step half of a joint iteration over the line blocks (gfbe_line_step): back-substitution, the lines' dogleg shares, the
         dogleg coefficients from rest + shares, the candidate lines / poses and the candidate line cost. records: line_reduce_v's result.
         For device-resident tables: line_tables(...).keep_records() / reduce_v / step / commit."""
-        try:
-            return abi.line_step(self.lib, "gfbe_", self.ctx, windows, records, y_p, v_p, rest, radius, sqrt_info, huber_width, mu, want)
-        except RuntimeError as e:
-            raise BackendError("%s: %s" % (e, self._err()))
+        return self._call(abi.line_step, windows, records, y_p, v_p, rest, radius, sqrt_info, huber_width, mu, want)
 
     def line_tables(self, n_tables=1, capacity=1024):
         """W device-resident line tables (abi.LineTables: FeatureManager::linefeature and its per-frame operations, gfbe_ltab_*)."""
-        try:
-            return abi.LineTables(self.lib, "gfbe_", self.ctx, n_tables, capacity)
-        except RuntimeError as e:
-            raise BackendError("%s: %s" % (e, self._err()))
+        return self._call(abi.LineTables, n_tables, capacity)
 
     def voxel_map(self, voxel_capacity=1 << 16, **options):
         """A device-resident voxel map of the LiDAR odometry (abi.VoxelMap: map_incremental, lasermap_fov_segment and the scan-to-map
         association of addSurfCostFactor, gfbe_vmap_*). options: fields of gfbe_vmap_options."""
-        try:
-            return abi.VoxelMap(self.lib, "gfbe_", self.ctx, voxel_capacity, **options)
-        except RuntimeError as e:
-            raise BackendError("%s: %s" % (e, self._err()))
+        return self._call(abi.VoxelMap, voxel_capacity, **options)
 
     def scan(self, capacity=1 << 16):
         """A device-resident LiDAR scan (abi.Scan: subSampleFrame, Undistort, transformPoint + gridSampling, gfbe_scan_*) for
         VoxelMap.register_scan / add_scan_handle."""
-        try:
-            return abi.Scan(self.lib, "gfbe_", self.ctx, capacity)
-        except RuntimeError as e:
-            raise BackendError("%s: %s" % (e, self._err()))
+        return self._call(abi.Scan, capacity)
 
     def dense_map(self, point_capacity=1 << 16, keyframe_capacity=1024, **options):
         """The dense RGB-D map of the loop-closure thread held on the device (abi.DenseMap: addKeyFrame's capped insert, updatePath's
         rebuild at the corrected poses and the radius filter, gfbe_dmap_*). options: fields of gfbe_dmap_options."""
-        try:
-            return abi.DenseMap(self.lib, "gfbe_", self.ctx, point_capacity, keyframe_capacity, **options)
-        except RuntimeError as e:
-            raise BackendError("%s: %s" % (e, self._err()))
+        return self._call(abi.DenseMap, point_capacity, keyframe_capacity, **options)
 
     def loop_database(self, voc, keyframe_capacity=1024, descriptor_capacity=1 << 20, **options):
         """The loop database of the loop-closure thread held on the device (abi.LoopDatabase: detectLoop's vocabulary query and decision,
         addKeyFrameIntoVoc and searchByBRIEFDes, gfbe_ldb_*). voc: abi.LdbVocabHolder or its dict; options: fields of gfbe_ldb_options."""
-        try:
-            return abi.LoopDatabase(self.lib, "gfbe_", self.ctx, voc, keyframe_capacity, descriptor_capacity, **options)
-        except RuntimeError as e:
-            raise BackendError("%s: %s" % (e, self._err()))
+        return self._call(abi.LoopDatabase, voc, keyframe_capacity, descriptor_capacity, **options)
 
     # ---- device-resident batch
     def batch_upload(self, snaps):
@@ -285,25 +222,13 @@ class Backend(abi.CApi):
     def batch_upload_tables(self, tables, snaps):
         """snaps: window snapshots WITHOUT visual factors (state, pre-integrations, prior, flags); the landmarks of window w
         come from table w of `tables` (abi.FeatureTables on this library) without leaving the device."""
-        if isinstance(snaps, WindowSet):
-            batch = C.c_void_p()
-            self.lib.gfbe_batch_upload_tables.restype = abi.c_i
-            self.check(self.lib.gfbe_batch_upload_tables(self.ctx, tables.h, len(snaps.holders), snaps.arr, C.byref(batch)), "batch_upload_tables")
-            return Batch(self, batch, snaps.holders)
-        holders = []
-        for s in snaps:
-            s = dict(s)
-            for k in ("vis_feature_index", "vis_imu_i", "vis_imu_j", "vis_pts_i", "vis_pts_j", "vis_vel_i", "vis_vel_j", "vis_td_i", "vis_td_j"):
-                s[k] = np.zeros(0)
-            s["para_feature"], s["feature_const"] = np.zeros(0), np.zeros(0, np.uint8)
-            holders.append(abi.WindowHolder(s))
-        arr = (C.POINTER(abi.Window) * len(holders))(*[C.pointer(h.c) for h in holders])
+        ws = snaps if isinstance(snaps, WindowSet) else WindowSet([strip_visual(s) for s in snaps])
         batch = C.c_void_p()
-        self.lib.gfbe_batch_upload_tables.restype = abi.c_i
-        self.check(self.lib.gfbe_batch_upload_tables(self.ctx, tables.h, len(holders), arr, C.byref(batch)), "batch_upload_tables")
-        for w, h in enumerate(holders):
-            h.n_feature_override = int(self.lib.gfbe_batch_feature_count(batch, w))
-        return Batch(self, batch, holders)
+        self.check(self.lib.gfbe_batch_upload_tables(self.ctx, tables.h, len(ws.holders), ws.arr, C.byref(batch)), "batch_upload_tables")
+        if ws is not snaps:       # (a prebuilt WindowSet is the caller's: its holders are left as they are)
+            for w, h in enumerate(ws.holders):
+                h.n_feature_override = int(self.lib.gfbe_batch_feature_count(batch, w))
+        return Batch(self, batch, ws.holders)
 
     def solve_batch(self, snaps, margin_flag=abi.MARGIN_NONE):
         b = self.batch_upload(snaps)
@@ -334,21 +259,18 @@ class Backend(abi.CApi):
     def host_times(self):
         """gfbe_host_times: ms of the calling thread in the last upload (packing | the rest) and the last download (waiting for the device | unpacking)."""
         out = (C.c_double * 4)()
-        self.lib.gfbe_host_times.restype = None
-        self.lib.gfbe_host_times.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         self.lib.gfbe_host_times(self.ctx, out)
         return dict(upload_pack_ms=out[0], upload_rest_ms=out[1], download_wait_ms=out[2], download_unpack_ms=out[3])
 
     # ---- multi-GPU landmark sharding: the native hook (libgfbe_rccl.so: ncclAllReduce on the solver's stream)
     def set_allreduce_native(self, fn_ptr, user_ptr, rank, world_size):
         """fn_ptr: address of a gfbe_allreduce_fn (e.g. gfbe_rccl_allreduce), user_ptr: its handle."""
-        CB = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)
-        self._cb = C.cast(fn_ptr, CB)
+        self._cb = C.cast(fn_ptr, signatures.ALLREDUCE_FN)
         self.check(self.lib.gfbe_set_allreduce(self.ctx, self._cb, C.c_void_p(user_ptr), int(rank), int(world_size)), "set_allreduce")
 
     # ---- the same through a Python callable (torch.distributed in the caller; the tests' gloo flavour)
     def set_allreduce(self, fn, rank, world_size):
-        CB = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)
+        CB = signatures.ALLREDUCE_FN
 
         def call(user, ptr, n, stream):      # (0, or 1 when the Python hook raised: the solve then returns GFBE_DEVICE_ERROR)
             try:

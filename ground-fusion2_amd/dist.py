@@ -101,20 +101,14 @@ class RcclHook:
         import os
         import torch
         import torch.distributed as dist
-        from . import backend
+        from . import abi, backend
         # One ROCm runtime per process: inside a Python process torch's bundled librccl.so.1 / libamdhip64 / libhsa-runtime64 are the
         # ones in use. Loaded here first (same SONAME as /opt/rocm's), it is the copy libgfbe_rccl.so's NEEDED entry resolves to —
         # /opt/rocm's RCCL would dlopen a second, uninitialised HSA runtime ("pfn_hsa_system_get_info failed", measured on the test box).
         tl = os.path.join(os.path.dirname(torch.__file__), "lib", "librccl.so")
         if os.path.exists(tl):
             self._rccl = C.CDLL(tl, mode=C.RTLD_GLOBAL)
-        self.lib = C.CDLL(backend._RCCL_SO)
-        self.lib.gfbe_rccl_unique_id.restype = C.c_int32
-        self.lib.gfbe_rccl_create.restype = C.c_int32
-        self.lib.gfbe_rccl_last_error.restype = C.c_int32
-        self.lib.gfbe_rccl_calls.restype = C.c_int64
-        self.lib.gfbe_rccl_bytes.restype = C.c_int64
-        self.lib.gfbe_rccl_comm_count.restype = C.c_int32
+        self.lib = abi.bind(C.CDLL(backend._RCCL_SO), "gfbe_rccl_")
         idbuf = C.create_string_buffer(128)
         if rank == 0:
             rc = self.lib.gfbe_rccl_unique_id(idbuf)

@@ -1,0 +1,188 @@
+"""The signature of every C entry point, declared once: name without its prefix -> (restype, [argtypes]).
+
+GFBE holds the exports of include/gfbe.h, RCCL those of include/gfbe_rccl.h, GFO what the CPU oracle (prefix gfo_) shares with
+the product. tests/test_abi.py checks GFBE and RCCL against the prototypes of the two headers. abi.bind(lib, prefix) applies a
+table to a loaded library; nothing else in the package assigns restype / argtypes.
+
+Spelling: opaque handles (gfbe_ctx *, gfbe_ftab *, gfbe_batch *, ...) and void * are V, their out-parameters PV; gfbe_status is
+an int32; struct pointers are pointers to the ctypes mirrors of abi.py.
+"""
+import ctypes as C
+
+from .abi import (DmapOptions, FeatureList, FtabOptions, GnssObs, GnssState, ImuPreint, Lc4Options, LdbOptions, LdbVocab, LineReducedV,
+                  LineStepped, LineWindow, Options, Prior, State, Summary, VmapOptions, VregOptions, VregSummary, WheelPreint, Window)
+
+P = C.POINTER
+i, i64, d, V, PV, STR = C.c_int32, C.c_int64, C.c_double, C.c_void_p, P(C.c_void_p), C.c_char_p
+PD, PF, PI, PI16, PI64, PU8, PU64, PC = P(d), P(C.c_float), P(i), P(C.c_int16), P(i64), P(C.c_uint8), P(C.c_uint64), P(C.c_char)
+PPW, PPLW = P(P(Window)), P(P(LineWindow))          # const gfbe_window *const *, const gfbe_line_window *const *
+ALLREDUCE_FN = C.CFUNCTYPE(i, V, V, i64, V)          # gfbe_allreduce_fn(user, device_ptr, n_doubles, hip_stream)
+
+_LC4_SOLVE = (i, [V, P(Lc4Options), i, PD, PD, PI, PU8, i, PI, PI, PD, PD, PD, PD, P(Summary)])
+
+GFBE = {
+    # context
+    "default_options": (None, [P(Options)]),
+    "options_size": (i, []),
+    "create": (i, [PV, i, P(Options)]),
+    "destroy": (None, [V]),
+    "last_error": (STR, [V]),
+    "create_note": (STR, [V]),
+    "version": (STR, []),
+    "set_stream": (i, [V, V]),
+    # a13: landmark bookkeeping
+    "feature_count": (i, [P(FeatureList)]),
+    "visual_factor_count": (i, [P(FeatureList), i]),
+    "build_visual_factors": (i, [P(FeatureList), i, PI, PI, PI, PD, PD, PD, PD, PD, PD, PD, PU8]),
+    "set_depth": (None, [P(FeatureList), PD, PD, PI]),
+    # f1: feature tables
+    "ftab_default_options": (None, [P(FtabOptions)]),
+    "ftab_create": (i, [V, i, i, P(FtabOptions), PV]),
+    "ftab_destroy": (None, [V, V]),
+    "ftab_add_frame": (i, [V, V, PI, PI, PI, PD, PD, PI, PI, PD]),
+    "ftab_remove_back_shift_depth": (i, [V, V, PD, PD]),
+    "ftab_remove_back": (i, [V, V]),
+    "ftab_remove_front": (i, [V, V, PI]),
+    "ftab_remove_outlier": (i, [V, V, PI, PI]),
+    "ftab_remove_failures": (i, [V, V]),
+    "ftab_clear_depth": (i, [V, V]),
+    "ftab_set_depth": (i, [V, V, PI, PD]),
+    "ftab_get_depth_vector": (i, [V, V, PI, PD, PI]),
+    "ftab_triangulate": (i, [V, V, PD, PD, i]),
+    "ftab_check_outliers": (i, [V, V, PD, PD, i, PI, PI, PI]),
+    "ftab_size": (i, [V, V, PI]),
+    "ftab_download": (i, [V, V, i, PI, PI, PI, PD, PD, PD, PI, PI]),
+    "batch_upload_tables": (i, [V, V, i, PPW, PV]),
+    "batch_feature_count": (i, [V, i]),
+    "slide_window_state": (None, [P(State), i]),
+    # f3: pose graph, f3b: loop-closure graph
+    "pg_eval": (i, [V, i, PD, i, PI, PD, d, d, i, PI, PD, d, PD, PD, PD, PD]),
+    "pg_solve": (i, [V, i, PD, i, PI, PD, d, d, i, PI, PD, d, i, PD, P(Summary)]),
+    "lc4_default_options": (None, [P(Lc4Options)]),
+    "lc4_eval": (i, [V, P(Lc4Options), i, PD, PD, i, PI, PI, PU8, PD, PD, PD, PD]),
+    "lc4_solve": _LC4_SOLVE,
+    "lc4_solve_long": _LC4_SOLVE,
+    # f3c: dense map
+    "dmap_default_options": (None, [P(DmapOptions)]),
+    "dmap_create": (i, [V, i, i, P(DmapOptions), PV]),
+    "dmap_destroy": (None, [V, V]),
+    "dmap_add_keyframe": (i, [V, V, PD, i, PF, PU8]),
+    "dmap_rebuild": (i, [V, V, i, PD]),
+    "dmap_filter": (i, [V, V, PU8, PI, PF, PU8]),
+    "dmap_size": (i, [V, V, PI]),
+    "dmap_download_cloud": (i, [V, V, PF, PU8, PI, PI]),
+    "dmap_download_keyframe": (i, [V, V, i, PI, PF, PU8]),
+    # f3d: loop database
+    "ldb_default_options": (None, [P(LdbOptions)]),
+    "ldb_create": (i, [V, P(LdbVocab), i, i64, P(LdbOptions), PV]),
+    "ldb_destroy": (None, [V, V]),
+    "ldb_transform": (i, [V, V, i, PU64, PI, PI, PI, PD]),
+    "ldb_add_keyframe": (i, [V, V, i, PU64, PF, PF, i, PI, PI, PI, PI, PD]),
+    "ldb_match": (i, [V, V, i, i, PU64, PU8, PI, PI, PI, PI, PF, PF]),
+    "ldb_size": (i, [V, V, PI]),
+    "ldb_download_entry": (i, [V, V, i, PI, PI, PD, PI, PU64, PF, PF]),
+    # f4: LiDAR factors, voxel map, registration, scan
+    "lio_linearize": (i, [V, i, i, PD, PD, PD, PD, PD, d, PD, PD, PD, PD, PD, PD, PD]),
+    "vmap_default_options": (None, [P(VmapOptions)]),
+    "vmap_create": (i, [V, i, P(VmapOptions), PV]),
+    "vmap_destroy": (None, [V, V]),
+    "vmap_add_points": (i, [V, V, i, PD, i]),
+    "vmap_erase_far": (i, [V, V, PD]),
+    "vmap_size": (i, [V, V, PI, PI, PI, PI]),
+    "vmap_download": (i, [V, V, PI16, PI, PD]),
+    "vmap_upload": (i, [V, V, i, PI16, PI, PD]),
+    "vmap_associate": (i, [V, V, i, i, PD, PD, PD, PD, i, PI, PI, PD, PD, PD, PD, PD, PI, PD, PI, PI]),
+    "vmap_linearize": (i, [V, V, i, d, PD, PD, PD, PD, PD, PD, PD]),
+    "vmap_localizability": (i, [V, V, PD, PI]),
+    "vreg_default_options": (None, [P(VregOptions)]),
+    "vmap_register": (i, [V, V, P(VregOptions), i, i, PD, PD, PD, PD, PD, PD, i, PD, PD, P(VregSummary)]),
+    "vmap_add_scan": (i, [V, V, i, i, PD, PD, PD, PD, i, PD]),
+    "scan_create": (i, [V, i, PV]),
+    "scan_destroy": (None, [V, V]),
+    "scan_upload": (i, [V, V, i, PD, PD, PD, PD]),
+    "scan_subsample": (i, [V, V, d]),
+    "scan_undistort": (i, [V, V, i, PD, PD]),
+    "scan_keypoints": (i, [V, V, i, PD, PD, d, PI]),
+    "scan_size": (i, [V, V, PI, PI, PI]),
+    "scan_download": (i, [V, V, i, PI, PD, PD, PD]),
+    "vmap_register_scan": (i, [V, V, P(VregOptions), i, V, PD, PD, PD, PD, i, PD, PD, P(VregSummary)]),
+    "vmap_add_scan_handle": (i, [V, V, i, V, PD, PD, i]),
+    # f2: optional in-window factors, GNSS
+    "plane_eval": (i, [V, i, PD, PD, PD, d, PD, PD, PD, PD]),
+    "anchor_eval": (i, [V, i, PD, PD, d, PD, PD, PD]),
+    "orientation_subset_plus": (None, [PD, PD, PU8, PD]),
+    "gnss_eval": (i, [V, i, P(GnssObs), PD, P(State), P(GnssState), PD, d, PD, PD, PD, PD, PD]),
+    # line landmarks and line tables
+    "line_eval": (i, [V, i, PD, PD, PD, PD, d, i, PD, PD, PD, PD, PD]),
+    "line_refine": (i, [V, i, PPLW, d, d, i, PD, PU8, P(Summary)]),
+    "line_reduce": (i, [V, i, PPLW, i, d, d, d, P(LineReducedV)]),
+    "line_step": (i, [V, i, PPLW, P(LineReducedV), d, d, d, PD, PD, PD, PD, P(LineStepped)]),
+    "ltab_create": (i, [V, i, i, PV]),
+    "ltab_destroy": (None, [V, V]),
+    "ltab_add_frame": (i, [V, V, PI, PI, PI, PD, PI]),
+    "ltab_triangulate": (i, [V, V, PD, PD]),
+    "ltab_remove_back_shift": (i, [V, V, PD, PD]),
+    "ltab_remove_back": (i, [V, V]),
+    "ltab_remove_front": (i, [V, V, PI]),
+    "ltab_refine": (i, [V, V, PD, PD, d, d, i, P(Summary)]),
+    "ltab_reduce": (i, [V, V, i, PD, PD, d, d, d, P(LineReducedV)]),
+    "ltab_keep_records": (i, [V, V, i]),
+    "ltab_step": (i, [V, V, PD, PD, d, d, PD, PD, PD, PD, P(LineStepped)]),
+    "ltab_commit": (i, [V, V, PU8]),
+    "ltab_size": (i, [V, V, PI]),
+    "ltab_line_count": (i, [V, V, PI]),
+    "ltab_download": (i, [V, V, i, PI, PI, PI, PD, PU8, PD]),
+    "ltab_upload": (i, [V, V, i, i, PI, PI, PI, PD, PU8, PD]),
+    # the window solve, batches, profiling, sharding
+    "eval_factors": (i, [V, P(Window), i, PD, PD, PD, PD, PD, PD, PD, PD]),
+    "preintegrate_imu": (i, [V, i, PI, PD, PD, PD, PD, P(ImuPreint)]),
+    "preintegrate_wheel": (i, [V, i, PI, PD, PD, PD, PD, P(WheelPreint)]),
+    "solve_window": (i, [V, P(Window), i, P(State), PD, P(Prior), P(Summary)]),
+    "solve_batch": (i, [V, i, PPW, i, P(State), P(PD), P(P(Prior)), P(Summary)]),
+    "batch_upload": (i, [V, i, PPW, PV]),
+    "batch_solve": (i, [V, V, i]),
+    "batch_download": (i, [V, V, P(State), P(PD), P(P(Prior)), P(Summary)]),
+    "batch_free": (None, [V, V]),
+    "profile_enable": (i, [V, i]),
+    "profile_count": (i, [V]),
+    "profile_get": (i, [V, i, P(STR), PI64, PD, PD]),
+    "profile_reset": (None, [V]),
+    "host_times": (None, [V, PD]),
+    "debug_timing": (i, [V, V, i, PD]),
+    "debug_vector": (i, [V, V, i, i, PD]),
+    "set_allreduce": (i, [V, ALLREDUCE_FN, V, i, i]),
+}
+
+RCCL = {            # prefix gfbe_rccl_
+    "unique_id": (i, [PC]),
+    "create": (i, [PV, PC, i, i, i]),
+    "destroy": (None, [V]),
+    "allreduce": (i, [V, V, i64, V]),
+    "last_error": (i, [V]),
+    "calls": (i64, [V]),
+    "bytes": (i64, [V]),
+    "comm_count": (i, [V]),
+}
+
+
+def _oracle(name):
+    """The oracle's flavour of a shared entry point: the compute calls take `const gfbe_options *` where the product takes its
+    context, the pre-integrations take no leading argument; the rest (the ftab / pg / eval calls ignore their void *) is the same."""
+    res, args = GFBE[name]
+    if name in ("eval_factors", "solve_window"):
+        return res, [P(Options)] + args[1:]
+    if name in ("preintegrate_imu", "preintegrate_wheel"):
+        return res, args[1:]
+    return res, args
+
+
+GFO = {name: _oracle(name) for name in GFBE}
+TABLES = {"gfbe_": GFBE, "gfo_": GFO, "gfbe_rccl_": RCCL}
+
+
+def declare(lib, prefix, table):
+    """Types every entry of `table` that `lib` exports under `prefix`; the others are skipped (a test's host-only build, the oracle)."""
+    for name, (res, args) in table.items():
+        f = getattr(lib, prefix + name, None)
+        if f is not None:
+            f.restype, f.argtypes = res, args

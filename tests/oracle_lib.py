@@ -26,11 +26,25 @@ def oracle_options():
     return o
 
 
+def _oracle_only():
+    """The entry points only the oracle has (oracle/gfo_api.h), in the spelling of the package's signature tables."""
+    s = gf.signatures
+    P, i, PD = C.POINTER, C.c_int32, s.PD
+    return {
+        "linearize": (i, [P(abi.Options), P(abi.Window), PD, PD, PD, PD, PD, PD]),
+        "reanchor": (i, [P(abi.State), P(abi.State), P(abi.State)]),
+        "marginalize": (i, [P(abi.Options), P(abi.Window), i, P(abi.Prior), PD, PD]),
+        "sqrt_info": (i, [PD, PD, i]),
+        "sym_eig": (None, [PD, i, PD, PD]),
+    }
+
+
 class Oracle(abi.CApi):
     prefix = "gfo_"
 
     def __init__(self, lib, opt=None):
         self.lib = abi.bind(lib, "gfo_")
+        gf.signatures.declare(lib, "gfo_", _oracle_only())
         self.opt = opt or oracle_options()
         self.head = C.byref(self.opt)
 
