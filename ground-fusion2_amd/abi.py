@@ -820,6 +820,62 @@ class LoopGraph:
 
 
 # ---------------------------------------------------------------------------------------------
+# loop-closure pose graph of dense_map, 6-DoF (gfbe_lc6_* of include/gfbe_lc6.h; the model is tests/lc6_np.py, there is no oracle row)
+# ---------------------------------------------------------------------------------------------
+LC6_MAX_LOOPS = 128
+LC6_PREFIX = "gfbe_lc6_"
+
+
+class Lc6Options(C.Structure):
+    _fields_ = [("struct_size", c_i), ("max_num_iterations", c_i), ("span", c_i), ("reserved", c_i), ("huber_delta", c_d), ("t_var", c_d), ("q_var", c_d)]
+
+
+def lc6_default_options(lib, **kw):
+    return options_struct(lib, LC6_PREFIX, "", Lc6Options, kw)
+
+
+class LoopGraph6:
+    """Keyframes t [n,3], q [n,4] (w, x, y, z); see include/gfbe_lc6.h. `lib` is the product library."""
+
+    def __init__(self, lib, ctx):
+        self.lib, self.ctx = bind(lib, LC6_PREFIX), ctx
+
+    def options(self, **kw):
+        return lc6_default_options(self.lib, **kw)
+
+    def eval_rc(self, t, q, edge_i, edge_j, kind, meas, opt=None):
+        t, q, meas = _f64(t).reshape(-1, 3), _f64(q).reshape(-1, 4), _f64(meas).reshape(-1, 7)
+        ei, ej, kd = _i32(edge_i), _i32(edge_j), _u8(kind)
+        E = len(ei)
+        r, J, cost = np.zeros((E, 6)), np.zeros((E, 6, 12)), np.zeros(1)
+        rc = self.lib.gfbe_lc6_eval(self.ctx, C.byref(opt) if opt is not None else None, len(t), _pd(t), _pd(q), E, _pi(ei), _pi(ej), kd.ctypes.data_as(PU8),
+                                    _pd(meas), _pd(r), _pd(J), _pd(cost))
+        return rc, dict(r=r, J=J, cost=float(cost[0]))
+
+    def eval(self, *a, **kw):
+        rc, out = self.eval_rc(*a, **kw)
+        if rc != OK:
+            raise RuntimeError("gfbe_lc6_eval failed with status %d" % rc)
+        return out
+
+    def solve_rc(self, t, q, sequence, fixed, loop_i, loop_c, loop_meas, opt=None, fill=np.nan):
+        """The outputs start as `fill`: a refused call leaves them so."""
+        t, q, lm = _f64(t).reshape(-1, 3), _f64(q).reshape(-1, 4), _f64(loop_meas).reshape(-1, 7)
+        seq, fx, li, lc = _i32(sequence), _u8(fixed), _i32(loop_i), _i32(loop_c)
+        n = len(t)
+        t_out, q_out, drift, sm = np.full((n, 3), fill), np.full((n, 4), fill), np.full(7, fill), Summary()
+        rc = self.lib.gfbe_lc6_solve(self.ctx, C.byref(opt) if opt is not None else None, n, _pd(t), _pd(q), _pi(seq), fx.ctypes.data_as(PU8), len(li), _pi(li), _pi(lc),
+                                     _pd(lm), _pd(t_out), _pd(q_out), _pd(drift), C.byref(sm))
+        return rc, dict(t=t_out, q=q_out, drift=drift, summary=summary_to_dict(sm), status=rc)
+
+    def solve(self, *a, **kw):
+        rc, out = self.solve_rc(*a, **kw)
+        if rc not in (OK, NO_CONVERGENCE):
+            raise RuntimeError("gfbe_lc6_solve failed with status %d" % rc)
+        return out
+
+
+# ---------------------------------------------------------------------------------------------
 # f4: LIO point-to-plane factors (gfbe_lio_linearize / gfo_lio_linearize)
 # ---------------------------------------------------------------------------------------------
 def lio_linearize(lib, prefix, ctx, ct, pts, normals, offsets, alpha, weights, sqrt_info, pose_begin, pose_end=None, blocks=True):

@@ -22,6 +22,7 @@ _SO = os.environ.get("GFBE_LIB") or os.path.join(_CSRC, "libgfbe.so")
 # tests/test_abi.py on CPU).
 EXPORTS = ["gfbe_" + name for name in signatures.GFBE]
 RCCL_EXPORTS = ["gfbe_rccl_" + name for name in signatures.RCCL]
+LC6_EXPORTS = ["gfbe_lc6_" + name for name in signatures.LC6]      # include/gfbe_lc6.h: symbols of the product library
 
 
 class BackendError(RuntimeError):
@@ -50,7 +51,7 @@ def build_native(force=False, verbose=False, out=None, extra_flags=None, fp_cont
     so = out or os.path.join(_CSRC, "libgfbe.so")
     srcs = sources()
     hdrs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".h", ".hpp"))]
-    hdrs.append(os.path.join(os.path.dirname(_HERE), "include", "gfbe.h"))
+    hdrs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("gfbe.h", "gfbe_lc6.h")]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = os.environ.get("GFBE_EXTRA_FLAGS", "").split() if extra_flags is None else list(extra_flags)
     cflags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=" + fp_contract, "-munsafe-fp-atomics",
@@ -108,7 +109,7 @@ class Backend(abi.CApi):
         _SO = so or globals()["_SO"]          # (so: another build of the library, e.g. DIAG_SO)
         if not os.path.exists(_SO):
             raise BackendError("HIP extension %s is missing: run __graft_entry__.build() (no CPU fallback)" % _SO)
-        self.lib = abi.bind(C.CDLL(_SO), "gfbe_")
+        self.lib = abi.bind(abi.bind(C.CDLL(_SO), "gfbe_"), abi.LC6_PREFIX)
         self.opt = options or abi.default_options()
         self.ctx = C.c_void_p()
         rc = self.lib.gfbe_create(C.byref(self.ctx), int(device), C.byref(self.opt))
@@ -202,6 +203,10 @@ class Backend(abi.CApi):
         """The dense RGB-D map of the loop-closure thread held on the device (abi.DenseMap: addKeyFrame's capped insert, updatePath's
         rebuild at the corrected poses and the radius filter, gfbe_dmap_*). options: fields of gfbe_dmap_options."""
         return self._call(abi.DenseMap, point_capacity, keyframe_capacity, **options)
+
+    def loop_graph6(self):
+        """The 6-DoF loop-closure graph (include/gfbe_lc6.h) on this context."""
+        return abi.LoopGraph6(self.lib, self.ctx)
 
     def loop_database(self, voc, keyframe_capacity=1024, descriptor_capacity=1 << 20, **options):
         """The loop database of the loop-closure thread held on the device (abi.LoopDatabase: detectLoop's vocabulary query and decision,

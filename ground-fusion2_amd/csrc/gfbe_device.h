@@ -399,6 +399,8 @@ int ctx_device(const gfbe_ctx *c);
 void ctx_set_error(gfbe_ctx *c, const char *msg);
 void *ctx_scratch(gfbe_ctx *c, size_t bytes);   // grow-only device scratch of the context (one caller at a time), nullptr on failure
 void *ctx_scratch_pinned(gfbe_ctx *c, size_t bytes);   // its pinned host mirror (grow-only, same rules)
+struct Lc4State;   // gfbe_loopgraph.h
+void launch_lc4_cap_factor(int N, const Lc4State *st, double *Sm, double *Lb, double *Dinv, double *v, double *w, int *fail, hipStream_t s);   // gfbe_loopgraph.hip
 void launch_xchg_gram(const BatchDev &d, hipStream_t s);
 void launch_xchg_cand(const BatchDev &d, hipStream_t s);
 void launch_lam_mask(const BatchDev &d, hipStream_t s);

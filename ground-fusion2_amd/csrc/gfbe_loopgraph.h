@@ -162,6 +162,16 @@ LC4_HD inline bool lc4_long_plan(int n, int n_loop, Lc4LongPlan *q) {
   return true;
 }
 
+// The Levenberg-Marquardt loop's state on the device (PgState's fields; the statements of k_pg_decide restated in k_lc4_decide). The
+// 6-DoF graph (gfbe_loopgraph6.hip) runs the same loop on the same struct: the capacitance kernels it shares read `done` from it.
+struct Lc4State {
+  double cost, radius, decrease, x_norm, model_change, step2, cand_x2, initial_cost;
+  int it, invalid, reuse, have_scale, done, termination, status, num_successful;
+  int cur, lb, cand_on, pad;
+  int accepted[16];
+  double cost_history[16];
+};
+
 // Input validation of gfbe_lc4_solve / gfbe_lc4_solve_long (the GFBE_BAD_INPUT cases that need no device): 0 = fine, else which rule
 // failed (2: more than max_loops loop edges).
 inline int lc4_check_graph_within(int n, int n_loop, int max_loops, const int32_t *loop_i, const int32_t *loop_c, int span, uint8_t *has_loop /* [n], scratch */) {

@@ -45,14 +45,6 @@ struct Lc4Dev {
   double delta, yaw_div;
 };
 
-// the Levenberg-Marquardt loop's state (PgState's fields; the statements of k_pg_decide restated in k_lc4_decide)
-struct Lc4State {
-  double cost, radius, decrease, x_norm, model_change, step2, cand_x2, initial_cost;
-  int it, invalid, reuse, have_scale, done, termination, status, num_successful;
-  int cur, lb, cand_on, pad;
-  int accepted[16];
-  double cost_history[16];
-};
 struct Lc4Sets {
   double *x[2];                                  // [n][4] yaw | t
   double *Hb[2], *Ha[2], *Hc[2], *g[2];          // [M][16][16] diagonal / (m, m - 1) / (m, m + 1) super-blocks, [rows]
@@ -753,6 +745,24 @@ struct Lc4Buffers {
   }
 };
 
+}  // namespace
+
+// The blocked factorisation of an SPD capacitance system S w = v that lies in device memory (N a multiple of 16, at most LC4_BACK_N;
+// S and v as k_lc4_cap_gather leaves them, identity padding included): per pivot step one k_lc4_cap_panel and one k_lc4_cap_trail
+// launch, then k_lc4_cap_back, 2 N / 16 launches in all. gfbe_lc4_solve_long and gfbe_lc6_solve (gfbe_loopgraph6.hip) share it; `st` is
+// the loop's state whose `done` the kernels read first.
+void gfd::launch_lc4_cap_factor(int N, const Lc4State *st, double *Sm, double *Lb, double *Dinv, double *v, double *w, int *fail, hipStream_t s) {
+  const int cap_nt = N / LC4_SB;
+  for (int p = 0; p < cap_nt; p++) {
+    const int nrem = cap_nt - 1 - p;
+    hipLaunchKernelGGL(k_lc4_cap_panel, dim3(std::max(1, (nrem + 3) / 4)), dim3(256), 0, s, N, p, st, Sm, Lb, Dinv, v, fail);
+    if (nrem) hipLaunchKernelGGL(k_lc4_cap_trail, dim3(nrem, (nrem + 3) / 4), dim3(256), 0, s, N, p, st, Sm, Lb);
+  }
+  hipLaunchKernelGGL(k_lc4_cap_back, dim3(1), dim3(LC4_BACK_THREADS), 0, s, N, st, Lb, Dinv, v, w);
+}
+
+namespace {
+
 bool options_ok(const gfbe_lc4_options *opt, gfbe_lc4_options *o) {
   gfbe_lc4_default_options(o);
   if (!opt) return true;
@@ -925,7 +935,6 @@ gfbe_status lc4_solve_body(const char *name, const char *limit_name, int max_loo
   decide(0);
   const dim3 gp(M, (plan.ntile + 3) / 4);
   const int fill_blocks = (int)std::min<size_t>(((size_t)rows * plan.ld + 255) / 256, 4096);
-  const int cap_nt = plan.cap_ld / LC4_SB;
   const int gather_blocks = (int)std::min<size_t>(((size_t)plan.cap_ld * (plan.cap_ld + 1) + 255) / 256, LC4_GATHER_BLOCKS);
   // max_it passes, enqueued blindly: every kernel of a pass returns at once when the loop has ended
   for (int pass = 0; pass < max_it; pass++) {
@@ -946,12 +955,7 @@ gfbe_status lc4_solve_body(const char *name, const char *limit_name, int max_loo
     if (L && !blocked) hipLaunchKernelGGL(k_lc4_cap, dim3(1), b256, 0, s, P, dst, Us, Z, Sm, Lb, Dinv, w, fail);
     if (blocked) {      // 2 + 2 cap_nt - 1 launches
       hipLaunchKernelGGL(k_lc4_cap_gather, dim3(gather_blocks), b256, 0, s, P, dst, Us, Z, Sm, vcap);
-      for (int p = 0; p < cap_nt; p++) {
-        const int nrem = cap_nt - 1 - p;
-        hipLaunchKernelGGL(k_lc4_cap_panel, dim3(std::max(1, (nrem + 3) / 4)), b256, 0, s, plan.cap_ld, p, dst, Sm, Lb, Dinv, vcap, fail);
-        if (nrem) hipLaunchKernelGGL(k_lc4_cap_trail, dim3(nrem, (nrem + 3) / 4), b256, 0, s, plan.cap_ld, p, dst, Sm, Lb);
-      }
-      hipLaunchKernelGGL(k_lc4_cap_back, dim3(1), dim3(LC4_BACK_THREADS), 0, s, plan.cap_ld, dst, Lb, Dinv, vcap, w);
+      launch_lc4_cap_factor(plan.cap_ld, dst, Sm, Lb, Dinv, vcap, w, fail, s);
     }
     hipLaunchKernelGGL(k_lc4_apply, gr, b256, 0, s, rows, plan.ld, 4 * L, dst, Z, w, y);
     hipLaunchKernelGGL(k_lc4_candidate, dim3((rows + L + 255) / 256), b256, 0, s, P, dst, S, Bs, As, Cs, gs, Us, y, scale, model_r, step2_i, xn2_i);

@@ -583,3 +583,37 @@ def loop_graph(n=200, n_loop=8, seed=0, laps=2, yaw0=0.0, yaw_bias=0.02, scale_e
         fixed[:n_fixed_sequence] = 1
     return dict(t=t, ypr=ypr, sequence=sequence, fixed=fixed, loop_i=loop_i.astype(np.int32), loop_c=loop_c.astype(np.int32), loop_meas=meas,
                 true_t=true_t, true_yaw=true_yaw)
+
+
+def _ypr_to_q_wxyz(ypr_deg):
+    y, p, r = np.deg2rad(ypr_deg)
+    x_, y_, z_, w_ = rot2q(rz(y) @ ry(p) @ rx(r))
+    return np.array([w_, x_, y_, z_])
+
+
+def loop_graph6(loops=None, meas_noise=1e-3, **kw):
+    """loop_graph's figure-of-eight for the 6-DoF loop-closure pose graph (gfbe_lc6_solve): the same keyframes with the full rotation as a
+    unit quaternion q [n, 4] in the order w, x, y, z (of Rz(yaw) Ry(pitch) Rx(roll)), and loop measurements [n_loop, 7] = relative t |
+    relative q (w, x, y, z): the true relative translation and yaw plus meas_noise, with the VO's pitch and roll. loops: a list of
+    (loop_c, loop_i) pairs that replaces loop_graph's choice (n_loop is then ignored).
+    Returns dict(t, q, sequence, fixed, loop_i, loop_c, loop_meas, true_t, true_yaw)."""
+    g = loop_graph(meas_noise=meas_noise, **kw)
+    loop_i, loop_c, m4 = g["loop_i"], g["loop_c"], g["loop_meas"]
+    if loops is not None:
+        rng = np.random.default_rng(20251020 + kw.get("seed", 0))
+        pairs = sorted(loops, key=lambda ci: ci[1])
+        loop_c, loop_i = np.array([c for c, _ in pairs], np.int32), np.array([i for _, i in pairs], np.int32)
+        m4 = np.zeros((len(pairs), 4))
+        for l, (c, i) in enumerate(pairs):
+            R = rz(np.deg2rad(g["true_yaw"][c])) @ ry(np.deg2rad(g["ypr"][c, 1])) @ rx(np.deg2rad(g["ypr"][c, 2]))
+            m4[l, :3] = R.T @ (g["true_t"][i] - g["true_t"][c]) + rng.normal(0, meas_noise, 3)
+            m4[l, 3] = _wrap_deg(g["true_yaw"][i] - g["true_yaw"][c]) + rng.normal(0, 10 * meas_noise)
+    q = np.array([_ypr_to_q_wxyz(v) for v in g["ypr"]])
+    meas = np.zeros((len(loop_i), 7))
+    for l, (i, c) in enumerate(zip(loop_i, loop_c)):
+        Rc = rz(np.deg2rad(g["true_yaw"][c])) @ ry(np.deg2rad(g["ypr"][c, 1])) @ rx(np.deg2rad(g["ypr"][c, 2]))
+        Ri = rz(np.deg2rad(g["true_yaw"][c] + m4[l, 3])) @ ry(np.deg2rad(g["ypr"][i, 1])) @ rx(np.deg2rad(g["ypr"][i, 2]))
+        x_, y_, z_, w_ = rot2q(Rc.T @ Ri)
+        meas[l] = [*m4[l, :3], w_, x_, y_, z_]
+    return dict(t=g["t"], q=q, sequence=g["sequence"], fixed=g["fixed"], loop_i=loop_i, loop_c=loop_c, loop_meas=meas, true_t=g["true_t"],
+                true_yaw=g["true_yaw"])
