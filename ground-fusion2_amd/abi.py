@@ -1792,3 +1792,124 @@ class LoopDatabase(Handle):
         self._check(self._f("download_entry")(self.ctx, self.h, int(e), C.byref(nb), _pi(bw), _pd(bv), C.byref(nd), d.ctypes.data_as(PU64), p.ctypes.data_as(PF),
                                               pn.ctypes.data_as(PF)), "download_entry")
         return dict(bow_word=bw, bow_value=bv, desc=d, pts=p, pts_norm=pn)
+
+
+# ---------------------------------------------------------------------------------------------
+# the optical-flow tracker (gfbe_klt_* of include/gfbe_klt.h; the model is tests/klt_np.py, there is no oracle row)
+# ---------------------------------------------------------------------------------------------
+KLT_PREFIX = "gfbe_klt_"
+KLT_WIN, KLT_MAX_LEVEL = 21, 7
+KLT_COUNTERS = ("in", "forward", "reverse", "kept")
+PI16 = C.POINTER(C.c_int16)
+
+
+class KltOptions(C.Structure):
+    _fields_ = [("struct_size", c_i), ("max_level", c_i), ("max_count", c_i), ("flow_back", c_i), ("border", c_i), ("grey_max", c_i),
+                ("prediction_min_success", c_i), ("reserved", c_i), ("epsilon", c_d), ("min_eig_threshold", c_d), ("flow_back_dist", c_d)]
+
+
+def klt_default_options(lib, **kw):
+    return options_struct(lib, KLT_PREFIX, "", KltOptions, kw)
+
+
+def _offsets(counts_or_lists):
+    off = np.zeros(len(counts_or_lists) + 1, np.int32)
+    off[1:] = np.cumsum([int(n) for n in counts_or_lists])
+    return off
+
+
+class Tracker(Handle):
+    """The tracker behind `lib` (the product library, ctx = gfbe_ctx*) for n_cameras cameras of rows x cols uint8 images and up to
+    point_capacity points a camera; see include/gfbe_klt.h. Per-camera arguments and results are lists of length n_cameras. options:
+    fields of gfbe_klt_options. The *_raw methods return the status first; the others raise."""
+
+    def __init__(self, lib, ctx, n_cameras, rows, cols, point_capacity=512, **options):
+        Handle.__init__(self, lib, KLT_PREFIX, ctx)
+        self.n_cameras, self.rows, self.cols, self.cap = int(n_cameras), int(rows), int(cols), int(point_capacity)
+        self.opt = self._options(KltOptions, options)
+        self._check(self._f("create")(self.ctx, self.n_cameras, self.rows, self.cols, self.cap, C.byref(self.opt), C.byref(self.h)), "create")
+        self.held = [0] * self.n_cameras
+
+    def push_image_raw(self, images):
+        im = _u8(images)
+        assert im.size == self.n_cameras * self.rows * self.cols, im.shape
+        return self._f("push_image")(self.ctx, self.h, im.ctypes.data_as(PU8))
+
+    def push_image(self, images):
+        """images [n_cameras, rows, cols] uint8: the current set becomes the previous one (does not wait for the device)."""
+        self._check(self.push_image_raw(images), "push_image")
+
+    def set_points_raw(self, pts, ids, track_cnt):
+        off = _offsets([len(p) for p in pts])
+        cat = lambda xs, dt, shape: np.ascontiguousarray(np.concatenate([np.asarray(x, dt).reshape(shape) for x in xs]) if len(xs) else np.zeros(shape, dt), dt)
+        p, i_, t = cat(pts, np.float32, (-1, 2)), cat(ids, np.int32, (-1,)), cat(track_cnt, np.int32, (-1,))
+        rc = self._f("set_points")(self.ctx, self.h, _pi(off), p.ctypes.data_as(PF), _pi(i_), _pi(t))
+        if rc == OK:
+            self.held = [int(n) for n in np.diff(off)]
+        return rc
+
+    def set_points(self, pts, ids, track_cnt):
+        """The points of the current image, per camera: pts [n, 2] float32, ids [n], track_cnt [n]."""
+        self._check(self.set_points_raw(pts, ids, track_cnt), "set_points")
+
+    def track_raw(self, predict=None, fill=-7):
+        """predict: None, or per camera None / [n, 2] predicted positions of the held points. Returns (status, per-camera list of
+        dict(prev_pts, cur_pts, ids, track_cnt, counters)); the flat outputs start as `fill`."""
+        n, C_ = sum(self.held), self.n_cameras
+        has = np.zeros(C_, np.uint8)
+        pp = np.zeros((n, 2), np.float32)
+        if predict is not None:
+            off = _offsets(self.held)
+            for k, p in enumerate(predict):
+                if p is not None:
+                    has[k] = 1
+                    pp[off[k]:off[k + 1]] = np.asarray(p, np.float32).reshape(-1, 2)
+        off_out = np.full(C_ + 1, fill, np.int32)
+        prev, cur = np.full((n, 2), fill, np.float32), np.full((n, 2), fill, np.float32)
+        ids, cnt, counters = np.full(n, fill, np.int32), np.full(n, fill, np.int32), np.full((C_, 4), fill, np.int32)
+        rc = self._f("track")(self.ctx, self.h, has.ctypes.data_as(PU8) if predict is not None else None, pp.ctypes.data_as(PF) if predict is not None else None,
+                              _pi(off_out), prev.ctypes.data_as(PF), cur.ctypes.data_as(PF), _pi(ids), _pi(cnt), _pi(counters))
+        raw = dict(offset=off_out, prev_pts=prev, cur_pts=cur, ids=ids, track_cnt=cnt, counters=counters)
+        if rc != OK:
+            return rc, raw
+        self.held = [int(x) for x in np.diff(off_out)]
+        out = []
+        for k in range(C_):
+            a, b = off_out[k], off_out[k + 1]
+            out.append(dict(prev_pts=prev[a:b].copy(), cur_pts=cur[a:b].copy(), ids=ids[a:b].copy(), track_cnt=cnt[a:b].copy(),
+                            counters=dict(zip(KLT_COUNTERS, counters[k].tolist()))))
+        return rc, out
+
+    def track(self, predict=None):
+        """The tracking half of trackImage for every camera (one wait); the survivors become the held points."""
+        rc, out = self.track_raw(predict)
+        self._check(rc, "track")
+        return out
+
+    def flow_raw(self, pts, direction=0, max_level=3, next_pts=None, fill=-7):
+        """calcOpticalFlowPyrLK on explicit per-camera points; next_pts: the per-camera initial flow (OPTFLOW_USE_INITIAL_FLOW) or None."""
+        off = _offsets([len(p) for p in pts])
+        n = int(off[-1])
+        cat = lambda xs: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 2) for x in xs]) if len(xs) else np.zeros((0, 2)), np.float32)
+        p = cat(pts)
+        nx = cat(next_pts) if next_pts is not None else np.full((n, 2), fill, np.float32)
+        st, err = np.full(n, fill % 256, np.uint8), np.full(n, fill, np.float32)
+        rc = self._f("flow")(self.ctx, self.h, int(direction), int(max_level), int(next_pts is not None), _pi(off), p.ctypes.data_as(PF), nx.ctypes.data_as(PF),
+                             st.ctypes.data_as(PU8), err.ctypes.data_as(PF))
+        return rc, [dict(next_pts=nx[a:b], status=st[a:b], err=err[a:b]) for a, b in zip(off[:-1], off[1:])]
+
+    def flow(self, *a, **kw):
+        rc, out = self.flow_raw(*a, **kw)
+        self._check(rc, "flow")
+        return out
+
+    def level(self, which, camera, level):
+        """dict(image [(h + 42), (w + 42)] uint8, deriv [(h + 42), (w + 42), 2] int16, w, h, n_levels) of a level of set `which`
+        (0: previous, 1: current) as the device holds it."""
+        dims = np.zeros(4, np.int32)
+        self._check(self._f("download_level")(self.ctx, self.h, int(which), int(camera), int(level), None, None, _pi(dims)), "download_level")
+        w, h = int(dims[0]), int(dims[1])
+        im, de = np.zeros((h + 2 * KLT_WIN, w + 2 * KLT_WIN), np.uint8), np.zeros((h + 2 * KLT_WIN, w + 2 * KLT_WIN, 2), np.int16)
+        self._check(self._f("download_level")(self.ctx, self.h, int(which), int(camera), int(level), im.ctypes.data_as(PU8), de.ctypes.data_as(PI16), _pi(dims)),
+                    "download_level")
+        return dict(image=im, deriv=de, w=w, h=h, n_levels=int(dims[3]))

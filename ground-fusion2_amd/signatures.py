@@ -1,8 +1,9 @@
 """The signature of every C entry point, declared once: name without its prefix -> (restype, [argtypes]).
 
 GFBE holds the exports of include/gfbe.h, RCCL those of include/gfbe_rccl.h, LC6 those of include/gfbe_lc6.h (they live in the
-product library under the prefix gfbe_lc6_), GFO what the CPU oracle (prefix gfo_) shares with the product. tests/test_abi.py
-checks GFBE and RCCL against the prototypes of their headers, tests/test_lc6_host.py LC6. abi.bind(lib, prefix) applies a
+product library under the prefix gfbe_lc6_), KLT those of include/gfbe_klt.h (prefix gfbe_klt_, likewise), GFO what the CPU oracle
+(prefix gfo_) shares with the product. tests/test_abi.py checks GFBE and RCCL against the prototypes of their headers,
+tests/test_lc6_host.py LC6, tests/test_klt_model.py KLT. abi.bind(lib, prefix) applies a
 table to a loaded library; nothing else in the package assigns restype / argtypes.
 
 Spelling: opaque handles (gfbe_ctx *, gfbe_ftab *, gfbe_batch *, ...) and void * are V, their out-parameters PV; gfbe_status is
@@ -10,7 +11,7 @@ an int32; struct pointers are pointers to the ctypes mirrors of abi.py.
 """
 import ctypes as C
 
-from .abi import (DmapOptions, FeatureList, FtabOptions, GnssObs, GnssState, ImuPreint, Lc4Options, Lc6Options, LdbOptions, LdbVocab, LineReducedV,
+from .abi import (DmapOptions, FeatureList, FtabOptions, GnssObs, GnssState, ImuPreint, KltOptions, Lc4Options, Lc6Options, LdbOptions, LdbVocab, LineReducedV,
                   LineStepped, LineWindow, Options, Prior, State, Summary, VmapOptions, VregOptions, VregSummary, WheelPreint, Window)
 
 P = C.POINTER
@@ -171,6 +172,17 @@ LC6 = {             # prefix gfbe_lc6_ (the 6-DoF loop-closure graph; symbols of
     "solve": (i, [V, P(Lc6Options), i, PD, PD, PI, PU8, i, PI, PI, PD, PD, PD, PD, P(Summary)]),
 }
 
+KLT = {             # prefix gfbe_klt_ (the optical-flow tracker; symbols of the product library)
+    "default_options": (None, [P(KltOptions)]),
+    "create": (i, [V, i, i, i, i, P(KltOptions), PV]),
+    "destroy": (None, [V, V]),
+    "push_image": (i, [V, V, PU8]),
+    "set_points": (i, [V, V, PI, PF, PI, PI]),
+    "track": (i, [V, V, PU8, PF, PI, PF, PF, PI, PI, PI]),
+    "flow": (i, [V, V, i, i, i, PI, PF, PF, PU8, PF]),
+    "download_level": (i, [V, V, i, i, i, PU8, PI16, PI]),
+}
+
 
 def _oracle(name):
     """The oracle's flavour of a shared entry point: the compute calls take `const gfbe_options *` where the product takes its
@@ -184,7 +196,7 @@ def _oracle(name):
 
 
 GFO = {name: _oracle(name) for name in GFBE}
-TABLES = {"gfbe_": GFBE, "gfo_": GFO, "gfbe_rccl_": RCCL, "gfbe_lc6_": LC6}
+TABLES = {"gfbe_": GFBE, "gfo_": GFO, "gfbe_rccl_": RCCL, "gfbe_lc6_": LC6, "gfbe_klt_": KLT}
 
 
 def declare(lib, prefix, table):

@@ -617,3 +617,35 @@ def loop_graph6(loops=None, meas_noise=1e-3, **kw):
         meas[l] = [*m4[l, :3], w_, x_, y_, z_]
     return dict(t=g["t"], q=q, sequence=g["sequence"], fixed=g["fixed"], loop_i=loop_i, loop_c=loop_c, loop_meas=meas, true_t=g["true_t"],
                 true_yaw=g["true_yaw"])
+
+
+# ---- images for the optical-flow tracker (gfbe_klt_*): a smooth texture sampled analytically, so that a planted translation is exact
+def klt_texture(rows, cols, seed=0, shift=(0.0, 0.0), n_waves=24):
+    """A [rows, cols] uint8 image: 128 + a seeded sum of sinusoids (wavelengths 7 .. 90 px, the long ones strongest) sampled at
+    (x + shift[0], y + shift[1]) and rounded. The same seed with another shift is the same scene moved by -shift: a point at p in
+    the image of shift 0 is at p - shift in this one."""
+    rng = np.random.default_rng(20260101 + int(seed))
+    lam = np.exp(rng.uniform(np.log(7.0), np.log(90.0), n_waves))
+    ang = rng.uniform(0.0, 2.0 * np.pi, n_waves)
+    pha = rng.uniform(0.0, 2.0 * np.pi, n_waves)
+    amp = lam ** 0.5 * rng.uniform(0.5, 1.0, n_waves)
+    amp *= 280.0 / amp.sum()
+    x = np.arange(cols, dtype=np.float64)[None, :] + float(shift[0])
+    y = np.arange(rows, dtype=np.float64)[:, None] + float(shift[1])
+    v = np.full((rows, cols), 128.0)
+    for k in range(n_waves):
+        f = 2.0 * np.pi / lam[k]
+        v += amp[k] * np.sin(f * (np.cos(ang[k]) * x + np.sin(ang[k]) * y) + pha[k])
+    return np.clip(np.rint(v), 0, 255).astype(np.uint8)
+
+
+def klt_image_pair(rows, cols, seed=0, shift=(2.6, -1.3)):
+    """(previous, current): the texture and the texture moved so that a point p of the previous image is at p + shift in the current one."""
+    return klt_texture(rows, cols, seed), klt_texture(rows, cols, seed, shift=(-float(shift[0]), -float(shift[1])))
+
+
+def klt_grid_points(rows, cols, n, seed=0, margin=12.0):
+    """n seeded float32 points [n, 2] (x, y) inside the image, `margin` px from its edges, on a 1/64 px lattice."""
+    rng = np.random.default_rng(20260202 + int(seed))
+    p = np.stack([rng.uniform(margin, cols - 1 - margin, n), rng.uniform(margin, rows - 1 - margin, n)], 1)
+    return (np.rint(p * 64.0) / 64.0).astype(np.float32)
