@@ -6,7 +6,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 
+#include <algorithm>
 #include <type_traits>
 #include <vector>
 
@@ -399,8 +401,51 @@ int ctx_device(const gfbe_ctx *c);
 void ctx_set_error(gfbe_ctx *c, const char *msg);
 void *ctx_scratch(gfbe_ctx *c, size_t bytes);   // grow-only device scratch of the context (one caller at a time), nullptr on failure
 void *ctx_scratch_pinned(gfbe_ctx *c, size_t bytes);   // its pinned host mirror (grow-only, same rules)
-struct Lc4State;   // gfbe_loopgraph.h
-void launch_lc4_cap_factor(int N, const Lc4State *st, double *Sm, double *Lb, double *Dinv, double *v, double *w, int *fail, hipStream_t s);   // gfbe_loopgraph.hip
+// All device buffers of one call (gfbe_pg_*, gfbe_lc4_*, gfbe_lc6_*) come out of ONE allocation, a bump allocator over a slab of the
+// context's grow-only scratch sized by a dry run: a solve makes ~30 buffers, and hipMalloc / hipFree cost more than the kernels at
+// these problem sizes. The caller carves twice, `if (pass == 0 && !buf.commit(...)) fail` between the two passes.
+struct CallBuffers {
+  enum { RESULT_BYTES = 1024 };      // the pinned result slot: a reduction's scalars, a solve's final state
+  gfbe_ctx *c;
+  char *slab = nullptr, *pin = nullptr;
+  size_t cap = 0, used = 0, pin_cap = 0, pin_used = 0;
+  bool dry = true;
+  explicit CallBuffers(gfbe_ctx *ctx) : c(ctx) {}
+  ~CallBuffers() { (void)hipStreamSynchronize(ctx_stream(c)); }
+  // end of the dry run: take what was asked for, restart. clear_bytes: the head of the slab that is cleared (SIZE_MAX: all of it).
+  // The host arrays travel through the context's PINNED scratch (a copy from pageable memory is staged by the runtime, synchronously,
+  // piece by piece); its last RESULT_BYTES are where the kernels leave what the host reads.
+  bool commit(size_t clear_bytes) {
+    cap = used; used = 0; dry = false;
+    pin_cap = pin_used; pin_used = 0;
+    slab = (char *)ctx_scratch(c, std::max<size_t>(cap, 256));
+    pin = (char *)ctx_scratch_pinned(c, pin_cap + RESULT_BYTES);
+    if (!slab || !pin) return false;
+    return hipMemsetAsync(slab, 0, std::max<size_t>(std::min(clear_bytes, cap), 256), ctx_stream(c)) == hipSuccess;
+  }
+  void *result() const { return pin + pin_cap; }
+  // pinned host memory a kernel writes (device-accessible under the same pointer): results that cross PCIe as the kernel's own stores
+  template <typename T>
+  T *pinned(size_t n) {
+    const size_t bytes = (std::max<size_t>(n, 1) * sizeof(T) + 255) & ~(size_t)255, at = pin_used;
+    pin_used += bytes;
+    return dry ? nullptr : (T *)(pin + at);
+  }
+  // device memory, filled from the host array h when there is one
+  template <typename T>
+  T *dev(size_t n, const T *h = nullptr) {
+    const size_t bytes = (std::max<size_t>(n, 1) * sizeof(T) + 255) & ~(size_t)255, at = used, pat = pin_used;
+    used += bytes;
+    if (h && n) pin_used += bytes;
+    if (dry) return nullptr;
+    T *q = (T *)(slab + at);
+    if (h && n) {
+      memcpy(pin + pat, h, n * sizeof(T));
+      (void)hipMemcpyAsync(q, pin + pat, n * sizeof(T), hipMemcpyHostToDevice, ctx_stream(c));
+    }
+    return q;
+  }
+};
 void launch_xchg_gram(const BatchDev &d, hipStream_t s);
 void launch_xchg_cand(const BatchDev &d, hipStream_t s);
 void launch_lam_mask(const BatchDev &d, hipStream_t s);

@@ -1,6 +1,6 @@
 // gfbe_loopgraph.h — the HIP-free half of the loop-closure pose graph (gfbe_loopgraph.hip): the 4-DoF factor with its analytic
-// tangent Jacobian, the Huber corrector and the plan of a solve (super-block count, padding, sweep count, panel width, scratch
-// carve). No HIP call and no HIP header: a plain C++ compiler builds it for the host (tests/lc4_host_shim.cpp).
+// tangent Jacobian, the Huber corrector, and for both graphs (the 6-DoF factor is gfbe_loopgraph6.h's) the plan of a solve (super-block count, padding, sweep
+// count, panel width, scratch carve), the graph check, the graph construction and the loop's state. No HIP call and no HIP header: a plain C++ compiler builds it for the host (tests/lc4_host_shim.cpp).
 //
 //   PoseGraph::optimize4DoF             dense_map/src/pose_graph.cpp:529-705
 //   FourDOFError, FourDOFWeightError    dense_map/src/pose_graph.h:199-288
@@ -11,6 +11,8 @@
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include <vector>
 
 #if defined(__HIPCC__)
 #define LC4_HD __host__ __device__
@@ -96,41 +98,50 @@ LC4_HD inline void lc4_sequence_meas(const double *ta, const double *ypr_a, cons
   meas[4] = ypr_a[1]; meas[5] = ypr_a[2];
 }
 
-// ---- the plan of a solve
-struct Lc4Plan {
+// ---- the plan of a solve, for both graphs: `dof` tangent dimensions per pose (4 or 6), `pose_rows` rows per pose in the padded
+// system (4, or 8 = 6 + 2 identity rows), so four consecutive poses form one super-block of 4 pose_rows rows; the panel and the
+// capacitance system are padded to the 16-wide matrix-core tile
+constexpr int LC_TILE = 16;
+struct LcPlan {
   int n, n_loop;
   int M;            // super-blocks: ceil(n / 4)
-  int rows;         // 16 M (the padding poses of the last super-block are identity rows)
+  int rows;         // 4 pose_rows M (the padding rows of a pose and the padding poses of the last super-block are identity rows)
   int pad_poses;    // 4 M - n
   int sweeps;       // ceil(log2 M) sweeps of parallel block cyclic reduction
-  int ncol;         // columns of the panel [g | U]: 1 + 4 n_loop
+  int ncol;         // columns of the panel [g | U]: 1 + dof n_loop
   int ld;           // its leading dimension: ncol rounded up to a 16-column tile
   int ntile;        // ld / 16 (tile columns that are computed)
-  int cap;          // dimension of the capacitance system, 4 n_loop
+  int cap;          // dimension of the capacitance system, dof n_loop
   int cap_ld;       // rounded up to a tile (identity padding), at least one tile
-  // offsets in doubles into the context's scratch, each a multiple of 32 doubles (256 bytes)
-  size_t off_panel[2], off_band[2][4] /* A B C Binv */, off_alpha, off_gamma, off_S, off_L, off_Dinv, off_w, off_y, total;
+  // offsets in doubles into the context's scratch, each a multiple of 32 doubles (256 bytes). off_Dinv holds the cap_ld / 16 pivot
+  // tiles' inverses (256 doubles each); off_v, the right-hand side v = U^T z_0 that the blocked factorisation carries through its
+  // forward substitution, is carved last and only when asked for (otherwise off_v == total)
+  size_t off_panel[2], off_band[2][4] /* A B C Binv */, off_alpha, off_gamma, off_S, off_L, off_Dinv, off_w, off_y, off_v, total;
 };
+
+typedef LcPlan Lc4Plan, Lc6Plan;      // (the names the two families' callers use)
 
 LC4_HD inline size_t lc4_align32(size_t v) { return (v + 31) & ~(size_t)31; }
 
-// false for n < 1 or n_loop outside [0, max_loops]
-LC4_HD inline bool lc4_plan_within(int n, int n_loop, int max_loops, Lc4Plan *p) {
+// false for n < 1 or n_loop outside [0, max_loops]. total = 2 rows ld + 10 M (4 pose_rows)^2 + 2 cap_ld^2 + 17 cap_ld + rows doubles
+// (+ cap_ld with v), rounded up to 256-byte units
+LC4_HD inline bool lc_plan(int n, int n_loop, int max_loops, int dof, int pose_rows, bool with_v, LcPlan *p) {
   if (n < 1 || n_loop < 0 || n_loop > max_loops) return false;
+  const int sb = 4 * pose_rows;
   p->n = n; p->n_loop = n_loop;
   p->M = (n + 3) / 4;
-  p->rows = LC4_SB * p->M;
+  p->rows = sb * p->M;
   p->pad_poses = 4 * p->M - n;
   int s = 0;
   while (((size_t)1 << s) < (size_t)p->M) s++;
   p->sweeps = s;
-  p->ncol = 1 + 4 * n_loop;
-  p->ntile = (p->ncol + LC4_SB - 1) / LC4_SB;
-  p->ld = LC4_SB * p->ntile;
-  p->cap = 4 * n_loop;
-  p->cap_ld = p->cap ? LC4_SB * ((p->cap + LC4_SB - 1) / LC4_SB) : LC4_SB;
+  p->ncol = 1 + dof * n_loop;
+  p->ntile = (p->ncol + LC_TILE - 1) / LC_TILE;
+  p->ld = LC_TILE * p->ntile;
+  p->cap = dof * n_loop;
+  p->cap_ld = p->cap ? LC_TILE * ((p->cap + LC_TILE - 1) / LC_TILE) : LC_TILE;
   size_t at = 0;
-  const size_t blk = lc4_align32((size_t)p->M * 256), pan = lc4_align32((size_t)p->rows * p->ld);
+  const size_t blk = lc4_align32((size_t)p->M * sb * sb), pan = lc4_align32((size_t)p->rows * p->ld);
   for (int q = 0; q < 2; q++) { p->off_panel[q] = at; at += pan; }
   for (int q = 0; q < 2; q++)
     for (int k = 0; k < 4; k++) { p->off_band[q][k] = at; at += blk; }
@@ -138,33 +149,29 @@ LC4_HD inline bool lc4_plan_within(int n, int n_loop, int max_loops, Lc4Plan *p)
   p->off_gamma = at; at += blk;
   p->off_S = at; at += lc4_align32((size_t)p->cap_ld * p->cap_ld);
   p->off_L = at; at += lc4_align32((size_t)p->cap_ld * p->cap_ld);
-  p->off_Dinv = at; at += lc4_align32((size_t)p->cap_ld * LC4_SB);
+  p->off_Dinv = at; at += lc4_align32((size_t)p->cap_ld * LC_TILE);
   p->off_w = at; at += lc4_align32((size_t)p->cap_ld);
   p->off_y = at; at += lc4_align32((size_t)p->rows);
+  p->off_v = at; if (with_v) at += lc4_align32((size_t)p->cap_ld);
   p->total = at;
   return true;
 }
-// false for n < 1 or n_loop outside [0, LC4_MAX_LOOPS]
-LC4_HD inline bool lc4_plan(int n, int n_loop, Lc4Plan *p) { return lc4_plan_within(n, n_loop, LC4_MAX_LOOPS, p); }
-
-// The plan of gfbe_lc4_solve_long: the same carve up to LC4_LONG_MAX_LOOPS loop edges (off_Dinv holds the cap_ld / 16 pivot tiles'
-// inverses, 256 doubles each), and behind it the right-hand side v = U^T z_0 of the capacitance system, which the blocked
-// factorisation carries through its forward substitution. p.total includes it: 2 rows ld + 2 cap_ld^2 + 161 rows + 18 cap_ld doubles
-// (rounded up to 256-byte units); at n = 5000 with 512 loop edges 2 panels of 20 000 x 2064 and S, L of 2048 x 2048, 0.75 GB in all.
+// gfbe_lc4_solve: up to LC4_MAX_LOOPS loop edges, the capacitance system in one workgroup (no v)
+LC4_HD inline bool lc4_plan(int n, int n_loop, LcPlan *p) { return lc_plan(n, n_loop, LC4_MAX_LOOPS, 4, 4, false, p); }
+// gfbe_lc4_solve_long: the same carve up to LC4_LONG_MAX_LOOPS loop edges with v behind it; at n = 5000 with 512 loop edges 2 panels
+// of 20 000 x 2064 and S, L of 2048 x 2048, 0.75 GB in all
 struct Lc4LongPlan {
-  Lc4Plan p;
-  size_t off_v;      // [cap_ld]
+  LcPlan p;
+  size_t off_v;      // [cap_ld], p.off_v
 };
 LC4_HD inline bool lc4_long_plan(int n, int n_loop, Lc4LongPlan *q) {
-  if (!lc4_plan_within(n, n_loop, LC4_LONG_MAX_LOOPS, &q->p)) return false;
-  q->off_v = q->p.total;
-  q->p.total += lc4_align32((size_t)q->p.cap_ld);
+  if (!lc_plan(n, n_loop, LC4_LONG_MAX_LOOPS, 4, 4, true, &q->p)) return false;
+  q->off_v = q->p.off_v;
   return true;
 }
 
-// The Levenberg-Marquardt loop's state on the device (PgState's fields; the statements of k_pg_decide restated in k_lc4_decide). The
-// 6-DoF graph (gfbe_loopgraph6.hip) runs the same loop on the same struct: the capacitance kernels it shares read `done` from it.
-struct Lc4State {
+// The Levenberg-Marquardt loop's state on the device (PgState's fields), for both graphs
+struct LcState {
   double cost, radius, decrease, x_norm, model_change, step2, cand_x2, initial_cost;
   int it, invalid, reuse, have_scale, done, termination, status, num_successful;
   int cur, lb, cand_on, pad;
@@ -172,12 +179,12 @@ struct Lc4State {
   double cost_history[16];
 };
 
-// Input validation of gfbe_lc4_solve / gfbe_lc4_solve_long (the GFBE_BAD_INPUT cases that need no device): 0 = fine, else which rule
-// failed (2: more than max_loops loop edges).
-inline int lc4_check_graph_within(int n, int n_loop, int max_loops, const int32_t *loop_i, const int32_t *loop_c, int span, uint8_t *has_loop /* [n], scratch */) {
+// Input validation of a solve (the GFBE_BAD_INPUT cases that need no device): 0 = fine, else which rule failed (2: more than
+// max_loops loop edges).
+inline int lc_check_graph(int n, int n_loop, int max_loops, int max_span, const int32_t *loop_i, const int32_t *loop_c, int span, uint8_t *has_loop /* [n], scratch */) {
   if (n < 1) return 1;
   if (n_loop < 0 || n_loop > max_loops) return 2;
-  if (span < 1 || span > LC4_MAX_SPAN) return 3;
+  if (span < 1 || span > max_span) return 3;
   for (int i = 0; i < n; i++) has_loop[i] = 0;
   for (int l = 0; l < n_loop; l++) {
     if (loop_i[l] < 0 || loop_i[l] >= n || loop_c[l] < 0 || loop_c[l] >= n) return 4;
@@ -188,10 +195,45 @@ inline int lc4_check_graph_within(int n, int n_loop, int max_loops, const int32_
   return 0;
 }
 inline int lc4_check_graph(int n, int n_loop, const int32_t *loop_i, const int32_t *loop_c, int span, uint8_t *has_loop) {
-  return lc4_check_graph_within(n, n_loop, LC4_MAX_LOOPS, loop_i, loop_c, span, has_loop);
+  return lc_check_graph(n, n_loop, LC4_MAX_LOOPS, LC4_MAX_SPAN, loop_i, loop_c, span, has_loop);
 }
 inline int lc4_long_check_graph(int n, int n_loop, const int32_t *loop_i, const int32_t *loop_c, int span, uint8_t *has_loop) {
-  return lc4_check_graph_within(n, n_loop, LC4_LONG_MAX_LOOPS, loop_i, loop_c, span, has_loop);
+  return lc_check_graph(n, n_loop, LC4_LONG_MAX_LOOPS, LC4_MAX_SPAN, loop_i, loop_c, span, has_loop);
+}
+
+// ---- the graph of a solve as the kernels read it: which sequence edges exist (with their measurements, formed from the input poses
+// by seq_meas(lo, hi, out[meas_len])), which loop edges are kept, who is in the problem, and per pose the loop edges whose shares its
+// rows take. A sequence edge joins two poses of one sequence at most `span` apart unless both are constant; a loop edge between two
+// constant poses is dropped; a pose is in the problem when a kept edge touches it and it is not constant.
+struct LcGraph {
+  std::vector<unsigned char> emask;      // [n] bit k - 1: the sequence edge (i - k, i) exists
+  std::vector<unsigned char> free_;      // [n] the pose is in the problem
+  std::vector<unsigned char> loop_on;    // [max(n_loop, 1)]
+  std::vector<double> meas;              // [n][4][meas_len]
+  std::vector<int> lp_begin, lp_entry;   // CSR per pose of 2 l + side (0: the pose is loop_c[l], 1: loop_i[l]), ascending l
+};
+template <typename SeqMeas>
+inline void lc_build_graph(int n, int span, int meas_len, const int32_t *sequence, const uint8_t *fixed, int n_loop, const int32_t *loop_i, const int32_t *loop_c,
+                           SeqMeas seq_meas, LcGraph *g) {
+  g->emask.assign(n, 0); g->free_.assign(n, 0); g->loop_on.assign(n_loop > 1 ? n_loop : 1, 0);
+  g->meas.assign((size_t)4 * meas_len * n, 0.0);
+  for (int i = 0; i < n; i++)
+    for (int k = 1; k <= span; k++)
+      if (i - k >= 0 && sequence[i] == sequence[i - k] && !(fixed[i] && fixed[i - k])) {
+        g->emask[i] |= (unsigned char)(1 << (k - 1));
+        seq_meas(i - k, i, &g->meas[((size_t)i * 4 + (k - 1)) * meas_len]);
+        g->free_[i] = g->free_[i - k] = 1;
+      }
+  g->lp_begin.assign(n + 1, 0);
+  for (int l = 0; l < n_loop; l++) {
+    g->loop_on[l] = !(fixed[loop_c[l]] && fixed[loop_i[l]]);
+    if (g->loop_on[l]) { g->free_[loop_c[l]] = g->free_[loop_i[l]] = 1; g->lp_begin[loop_c[l] + 1]++; g->lp_begin[loop_i[l] + 1]++; }
+  }
+  for (int i = 0; i < n; i++) { g->lp_begin[i + 1] += g->lp_begin[i]; if (fixed[i]) g->free_[i] = 0; }
+  g->lp_entry.assign(g->lp_begin[n] > 1 ? g->lp_begin[n] : 1, 0);
+  std::vector<int> fill(g->lp_begin.begin(), g->lp_begin.end() - 1);
+  for (int l = 0; l < n_loop; l++)
+    if (g->loop_on[l]) { g->lp_entry[fill[loop_c[l]]++] = 2 * l; g->lp_entry[fill[loop_i[l]]++] = 2 * l + 1; }
 }
 
 }  // namespace gfd

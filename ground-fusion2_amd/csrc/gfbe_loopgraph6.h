@@ -1,6 +1,6 @@
-// gfbe_loopgraph6.h — the HIP-free half of the 6-DoF loop-closure pose graph (gfbe_loopgraph6.hip): the relative-pose factor with its
+// gfbe_loopgraph6.h — the HIP-free half of the 6-DoF loop-closure pose graph (gfbe_loopgraph.hip): the relative-pose factor with its
 // analytic tangent Jacobian, the Huber corrector (gfbe_loopgraph.h's), the sequence measurement, QuaternionParameterization::Plus, the
-// graph check and the plan of a solve (super-block count, padding, sweep count, panel width, capacitance size, scratch carve). No HIP
+// finiteness check, and the 6-DoF callers of gfbe_loopgraph.h's plan and graph check. No HIP
 // call and no HIP header: a plain C++ compiler builds it for the host (tests/lc6_host_shim.cpp).
 //
 //   PoseGraph::optimize6DoF             dense_map/src/pose_graph.cpp:707-873 (options :736-745)
@@ -30,7 +30,6 @@ namespace gfd {
 constexpr int LC6_MAX_LOOPS = 128;     // GFBE_LC6_MAX_LOOPS: the capacitance system has at most 768 rows (48 tile columns)
 constexpr int LC6_SB = 32;             // a super-block: four consecutive poses x eight rows
 constexpr int LC6_PR = 8;              // rows of a pose in the padded system (6 tangent dimensions + 2 identity rows)
-constexpr int LC6_TILE = 16;           // the matrix-core tile
 constexpr int LC6_MAX_SPAN = 4;        // sequence edges reach at most four poses back: neighbours share or touch a super-block
 
 // a * b, quaternions as (w, x, y, z); out may not alias
@@ -161,68 +160,13 @@ LC6_HD void lc6_plus(const double *q, const double *d, double *out) {
   }
 }
 
-// ---- the plan of a solve
-struct Lc6Plan {
-  int n, n_loop;
-  int M;            // super-blocks: ceil(n / 4)
-  int rows;         // 32 M (the padding rows of a pose and the padding poses of the last super-block are identity rows)
-  int pad_poses;    // 4 M - n
-  int sweeps;       // ceil(log2 M) sweeps of parallel block cyclic reduction
-  int ncol;         // columns of the panel [g | U]: 1 + 6 n_loop
-  int ld;           // its leading dimension: ncol rounded up to a 16-column tile
-  int ntile;        // ld / 16 (tile columns that are computed)
-  int cap;          // dimension of the capacitance system, 6 n_loop
-  int cap_ld;       // rounded up to a tile (identity padding), at least one tile: 768 at the cap
-  // offsets in doubles into the context's scratch, each a multiple of 32 doubles (256 bytes)
-  size_t off_panel[2], off_band[2][4] /* A B C Binv */, off_alpha, off_gamma, off_S, off_L, off_Dinv, off_v, off_w, off_y, total;
-};
-
-// false for n < 1 or n_loop outside [0, LC6_MAX_LOOPS]. total = 2 rows ld + 320 rows + 2 cap_ld^2 + 18 cap_ld + rows doubles, rounded up
-// to 256-byte units: at n = 5000 with 128 loop edges 2 panels of 40 000 x 784 (0.50 GB), 0.61 GB in all.
-LC4_HD inline bool lc6_plan(int n, int n_loop, Lc6Plan *p) {
-  if (n < 1 || n_loop < 0 || n_loop > LC6_MAX_LOOPS) return false;
-  p->n = n; p->n_loop = n_loop;
-  p->M = (n + 3) / 4;
-  p->rows = LC6_SB * p->M;
-  p->pad_poses = 4 * p->M - n;
-  int s = 0;
-  while (((size_t)1 << s) < (size_t)p->M) s++;
-  p->sweeps = s;
-  p->ncol = 1 + 6 * n_loop;
-  p->ntile = (p->ncol + LC6_TILE - 1) / LC6_TILE;
-  p->ld = LC6_TILE * p->ntile;
-  p->cap = 6 * n_loop;
-  p->cap_ld = p->cap ? LC6_TILE * ((p->cap + LC6_TILE - 1) / LC6_TILE) : LC6_TILE;
-  size_t at = 0;
-  const size_t blk = lc4_align32((size_t)p->M * LC6_SB * LC6_SB), pan = lc4_align32((size_t)p->rows * p->ld);
-  for (int q = 0; q < 2; q++) { p->off_panel[q] = at; at += pan; }
-  for (int q = 0; q < 2; q++)
-    for (int k = 0; k < 4; k++) { p->off_band[q][k] = at; at += blk; }
-  p->off_alpha = at; at += blk;
-  p->off_gamma = at; at += blk;
-  p->off_S = at; at += lc4_align32((size_t)p->cap_ld * p->cap_ld);
-  p->off_L = at; at += lc4_align32((size_t)p->cap_ld * p->cap_ld);
-  p->off_Dinv = at; at += lc4_align32((size_t)p->cap_ld * LC6_TILE);
-  p->off_v = at; at += lc4_align32((size_t)p->cap_ld);
-  p->off_w = at; at += lc4_align32((size_t)p->cap_ld);
-  p->off_y = at; at += lc4_align32((size_t)p->rows);
-  p->total = at;
-  return true;
-}
+// ---- the plan of a solve (lc_plan of gfbe_loopgraph.h; the capacitance system is always factorised by the blocked kernels, which
+// carry v). At n = 5000 with 128 loop edges 2 panels of 40 000 x 784 (0.50 GB), 0.61 GB in all; cap_ld is 768 at the cap.
+LC4_HD inline bool lc6_plan(int n, int n_loop, LcPlan *p) { return lc_plan(n, n_loop, LC6_MAX_LOOPS, 6, LC6_PR, true, p); }
 
 // Input validation of gfbe_lc6_solve (the GFBE_BAD_INPUT cases that need no device): 0 = fine, else which rule failed.
 inline int lc6_check_graph(int n, int n_loop, const int32_t *loop_i, const int32_t *loop_c, int span, uint8_t *has_loop /* [n], scratch */) {
-  if (n < 1) return 1;
-  if (n_loop < 0 || n_loop > LC6_MAX_LOOPS) return 2;
-  if (span < 1 || span > LC6_MAX_SPAN) return 3;
-  for (int i = 0; i < n; i++) has_loop[i] = 0;
-  for (int l = 0; l < n_loop; l++) {
-    if (loop_i[l] < 0 || loop_i[l] >= n || loop_c[l] < 0 || loop_c[l] >= n) return 4;
-    if (loop_c[l] >= loop_i[l]) return 5;
-    if (has_loop[loop_i[l]]) return 6;
-    has_loop[loop_i[l]] = 1;
-  }
-  return 0;
+  return lc_check_graph(n, n_loop, LC6_MAX_LOOPS, LC6_MAX_SPAN, loop_i, loop_c, span, has_loop);
 }
 // every one of the `count` doubles is finite (rule 7 of gfbe_lc6_solve: a non-finite pose or measurement is refused)
 inline bool lc6_all_finite(const double *p, size_t count) {

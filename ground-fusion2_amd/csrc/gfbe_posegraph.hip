@@ -502,53 +502,6 @@ __global__ __launch_bounds__(192) void k_pg_candidate(int n, const double *Bs, c
   step2_i[i] = s2; xn2_i[i] = x2;
 }
 
-// All device buffers of one call come out of ONE allocation (a bump allocator over a slab sized by a dry run):
-// the solve makes ~30 buffers, and hipMalloc / hipFree cost more than the kernels at this problem size.
-enum { PG_RESULT_BYTES = 1024 };      // (the pinned result slot: the reductions' scalars of gfbe_pg_eval, the final PgState of gfbe_pg_solve)
-struct PgBuffers {
-  gfbe_ctx *c;
-  char *slab = nullptr, *pin = nullptr;
-  size_t cap = 0, used = 0, pin_cap = 0, pin_used = 0;
-  bool dry = true;
-  explicit PgBuffers(gfbe_ctx *ctx) : c(ctx) {}
-  ~PgBuffers() { (void)hipStreamSynchronize(ctx_stream(c)); }
-  // end of the dry run: take what was asked for from the context's grow-only scratch, restart. The host arrays travel through the
-  // context's PINNED scratch (round 6: a copy from pageable memory is staged by the runtime, synchronously, piece by piece — five of
-  // them at the head of every call); its last PG_RESULT_BYTES are where the reduction kernels leave what the host decides on.
-  bool commit() {
-    cap = used; used = 0; dry = false;
-    pin_cap = pin_used; pin_used = 0;
-    slab = (char *)ctx_scratch(c, std::max<size_t>(cap, 256));
-    pin = (char *)ctx_scratch_pinned(c, pin_cap + PG_RESULT_BYTES);
-    if (!slab || !pin) return false;
-    (void)hipMemsetAsync(slab, 0, std::max<size_t>(cap, 256), ctx_stream(c));
-    return true;
-  }
-  double *result() const { return (double *)(pin + pin_cap); }
-  // pinned host memory a kernel writes (device-accessible under the same pointer): results that cross PCIe as the kernel's own stores
-  template <typename T>
-  T *pinned(size_t n) {
-    const size_t bytes = (std::max<size_t>(n, 1) * sizeof(T) + 255) & ~(size_t)255;
-    const size_t pat = pin_used;
-    pin_used += bytes;
-    return dry ? nullptr : (T *)(pin + pat);
-  }
-  template <typename T>
-  T *dev(size_t n, const T *h = nullptr) {
-    const size_t bytes = (std::max<size_t>(n, 1) * sizeof(T) + 255) & ~(size_t)255;
-    const size_t at = used, pat = pin_used;
-    used += bytes;
-    if (h && n) pin_used += bytes;
-    if (dry) return nullptr;
-    T *q = (T *)(slab + at);
-    if (h && n) {
-      std::memcpy(pin + pat, h, n * sizeof(T));
-      (void)hipMemcpyAsync(q, pin + pat, n * sizeof(T), hipMemcpyHostToDevice, ctx_stream(c));
-    }
-    return q;
-  }
-};
-
 // Per-pose values -> up to three scalars on the device, 24 bytes back to the host instead of n doubles per sum. Two stages,
 // fixed order: workgroup b reduces the segment [b * PGR_SEG, (b + 1) * PGR_SEG) (coalesced loads, thread t takes t, t + 256, ...,
 // LDS tree), then one workgroup adds the segment partials in segment order. take_max: the first array is reduced with max
@@ -694,7 +647,7 @@ __global__ __launch_bounds__(256) void k_pg_finish(int n, const PgState *st, PgS
   for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < (size_t)7 * n; e += (size_t)gridDim.x * 256) pose_out[e] = x[e];
   if (blockIdx.x == 0 && threadIdx.x == 0) *st_out = *st;
 }
-// dscratch: 4 * PGR_MAXSEG doubles; res: the call's pinned result slot (PgBuffers::result)
+// dscratch: 4 * PGR_MAXSEG doubles; res: the call's pinned result slot (CallBuffers::result)
 void dev_reduce(gfbe_ctx *c, int n, const double *a, const double *b, const double *c3, const double *d4, bool take_max, double *dscratch, double *res,
                 double out[4], const int *fail = nullptr, int *hfail = nullptr) {
   const int nseg = (n + PGR_SEG - 1) / PGR_SEG;
@@ -740,7 +693,7 @@ gfbe_status gfbe_pg_eval(gfbe_ctx *c, int32_t n, const double *pose, int32_t n_r
   std::vector<double> fix_sorted;
   gfbe_status st = pg_prepare(c, n, n_rel, rel_i, n_fix, fix_i, fix_meas, rel_of, fix_begin, fix_sorted, fix_order);
   if (st != GFBE_OK) return st;
-  PgBuffers buf(c);
+  CallBuffers buf(c);
   PgDev P;
   double *dpose, *dcost, *dr, *dJ, *dfr, *Hd, *Ho, *g, *red3;
   for (int pass = 0; pass < 2; pass++) {
@@ -750,10 +703,10 @@ gfbe_status gfbe_pg_eval(gfbe_ctx *c, int32_t n, const double *pose, int32_t n_r
     dJ = buf.dev<double>((size_t)72 * n_rel); dfr = buf.dev<double>((size_t)3 * n_fix);
     Hd = buf.dev<double>((size_t)36 * n); Ho = buf.dev<double>((size_t)36 * n); g = buf.dev<double>((size_t)6 * n);
     red3 = buf.dev<double>(4 + 4 * (size_t)PGR_MAXSEG);
-    if (pass == 0 && !buf.commit()) { ctx_set_error(c, "gfbe_pg_eval: device allocation failed"); return GFBE_DEVICE_ERROR; }
+    if (pass == 0 && !buf.commit(SIZE_MAX)) { ctx_set_error(c, "gfbe_pg_eval: device allocation failed"); return GFBE_DEVICE_ERROR; }
   }
   hipLaunchKernelGGL(k_pg_lin, dim3((n + 127) / 128), dim3(128), 0, ctx_stream(c), P, dpose, dcost, Hd, Ho, g, dr, dJ, dfr);
-  const double total = host_sum(c, dcost, n, red3, buf.result());
+  const double total = host_sum(c, dcost, n, red3, (double *)buf.result());
   if (cost) *cost = total;
   if (rel_r && n_rel) (void)hipMemcpy(rel_r, dr, sizeof(double) * 6 * n_rel, hipMemcpyDeviceToHost);
   if (rel_J && n_rel) (void)hipMemcpy(rel_J, dJ, sizeof(double) * 72 * n_rel, hipMemcpyDeviceToHost);
@@ -775,8 +728,8 @@ gfbe_status gfbe_pg_solve(gfbe_ctx *c, int32_t n, const double *pose_in, int32_t
   if (!pose_in || !pose_out) return GFBE_BAD_INPUT;
   max_it = std::min(max_it, 15);
   hipStream_t s = ctx_stream(c);
-  static_assert(sizeof(PgState) <= PG_RESULT_BYTES, "the pinned result slot holds the loop's state");
-  PgBuffers buf(c);
+  static_assert(sizeof(PgState) <= CallBuffers::RESULT_BYTES, "the pinned result slot holds the loop's state");
+  CallBuffers buf(c);
   PgDev P;
   PgSets S;
   double *per, *per2, *per3, *per4, *scale, *diag2, *Bs, *A0, *C0, *Ab[2], *Bb[2], *Cb[2], *db[2], *Ib[2], *d0, *y, *xo;
@@ -800,7 +753,7 @@ gfbe_status gfbe_pg_solve(gfbe_ctx *c, int32_t n, const double *pose_in, int32_t
     dst = (PgState *)buf.dev<double>((sizeof(PgState) + 7) / 8);      // (cleared with the slab: cur = lb = 0, done = 0, ...)
     red3 = buf.dev<double>(4 + 4 * (size_t)PGR_MAXSEG);
     xo = buf.pinned<double>((size_t)7 * n);
-    if (pass == 0 && !buf.commit()) { ctx_set_error(c, "gfbe_pg_solve: device allocation failed"); return GFBE_DEVICE_ERROR; }
+    if (pass == 0 && !buf.commit(SIZE_MAX)) { ctx_set_error(c, "gfbe_pg_solve: device allocation failed"); return GFBE_DEVICE_ERROR; }
   }
   const dim3 g6((6 * n + 191) / 192), b6(192);
   const int nseg = (n + PGR_SEG - 1) / PGR_SEG;

@@ -41,4 +41,18 @@ int shim_lc4_check_graph(int n, int n_loop, const int32_t *loop_i, const int32_t
   return lc4_check_graph(n, n_loop, loop_i, loop_c, span, scratch);
 }
 
+// the graph of a solve as lc_build_graph makes it: emask [n], free_ [n], loop_on [max(n_loop, 1)], lp_begin [n + 1], lp_entry [2 n_loop]
+// (returns how many of its entries are used), meas [n][4][6]; poses as t [.][3], ypr [.][3]
+int shim_lc4_graph(int n, int span, const double *t, const double *ypr, const int32_t *sequence, const unsigned char *fixed, int n_loop, const int32_t *loop_i,
+                   const int32_t *loop_c, unsigned char *emask, unsigned char *free_, unsigned char *loop_on, int *lp_begin, int *lp_entry, double *meas) {
+  LcGraph g;
+  lc_build_graph(n, span, 6, sequence, fixed, n_loop, loop_i, loop_c, [&](int lo, int hi, double *m) { lc4_sequence_meas(t + 3 * lo, ypr + 3 * lo, t + 3 * hi, ypr + 3 * hi, m); }, &g);
+  for (int i = 0; i < n; i++) { emask[i] = g.emask[i]; free_[i] = g.free_[i]; }
+  for (int l = 0; l < n_loop; l++) loop_on[l] = g.loop_on[l];
+  for (int i = 0; i <= n; i++) lp_begin[i] = g.lp_begin[i];
+  for (int e = 0; e < g.lp_begin[n]; e++) lp_entry[e] = g.lp_entry[e];
+  for (size_t k = 0; k < g.meas.size(); k++) meas[k] = g.meas[k];
+  return g.lp_begin[n];
+}
+
 }  // extern "C"

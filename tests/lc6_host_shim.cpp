@@ -28,9 +28,9 @@ int shim_lc6_plan(int n, int n_loop, long long *out) {
   // every carved array ends inside the slab and starts on a 256-byte boundary, in the order of the struct
   const size_t blk = (size_t)p.M * 1024;
   const size_t offs[] = {p.off_panel[0], p.off_panel[1], p.off_band[0][0], p.off_band[0][1], p.off_band[0][2], p.off_band[0][3], p.off_band[1][0], p.off_band[1][1],
-                         p.off_band[1][2], p.off_band[1][3], p.off_alpha, p.off_gamma, p.off_S, p.off_L, p.off_Dinv, p.off_v, p.off_w, p.off_y, p.total};
+                         p.off_band[1][2], p.off_band[1][3], p.off_alpha, p.off_gamma, p.off_S, p.off_L, p.off_Dinv, p.off_w, p.off_y, p.off_v, p.total};
   const size_t need[] = {(size_t)p.rows * p.ld, (size_t)p.rows * p.ld, blk, blk, blk, blk, blk, blk, blk, blk, blk, blk, (size_t)p.cap_ld * p.cap_ld,
-                         (size_t)p.cap_ld * p.cap_ld, (size_t)p.cap_ld * 16, (size_t)p.cap_ld, (size_t)p.cap_ld, (size_t)p.rows};
+                         (size_t)p.cap_ld * p.cap_ld, (size_t)p.cap_ld * 16, (size_t)p.cap_ld, (size_t)p.rows, (size_t)p.cap_ld};
   int ok = 1;
   for (int q = 0; q < 18; q++) ok = ok && offs[q] % 32 == 0 && offs[q] + need[q] <= offs[q + 1];
   out[10] = ok;
@@ -42,5 +42,19 @@ int shim_lc6_check_graph(int n, int n_loop, const int32_t *loop_i, const int32_t
 }
 
 int shim_lc6_all_finite(const double *p, long long count) { return lc6_all_finite(p, (size_t)count) ? 1 : 0; }
+
+// the graph of a solve as lc_build_graph makes it: emask [n], free_ [n], loop_on [max(n_loop, 1)], lp_begin [n + 1], lp_entry [2 n_loop]
+// (returns how many of its entries are used), meas [n][4][7]; poses as t [.][3], q [.][4]
+int shim_lc6_graph(int n, int span, const double *t, const double *q, const int32_t *sequence, const unsigned char *fixed, int n_loop, const int32_t *loop_i,
+                   const int32_t *loop_c, unsigned char *emask, unsigned char *free_, unsigned char *loop_on, int *lp_begin, int *lp_entry, double *meas) {
+  LcGraph g;
+  lc_build_graph(n, span, 7, sequence, fixed, n_loop, loop_i, loop_c, [&](int lo, int hi, double *m) { lc6_sequence_meas(t + 3 * lo, q + 4 * lo, t + 3 * hi, q + 4 * hi, m); }, &g);
+  for (int i = 0; i < n; i++) { emask[i] = g.emask[i]; free_[i] = g.free_[i]; }
+  for (int l = 0; l < n_loop; l++) loop_on[l] = g.loop_on[l];
+  for (int i = 0; i <= n; i++) lp_begin[i] = g.lp_begin[i];
+  for (int e = 0; e < g.lp_begin[n]; e++) lp_entry[e] = g.lp_entry[e];
+  for (size_t k = 0; k < g.meas.size(); k++) meas[k] = g.meas[k];
+  return g.lp_begin[n];
+}
 
 }  // extern "C"
