@@ -1913,3 +1913,80 @@ class Tracker(Handle):
         self._check(self._f("download_level")(self.ctx, self.h, int(which), int(camera), int(level), im.ctypes.data_as(PU8), de.ctypes.data_as(PI16), _pi(dims)),
                     "download_level")
         return dict(image=im, deriv=de, w=w, h=h, n_levels=int(dims[3]))
+
+
+# ---------------------------------------------------------------------------------------------
+# corner detection behind the tracker (gfbe_det_* of include/gfbe_det.h; the model is tests/det_np.py, there is no oracle row)
+# ---------------------------------------------------------------------------------------------
+DET_PREFIX = "gfbe_det_"
+DET_MAX_POINTS = 2048
+DET_COUNTERS = ("in", "kept", "candidates", "added", "next_id", "overflow")
+
+
+class DetOptions(C.Structure):
+    _fields_ = [("struct_size", c_i), ("max_cnt", c_i), ("min_dist", c_i), ("candidate_capacity", c_i), ("sort_chunk", c_i), ("reserved", c_i), ("quality", c_d)]
+
+
+def det_default_options(lib, **kw):
+    return options_struct(lib, DET_PREFIX, "", DetOptions, kw)
+
+
+class Detector(Handle):
+    """setMask, goodFeaturesToTrack and addPoints on the current image and the held points of `tracker` (a Tracker on the same library
+    and context); see include/gfbe_det.h. Close it before the tracker. options: fields of gfbe_det_options. The *_raw methods return
+    the status first; the others raise."""
+
+    def __init__(self, lib, ctx, tracker, **options):
+        Handle.__init__(self, lib, DET_PREFIX, ctx)
+        self.tracker = tracker
+        self.opt = self._options(DetOptions, options)
+        self._check(self._f("create")(self.ctx, tracker.h, C.byref(self.opt), C.byref(self.h)), "create")
+
+    def set_next_id(self, next_id):
+        """n_id of addPoints per camera (it starts at 0)."""
+        v = _i32(next_id)
+        assert len(v) == self.tracker.n_cameras
+        self._check(self._f("set_next_id")(self.ctx, self.h, _pi(v)), "set_next_id")
+
+    def detect_raw(self, fill=-7):
+        """Returns (status, per-camera list of dict(pts, ids, track_cnt, counters)); the flat outputs start as `fill`."""
+        t = self.tracker
+        C_ = t.n_cameras
+        room = sum(max(n, self.opt.max_cnt) for n in t.held)
+        off = np.full(C_ + 1, fill, np.int32)
+        pts, ids, cnt = np.full((room, 2), fill, np.float32), np.full(room, fill, np.int32), np.full(room, fill, np.int32)
+        counters = np.full((C_, 6), fill, np.int32)
+        rc = self._f("detect")(self.ctx, self.h, _pi(off), pts.ctypes.data_as(PF), _pi(ids), _pi(cnt), _pi(counters))
+        if rc != OK:
+            return rc, dict(offset=off, pts=pts, ids=ids, track_cnt=cnt, counters=counters)
+        t.held = [int(x) for x in np.diff(off)]
+        return rc, [dict(pts=pts[a:b].copy(), ids=ids[a:b].copy(), track_cnt=cnt[a:b].copy(), counters=dict(zip(DET_COUNTERS, counters[k].tolist())))
+                    for k, (a, b) in enumerate(zip(off[:-1], off[1:]))]
+
+    def detect(self):
+        """G1, G3, G4, G5 for every camera (one wait); the result becomes the tracker's held points."""
+        rc, out = self.detect_raw()
+        self._check(rc, "detect")
+        return out
+
+    def corners_raw(self, max_corners, quality=0.01, min_dist=10, fill=-7):
+        """goodFeaturesToTrack with no mask: (status, per-camera list of dict(pts [n, 2], response [n]) in order of acceptance)."""
+        C_ = self.tracker.n_cameras
+        room = C_ * max(int(max_corners), 0)
+        off, pts, resp = np.full(C_ + 1, fill, np.int32), np.full((room, 2), fill, np.float32), np.full(room, fill, np.float32)
+        rc = self._f("corners")(self.ctx, self.h, int(max_corners), float(quality), int(min_dist), _pi(off), pts.ctypes.data_as(PF), resp.ctypes.data_as(PF))
+        if rc != OK:
+            return rc, dict(offset=off, pts=pts, response=resp)
+        return rc, [dict(pts=pts[a:b].copy(), response=resp[a:b].copy()) for a, b in zip(off[:-1], off[1:])]
+
+    def corners(self, max_corners, quality=0.01, min_dist=10):
+        rc, out = self.corners_raw(max_corners, quality, min_dist)
+        self._check(rc, "corners")
+        return out
+
+    def planes(self, camera):
+        """dict(eig [rows, cols] float32, mask [rows, cols] uint8) of a camera: the response plane and the mask of the last detect."""
+        t = self.tracker
+        eig, mask = np.zeros((t.rows, t.cols), np.float32), np.zeros((t.rows, t.cols), np.uint8)
+        self._check(self._f("download")(self.ctx, self.h, int(camera), eig.ctypes.data_as(PF), mask.ctypes.data_as(PU8)), "download")
+        return dict(eig=eig, mask=mask)

@@ -23,6 +23,7 @@
 #include "../../include/gfbe_klt.h"
 #include "gfbe_device.h"
 #include "gfbe_klt.h"
+#include "gfbe_klt_priv.h"
 #include "gfbe_tabstage.h"
 
 using namespace gfd;
@@ -30,50 +31,10 @@ using namespace gfd;
 namespace {
 constexpr int KLT_THREADS = 256, KLT_WAVES = KLT_THREADS / 64, KLT_DECIDE_THREADS = 1024, KLT_LANE_PIX = 7;
 
-// where the levels of one camera's set lie: images in bytes, derivatives in int16 elements, from the camera's base
-struct KltGeom {
-  int n_levels;
-  int w[KLT_MAX_LEVELS], h[KLT_MAX_LEVELS];
-  long long img_off[KLT_MAX_LEVELS], der_off[KLT_MAX_LEVELS];
-  long long img_cam, der_cam;
-};
-__host__ __device__ inline KltLevel klt_view(const KltGeom &g, const uint8_t *img, const int16_t *der, int cam, int l) {
-  return KltLevel{img + (size_t)cam * (size_t)g.img_cam + (size_t)g.img_off[l], der + (size_t)cam * (size_t)g.der_cam + (size_t)g.der_off[l], g.w[l], g.h[l],
-                  g.w[l] + 2 * KLT_WIN};
-}
 struct KltDevPyramid {      // klt_point's view of a camera's set
   const KltGeom &g; const uint8_t *img; const int16_t *der; int cam;
   __device__ KltLevel level(int l) const { return klt_view(g, img, der, cam, l); }
 };
-}  // namespace
-
-struct gfbe_klt : gfbe_tab_staging {
-  gfbe_ctx *owner = nullptr;
-  gfbe_klt_options opt;
-  int n_cam = 0, rows = 0, cols = 0, cap = 0;
-  KltGeom g;
-  uint8_t *img[2] = {nullptr, nullptr};       // the two sets; `cur_set` is the current image's
-  int16_t *der[2] = {nullptr, nullptr};
-  int cur_set = 0;
-  long long n_pushed = 0;
-  uint8_t *raw_d = nullptr, *raw_h = nullptr;      // the upload of a push and its pinned mirror
-  hipEvent_t ev_raw = nullptr;
-  bool raw_busy = false;
-  // the held points (two halves: a track compacts from one into the other), rows [n_cam * cap]
-  float *pts[2] = {nullptr, nullptr};
-  int *ids[2] = {nullptr, nullptr}, *cnt[2] = {nullptr, nullptr};
-  int *seg_count[2] = {nullptr, nullptr};
-  int *seg_begin = nullptr;
-  int half = 0;
-  // a track's scratch
-  float *w_cur = nullptr, *w_rev = nullptr, *w_err = nullptr;
-  uint8_t *w_st = nullptr, *w_rst = nullptr, *w_dec = nullptr;      // forward / reverse status, the decision of a point
-  int *gate = nullptr;
-  std::vector<void *> allocs;
-  std::vector<int> begin_h, count_h;          // exact host mirrors
-};
-
-namespace {
 
 // ---- R1 / R2 ----------------------------------------------------------------------------------------------------------------------
 // level 0 with its reflected border from the uploaded image

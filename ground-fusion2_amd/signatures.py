@@ -1,9 +1,10 @@
 """The signature of every C entry point, declared once: name without its prefix -> (restype, [argtypes]).
 
 GFBE holds the exports of include/gfbe.h, RCCL those of include/gfbe_rccl.h, LC6 those of include/gfbe_lc6.h (they live in the
-product library under the prefix gfbe_lc6_), KLT those of include/gfbe_klt.h (prefix gfbe_klt_, likewise), GFO what the CPU oracle
+product library under the prefix gfbe_lc6_), KLT those of include/gfbe_klt.h (prefix gfbe_klt_, likewise), DET those of
+include/gfbe_det.h (prefix gfbe_det_, likewise), GFO what the CPU oracle
 (prefix gfo_) shares with the product. tests/test_abi.py checks GFBE and RCCL against the prototypes of their headers,
-tests/test_lc6_host.py LC6, tests/test_klt_model.py KLT. abi.bind(lib, prefix) applies a
+tests/test_lc6_host.py LC6, tests/test_klt_model.py KLT, tests/test_det_model.py DET. abi.bind(lib, prefix) applies a
 table to a loaded library; nothing else in the package assigns restype / argtypes.
 
 Spelling: opaque handles (gfbe_ctx *, gfbe_ftab *, gfbe_batch *, ...) and void * are V, their out-parameters PV; gfbe_status is
@@ -11,7 +12,7 @@ an int32; struct pointers are pointers to the ctypes mirrors of abi.py.
 """
 import ctypes as C
 
-from .abi import (DmapOptions, FeatureList, FtabOptions, GnssObs, GnssState, ImuPreint, KltOptions, Lc4Options, Lc6Options, LdbOptions, LdbVocab, LineReducedV,
+from .abi import (DetOptions, DmapOptions, FeatureList, FtabOptions, GnssObs, GnssState, ImuPreint, KltOptions, Lc4Options, Lc6Options, LdbOptions, LdbVocab, LineReducedV,
                   LineStepped, LineWindow, Options, Prior, State, Summary, VmapOptions, VregOptions, VregSummary, WheelPreint, Window)
 
 P = C.POINTER
@@ -183,6 +184,16 @@ KLT = {             # prefix gfbe_klt_ (the optical-flow tracker; symbols of the
     "download_level": (i, [V, V, i, i, i, PU8, PI16, PI]),
 }
 
+DET = {             # prefix gfbe_det_ (corner detection on a tracker's images and points; symbols of the product library)
+    "default_options": (None, [P(DetOptions)]),
+    "create": (i, [V, V, P(DetOptions), PV]),
+    "destroy": (None, [V, V]),
+    "set_next_id": (i, [V, V, PI]),
+    "detect": (i, [V, V, PI, PF, PI, PI, PI]),
+    "corners": (i, [V, V, i, d, i, PI, PF, PF]),
+    "download": (i, [V, V, i, PF, PU8]),
+}
+
 
 def _oracle(name):
     """The oracle's flavour of a shared entry point: the compute calls take `const gfbe_options *` where the product takes its
@@ -196,7 +207,7 @@ def _oracle(name):
 
 
 GFO = {name: _oracle(name) for name in GFBE}
-TABLES = {"gfbe_": GFBE, "gfo_": GFO, "gfbe_rccl_": RCCL, "gfbe_lc6_": LC6, "gfbe_klt_": KLT}
+TABLES = {"gfbe_": GFBE, "gfo_": GFO, "gfbe_rccl_": RCCL, "gfbe_lc6_": LC6, "gfbe_klt_": KLT, "gfbe_det_": DET}
 
 
 def declare(lib, prefix, table):
