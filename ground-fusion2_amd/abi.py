@@ -1990,3 +1990,118 @@ class Detector(Handle):
         eig, mask = np.zeros((t.rows, t.cols), np.float32), np.zeros((t.rows, t.cols), np.uint8)
         self._check(self._f("download")(self.ctx, self.h, int(camera), eig.ctypes.data_as(PF), mask.ctypes.data_as(PU8)), "download")
         return dict(eig=eig, mask=mask)
+
+
+# ---------------------------------------------------------------------------------------------
+# the frame observations between the tracker and the feature tables (gfbe_obs_* of include/gfbe_obs.h; the model is tests/obs_np.py,
+# there is no oracle row)
+# ---------------------------------------------------------------------------------------------
+OBS_PREFIX = "gfbe_obs_"
+OBS_COUNTERS = ("points", "found", "outside", "duplicate")
+PU16 = C.POINTER(C.c_uint16)
+
+
+class ObsOptions(C.Structure):
+    _fields_ = [("struct_size", c_i), ("depth_cam", c_i), ("match_tile", c_i), ("reserved", c_i)]
+
+
+def obs_default_options(lib, **kw):
+    return options_struct(lib, OBS_PREFIX, "", ObsOptions, kw)
+
+
+class Observer(Handle):
+    """undistortedPts, ptsVelocity, the depth lookup and the id-ordered frame on the held points of `tracker` (a Tracker on the same
+    library and context), the frame's hand-over to a FeatureTables with one table a camera, removeOutliers and the prediction; see
+    include/gfbe_obs.h. cameras [n_cameras, 8] = fx fy cx cy k1 k2 p1 p2. Close it before the tracker. options: fields of
+    gfbe_obs_options. The *_raw methods return the status first; the others raise."""
+
+    def __init__(self, lib, ctx, tracker, cameras, **options):
+        Handle.__init__(self, lib, OBS_PREFIX, ctx)
+        self.tracker = tracker
+        self.opt = self._options(ObsOptions, options)
+        cams = _f64(cameras).reshape(-1, 8)
+        assert len(cams) == tracker.n_cameras, cams.shape
+        self._check(self._f("create")(self.ctx, tracker.h, _pd(cams), C.byref(self.opt), C.byref(self.h)), "create")
+
+    def reset(self):
+        """Forgets the previous lists and the times."""
+        self._check(self._f("reset")(self.ctx, self.h), "reset")
+
+    def observe_raw(self, cur_time, depth=None, outputs=True, fill=-7):
+        """cur_time [n_cameras]; depth [n_cameras, rows, cols] uint16 or None. Returns (status, per-camera list of dict(ids, obs8
+        [n, 8], counters)); outputs False: only the counters are downloaded (ids / obs8 None). The flat outputs start as `fill`."""
+        t = self.tracker
+        C_, n = t.n_cameras, sum(t.held)
+        tm = _f64(cur_time)
+        assert len(tm) == C_
+        dp = None
+        if depth is not None:
+            dp = np.ascontiguousarray(depth, np.uint16)
+            assert dp.size == C_ * t.rows * t.cols, dp.shape
+        off, counters = np.full(C_ + 1, fill, np.int32), np.full((C_, 4), fill, np.int32)
+        ids, obs8 = np.full(n, fill, np.int32), np.full((n, 8), float(fill))
+        rc = self._f("observe")(self.ctx, self.h, _pd(tm), dp.ctypes.data_as(PU16) if dp is not None else None, _pi(off) if outputs else None,
+                                _pi(ids) if outputs else None, _pd(obs8) if outputs else None, _pi(counters))
+        if rc != OK:
+            return rc, dict(offset=off, ids=ids, obs8=obs8, counters=counters)
+        if not outputs:
+            return rc, [dict(ids=None, obs8=None, counters=dict(zip(OBS_COUNTERS, counters[k].tolist()))) for k in range(C_)]
+        return rc, [dict(ids=ids[a:b].copy(), obs8=obs8[a:b].copy(), counters=dict(zip(OBS_COUNTERS, counters[k].tolist())))
+                    for k, (a, b) in enumerate(zip(off[:-1], off[1:]))]
+
+    def observe(self, cur_time, depth=None, outputs=True):
+        """O3 .. O6 for every camera (one wait); the frame stays on the device for add_frame."""
+        rc, out = self.observe_raw(cur_time, depth, outputs)
+        self._check(rc, "observe")
+        return out
+
+    def add_frame_raw(self, tables, frame_count, td, fill=-7):
+        """The held frame into `tables` (a FeatureTables of n_cameras tables). Returns (status, (keyframe, counters [W, 3], avg_parallax))."""
+        W = self.tracker.n_cameras
+        fc, tdv = _i32(frame_count), _f64(td)
+        assert len(fc) == W and len(tdv) == W
+        kf, cnt, avg = np.full(W, fill, np.int32), np.full((W, 3), fill, np.int32), np.full(W, float(fill))
+        rc = self._f("add_frame")(self.ctx, self.h, tables.h, _pi(fc), _pd(tdv), _pi(kf), _pi(cnt), _pd(avg))
+        return rc, (kf, cnt, avg)
+
+    def add_frame(self, tables, frame_count, td):
+        rc, out = self.add_frame_raw(tables, frame_count, td)
+        self._check(rc, "add_frame")
+        return out
+
+    def remove_outliers_raw(self, ids):
+        """ids: per camera the feature ids to drop from the held points."""
+        off = _offsets([len(x) for x in ids])
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(x, np.int32).ravel() for x in ids]) if len(ids) else np.zeros(0), np.int32)
+        held = np.zeros(self.tracker.n_cameras, np.int32)
+        rc = self._f("remove_outliers")(self.ctx, self.h, _pi(off), _pi(flat), _pi(held))
+        if rc == OK:
+            self.tracker.held = [int(x) for x in held]
+        return rc
+
+    def remove_outliers(self, ids):
+        self._check(self.remove_outliers_raw(ids), "remove_outliers")
+
+    def predict_raw(self, tables, frame_count, poses, tic_ric, next_pose, fill=-7):
+        """poses [W, 11, 12], tic_ric [W, 12], next_pose [W, 12] (rows [P | R]). Returns (status, (per-camera predict_pts [n, 2] in held
+        order, n_predicted [W]))."""
+        t = self.tracker
+        W, n = t.n_cameras, sum(t.held)
+        fc, p, e, nx = _i32(frame_count), _f64(poses).reshape(W, 132), _f64(tic_ric).reshape(W, 12), _f64(next_pose).reshape(W, 12)
+        assert len(fc) == W
+        pred, npred = np.full((n, 2), fill, np.float32), np.full(W, fill, np.int32)
+        rc = self._f("predict")(self.ctx, self.h, tables.h, _pi(fc), _pd(p), _pd(e), _pd(nx), pred.ctypes.data_as(PF), _pi(npred))
+        off = _offsets(t.held)
+        return rc, ([pred[a:b] for a, b in zip(off[:-1], off[1:])], npred)
+
+    def predict(self, tables, frame_count, poses, tic_ric, next_pose):
+        rc, out = self.predict_raw(tables, frame_count, poses, tic_ric, next_pose)
+        self._check(rc, "predict")
+        return out
+
+    def previous(self, camera):
+        """dict(ids [n], un_pts [n, 2]) of a camera's previous list, ascending in id."""
+        cap = self.tracker.cap
+        n, ids, un = c_i(-1), np.zeros(cap, np.int32), np.zeros((cap, 2), np.float32)
+        self._check(self._f("download_prev")(self.ctx, self.h, int(camera), C.byref(n), _pi(ids), un.ctypes.data_as(PF)), "download_prev")
+        return dict(ids=ids[:n.value].copy(), un_pts=un[:n.value].copy())

@@ -25,6 +25,7 @@ RCCL_EXPORTS = ["gfbe_rccl_" + name for name in signatures.RCCL]
 LC6_EXPORTS = ["gfbe_lc6_" + name for name in signatures.LC6]      # include/gfbe_lc6.h: symbols of the product library
 KLT_EXPORTS = ["gfbe_klt_" + name for name in signatures.KLT]      # include/gfbe_klt.h: likewise
 DET_EXPORTS = ["gfbe_det_" + name for name in signatures.DET]      # include/gfbe_det.h: likewise
+OBS_EXPORTS = ["gfbe_obs_" + name for name in signatures.OBS]      # include/gfbe_obs.h: likewise
 
 
 class BackendError(RuntimeError):
@@ -53,7 +54,7 @@ def build_native(force=False, verbose=False, out=None, extra_flags=None, fp_cont
     so = out or os.path.join(_CSRC, "libgfbe.so")
     srcs = sources()
     hdrs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".h", ".hpp"))]
-    hdrs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("gfbe.h", "gfbe_lc6.h", "gfbe_klt.h", "gfbe_det.h")]
+    hdrs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("gfbe.h", "gfbe_lc6.h", "gfbe_klt.h", "gfbe_det.h", "gfbe_obs.h")]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = os.environ.get("GFBE_EXTRA_FLAGS", "").split() if extra_flags is None else list(extra_flags)
     cflags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=" + fp_contract, "-munsafe-fp-atomics",
@@ -111,7 +112,7 @@ class Backend(abi.CApi):
         _SO = so or globals()["_SO"]          # (so: another build of the library, e.g. DIAG_SO)
         if not os.path.exists(_SO):
             raise BackendError("HIP extension %s is missing: run __graft_entry__.build() (no CPU fallback)" % _SO)
-        self.lib = abi.bind(abi.bind(abi.bind(abi.bind(C.CDLL(_SO), "gfbe_"), abi.LC6_PREFIX), abi.KLT_PREFIX), abi.DET_PREFIX)
+        self.lib = abi.bind(abi.bind(abi.bind(abi.bind(abi.bind(C.CDLL(_SO), "gfbe_"), abi.LC6_PREFIX), abi.KLT_PREFIX), abi.DET_PREFIX), abi.OBS_PREFIX)
         self.opt = options or abi.default_options()
         self.ctx = C.c_void_p()
         rc = self.lib.gfbe_create(C.byref(self.ctx), int(device), C.byref(self.opt))
@@ -219,6 +220,12 @@ class Backend(abi.CApi):
         """Corner detection on a tracker's images and held points (abi.Detector: setMask, goodFeaturesToTrack and addPoints of
         trackImage, include/gfbe_det.h). Close it before its tracker. options: fields of gfbe_det_options."""
         return abi.Detector(self.lib, self.ctx, tracker, **options)
+
+    def observer(self, tracker, cameras, **options):
+        """The frame observations on a tracker's held points (abi.Observer: undistortedPts, ptsVelocity, the depth lookup and the
+        id-ordered frame of trackImage, its hand-over to FeatureTables, removeOutliers and the prediction, include/gfbe_obs.h).
+        cameras [n_cameras, 8] = fx fy cx cy k1 k2 p1 p2. Close it before its tracker. options: fields of gfbe_obs_options."""
+        return abi.Observer(self.lib, self.ctx, tracker, cameras, **options)
 
     def loop_database(self, voc, keyframe_capacity=1024, descriptor_capacity=1 << 20, **options):
         """The loop database of the loop-closure thread held on the device (abi.LoopDatabase: detectLoop's vocabulary query and decision,

@@ -491,6 +491,11 @@ void launch_ftab_count(const FtabDev &T, int cur, int w0, int n, int *counts, hi
 // fills the landmark arrays of a batch from the tables (layout tables from the host: per window FT_BINS slot bases, NF group
 // bases, NPAIR + 1 pair_begin, lm_off); slot_of [n][F] receives the slot of landmark k (list order) for the download
 void launch_ftab_pack(const FtabDev &T, int cur, int w0, int n, const BatchDev &d, const int *layout, int *slot_of, hipStream_t s);
+// what gfbe_obs.hip (include/gfbe_obs.h) must see of the tables: the wait every table operation starts with, and gfbe_ftab_add_frame's
+// launch half for a frame that lies on the device (M rows, at most mmax a table; offset [W + 1], feature_id [M], obs8 [M][8] device pointers)
+gfbe_status ftab_ready(gfbe_ctx *c, gfbe_ftab *t);
+gfbe_status ftab_add_frame_device(gfbe_ctx *c, gfbe_ftab *t, const int32_t *frame_count, const double *td, int M, int mmax, const int *offset, const int *feature_id,
+                                  const double *obs8, int32_t *keyframe, int32_t *counters, double *avg_parallax);
 
 
 // ---- device-resident line tables (gfbe_ltab.hip) and the table-fed line refinement (k_line_refine<true>, gfbe_line.hip)

@@ -552,6 +552,22 @@ gfbe_status ft_finish(gfbe_ctx *c, gfbe_ftab *t) {
   if (t && t->ev_ops) FT_CHECK(c, hipEventRecord(t->ev_ops, ctx_stream(c)));      // (what gfbe_batch_upload_tables waits for)
   return GFBE_OK;
 }
+// the launch half of addFeatureCheckParallax: a frame that lies on the device (M rows in all, at most mmax a table) into the tables.
+// match [M] is scratch; keyframe [W], counters [3 W], avg_parallax [W] and the tables' error flags err [W] are left on the device.
+void ft_launch_add(gfbe_ctx *c, gfbe_ftab *t, int M, int mmax, const int *dfc, const int *doff, const int *dfid, const double *dobs, const double *dtd, int *dmatch,
+                   int *dkf, int *dcnt, double *davg, int *derr) {
+  const int W = t->d.W;
+  (void)hipMemsetAsync(dmatch, 0xFF, sizeof(int) * (size_t)std::max(M, 1), ctx_stream(c));     // -1: not in the list
+  hipLaunchKernelGGL(k_ftab_match, dim3((mmax + 63) / 64, (t->d.F + FT_MATCH_TILE - 1) / FT_MATCH_TILE, W), dim3(64), 0, ctx_stream(c), t->d, t->cur, doff, dfid, dmatch);
+  hipLaunchKernelGGL(k_ftab_add, dim3(W), dim3(FT_THREADS), 0, ctx_stream(c), t->d, t->cur, dfc, doff, dfid, dobs, dtd, dmatch, dkf, dcnt, davg);
+  // the tables' sticky error flags (only this operation raises them) travel back with the results: one copy, one wait
+  (void)hipMemcpyAsync(derr, t->d.err, sizeof(int) * W, hipMemcpyDeviceToDevice, ctx_stream(c));
+}
+gfbe_status ft_add_result(gfbe_ctx *c, gfbe_ftab *t, const std::vector<int> &err) {
+  for (int w = 0; w < t->d.W; w++)
+    if (err[w]) { ctx_set_error(c, err[w] & 1 ? "feature table capacity exceeded" : "a feature received more than WINDOW_SIZE + 1 observations"); return GFBE_BAD_INPUT; }
+  return ft_finish(c, t);
+}
 }  // namespace
 
 namespace gfd {
@@ -563,6 +579,30 @@ void launch_ftab_pack(const FtabDev &T, int cur, int w0, int n, const BatchDev &
   (void)hipMemsetAsync(d.lm_abi, 0xFF, sizeof(int) * (size_t)d.tot_lm, s);     // padding slots: -1
   hipLaunchKernelGGL(k_ftab_landmarks, dim3(n), dim3(FT_THREADS), 0, s, T, cur, w0, d, layout, slot_of);
   hipLaunchKernelGGL(k_ftab_landmarks_write, dim3((unsigned)(((size_t)T.F * NOBS + 255) / 256), n), dim3(256), 0, s, T, cur, w0, d, layout);
+}
+gfbe_status ftab_ready(gfbe_ctx *c, gfbe_ftab *t) { return ft_ready(c, t); }
+// gfbe_ftab_add_frame for a frame that already lies on the device (gfbe_obs_add_frame): only frame_count and td are uploaded
+gfbe_status ftab_add_frame_device(gfbe_ctx *c, gfbe_ftab *t, const int32_t *frame_count, const double *td, int M, int mmax, const int *doff, const int *dfid,
+                                  const double *dobs, int32_t *keyframe, int32_t *counters, double *avg_parallax) {
+  gfbe_status st = ft_ready(c, t);
+  if (st != GFBE_OK) return st;
+  if (!frame_count || !td) return GFBE_BAD_INPUT;
+  const int W = t->d.W;
+  std::vector<int> err(W, 0);
+  {
+    Staged s(c, t, (size_t)M * 8 + (size_t)W * 64 + 16 * 256);
+    int *dfc = s.up(frame_count, W);
+    double *dtd = s.up(td, W);
+    int *dmatch = s.up<int>(nullptr, M);
+    int *dkf = s.up<int>(nullptr, W), *dcnt = s.up<int>(nullptr, 3 * W);
+    double *davg = s.up<double>(nullptr, W);
+    int *derr = s.up<int>(nullptr, W);
+    if (!s.ok) { ctx_set_error(c, "gfbe_obs_add_frame: staging allocation failed"); return GFBE_DEVICE_ERROR; }
+    s.flush();
+    ft_launch_add(c, t, M, std::max(mmax, 1), dfc, doff, dfid, dobs, dtd, dmatch, dkf, dcnt, davg, derr);
+    s.down(keyframe, dkf, W); s.down(counters, dcnt, 3 * (size_t)W); s.down(avg_parallax, davg, W); s.down(err.data(), derr, W);
+  }
+  return ft_add_result(c, t, err);
 }
 }  // namespace gfd
 
@@ -633,6 +673,7 @@ gfbe_status gfbe_ftab_add_frame(gfbe_ctx *c, gfbe_ftab *t, const int32_t *frame_
       if (feature_id[k] <= feature_id[k - 1]) { ctx_set_error(c, "gfbe_ftab_add_frame: feature ids of a table must be strictly ascending"); return GFBE_BAD_INPUT; }
   std::vector<int> err(W, 0);
   {
+    // the upload half: the frame goes into the staging chunk
     Staged s(c, t, (size_t)M * (OW * 8 + 8) + (size_t)W * 64 + 16 * 256);
     int *dfc = s.up(frame_count, W), *doff = s.up(offset, W + 1), *dfid = s.up(feature_id, M);
     double *dobs = s.up(obs8, (size_t)M * OW), *dtd = s.up(td, W);
@@ -644,16 +685,10 @@ gfbe_status gfbe_ftab_add_frame(gfbe_ctx *c, gfbe_ftab *t, const int32_t *frame_
     s.flush();
     int mmax = 1;
     for (int w = 0; w < W; w++) mmax = std::max(mmax, offset[w + 1] - offset[w]);
-    (void)hipMemsetAsync(dmatch, 0xFF, sizeof(int) * (size_t)std::max(M, 1), ctx_stream(c));     // -1: not in the list
-    hipLaunchKernelGGL(k_ftab_match, dim3((mmax + 63) / 64, (t->d.F + FT_MATCH_TILE - 1) / FT_MATCH_TILE, W), dim3(64), 0, ctx_stream(c), t->d, t->cur, doff, dfid, dmatch);
-    hipLaunchKernelGGL(k_ftab_add, dim3(W), dim3(FT_THREADS), 0, ctx_stream(c), t->d, t->cur, dfc, doff, dfid, dobs, dtd, dmatch, dkf, dcnt, davg);
-    // the tables' sticky error flags (only this operation raises them) travel back with the results: one copy, one wait
-    (void)hipMemcpyAsync(derr, t->d.err, sizeof(int) * W, hipMemcpyDeviceToDevice, ctx_stream(c));
+    ft_launch_add(c, t, M, mmax, dfc, doff, dfid, dobs, dtd, dmatch, dkf, dcnt, davg, derr);
     s.down(keyframe, dkf, W); s.down(counters, dcnt, 3 * (size_t)W); s.down(avg_parallax, davg, W); s.down(err.data(), derr, W);
   }
-  for (int w = 0; w < W; w++)
-    if (err[w]) { ctx_set_error(c, err[w] & 1 ? "feature table capacity exceeded" : "a feature received more than WINDOW_SIZE + 1 observations"); return GFBE_BAD_INPUT; }
-  return ft_finish(c, t);
+  return ft_add_result(c, t, err);
 }
 
 static gfbe_status ft_erase(gfbe_ctx *c, gfbe_ftab *t, int op, const double *a, const double *b, const int32_t *iarg, const int32_t *off, const int32_t *ids) {

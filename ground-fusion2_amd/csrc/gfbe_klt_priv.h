@@ -1,5 +1,6 @@
 // gfbe_klt_priv.h — the tracker's handle as the library's own sources see it: gfbe_klt.hip owns it, gfbe_det.hip (the corner detector,
-// include/gfbe_det.h) borrows the current image set and the held points from it. Nothing here is part of the C ABI.
+// include/gfbe_det.h) borrows the current image set and the held points from it, gfbe_obs.hip (the frame observations,
+// include/gfbe_obs.h) the held points. Nothing here is part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 

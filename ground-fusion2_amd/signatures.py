@@ -2,9 +2,9 @@
 
 GFBE holds the exports of include/gfbe.h, RCCL those of include/gfbe_rccl.h, LC6 those of include/gfbe_lc6.h (they live in the
 product library under the prefix gfbe_lc6_), KLT those of include/gfbe_klt.h (prefix gfbe_klt_, likewise), DET those of
-include/gfbe_det.h (prefix gfbe_det_, likewise), GFO what the CPU oracle
+include/gfbe_det.h (prefix gfbe_det_, likewise), OBS those of include/gfbe_obs.h (prefix gfbe_obs_, likewise), GFO what the CPU oracle
 (prefix gfo_) shares with the product. tests/test_abi.py checks GFBE and RCCL against the prototypes of their headers,
-tests/test_lc6_host.py LC6, tests/test_klt_model.py KLT, tests/test_det_model.py DET. abi.bind(lib, prefix) applies a
+tests/test_lc6_host.py LC6, tests/test_klt_model.py KLT, tests/test_det_model.py DET, tests/test_obs_model.py OBS. abi.bind(lib, prefix) applies a
 table to a loaded library; nothing else in the package assigns restype / argtypes.
 
 Spelling: opaque handles (gfbe_ctx *, gfbe_ftab *, gfbe_batch *, ...) and void * are V, their out-parameters PV; gfbe_status is
@@ -13,11 +13,11 @@ an int32; struct pointers are pointers to the ctypes mirrors of abi.py.
 import ctypes as C
 
 from .abi import (DetOptions, DmapOptions, FeatureList, FtabOptions, GnssObs, GnssState, ImuPreint, KltOptions, Lc4Options, Lc6Options, LdbOptions, LdbVocab, LineReducedV,
-                  LineStepped, LineWindow, Options, Prior, State, Summary, VmapOptions, VregOptions, VregSummary, WheelPreint, Window)
+                  LineStepped, LineWindow, ObsOptions, Options, Prior, State, Summary, VmapOptions, VregOptions, VregSummary, WheelPreint, Window)
 
 P = C.POINTER
 i, i64, d, V, PV, STR = C.c_int32, C.c_int64, C.c_double, C.c_void_p, P(C.c_void_p), C.c_char_p
-PD, PF, PI, PI16, PI64, PU8, PU64, PC = P(d), P(C.c_float), P(i), P(C.c_int16), P(i64), P(C.c_uint8), P(C.c_uint64), P(C.c_char)
+PD, PF, PI, PI16, PI64, PU8, PU16, PU64, PC = P(d), P(C.c_float), P(i), P(C.c_int16), P(i64), P(C.c_uint8), P(C.c_uint16), P(C.c_uint64), P(C.c_char)
 PPW, PPLW = P(P(Window)), P(P(LineWindow))          # const gfbe_window *const *, const gfbe_line_window *const *
 ALLREDUCE_FN = C.CFUNCTYPE(i, V, V, i64, V)          # gfbe_allreduce_fn(user, device_ptr, n_doubles, hip_stream)
 
@@ -194,6 +194,18 @@ DET = {             # prefix gfbe_det_ (corner detection on a tracker's images a
     "download": (i, [V, V, i, PF, PU8]),
 }
 
+OBS = {             # prefix gfbe_obs_ (the frame observations between the tracker and the feature tables; symbols of the product library)
+    "default_options": (None, [P(ObsOptions)]),
+    "create": (i, [V, V, PD, P(ObsOptions), PV]),
+    "destroy": (None, [V, V]),
+    "reset": (i, [V, V]),
+    "observe": (i, [V, V, PD, PU16, PI, PI, PD, PI]),
+    "add_frame": (i, [V, V, V, PI, PD, PI, PI, PD]),
+    "remove_outliers": (i, [V, V, PI, PI, PI]),
+    "predict": (i, [V, V, V, PI, PD, PD, PD, PF, PI]),
+    "download_prev": (i, [V, V, i, PI, PI, PF]),
+}
+
 
 def _oracle(name):
     """The oracle's flavour of a shared entry point: the compute calls take `const gfbe_options *` where the product takes its
@@ -207,7 +219,7 @@ def _oracle(name):
 
 
 GFO = {name: _oracle(name) for name in GFBE}
-TABLES = {"gfbe_": GFBE, "gfo_": GFO, "gfbe_rccl_": RCCL, "gfbe_lc6_": LC6, "gfbe_klt_": KLT, "gfbe_det_": DET}
+TABLES = {"gfbe_": GFBE, "gfo_": GFO, "gfbe_rccl_": RCCL, "gfbe_lc6_": LC6, "gfbe_klt_": KLT, "gfbe_det_": DET, "gfbe_obs_": OBS}
 
 
 def declare(lib, prefix, table):
