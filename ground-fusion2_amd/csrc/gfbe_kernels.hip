@@ -1775,6 +1775,20 @@ __device__ __forceinline__ int schur_pair(int I, int J) { return I * 5 - I * (I 
 // (the groups follow the tile rows a start frame's landmarks can reach — I0 = 6 s / 16 steps at s = 3 and s = 6 — so that no group
 //  multiplies tile pairs its later start frames do not touch; work ~ tiles x pairs: {0,1} 30, {2} 15, {3,4,5} 30, {6..10} 12)
 __device__ __forceinline__ int schur_group_first(int g, int ng) { return ng >= NF ? g : (g == 0 ? 0 : (g == 1 ? 2 : (g == 2 ? 3 : 6))); }
+// LEAN (the solve pass of a throughput batch with constant extrinsic / td: compact panel, compressed rows, SCHUR_GROUPS groups) does
+// the same arithmetic in the same order as the general form — the same bits — without the work that the result does not need:
+//   * the prefetch loads the TWELVE doubles per thread and tile that the compressed rows hold (x once, not once per observing pose;
+//     no extrinsic / td rows) where the general form loads twenty: 14 + 3 instead of 22 + 3 vector loads per thread and tile
+//   * the multiply skips, four k-steps at a time, the k-steps (rows 4 k .. 4 k + 3) behind the tile's last landmark: products of exact
+//     zeros added to accumulators that are never -0.0
+// (the LDS of schur_body: one object for both of its forms, which k_schur holds side by side)
+struct SchurLds {
+  double hs[LM_TILE * HS_LD + 8];      // the panel (+ the overrun of the last row's last block)
+  double s_rt[NF][12];                 // yrows: R_f | t_f = P_f - P_0 of the linearisation point (FrameConst of the pair table)
+  int s_sf[NF + 1];
+};
+__device__ __forceinline__ SchurLds &schur_lds() { __shared__ SchurLds s; return s; }
+template <bool LEAN>
 __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, const int w, const int grp) {
   const WinDesc &ds = d.desc[w];
   WinCtl &c = d.ctl[w];
@@ -1792,7 +1806,8 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
     if (marg) for (int q = threadIdx.x; q < SCHUR_STRIDE; q += 256) d.schur_part[((size_t)w * d.schur_groups) * SCHUR_STRIDE + q] = 0.0;
     return;
   }
-  __shared__ double hs[LM_TILE * HS_LD + 8];      // (+ the overrun of the last row's last block)
+  SchurLds &lds_ = schur_lds();
+  double *const hs = lds_.hs;
   const size_t TL = d.tot_lm;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   // output tiles of this group: tile rows/cols >= I0 (of its first start frame), upper pairs, round-robin over the 4 waves
@@ -1830,7 +1845,7 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
   // were formed with another mu (WinCtl::sw_mu)
   const bool spec_sw = !marg && d.spec && c.sw_mu[c.lb] != c.mu;
   const double spec_mu = spec_sw ? c.mu : 0.0;
-  const bool hc_full = marg || d.vis_full;      // the linearisation of a batch with constant extrinsic / td everywhere leaves rows 6..12 of lm_hC alone
+  const bool hc_full = !LEAN && (marg || d.vis_full);      // the linearisation of a batch with constant extrinsic / td everywhere leaves rows 6..12 of lm_hC alone
   // What a thread holds of one landmark tile between its loads and its staging. DEEP (throughput batches): the tiles t + 1 AND t + 2
   // are in flight while the matrix cores work on tile t — with one tile ahead a light tile (a few tile pairs) took a whole
   // memory round trip under load, ~5 us, whatever its arithmetic; two register sets, two workgroups per CU instead of three.
@@ -1839,9 +1854,9 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
   // start frame of a tile from the descriptor's table (scalar loads): no dependent load before the rows can be fetched
   // (the table staged in LDS once and the trust-region scalar read once: a vector-memory load inside the tile loop would make every
   //  staging wait for ALL loads in flight — the counter is in order — and undo the two-deep prefetch)
-  __shared__ int s_sf[NF + 1];
-  __shared__ double s_rt[NF][12];       // yrows: R_f | t_f = P_f - P_0 of the linearisation point (FrameConst of the pair table)
-  const bool yrows = !marg && !d.vis_full;      // the rows are in the compressed form of k_vis<0, false> (gfbe_devutil.h)
+  int *const s_sf = lds_.s_sf;
+  double (*const s_rt)[12] = lds_.s_rt;
+  const bool yrows = LEAN || (!marg && !d.vis_full);      // the rows are in the compressed form of k_vis<0, false> (gfbe_devutil.h)
   if (t <= NF) s_sf[t] = ds.sf_tile_begin[t];
   if (yrows && t < NF * 12) s_rt[t / 12][t % 12] = d.pc[(((size_t)w * 3 + c.cur) * NPAIR + (t / 12) * (NF + 1)) * PC_DOUBLES + LM_RT_OFF + t % 12];
   const int lm_off_c = ds.lm_off;
@@ -1853,6 +1868,7 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
   // compiler's wait-count insertion can then let the younger set's loads stay in flight while the older set is staged
   // (s_waitcnt vmcnt(23+) instead of vmcnt(0)); rows a thread does not need are loaded from a neighbouring valid row and ignored.
 #define SCHUR_PV 20
+#define SCHUR_PV_LEAN 12
 #define SCHUR_PREFETCH(PV, PHLL, PSL, PINFO, PS, TILE)                                                                 \
   {                                                                                                                      \
     const int tile_ = min((TILE), te - 1);                                                                               \
@@ -1863,6 +1879,19 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
     PHLL = (marg || spec_sw ? d.lm_Hll : d.lm_sw)[slot_];      /* solve: sqrt(w_l), left by the linearisation */         \
     if (spec_sw) PSL = d.lm_sl[slot_];              /* (speculative batches: Hll and s_l, sqrt(w_l) formed at the staging) */    \
     const double *gl_ = d.lm_gl + slot_;                                                                                 \
+    /* LEAN (compressed rows, constant extrinsic / td): the twelve doubles a thread stages, nothing else — x (lm_hC rows 3..5) once, */ \
+    /* then part 0: D | g_l (+ two ignored) | d of the tenth pose, parts 1..3: d of their three poses                              */ \
+    if (LEAN) {                                                                                                          \
+      _Pragma("unroll") for (int idx_ = 0; idx_ < SCHUR_PV_LEAN; idx_++) {                                                 \
+        const int u_ = max(idx_ - 3, 0) / 3, q_ = max(idx_ - 3, 0) - 3 * u_;                                             \
+        const int kk_ = min(part - 1 + 3 * u_, klast_), k9_ = min(9, klast_);                                            \
+        const double *src_ = idx_ < 3 ? d.lm_hC + (size_t)(3 + idx_) * TL + slot_                                       \
+                           : (part == 0 ? (u_ == 0 ? d.lm_hC + (size_t)q_ * TL + slot_                                  \
+                                                   : (u_ == 1 ? gl_ : d.lm_hP + ((size_t)k9_ * 6 + q_) * TL + slot_))   \
+                                        : d.lm_hP + ((size_t)kk_ * 6 + q_) * TL + slot_);                                \
+        PV[idx_] = *src_;                                                                                                \
+      }                                                                                                                  \
+    } else                                                                                                               \
     _Pragma("unroll") for (int idx_ = 0; idx_ < SCHUR_PV; idx_++) {                                                      \
       const int u_ = idx_ / 6, q_ = idx_ - 6 * u_;                                                                       \
       const int kk_ = min(part - 1 + 3 * u_, klast_), k9_ = min(9, klast_);                                              \
@@ -1888,6 +1917,16 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
         _Pragma("unroll") for (int kk = 0; kk < LM_TILE / 8; kk++) ACC = __builtin_amdgcn_mfma_f64_16x16x4f64(va[kk], vb[kk], ACC, 0, 0, 0); \
       }                                                                                             \
     }
+  // (LEAN) the same chain of sixteen k-steps per pair, four at a time; a chunk whose rows lie behind the tile's last landmark is skipped
+#define SCHUR_LEAN_SLOT(Q, ACC)                                                                                        \
+    if (pI[Q] >= 0 && pJ[Q] <= jl) {                                                                                     \
+      const double *pa = hs + 16 * pI[Q] + lr + lk * HS_LD, *pb = hs + 16 * pJ[Q] + lr + lk * HS_LD;                     \
+      _Pragma("unroll") for (int c_ = 0; c_ < 4; c_++) if (4 * c_ < nk) {                                                \
+        double va[4], vb[4];                                                                                             \
+        _Pragma("unroll") for (int kk = 0; kk < 4; kk++) { va[kk] = pa[4 * (4 * c_ + kk) * HS_LD]; vb[kk] = pb[4 * (4 * c_ + kk) * HS_LD]; } \
+        _Pragma("unroll") for (int kk = 0; kk < 4; kk++) ACC = __builtin_amdgcn_mfma_f64_16x16x4f64(va[kk], vb[kk], ACC, 0, 0, 0); \
+      }                                                                                                                  \
+    }
   // one tile: stage the register set into the LDS panel, refill the set with tile REFILL (if < te), multiply.
   // The tracks of a tile are sorted longest first (pm0: its first landmark, lane 0 of every wave): its rows are zero beyond the pose
   // columns of the first track's last observer, jl = the last 16-column block they reach (absolute layout: block 4 holds the
@@ -1899,6 +1938,9 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
     const int ps = PS, pm0 = __builtin_amdgcn_readfirstlane(PINFO);                                                      \
     const int jl = __builtin_amdgcn_readfirstlane(compact ? (d.vis_full ? nside - 1 : (6 * (ps - s_first + ((pm0 >> 8) & 0xff) + 1)) >> 4) \
                                                           : (6 * (ps + ((pm0 >> 8) & 0xff) + 1) - 1) >> 4);              \
+    /* (LEAN) the k-steps up to the tile's last valid landmark (lane = landmark in every wave): the rows behind it are zeros */ \
+    const unsigned long long vmask_ = LEAN ? __builtin_amdgcn_ballot_w64((PINFO >> 24) & 1) : ~0ull;                       \
+    const int nk = vmask_ ? (64 - __builtin_clzll(vmask_) + 3) >> 2 : 0;                                                 \
     {                                                                                                                    \
       const int s = ps, kmax = NF - 1 - s;          /* this tile's start frame */                                        \
       const bool valid = (PINFO >> 24) & 1;                                                                              \
@@ -1915,12 +1957,12 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
       if (part == 0) {                                                                                                   \
         for (int q = compact ? 6 * s_first : 16 * I0; q < 6 * s; q++) row[q] = 0.0;                                      \
         double blk0[6];                                                                                                  \
-        if (yrows) lm_row_block(s_rt[s], PV, PV + 3, true, blk0);                     /* [ D ; Ri^T ((x - t_i) x D) ] */ \
+        if (yrows) lm_row_block(s_rt[s], PV + (LEAN ? 3 : 0), PV + (LEAN ? 0 : 3), true, blk0);                     /* [ D ; Ri^T ((x - t_i) x D) ] */ \
         else { _Pragma("unroll") for (int q = 0; q < 6; q++) blk0[q] = PV[q]; }                                          \
         _Pragma("unroll") for (int q = 0; q < 6; q++) { row[6 * s + q] = sw * blk0[q]; row[T_EX + q] = hc_full ? sw * PV[6 + q] : 0.0; } \
         row[T_TD] = hc_full ? sw * PV[12] : 0.0;                                                                         \
         if (compact) {                                                                                                   \
-          row[-coff] = sw * PV[HC];                                     /* column 0: the gradient */                     \
+          row[-coff] = sw * PV[LEAN ? 6 : HC];                            /* column 0: the gradient */                     \
           for (int q = NV + coff; q < min(16 * nside, (int)HS_LD); q++) row[q - coff] = 0.0;     /* behind td, up to the last block any tile of the group multiplies */ \
         } else {                                                                                                         \
           row[NV] = sw * PV[HC];                                                                                         \
@@ -1929,7 +1971,7 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
         if (9 < kmax) {                                                  /* the tenth observing pose (start frame 0) */  \
           const bool written = valid && 9 < m;                                                                           \
           double blk9[6];                                                                                                \
-          if (yrows) lm_row_block(s_rt[min(s + 10, NF - 1)], PV + HC + 1, PV + 3, false, blk9);                          \
+          if (yrows) lm_row_block(s_rt[min(s + 10, NF - 1)], PV + (LEAN ? 9 : HC + 1), PV + (LEAN ? 0 : 3), false, blk9);                       \
           else { _Pragma("unroll") for (int q = 0; q < 6; q++) blk9[q] = PV[HC + 1 + q]; }                               \
           _Pragma("unroll") for (int q = 0; q < 6; q++) row[6 * (s + 10) + q] = written ? sw * blk9[q] : 0.0;            \
         }                                                                                                                \
@@ -1940,7 +1982,7 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
             /* (rows from the landmark's track length on were never written — lm_hP is not cleared at upload: zeros, not products) */ \
             const bool written = valid && k < m;                                                                         \
             double blkk[6];                                                                                              \
-            if (yrows) lm_row_block(s_rt[s + 1 + k], PV + u * 6, PV + u * 6 + 3, false, blkk);    /* [ -d ; Rj^T (d x (x - t_j)) ] */ \
+            if (yrows) lm_row_block(s_rt[s + 1 + k], PV + (LEAN ? 3 + 3 * u : 6 * u), PV + (LEAN ? 0 : 6 * u + 3), false, blkk);    /* [ -d ; Rj^T ... ] */ \
             else { _Pragma("unroll") for (int q = 0; q < 6; q++) blkk[q] = PV[u * 6 + q]; }                              \
             _Pragma("unroll") for (int q = 0; q < 6; q++) row[6 * (s + 1 + k) + q] = written ? sw * blkk[q] : 0.0;       \
           }                                                                                                              \
@@ -1950,10 +1992,14 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
     __syncthreads();                                                                                                     \
     if (stamp_wg && (TILE) == tfirst) stamp[2] = (double)wall_clock64();                                                 \
     SCHUR_PREFETCH(PV, PHLL, PSL, PINFO, PS, (REFILL))         /* (past the last tile: a repeat of it, never staged) */ \
-    SCHUR_SLOT(0, acc0)                                                                                                  \
-    SCHUR_SLOT(1, acc1)                                                                                                  \
-    SCHUR_SLOT(2, acc2)                                                                                                  \
-    SCHUR_SLOT(3, acc3)                                                                                                  \
+    if (LEAN) {                                                                                                         \
+      SCHUR_LEAN_SLOT(0, acc0) SCHUR_LEAN_SLOT(1, acc1) SCHUR_LEAN_SLOT(2, acc2) SCHUR_LEAN_SLOT(3, acc3)               \
+    } else {                                                                                                             \
+      SCHUR_SLOT(0, acc0)                                                                                                \
+      SCHUR_SLOT(1, acc1)                                                                                                \
+      SCHUR_SLOT(2, acc2)                                                                                                \
+      SCHUR_SLOT(3, acc3)                                                                                                \
+    }                                                                                                                    \
   }
   double preA[SCHUR_PV], aHll = 0.0, aSl = 0.0;
   int aInfo = 0, aS = 0;
@@ -1964,8 +2010,10 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
   for (int tile = tfirst; tile < te; tile += tstep) SCHUR_RUN_TILE(preA, aHll, aSl, aInfo, aS, tile, tile + tstep)
 #undef SCHUR_RUN_TILE
 #undef SCHUR_SLOT
+#undef SCHUR_LEAN_SLOT
 #undef SCHUR_PREFETCH
 #undef SCHUR_PV
+#undef SCHUR_PV_LEAN
   if (stamp_wg) { stamp[3] = (double)wall_clock64(); stamp[4] = (double)(te - tb); stamp[6] = (double)clock64(); }
   double *out = d.schur_part + ((size_t)w * d.schur_groups + grp) * SCHUR_STRIDE;
 #define SCHUR_OUT(Q, ACC)                                                         \
@@ -1984,7 +2032,9 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
 #endif
 __global__ __launch_bounds__(256, GFBE_SCHUR_WGS) void k_schur(BatchDev d0, int marg) {
   const BatchDev d = marg ? d0 : lin_view(d0, d0.ctl[blockIdx.x].lb);
-  schur_body(d, marg, blockIdx.x, blockIdx.y);   // group-major dispatch: the heavy first group of every window first
+  // group-major dispatch: the heavy first group of every window first
+  if (!marg && d.schur_groups == SCHUR_GROUPS && !d.vis_full) schur_body<true>(d, 0, blockIdx.x, blockIdx.y);
+  else schur_body<false>(d, marg, blockIdx.x, blockIdx.y);
 }
 // =============================================================================================
 // k_linschur (round 6): the linearisation of the visual factors AND the landmark elimination of
@@ -2288,7 +2338,7 @@ __global__ __launch_bounds__(256, GFBE_LINSCHUR_WGS) void k_linschur(BatchDev d0
 __global__ __launch_bounds__(VP_STRIDE) void k_pairsum_schur_marg(BatchDev d) {
   const int w = blockIdx.x, y = blockIdx.y;
   if (y < NF - 1) pairsum_body(d, 1, w, y);
-  else if (threadIdx.x < 256) schur_body(d, 1, w, 0);
+  else if (threadIdx.x < 256) schur_body<false>(d, 1, w, 0);
 }
 
 // =============================================================================================
@@ -2935,7 +2985,7 @@ __global__ __launch_bounds__(VB_GROUP) void k_schur_visblock_small(BatchDev d0) 
   const int w = blockIdx.x, y = blockIdx.y;
   const BatchDev d = lin_view(d0, d0.ctl[w].lb);
   if (y < d.schur_groups) {
-    if (threadIdx.x < 256) schur_body(d, 0, w, y);
+    if (threadIdx.x < 256) schur_body<false>(d, 0, w, y);
   } else {
     __shared__ double V[NV * V_LD];
     const int v = y - d.schur_groups;
