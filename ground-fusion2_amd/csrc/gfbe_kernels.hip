@@ -832,7 +832,9 @@ __global__ __launch_bounds__(LM_TILE, (MODE == 0 && !FULL) ? GFBE_KVIS_WAVES : 2
 // under load, then the LDS staging and its barrier — in front of 5.3 observation steps of ~2.4 us: a third of a wave's life. Here the pair
 // records of the start frame are staged once per wave, and a tile's landmark data (slot info, first observation, inverse depth, and what
 // the candidate's head needs) is requested while the tile before it is evaluated. Per tile the arithmetic is vis_body<0, false, 1, SPEC>'s,
-// operation for operation, in its order: every output bit for bit (the whole suite runs through it).
+// operation for operation, in its order: every output bit for bit (the whole suite runs through it) — except that the 7 x 7 sum of an
+// observation step stops at the last group of sixteen panel rows in which a lane has a factor: the rows behind are zeros, and a product
+// of zeros added to a sum that started at +0.0 leaves its bits (profiles/schur_steps_ab.txt).
 // Grid: (window, start frame x sub-chunk): blockIdx.y = s * nsub + sub takes the tiles [begin(s) + VIS_CHUNK sub, + VIS_CHUNK) of start
 // frame s (start frame 0 — the longest tracks — is dispatched first).
 // =============================================================================================
@@ -936,6 +938,10 @@ __global__ __launch_bounds__(LM_TILE, GFBE_KVIS_WAVES) void k_vis_chunk(BatchDev
     xr[7] = 0.0; xr[15] = 0.0;
     for (int k = 0; k < mmax; k++) {
       double r[2], Jl[2], hp[3];
+      // the panel rows this step multiplies, in groups of four k-steps (16 rows): up to the last lane that has a factor here. The rows
+      // behind would be zeros — products of exact zeros added to a sum that started at +0.0 — and are neither written nor read
+      const unsigned long long act = __builtin_amdgcn_ballot_w64(k < m);
+      const int ng = act ? (64 - __builtin_clzll(act) + 15) >> 4 : 0;      // (k < mmax: some lane has one)
       const double pjx = nob[0], pjy = nob[1];
       if (k + 1 < mmax) {
         const double *ob = d.lm_obs + (size_t)(k + 1) * 5 * TL + slot;
@@ -959,7 +965,7 @@ __global__ __launch_bounds__(LM_TILE, GFBE_KVIS_WAVES) void k_vis_chunk(BatchDev
 #pragma unroll
         for (int q = 0; q < 3; q++) { xr[q] = g0[q]; xr[3 + q] = y0[q]; xr[8 + q] = g1[q]; xr[11 + q] = y1[q]; }
         xr[6] = r[0]; xr[14] = r[1];
-      } else {
+      } else if (lane < 16 * ng) {
 #pragma unroll
         for (int q = 0; q < 7; q++) { xr[q] = 0.0; xr[8 + q] = 0.0; }
       }
@@ -974,13 +980,14 @@ __global__ __launch_bounds__(LM_TILE, GFBE_KVIS_WAVES) void k_vis_chunk(BatchDev
       const int lr = lane & 15, lk = lane >> 4;
       __threadfence_block();
       __builtin_amdgcn_wave_barrier();
+      // (a loop, not sixteen unrolled k-steps under four branches: the unrolled forms need 5 more VGPRs than the kernel had)
+#pragma unroll 1
+      for (int blk = 0; blk < ng; blk++) {
+        double va[4];
 #pragma unroll
-      for (int blk = 0; blk < LM_TILE / 4 / 8; blk++) {
-        double va[8];
+        for (int u = 0; u < 4; u++) va[u] = xs[(4 * (4 * blk + u) + lk) * XLD + lr];
 #pragma unroll
-        for (int u = 0; u < 8; u++) va[u] = xs[(4 * (8 * blk + u) + lk) * XLD + lr];
-#pragma unroll
-        for (int u = 0; u < 8; u++) acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(va[u], va[u], acc0, 0, 0, 0);
+        for (int u = 0; u < 4; u++) acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(va[u], va[u], acc0, 0, 0, 0);
       }
       __builtin_amdgcn_wave_barrier();
       const double s0 = acc0[0] + __shfl_down(acc0[2], 8, 64), s1 = acc0[1] + __shfl_down(acc0[3], 8, 64);
@@ -1781,6 +1788,11 @@ __device__ __forceinline__ int schur_group_first(int g, int ng) { return ng >= N
 //     no extrinsic / td rows) where the general form loads twenty: 14 + 3 instead of 22 + 3 vector loads per thread and tile
 //   * the multiply skips, four k-steps at a time, the k-steps (rows 4 k .. 4 k + 3) behind the tile's last landmark: products of exact
 //     zeros added to accumulators that are never -0.0
+//   * the same argument per 16-row chunk of a tile (profiles/schur_steps_ab.txt): the rows are sorted longest track first, so the chunk's
+//     first row is its widest, and the chunk multiplies the pairs (I, J) up to the last 16-column block THAT row reaches, not the tile's
+//   * the staging does not form the rows of an observation step the tile never ran (k >= m0, the track length of its first landmark):
+//     there it writes zeros, and only into columns a chunk of this tile reads; the columns in front of the start block are cleared
+//     when the start frame changes, those behind the last pose once per workgroup
 // (the LDS of schur_body: one object for both of its forms, which k_schur holds side by side)
 struct SchurLds {
   double hs[LM_TILE * HS_LD + 8];      // the panel (+ the overrun of the last row's last block)
@@ -1917,11 +1929,12 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
         _Pragma("unroll") for (int kk = 0; kk < LM_TILE / 8; kk++) ACC = __builtin_amdgcn_mfma_f64_16x16x4f64(va[kk], vb[kk], ACC, 0, 0, 0); \
       }                                                                                             \
     }
-  // (LEAN) the same chain of sixteen k-steps per pair, four at a time; a chunk whose rows lie behind the tile's last landmark is skipped
+  // (LEAN) the same chain of sixteen k-steps per pair, four at a time; a chunk whose rows lie behind the tile's last landmark, or do not
+  // reach block J, is skipped
 #define SCHUR_LEAN_SLOT(Q, ACC)                                                                                        \
     if (pI[Q] >= 0 && pJ[Q] <= jl) {                                                                                     \
       const double *pa = hs + 16 * pI[Q] + lr + lk * HS_LD, *pb = hs + 16 * pJ[Q] + lr + lk * HS_LD;                     \
-      _Pragma("unroll") for (int c_ = 0; c_ < 4; c_++) if (4 * c_ < nk) {                                                \
+      _Pragma("unroll") for (int c_ = 0; c_ < 4; c_++) if (4 * c_ < nk && pJ[Q] <= jlc[c_]) {                            \
         double va[4], vb[4];                                                                                             \
         _Pragma("unroll") for (int kk = 0; kk < 4; kk++) { va[kk] = pa[4 * (4 * c_ + kk) * HS_LD]; vb[kk] = pb[4 * (4 * c_ + kk) * HS_LD]; } \
         _Pragma("unroll") for (int kk = 0; kk < 4; kk++) ACC = __builtin_amdgcn_mfma_f64_16x16x4f64(va[kk], vb[kk], ACC, 0, 0, 0); \
@@ -1935,12 +1948,21 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
   {                                                                                                                      \
     __syncthreads();                                                                                                     \
     if (stamp_wg && (TILE) == tfirst) stamp[1] = (double)wall_clock64();                                                 \
-    const int ps = PS, pm0 = __builtin_amdgcn_readfirstlane(PINFO);                                                      \
+    const int ps = __builtin_amdgcn_readfirstlane(PS), pm0 = __builtin_amdgcn_readfirstlane(PINFO);                      \
     const int jl = __builtin_amdgcn_readfirstlane(compact ? (d.vis_full ? nside - 1 : (6 * (ps - s_first + ((pm0 >> 8) & 0xff) + 1)) >> 4) \
                                                           : (6 * (ps + ((pm0 >> 8) & 0xff) + 1) - 1) >> 4);              \
     /* (LEAN) the k-steps up to the tile's last valid landmark (lane = landmark in every wave): the rows behind it are zeros */ \
     const unsigned long long vmask_ = LEAN ? __builtin_amdgcn_ballot_w64((PINFO >> 24) & 1) : ~0ull;                       \
     const int nk = vmask_ ? (64 - __builtin_clzll(vmask_) + 3) >> 2 : 0;                                                 \
+    /* (LEAN) a tile's tracks are sorted longest first: the widest row of the 16-row chunk c is its first, lane 16 c, and the chunk */ \
+    /* multiplies the 16-column blocks 0 .. jlc[c] only; m0 = the observation steps the tile ran; dims below lim_ are the columns   */ \
+    /* some chunk of this tile reads                                                                                              */ \
+    int jlc[4];                                                                                                          \
+    _Pragma("unroll") for (int c_ = 0; c_ < 4; c_++)                                                                     \
+      jlc[c_] = LEAN ? (6 * (ps - s_first + ((__builtin_amdgcn_readlane(PINFO, 16 * c_) >> 8) & 0xff) + 1)) >> 4 : jl; \
+    const int m0_ = (pm0 >> 8) & 0xff, lim_ = 16 * (jl + 1) - coff;                                                      \
+    const bool first_ = !LEAN || prev_s < 0, fresh_ = !LEAN || ps != prev_s;                                             \
+    prev_s = ps;                                                                                                         \
     {                                                                                                                    \
       const int s = ps, kmax = NF - 1 - s;          /* this tile's start frame */                                        \
       const bool valid = (PINFO >> 24) & 1;                                                                              \
@@ -1955,20 +1977,26 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
       }                                                                                                                  \
       double *row = hs + l * HS_LD + coff;                                                                               \
       if (part == 0) {                                                                                                   \
-        for (int q = compact ? 6 * s_first : 16 * I0; q < 6 * s; q++) row[q] = 0.0;                                      \
+        /* (LEAN: the columns in front of the start block change only with the start frame, those behind the poses never) */ \
+        if (fresh_) for (int q = compact ? 6 * s_first : 16 * I0; q < 6 * s; q++) row[q] = 0.0;                          \
         double blk0[6];                                                                                                  \
         if (yrows) lm_row_block(s_rt[s], PV + (LEAN ? 3 : 0), PV + (LEAN ? 0 : 3), true, blk0);                     /* [ D ; Ri^T ((x - t_i) x D) ] */ \
         else { _Pragma("unroll") for (int q = 0; q < 6; q++) blk0[q] = PV[q]; }                                          \
-        _Pragma("unroll") for (int q = 0; q < 6; q++) { row[6 * s + q] = sw * blk0[q]; row[T_EX + q] = hc_full ? sw * PV[6 + q] : 0.0; } \
-        row[T_TD] = hc_full ? sw * PV[12] : 0.0;                                                                         \
+        _Pragma("unroll") for (int q = 0; q < 6; q++) row[6 * s + q] = sw * blk0[q];                                     \
+        if (first_) {                                                                                                    \
+          _Pragma("unroll") for (int q = 0; q < 6; q++) row[T_EX + q] = hc_full ? sw * PV[6 + q] : 0.0;                  \
+          row[T_TD] = hc_full ? sw * PV[12] : 0.0;                                                                       \
+        }                                                                                                                \
         if (compact) {                                                                                                   \
           row[-coff] = sw * PV[LEAN ? 6 : HC];                            /* column 0: the gradient */                     \
-          for (int q = NV + coff; q < min(16 * nside, (int)HS_LD); q++) row[q - coff] = 0.0;     /* behind td, up to the last block any tile of the group multiplies */ \
+          if (first_) for (int q = NV + coff; q < min(16 * nside, (int)HS_LD); q++) row[q - coff] = 0.0;     /* behind td, up to the last block any tile of the group multiplies */ \
         } else {                                                                                                         \
           row[NV] = sw * PV[HC];                                                                                         \
           _Pragma("unroll") for (int q = NV + 1; q < HS_LD; q++) row[q] = 0.0;                                           \
         }                                                                                                                \
-        if (9 < kmax) {                                                  /* the tenth observing pose (start frame 0) */  \
+        if (9 < kmax && LEAN && m0_ <= 9) {                              /* (a step the tile did not run: zeros where a chunk reads) */ \
+          _Pragma("unroll") for (int q = 0; q < 6; q++) if (6 * (s + 10) + q < lim_) row[6 * (s + 10) + q] = 0.0;        \
+        } else if (9 < kmax) {                                           /* the tenth observing pose (start frame 0) */  \
           const bool written = valid && 9 < m;                                                                           \
           double blk9[6];                                                                                                \
           if (yrows) lm_row_block(s_rt[min(s + 10, NF - 1)], PV + (LEAN ? 9 : HC + 1), PV + (LEAN ? 0 : 3), false, blk9);                       \
@@ -1977,8 +2005,10 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
         }                                                                                                                \
       } else {                                                                                                           \
         _Pragma("unroll") for (int u = 0; u < 3; u++) {                                                                  \
-          const int k = part - 1 + 3 * u;                                                                                \
-          if (k < kmax) {                                                                                                \
+          const int k = (LEAN ? wv : part) - 1 + 3 * u;                                                                  \
+          if (k < kmax && LEAN && k >= m0_) {                                                                            \
+            _Pragma("unroll") for (int q = 0; q < 6; q++) if (6 * (s + 1 + k) + q < lim_) row[6 * (s + 1 + k) + q] = 0.0; \
+          } else if (k < kmax) {                                                                                         \
             /* (rows from the landmark's track length on were never written — lm_hP is not cleared at upload: zeros, not products) */ \
             const bool written = valid && k < m;                                                                         \
             double blkk[6];                                                                                              \
@@ -2003,6 +2033,7 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
   }
   double preA[SCHUR_PV], aHll = 0.0, aSl = 0.0;
   int aInfo = 0, aS = 0;
+  int prev_s = -1;      // start frame of the tile staged before this one
   SCHUR_PREFETCH(preA, aHll, aSl, aInfo, aS, tfirst)
   // (measured, round 4: TWO tiles ahead — a second register set, the compiler's wait counts letting the younger set stay in flight —
   //  was slower at two and at three workgroups per CU, 183-198 against 169-175 us per 512 windows: the kernel is not bound by the
