@@ -29,14 +29,13 @@
 #include "gfbe_det.h"
 #include "gfbe_device.h"
 #include "gfbe_klt_priv.h"
-#include "gfbe_tabstage.h"
+#include "gfbe_handle.h"
 
 using namespace gfd;
 
 static_assert(DET_MAX_POINTS == GFBE_DET_MAX_POINTS, "the header's bound");
 
-struct gfbe_det {
-  gfbe_ctx *owner = nullptr;
+struct gfbe_det : gfbe_handle {
   gfbe_klt *trk = nullptr;
   gfbe_det_options opt;
   long long cand_cap = 0;
@@ -47,7 +46,6 @@ struct gfbe_det {
   unsigned long long *cand = nullptr;          // [n_cam][cand_cap]
   float *acc_pts = nullptr, *acc_resp = nullptr;      // [n_cam * cap][2], [n_cam * cap]: the corners a detect accepted
   int mask_min_dist = 0;                       // of the last detect
-  std::vector<void *> allocs;
 };
 
 namespace {
@@ -390,23 +388,6 @@ __global__ __launch_bounds__(DET_THREADS) void k_det_planes(KltGeom g, const uin
   mask[p] = clear ? 255 : 0;
 }
 
-#define DET_CHECK(c, call)                                                                                     \
-  do {                                                                                                         \
-    hipError_t e_ = (call);                                                                                    \
-    if (e_ != hipSuccess) { ctx_set_error(c, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); return GFBE_DEVICE_ERROR; } \
-  } while (0)
-
-gfbe_status det_bad(gfbe_ctx *c, const char *who, const char *what) {
-  ctx_set_error(c, (std::string(who) + ": " + what).c_str());
-  return GFBE_BAD_INPUT;
-}
-gfbe_status det_ready(gfbe_ctx *c, gfbe_det *m, const char *who) {
-  if (!c) return GFBE_BAD_INPUT;
-  if (ctx_device(c) < 0) { ctx_set_error(c, (std::string(who) + ": HIP device context required (no CPU fallback)").c_str()); return GFBE_NO_DEVICE; }
-  if (!m) return GFBE_BAD_INPUT;
-  if (m->owner != c) return det_bad(c, who, "the handle belongs to another context");
-  return GFBE_OK;
-}
 bool det_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 const char *det_options_error(const gfbe_det_options *o) {
   if (o->struct_size != (int32_t)sizeof(gfbe_det_options)) return "gfbe_det_options.struct_size does not match this library (ABI mismatch)";
@@ -451,8 +432,7 @@ void gfbe_det_default_options(gfbe_det_options *o) {
 
 void gfbe_det_destroy(gfbe_ctx *c, gfbe_det *m) {
   if (!m) return;
-  if (c && ctx_device(c) >= 0) (void)hipStreamSynchronize(ctx_stream(c));
-  for (void *p : m->allocs) (void)hipFree(p);
+  m->release(c);
   delete m;
 }
 
@@ -461,55 +441,48 @@ gfbe_status gfbe_det_create(gfbe_ctx *c, gfbe_klt *k, const gfbe_det_options *op
   *out = nullptr;
   gfbe_det_options o;
   if (opt) o = *opt; else gfbe_det_default_options(&o);
-  if (const char *bad = det_options_error(&o)) return det_bad(c, "gfbe_det_create", bad);
+  if (const char *bad = det_options_error(&o)) return handle_bad(c, "gfbe_det_create", bad);
   if (ctx_device(c) < 0) { ctx_set_error(c, "gfbe_det_create: HIP device context required (no CPU fallback)"); return GFBE_NO_DEVICE; }
-  if (!k) return det_bad(c, "gfbe_det_create", "tracker NULL");
-  if (k->owner != c) return det_bad(c, "gfbe_det_create", "the tracker belongs to another context");
-  if (k->cap > DET_MAX_POINTS) return det_bad(c, "gfbe_det_create", "the tracker's point_capacity is above GFBE_DET_MAX_POINTS");
-  if (o.max_cnt > k->cap) return det_bad(c, "gfbe_det_create", "max_cnt is above the tracker's point_capacity");
+  if (!k) return handle_bad(c, "gfbe_det_create", "tracker NULL");
+  if (k->owner != c) return handle_bad(c, "gfbe_det_create", "the tracker belongs to another context");
+  if (k->cap > DET_MAX_POINTS) return handle_bad(c, "gfbe_det_create", "the tracker's point_capacity is above GFBE_DET_MAX_POINTS");
+  if (o.max_cnt > k->cap) return handle_bad(c, "gfbe_det_create", "max_cnt is above the tracker's point_capacity");
   gfbe_det *m = new gfbe_det();
-  struct Guard { gfbe_ctx *c; gfbe_det *m; bool armed = true; ~Guard() { if (armed) gfbe_det_destroy(c, m); } } guard{c, m};
+  CreateGuard<gfbe_det> guard{c, m, gfbe_det_destroy};
   m->owner = c; m->trk = k; m->opt = o; m->mask_min_dist = o.min_dist;
   m->cand_cap = o.candidate_capacity > 0 ? (long long)o.candidate_capacity : (long long)(k->rows - 2) * (long long)(k->cols - 2);
   m->nbx = (k->cols + DET_TW - 1) / DET_TW; m->nby = (k->rows + DET_TH - 1) / DET_TH;
   hipStream_t st = ctx_stream(c);
-  auto alloc = [&](auto **p, size_t n) {
-    void *q = nullptr;
-    if (hipMalloc(&q, n * sizeof(**p)) != hipSuccess) return false;
-    m->allocs.push_back(q);
-    *p = (std::remove_reference_t<decltype(**p)> *)q;
-    return hipMemsetAsync(q, 0, n * sizeof(**p), st) == hipSuccess;
-  };
   const size_t C = (size_t)k->n_cam, N = C * (size_t)k->cap;
-  const bool ok = alloc(&m->kept_xy, 2 * N) && alloc(&m->kept, C) && alloc(&m->want, C) && alloc(&m->n_in, C) && alloc(&m->next_id, C) && alloc(&m->cand_n, C) &&
-                  alloc(&m->acc_n, C) && alloc(&m->ovf, C) && alloc(&m->none, C) && alloc(&m->zero, C) && alloc(&m->bmax, C * (size_t)m->nbx * (size_t)m->nby) &&
-                  alloc(&m->thr, C) && alloc(&m->cand, C * (size_t)m->cand_cap) && alloc(&m->acc_pts, 2 * N) && alloc(&m->acc_resp, N);
+  const bool ok = m->alloc(&m->kept_xy, 2 * N) && m->alloc(&m->kept, C) && m->alloc(&m->want, C) && m->alloc(&m->n_in, C) && m->alloc(&m->next_id, C) && m->alloc(&m->cand_n, C) &&
+                  m->alloc(&m->acc_n, C) && m->alloc(&m->ovf, C) && m->alloc(&m->none, C) && m->alloc(&m->zero, C) && m->alloc(&m->bmax, C * (size_t)m->nbx * (size_t)m->nby) &&
+                  m->alloc(&m->thr, C) && m->alloc(&m->cand, C * (size_t)m->cand_cap) && m->alloc(&m->acc_pts, 2 * N) && m->alloc(&m->acc_resp, N);
   if (!ok) { ctx_set_error(c, "gfbe_det_create: device allocation failed"); return GFBE_DEVICE_ERROR; }
-  DET_CHECK(c, hipStreamSynchronize(st));
+  GFBE_CHECK(c, hipStreamSynchronize(st));
   guard.armed = false;
   *out = m;
   return GFBE_OK;
 }
 
 gfbe_status gfbe_det_set_next_id(gfbe_ctx *c, gfbe_det *m, const int32_t *next_id) {
-  gfbe_status rc = det_ready(c, m, "gfbe_det_set_next_id");
+  gfbe_status rc = handle_ready(c, m, "gfbe_det_set_next_id");
   if (rc != GFBE_OK) return rc;
-  if (!next_id) return det_bad(c, "gfbe_det_set_next_id", "next_id NULL");
+  if (!next_id) return handle_bad(c, "gfbe_det_set_next_id", "next_id NULL");
   const size_t C = (size_t)m->trk->n_cam;
   Staged sg(c, m->trk, C * 4 + 4096);
   const int32_t *d = sg.up(next_id, C);
   if (!sg.ok) { ctx_set_error(c, "gfbe_det_set_next_id: staging allocation failed"); return GFBE_DEVICE_ERROR; }
   sg.flush();
-  DET_CHECK(c, hipMemcpyAsync(m->next_id, d, sizeof(int) * C, hipMemcpyDeviceToDevice, ctx_stream(c)));
+  GFBE_CHECK(c, hipMemcpyAsync(m->next_id, d, sizeof(int) * C, hipMemcpyDeviceToDevice, ctx_stream(c)));
   sg.finish();
   return GFBE_OK;
 }
 
 gfbe_status gfbe_det_detect(gfbe_ctx *c, gfbe_det *m, int32_t *offset_out, float *pts, int32_t *ids, int32_t *track_cnt, int32_t *counters) {
-  gfbe_status rc = det_ready(c, m, "gfbe_det_detect");
+  gfbe_status rc = handle_ready(c, m, "gfbe_det_detect");
   if (rc != GFBE_OK) return rc;
   gfbe_klt *k = m->trk;
-  if (k->n_pushed < 1) return det_bad(c, "gfbe_det_detect", "no image has been pushed");
+  if (k->n_pushed < 1) return handle_bad(c, "gfbe_det_detect", "no image has been pushed");
   const size_t C = (size_t)k->n_cam;
   size_t room = 0;      // rows of the result at most
   for (size_t q = 0; q < C; q++) room += (size_t)std::max(k->count_h[q], (int)m->opt.max_cnt);
@@ -540,7 +513,7 @@ gfbe_status gfbe_det_detect(gfbe_ctx *c, gfbe_det *m, int32_t *offset_out, float
     m->mask_min_dist = m->opt.min_dist;
     sg.dlo = (size_t)((const char *)o_off - sg.bd); sg.dhi = (size_t)((const char *)(o_pts + 2 * room) - sg.bd);
     sg.finish();      // the one wait
-    DET_CHECK(c, hipGetLastError());
+    GFBE_CHECK(c, hipGetLastError());
     auto host = [&](const auto *d) { return (decltype(d))(sg.bh + ((const char *)d - sg.bd)); };
     const int *h_off = host(o_off);
     const size_t n = (size_t)h_off[C];
@@ -555,12 +528,12 @@ gfbe_status gfbe_det_detect(gfbe_ctx *c, gfbe_det *m, int32_t *offset_out, float
 }
 
 gfbe_status gfbe_det_corners(gfbe_ctx *c, gfbe_det *m, int32_t max_corners, double quality, int32_t min_dist, int32_t *offset_out, float *pts, float *response) {
-  gfbe_status rc = det_ready(c, m, "gfbe_det_corners");
+  gfbe_status rc = handle_ready(c, m, "gfbe_det_corners");
   if (rc != GFBE_OK) return rc;
   gfbe_klt *k = m->trk;
-  if (k->n_pushed < 1) return det_bad(c, "gfbe_det_corners", "no image has been pushed");
-  if (max_corners <= 0 || max_corners > DET_MAX_POINTS) return det_bad(c, "gfbe_det_corners", "max_corners outside 1 .. GFBE_DET_MAX_POINTS");
-  if (!std::isfinite(quality) || quality < 0.0 || min_dist < 0 || min_dist > DET_MAX_DIST) return det_bad(c, "gfbe_det_corners", "quality negative or not finite, or min_dist outside 0 .. 32768");
+  if (k->n_pushed < 1) return handle_bad(c, "gfbe_det_corners", "no image has been pushed");
+  if (max_corners <= 0 || max_corners > DET_MAX_POINTS) return handle_bad(c, "gfbe_det_corners", "max_corners outside 1 .. GFBE_DET_MAX_POINTS");
+  if (!std::isfinite(quality) || quality < 0.0 || min_dist < 0 || min_dist > DET_MAX_DIST) return handle_bad(c, "gfbe_det_corners", "quality negative or not finite, or min_dist outside 0 .. 32768");
   const size_t C = (size_t)k->n_cam, R = C * (size_t)max_corners;
   hipStream_t st = ctx_stream(c);
   {
@@ -571,11 +544,11 @@ gfbe_status gfbe_det_corners(gfbe_ctx *c, gfbe_det *m, int32_t max_corners, doub
     float *o_resp = sg.up((const float *)nullptr, R), *o_pts = sg.up((const float *)nullptr, 2 * R);
     if (!sg.ok) { ctx_set_error(c, "gfbe_det_corners: staging allocation failed"); return GFBE_DEVICE_ERROR; }
     sg.flush();
-    DET_CHECK(c, hipMemsetAsync(m->cand_n, 0, sizeof(int) * C, st));
+    GFBE_CHECK(c, hipMemsetAsync(m->cand_n, 0, sizeof(int) * C, st));
     det_launch_corners(c, m, m->zero, d_want, min_dist, quality, max_corners, o_pts, o_resp, o_n);
     sg.dlo = (size_t)((const char *)o_n - sg.bd); sg.dhi = (size_t)((const char *)(o_pts + 2 * R) - sg.bd);
     sg.finish();
-    DET_CHECK(c, hipGetLastError());
+    GFBE_CHECK(c, hipGetLastError());
     auto host = [&](const auto *d) { return (decltype(d))(sg.bh + ((const char *)d - sg.bd)); };
     const int *h_n = host(o_n);
     const float *h_pts = host(o_pts), *h_resp = host(o_resp);
@@ -593,11 +566,11 @@ gfbe_status gfbe_det_corners(gfbe_ctx *c, gfbe_det *m, int32_t max_corners, doub
 }
 
 gfbe_status gfbe_det_download(gfbe_ctx *c, gfbe_det *m, int32_t camera, float *eig_out, uint8_t *mask_out) {
-  gfbe_status rc = det_ready(c, m, "gfbe_det_download");
+  gfbe_status rc = handle_ready(c, m, "gfbe_det_download");
   if (rc != GFBE_OK) return rc;
   gfbe_klt *k = m->trk;
-  if (k->n_pushed < 1) return det_bad(c, "gfbe_det_download", "no image has been pushed");
-  if (camera < 0 || camera >= k->n_cam) return det_bad(c, "gfbe_det_download", "camera outside the handle's");
+  if (k->n_pushed < 1) return handle_bad(c, "gfbe_det_download", "no image has been pushed");
+  if (camera < 0 || camera >= k->n_cam) return handle_bad(c, "gfbe_det_download", "camera outside the handle's");
   const size_t px = (size_t)k->rows * (size_t)k->cols;
   {
     Staged sg(c, k, px * 5 + 8192);
@@ -610,7 +583,7 @@ gfbe_status gfbe_det_download(gfbe_ctx *c, gfbe_det *m, int32_t camera, float *e
     sg.down(mask_out, (const uint8_t *)d_mask, px);
     sg.finish();
   }
-  DET_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   return GFBE_OK;
 }
 

@@ -470,7 +470,8 @@ void launch_marginalize(const BatchDev &d, int flag, hipStream_t s);
 void launch_gnss(const BatchDev &d, int mode, hipStream_t s, int sub = 0);
 bool lin_small_takes_gnss(const BatchDev &d, int mode);   // k_lin_small's candidate passes evaluate the batch's GNSS factors themselves (gfbe_gnss_item.h)
 
-// ---- device-resident feature tables (gfbe_ftab.hip; shared with the batch upload that reads them)
+// ---- device-resident feature tables (gfbe_ftab.hip; shared with the batch upload that reads them). The handles themselves, gfbe_ftab and
+// gfbe_ltab, are host structs on the shared handle base: gfbe_handle.h
 enum { FT_NOBS = GFBE_WINDOW_SIZE + 1, FT_OW = 8, FT_BINS = NF * 8,
        FT_LAY_BIN = 1, FT_LAY_GRP = 1 + FT_BINS, FT_LAY_PAIR = 1 + FT_BINS + NF, FT_LAY_STRIDE = 1 + FT_BINS + NF + NPAIR + 1 };   // bins: (start frame, factors 3..10) of a landmark
 struct FtabDev {
@@ -531,52 +532,3 @@ struct DevBuf {
 };
 
 }  // namespace gfd
-
-// argument staging of the table operations (gfbe_ftab, gfbe_ltab; used through gfd::Staged, gfbe_tabstage.h)
-struct gfbe_tab_staging {
-  // one device chunk + its pinned host mirror, grown on demand and kept (a hipMalloc / hipFree pair per argument cost more than the
-  // kernels: 0.4 ms per call measured)
-  char *stage_d = nullptr, *stage_h = nullptr;
-  size_t stage_cap = 0;
-  // the operations that return nothing (triangulate, setDepth, the erasing ones) do not wait for the device: their arguments go
-  // through a ring of small staging slots, a slot is reused when the event recorded behind its operation has passed
-  enum { RING = 8, RING_SLOT = 64 << 10 };
-  char *ring_d = nullptr, *ring_h = nullptr;
-  hipEvent_t ring_ev[RING] = {};
-  bool ring_used[RING] = {};
-  int ring_next = 0;
-};
-
-struct gfbe_ftab : gfbe_tab_staging {
-  gfd::FtabDev d;
-  int cur = 0;
-  std::vector<void *> allocs;
-  // gfbe_batch_upload_tables reads the tables on the context's COPY stream, beside the solves queued on the main one: it waits for
-  // ev_ops (recorded on the main stream behind every table operation) and leaves ev_read behind its last reader; the next table
-  // operation waits for that one (read_pending)
-  hipEvent_t ev_ops = nullptr, ev_read = nullptr;
-  bool read_pending = false;
-};
-
-struct gfbe_ltab : gfbe_tab_staging {
-  gfd::LtabDev d;
-  int cur = 0;
-  std::vector<void *> allocs;
-  gfd::DevBuf reduce_buf;        // gfbe_ltab_reduce's scratch and output staging, kept between calls (gfbe_line_reduce.hip)
-  // the step half of a joint iteration (gfbe_ltab_keep_records / gfbe_ltab_step / gfbe_ltab_commit, gfbe_line_step.hip)
-  unsigned long long gen = 0;    // bumped by every operation that may change the tables
-  bool keep_records = false;
-  gfd::DevBuf rec_buf;           // the per-line store of a solve-mode reduce: rec_off [W + 1], then Vinv, bl, W, V, failed per line slot
-  bool rec_valid = false;
-  unsigned long long rec_gen = 0;
-  double rec_mu = 0.0;
-  std::vector<double> rec_pose;  // [W][77] poses then [W][7] extrinsics of that reduce, bit for bit
-  std::vector<int> rec_off, rec_ne;      // [W + 1] first slot of a table, [W] entering lines
-  const double *rec_Vinv = nullptr, *rec_bl = nullptr, *rec_W = nullptr, *rec_V = nullptr;
-  const unsigned char *rec_failed = nullptr;
-  const int *rec_off_d = nullptr;
-  gfd::DevBuf step_buf;          // gfbe_ltab_step's inputs, outputs and the candidates, kept between calls
-  bool cand_valid = false;
-  const double *cand_plk = nullptr;      // [slots][6]
-  const int *cand_lineof = nullptr, *cand_ne = nullptr;      // [slots] line of a record, [W] entering lines
-};

@@ -25,7 +25,7 @@
 
 #include "gfbe_device.h"
 #include "gfbe_dmap.h"
-#include "gfbe_tabstage.h"
+#include "gfbe_handle.h"
 #include "gfbe_vmap.h"
 #include "gfbe_vmap_impl.h"
 
@@ -37,8 +37,7 @@ enum { DM_GATED = -2, DM_SKIPPED = -3, DM_REFUSED = -4 };
 constexpr int DM_THREADS = 256, DM_SCAN_THREADS = 1024, DM_NONE = 0x7F7F7F7F, DM_MAX_POINTS = 1 << 26;
 }  // namespace
 
-struct gfbe_dmap : gfbe_tab_staging {
-  gfbe_ctx *owner = nullptr;
+struct gfbe_dmap : gfbe_handle {
   gfbe_dmap_options opt;
   int pcap = 0, kcap = 0, slots = 0;
   // the keyframes' lists: one pool in keyframe order then list order
@@ -68,7 +67,6 @@ struct gfbe_dmap : gfbe_tab_staging {
   float *sorted = nullptr, *out_xyz = nullptr;                  // [pcap][3]
   uint8_t *keep_b = nullptr, *out_rgb = nullptr;                // [pcap], [pcap][3]
   int *meta = nullptr;                    // [DM_META]
-  std::vector<void *> allocs;
   int n_kf = 0;                           // exact: every accepted gfbe_dmap_add_keyframe adds one keyframe
   long long bound_stored = 0, bound_cloud = 0;      // the host's upper bounds of the device counts
 };
@@ -282,19 +280,7 @@ __global__ void k_df_begin(int *meta) {
   if (threadIdx.x == 0 && blockIdx.x == 0) { meta[DM_FAST] = 0; meta[DM_TOTAL] = 0; }
 }
 
-#define DM_CHECK(c, call)                                                                                      \
-  do {                                                                                                         \
-    hipError_t e_ = (call);                                                                                    \
-    if (e_ != hipSuccess) { ctx_set_error(c, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); return GFBE_DEVICE_ERROR; } \
-  } while (0)
-
-gfbe_status dm_ready(gfbe_ctx *c, gfbe_dmap *m, const char *who) {
-  if (!c) return GFBE_BAD_INPUT;
-  if (ctx_device(c) < 0) return GFBE_NO_DEVICE;
-  if (!m) return GFBE_BAD_INPUT;
-  if (m->owner != c) { ctx_set_error(c, (std::string(who) + ": the map handle belongs to another context").c_str()); return GFBE_BAD_INPUT; }
-  return GFBE_OK;
-}
+gfbe_status dm_ready(gfbe_ctx *c, gfbe_dmap *m, const char *who) { return handle_ready(c, m, who, "map handle"); }
 bool dm_finite(const double *p, size_t n) {
   for (size_t a = 0; a < n; a++) if (!std::isfinite(p[a])) return false;
   return true;
@@ -328,8 +314,8 @@ void dm_enqueue_cap(gfbe_ctx *c, gfbe_dmap *m, int mode, int cap, int G, const f
 DmPoint dm_point_args(const gfbe_dmap *m, int cap) { return DmPoint{m->opt.origin, m->opt.resolution, m->opt.z_min, m->opt.z_max, cap}; }
 
 gfbe_status dm_read_meta(gfbe_ctx *c, gfbe_dmap *m, int *h) {
-  DM_CHECK(c, hipMemcpyAsync(h, m->meta, sizeof(int) * DM_META, hipMemcpyDeviceToHost, ctx_stream(c)));
-  DM_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
+  GFBE_CHECK(c, hipMemcpyAsync(h, m->meta, sizeof(int) * DM_META, hipMemcpyDeviceToHost, ctx_stream(c)));
+  GFBE_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
   m->bound_stored = h[DM_NSTORED]; m->bound_cloud = h[DM_NCLOUD];
   return GFBE_OK;
 }
@@ -350,15 +336,7 @@ void gfbe_dmap_default_options(gfbe_dmap_options *o) {
 
 void gfbe_dmap_destroy(gfbe_ctx *c, gfbe_dmap *m) {
   if (!m) return;
-  if (c && ctx_device(c) >= 0) (void)hipStreamSynchronize(ctx_stream(c));
-  for (void *p : m->allocs) (void)hipFree(p);
-  if (m->pose_h) (void)hipHostFree(m->pose_h);
-  if (m->ev_pose) (void)hipEventDestroy(m->ev_pose);
-  if (m->stage_d) (void)hipFree(m->stage_d);
-  if (m->stage_h) (void)hipHostFree(m->stage_h);
-  if (m->ring_d) (void)hipFree(m->ring_d);
-  if (m->ring_h) (void)hipHostFree(m->ring_h);
-  for (hipEvent_t e : m->ring_ev) if (e) (void)hipEventDestroy(e);
+  m->release(c);
   delete m;
 }
 
@@ -375,33 +353,21 @@ gfbe_status gfbe_dmap_create(gfbe_ctx *c, int32_t point_capacity, int32_t keyfra
   }
   if (ctx_device(c) < 0) { ctx_set_error(c, "gfbe_dmap_create: HIP device context required (no CPU fallback)"); return GFBE_NO_DEVICE; }
   gfbe_dmap *m = new gfbe_dmap();
-  struct Guard { gfbe_ctx *c; gfbe_dmap *m; bool armed = true; ~Guard() { if (armed) gfbe_dmap_destroy(c, m); } } guard{c, m};
+  CreateGuard<gfbe_dmap> guard{c, m, gfbe_dmap_destroy};
   m->owner = c; m->opt = o; m->pcap = point_capacity; m->kcap = keyframe_capacity;
   long long slots = 64;
   while (slots < 2ll * point_capacity) slots <<= 1;
   m->slots = (int)slots;
   const size_t N = (size_t)point_capacity, K = (size_t)keyframe_capacity, S = (size_t)slots;
   hipStream_t st = ctx_stream(c);
-  auto alloc = [&](auto **p, size_t n, int fill) {
-    void *q = nullptr;
-    if (hipMalloc(&q, n * sizeof(**p)) != hipSuccess) return false;
-    m->allocs.push_back(q);
-    *p = (std::remove_reference_t<decltype(**p)> *)q;
-    return hipMemsetAsync(q, fill, n * sizeof(**p), st) == hipSuccess;
-  };
-  bool ok = alloc(&m->pool_xyz, 3 * N, 0) && alloc(&m->pool_rgb, 3 * N, 0) && alloc(&m->pool_kf, N, 0) && alloc(&m->kf_tab, 2 * K, 0) && alloc(&m->keys, S, 0xFF) &&
-            alloc(&m->cnt, S, 0) && alloc(&m->cl_xyz, 3 * N, 0) && alloc(&m->cl_rgb, 3 * N, 0) && alloc(&m->cl_kf, N, 0) && alloc(&m->cl_src, N, 0) &&
-            alloc(&m->rank_min[0], S, 0x7F) && alloc(&m->rank_min[1], S, 0x7F) && alloc(&m->slot_of, N, 0) && alloc(&m->won, N, 0) && alloc(&m->cand, 3 * N, 0) &&
-            alloc(&m->part, S / DM_THREADS + 2, 0) && alloc(&m->rp, 12 * K, 0) && alloc(&m->rp_ic, (size_t)12, 0) && alloc(&m->pose_d, 7 * K, 0) &&
-            alloc(&m->ckeys, S, 0xFF) && alloc(&m->ccnt, S, 0) && alloc(&m->cstart, S, 0) && alloc(&m->cfill, S, 0) && alloc(&m->cslot, N, 0) && alloc(&m->keep_i, N, 0) &&
-            alloc(&m->sorted, 3 * N, 0) && alloc(&m->out_xyz, 3 * N, 0) && alloc(&m->keep_b, N, 0) && alloc(&m->out_rgb, 3 * N, 0) && alloc(&m->meta, (size_t)DM_META, 0);
+  bool ok = m->alloc(&m->pool_xyz, 3 * N, 0) && m->alloc(&m->pool_rgb, 3 * N, 0) && m->alloc(&m->pool_kf, N, 0) && m->alloc(&m->kf_tab, 2 * K, 0) && m->alloc(&m->keys, S, 0xFF) &&
+            m->alloc(&m->cnt, S, 0) && m->alloc(&m->cl_xyz, 3 * N, 0) && m->alloc(&m->cl_rgb, 3 * N, 0) && m->alloc(&m->cl_kf, N, 0) && m->alloc(&m->cl_src, N, 0) &&
+            m->alloc(&m->rank_min[0], S, 0x7F) && m->alloc(&m->rank_min[1], S, 0x7F) && m->alloc(&m->slot_of, N, 0) && m->alloc(&m->won, N, 0) && m->alloc(&m->cand, 3 * N, 0) &&
+            m->alloc(&m->part, S / DM_THREADS + 2, 0) && m->alloc(&m->rp, 12 * K, 0) && m->alloc(&m->rp_ic, (size_t)12, 0) && m->alloc(&m->pose_d, 7 * K, 0) &&
+            m->alloc(&m->ckeys, S, 0xFF) && m->alloc(&m->ccnt, S, 0) && m->alloc(&m->cstart, S, 0) && m->alloc(&m->cfill, S, 0) && m->alloc(&m->cslot, N, 0) && m->alloc(&m->keep_i, N, 0) &&
+            m->alloc(&m->sorted, 3 * N, 0) && m->alloc(&m->out_xyz, 3 * N, 0) && m->alloc(&m->keep_b, N, 0) && m->alloc(&m->out_rgb, 3 * N, 0) && m->alloc(&m->meta, (size_t)DM_META, 0);
   if (!ok) { ctx_set_error(c, "gfbe_dmap_create: device allocation failed"); return GFBE_DEVICE_ERROR; }
-  DM_CHECK(c, hipHostMalloc((void **)&m->pose_h, sizeof(double) * 7 * K));
-  DM_CHECK(c, hipEventCreateWithFlags(&m->ev_pose, hipEventDisableTiming));
-  { Staged warm(c, m, 1 << 16); if (!warm.ok) { ctx_set_error(c, "gfbe_dmap_create: staging allocation failed"); return GFBE_DEVICE_ERROR; } }
-  DM_CHECK(c, hipMalloc((void **)&m->ring_d, (size_t)gfbe_dmap::RING * gfbe_dmap::RING_SLOT));
-  DM_CHECK(c, hipHostMalloc((void **)&m->ring_h, (size_t)gfbe_dmap::RING * gfbe_dmap::RING_SLOT));
-  for (int k = 0; k < gfbe_dmap::RING; k++) DM_CHECK(c, hipEventCreateWithFlags(&m->ring_ev[k], hipEventDisableTiming));
+  if (!m->alloc_pinned(&m->pose_h, 7 * K) || !m->create(&m->ev_pose) || !m->make_staging(c, "gfbe_dmap_create", 1 << 16, true)) return GFBE_DEVICE_ERROR;
   {
     Staged sg(c, m, 1024);
     const double *dex = sg.up(o.ex_cam, 7);
@@ -409,8 +375,8 @@ gfbe_status gfbe_dmap_create(gfbe_ctx *c, int32_t point_capacity, int32_t keyfra
     sg.flush();
     hipLaunchKernelGGL(k_dm_poses, dim3(1), dim3(64), 0, st, 1, dex, m->rp_ic);
   }
-  DM_CHECK(c, hipStreamSynchronize(st));
-  DM_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipStreamSynchronize(st));
+  GFBE_CHECK(c, hipGetLastError());
   guard.armed = false;
   *out = m;
   return GFBE_OK;
@@ -425,7 +391,7 @@ gfbe_status gfbe_dmap_add_keyframe(gfbe_ctx *c, gfbe_dmap *m, const double *pose
   hipStream_t st = ctx_stream(c);
   if (m->n_kf >= m->kcap) {      // the keyframe table is full: the whole call is refused and counted
     hipLaunchKernelGGL(k_dm_refuse_all, dim3(1), dim3(1), 0, st, m->meta, (int)n);
-    DM_CHECK(c, hipGetLastError());
+    GFBE_CHECK(c, hipGetLastError());
     return GFBE_OK;
   }
   const size_t N = (size_t)n;
@@ -448,7 +414,7 @@ gfbe_status gfbe_dmap_add_keyframe(gfbe_ctx *c, gfbe_dmap *m, const double *pose
   m->n_kf++;
   m->bound_stored = std::min<long long>(m->pcap, m->bound_stored + n);
   m->bound_cloud = std::min<long long>(m->pcap, m->bound_cloud + n);
-  DM_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   return GFBE_OK;
 }
 
@@ -460,16 +426,16 @@ gfbe_status gfbe_dmap_rebuild(gfbe_ctx *c, gfbe_dmap *m, int32_t n_keyframes, co
   if (!dm_finite(pose7, 7 * (size_t)n_keyframes)) { ctx_set_error(c, "gfbe_dmap_rebuild: a pose is not finite"); return GFBE_BAD_INPUT; }
   hipStream_t st = ctx_stream(c);
   const size_t K = (size_t)n_keyframes;
-  if (m->pose_busy) DM_CHECK(c, hipEventSynchronize(m->ev_pose));      // (the pinned mirror of the last rebuild's poses: long copied by now)
+  if (m->pose_busy) GFBE_CHECK(c, hipEventSynchronize(m->ev_pose));      // (the pinned mirror of the last rebuild's poses: long copied by now)
   if (K) {
     std::memcpy(m->pose_h, pose7, sizeof(double) * 7 * K);
-    DM_CHECK(c, hipMemcpyAsync(m->pose_d, m->pose_h, sizeof(double) * 7 * K, hipMemcpyHostToDevice, st));
-    DM_CHECK(c, hipEventRecord(m->ev_pose, st));
+    GFBE_CHECK(c, hipMemcpyAsync(m->pose_d, m->pose_h, sizeof(double) * 7 * K, hipMemcpyHostToDevice, st));
+    GFBE_CHECK(c, hipEventRecord(m->ev_pose, st));
     m->pose_busy = true;
     hipLaunchKernelGGL(k_dm_poses, dim3((unsigned)((K + 63) / 64)), dim3(64), 0, st, (int)K, (const double *)m->pose_d, m->rp);
   }
-  DM_CHECK(c, hipMemsetAsync(m->keys, 0xFF, sizeof(unsigned long long) * (size_t)m->slots, st));
-  DM_CHECK(c, hipMemsetAsync(m->cnt, 0, sizeof(int) * (size_t)m->slots, st));
+  GFBE_CHECK(c, hipMemsetAsync(m->keys, 0xFF, sizeof(unsigned long long) * (size_t)m->slots, st));
+  GFBE_CHECK(c, hipMemsetAsync(m->cnt, 0, sizeof(int) * (size_t)m->slots, st));
   hipLaunchKernelGGL(k_dm_begin, dim3(1), dim3(1), 0, st, m->meta, 1, 0, m->pcap, m->kcap);
   const int G = dm_grid(m->bound_stored);
   const VmDev T{m->keys, m->cnt, nullptr, m->slots - 1, 0, 0, nullptr};
@@ -478,7 +444,7 @@ gfbe_status gfbe_dmap_rebuild(gfbe_ctx *c, gfbe_dmap *m, int32_t n_keyframes, co
                        (const double *)m->rp_ic, (const float *)m->pool_xyz, (const int *)m->pool_kf, T, m->rank_min[0], m->slot_of, m->won, m->cand);
   dm_enqueue_cap(c, m, 1, m->opt.rebuild_cap, G, nullptr, nullptr);
   m->bound_cloud = m->bound_stored;
-  DM_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   return GFBE_OK;
 }
 
@@ -495,8 +461,8 @@ gfbe_status gfbe_dmap_filter(gfbe_ctx *c, gfbe_dmap *m, uint8_t *keep, int32_t *
   const VmDev C{m->ckeys, m->ccnt, nullptr, used - 1, 0, 0, nullptr};
   hipLaunchKernelGGL(k_df_begin, dim3(1), dim3(1), 0, st, m->meta);
   if (G > 0) {
-    DM_CHECK(c, hipMemsetAsync(m->ckeys, 0xFF, sizeof(unsigned long long) * (size_t)used, st));
-    DM_CHECK(c, hipMemsetAsync(m->ccnt, 0, sizeof(int) * (size_t)used, st));
+    GFBE_CHECK(c, hipMemsetAsync(m->ckeys, 0xFF, sizeof(unsigned long long) * (size_t)used, st));
+    GFBE_CHECK(c, hipMemsetAsync(m->ccnt, 0, sizeof(int) * (size_t)used, st));
     hipLaunchKernelGGL(k_df_cell, dim3(G), dim3(DM_THREADS), 0, st, (const int *)m->meta, (const float *)m->cl_xyz, side, C, m->cslot);
     hipLaunchKernelGGL(k_dm_partial, dim3(GS), dim3(DM_THREADS), 0, st, used, (const int *)m->ccnt, m->part);
     hipLaunchKernelGGL(k_dm_offsets, dim3(1), dim3(DM_SCAN_THREADS), 0, st, m->meta, GS, m->part);
@@ -510,17 +476,17 @@ gfbe_status gfbe_dmap_filter(gfbe_ctx *c, gfbe_dmap *m, uint8_t *keep, int32_t *
       hipLaunchKernelGGL(k_df_compact, dim3(G), dim3(DM_THREADS), 0, st, (const int *)m->meta, (const int *)m->keep_i, (const int *)m->part, (const float *)m->cl_xyz,
                          (const uint8_t *)m->cl_rgb, m->out_xyz, m->out_rgb);
   }
-  DM_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   int h[DM_META];
   if ((rc = dm_read_meta(c, m, h)) != GFBE_OK) return rc;      // the host wait: the counts
   const size_t n = (size_t)h[DM_NCLOUD], nk = (size_t)h[DM_TOTAL];
   if (n_keep) *n_keep = (int32_t)nk;
-  if (keep && n) DM_CHECK(c, hipMemcpyAsync(keep, m->keep_b, n, hipMemcpyDeviceToHost, st));
+  if (keep && n) GFBE_CHECK(c, hipMemcpyAsync(keep, m->keep_b, n, hipMemcpyDeviceToHost, st));
   if (xyz_out && nk) {
-    DM_CHECK(c, hipMemcpyAsync(xyz_out, m->out_xyz, sizeof(float) * 3 * nk, hipMemcpyDeviceToHost, st));
-    DM_CHECK(c, hipMemcpyAsync(rgb_out, m->out_rgb, 3 * nk, hipMemcpyDeviceToHost, st));
+    GFBE_CHECK(c, hipMemcpyAsync(xyz_out, m->out_xyz, sizeof(float) * 3 * nk, hipMemcpyDeviceToHost, st));
+    GFBE_CHECK(c, hipMemcpyAsync(rgb_out, m->out_rgb, 3 * nk, hipMemcpyDeviceToHost, st));
   }
-  DM_CHECK(c, hipStreamSynchronize(st));
+  GFBE_CHECK(c, hipStreamSynchronize(st));
   return GFBE_OK;
 }
 
@@ -544,11 +510,11 @@ gfbe_status gfbe_dmap_download_cloud(gfbe_ctx *c, gfbe_dmap *m, float *xyz, uint
   const size_t n = (size_t)h[DM_NCLOUD];
   if (n == 0) return GFBE_OK;
   hipStream_t st = ctx_stream(c);
-  if (xyz) DM_CHECK(c, hipMemcpyAsync(xyz, m->cl_xyz, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, st));
-  if (rgb) DM_CHECK(c, hipMemcpyAsync(rgb, m->cl_rgb, 3 * n, hipMemcpyDeviceToHost, st));
-  if (kf) DM_CHECK(c, hipMemcpyAsync(kf, m->cl_kf, sizeof(int) * n, hipMemcpyDeviceToHost, st));
-  if (src) DM_CHECK(c, hipMemcpyAsync(src, m->cl_src, sizeof(int) * n, hipMemcpyDeviceToHost, st));
-  DM_CHECK(c, hipStreamSynchronize(st));
+  if (xyz) GFBE_CHECK(c, hipMemcpyAsync(xyz, m->cl_xyz, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, st));
+  if (rgb) GFBE_CHECK(c, hipMemcpyAsync(rgb, m->cl_rgb, 3 * n, hipMemcpyDeviceToHost, st));
+  if (kf) GFBE_CHECK(c, hipMemcpyAsync(kf, m->cl_kf, sizeof(int) * n, hipMemcpyDeviceToHost, st));
+  if (src) GFBE_CHECK(c, hipMemcpyAsync(src, m->cl_src, sizeof(int) * n, hipMemcpyDeviceToHost, st));
+  GFBE_CHECK(c, hipStreamSynchronize(st));
   return GFBE_OK;
 }
 
@@ -558,13 +524,13 @@ gfbe_status gfbe_dmap_download_keyframe(gfbe_ctx *c, gfbe_dmap *m, int32_t k, in
   if (k < 0 || k >= m->n_kf) { ctx_set_error(c, "gfbe_dmap_download_keyframe: no such keyframe"); return GFBE_BAD_INPUT; }
   hipStream_t st = ctx_stream(c);
   int e[2];
-  DM_CHECK(c, hipMemcpyAsync(e, m->kf_tab + 2 * (size_t)k, sizeof e, hipMemcpyDeviceToHost, st));
-  DM_CHECK(c, hipStreamSynchronize(st));
+  GFBE_CHECK(c, hipMemcpyAsync(e, m->kf_tab + 2 * (size_t)k, sizeof e, hipMemcpyDeviceToHost, st));
+  GFBE_CHECK(c, hipStreamSynchronize(st));
   if (n) *n = e[1];
   if (e[1] == 0 || (!pts && !rgb)) return GFBE_OK;
-  if (pts) DM_CHECK(c, hipMemcpyAsync(pts, m->pool_xyz + 3 * (size_t)e[0], sizeof(float) * 3 * (size_t)e[1], hipMemcpyDeviceToHost, st));
-  if (rgb) DM_CHECK(c, hipMemcpyAsync(rgb, m->pool_rgb + 3 * (size_t)e[0], 3 * (size_t)e[1], hipMemcpyDeviceToHost, st));
-  DM_CHECK(c, hipStreamSynchronize(st));
+  if (pts) GFBE_CHECK(c, hipMemcpyAsync(pts, m->pool_xyz + 3 * (size_t)e[0], sizeof(float) * 3 * (size_t)e[1], hipMemcpyDeviceToHost, st));
+  if (rgb) GFBE_CHECK(c, hipMemcpyAsync(rgb, m->pool_rgb + 3 * (size_t)e[0], 3 * (size_t)e[1], hipMemcpyDeviceToHost, st));
+  GFBE_CHECK(c, hipStreamSynchronize(st));
   return GFBE_OK;
 }
 

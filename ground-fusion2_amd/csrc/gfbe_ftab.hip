@@ -21,7 +21,7 @@
 
 #include "gfbe_device.h"
 #include "gfbe_math.h"
-#include "gfbe_tabstage.h"
+#include "gfbe_handle.h"
 
 using namespace gfd;
 
@@ -523,33 +523,19 @@ __global__ __launch_bounds__(FT_THREADS) void k_ftab_pack(int W, int F, const in
 
 // ------------------------------------------------------------------------------------------------------------
 namespace {
-#define FT_CHECK(c, call)                                                                                      \
-  do {                                                                                                         \
-    hipError_t e_ = (call);                                                                                    \
-    if (e_ != hipSuccess) { ctx_set_error(c, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); return GFBE_DEVICE_ERROR; } \
-  } while (0)
-
-template <typename T>
-gfbe_status ft_alloc(gfbe_ctx *c, gfbe_ftab *t, T **p, size_t n) {
-  void *q = nullptr;
-  FT_CHECK(c, hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
-  FT_CHECK(c, hipMemsetAsync(q, 0, std::max<size_t>(n, 1) * sizeof(T), ctx_stream(c)));
-  t->allocs.push_back(q);
-  *p = (T *)q;
-  return GFBE_OK;
-}
 gfbe_status ft_ready(gfbe_ctx *c, gfbe_ftab *t) {
-  if (!c || !t) return GFBE_BAD_INPUT;
-  if (ctx_device(c) < 0) return GFBE_NO_DEVICE;
+  if (!t) return GFBE_BAD_INPUT;
+  const gfbe_status st = handle_device(c, t, "gfbe_ftab");
+  if (st != GFBE_OK) return st;
   // (a batch upload may still be reading the tables on the copy stream: this operation runs behind it)
-  if (t->read_pending && t->ev_read) { FT_CHECK(c, hipStreamWaitEvent(ctx_stream(c), t->ev_read, 0)); t->read_pending = false; }
+  if (t->read_pending && t->ev_read) { GFBE_CHECK(c, hipStreamWaitEvent(ctx_stream(c), t->ev_read, 0)); t->read_pending = false; }
   return GFBE_OK;
 }
 // launch errors of the operation (the sticky table errors — capacity, observation count — are raised by k_ftab_add alone and
 // come back with gfbe_ftab_add_frame's own results)
 gfbe_status ft_finish(gfbe_ctx *c, gfbe_ftab *t) {
-  FT_CHECK(c, hipGetLastError());
-  if (t && t->ev_ops) FT_CHECK(c, hipEventRecord(t->ev_ops, ctx_stream(c)));      // (what gfbe_batch_upload_tables waits for)
+  GFBE_CHECK(c, hipGetLastError());
+  if (t && t->ev_ops) GFBE_CHECK(c, hipEventRecord(t->ev_ops, ctx_stream(c)));      // (what gfbe_batch_upload_tables waits for)
   return GFBE_OK;
 }
 // the launch half of addFeatureCheckParallax: a frame that lies on the device (M rows in all, at most mmax a table) into the tables.
@@ -621,13 +607,13 @@ gfbe_status gfbe_ftab_create(gfbe_ctx *c, int32_t n_tables, int32_t cap, const g
   gfbe_ftab *t = new gfbe_ftab();
   *out = nullptr;
   // (a failed allocation leaves nothing behind: the table built so far is destroyed and *out stays null)
-  struct Guard { gfbe_ctx *c; gfbe_ftab *t; bool armed = true; ~Guard() { if (armed) gfbe_ftab_destroy(c, t); } } guard{c, t};
+  CreateGuard<gfbe_ftab> guard{c, t, gfbe_ftab_destroy};
+  t->owner = c;
   FtabDev &d = t->d;
   d.W = n_tables; d.F = cap;
   if (opt) d.opt = *opt; else gfbe_ftab_default_options(&d.opt);
   const size_t N = (size_t)n_tables * cap;
-  gfbe_status st;
-#define FA(p, n) if ((st = ft_alloc(c, t, &p, n)) != GFBE_OK) return st
+#define FA(p, n) if (!t->alloc(&p, n)) return GFBE_DEVICE_ERROR
   FA(d.count, n_tables); FA(d.err, n_tables); FA(d.keep, N); FA(d.ndepth, N); FA(d.ids_scratch, N); FA(d.cnt_scratch, n_tables);
   FA(d.hist, (size_t)n_tables * (FT_BINS + 2)); FA(d.layout, (size_t)n_tables * FT_LAY_STRIDE);
   for (int b = 0; b < 2; b++) {
@@ -635,14 +621,10 @@ gfbe_status gfbe_ftab_create(gfbe_ctx *c, int32_t n_tables, int32_t cap, const g
     FA(d.depth[b], N); FA(d.obs[b], N * NOBS * OW); FA(d.td[b], N * NOBS);
   }
 #undef FA
-  { Staged warm(c, t, (size_t)n_tables * cap * 8); }   // staging sized for the largest result (every id flagged) up front
-  FT_CHECK(c, hipMalloc((void **)&t->ring_d, (size_t)gfbe_ftab::RING * gfbe_ftab::RING_SLOT));
-  FT_CHECK(c, hipHostMalloc((void **)&t->ring_h, (size_t)gfbe_ftab::RING * gfbe_ftab::RING_SLOT));
-  for (int k = 0; k < gfbe_ftab::RING; k++) FT_CHECK(c, hipEventCreateWithFlags(&t->ring_ev[k], hipEventDisableTiming));
-  FT_CHECK(c, hipEventCreateWithFlags(&t->ev_ops, hipEventDisableTiming));
-  FT_CHECK(c, hipEventCreateWithFlags(&t->ev_read, hipEventDisableTiming));
-  FT_CHECK(c, hipEventRecord(t->ev_ops, ctx_stream(c)));
-  FT_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
+  // (staging sized for the largest result, every id flagged, up front)
+  if (!t->make_staging(c, "gfbe_ftab_create", (size_t)n_tables * cap * 8, true) || !t->create(&t->ev_ops) || !t->create(&t->ev_read)) return GFBE_DEVICE_ERROR;
+  GFBE_CHECK(c, hipEventRecord(t->ev_ops, ctx_stream(c)));
+  GFBE_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
   guard.armed = false;
   *out = t;
   return GFBE_OK;
@@ -650,15 +632,8 @@ gfbe_status gfbe_ftab_create(gfbe_ctx *c, int32_t n_tables, int32_t cap, const g
 
 void gfbe_ftab_destroy(gfbe_ctx *c, gfbe_ftab *t) {
   if (!t) return;
-  if (c && ctx_device(c) >= 0) (void)hipStreamSynchronize(ctx_stream(c));
-  for (void *p : t->allocs) (void)hipFree(p);
-  if (t->stage_d) (void)hipFree(t->stage_d);
-  if (t->stage_h) (void)hipHostFree(t->stage_h);
-  if (t->ring_d) (void)hipFree(t->ring_d);
-  if (t->ring_h) (void)hipHostFree(t->ring_h);
-  for (hipEvent_t e : t->ring_ev) if (e) (void)hipEventDestroy(e);
-  if (t->ev_read) { (void)hipEventSynchronize(t->ev_read); (void)hipEventDestroy(t->ev_read); }
-  if (t->ev_ops) (void)hipEventDestroy(t->ev_ops);
+  if (t->ev_read) (void)hipEventSynchronize(t->ev_read);      // (a batch upload may still be reading the tables on the copy stream)
+  t->release(c);
   delete t;
 }
 
@@ -793,8 +768,8 @@ gfbe_status gfbe_ftab_check_outliers(gfbe_ctx *c, gfbe_ftab *t, const double *po
   } else if (total) {   // the host copy moves exactly the flagged ids, through the pinned staging mirror (a pageable copy runs at a few 100 MB/s)
     Staged s2(c, t, sizeof(int32_t) * total);
     if (!s2.ok) { ctx_set_error(c, "gfbe_ftab_check_outliers: staging allocation failed"); return GFBE_DEVICE_ERROR; }
-    FT_CHECK(c, hipMemcpyAsync(t->stage_h, t->d.keep, sizeof(int32_t) * total, hipMemcpyDeviceToHost, ctx_stream(c)));
-    FT_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
+    GFBE_CHECK(c, hipMemcpyAsync(t->stage_h, t->d.keep, sizeof(int32_t) * total, hipMemcpyDeviceToHost, ctx_stream(c)));
+    GFBE_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
     const int32_t *tmp = (const int32_t *)t->stage_h;
     size_t run = 0;
     for (int w = 0; w < W; w++) {
@@ -809,8 +784,8 @@ gfbe_status gfbe_ftab_size(gfbe_ctx *c, gfbe_ftab *t, int32_t *n) {
   gfbe_status st = ft_ready(c, t);
   if (st != GFBE_OK) return st;
   if (!n) return GFBE_BAD_INPUT;
-  FT_CHECK(c, hipMemcpyAsync(t->stage_h, t->d.count, sizeof(int) * t->d.W, hipMemcpyDeviceToHost, ctx_stream(c)));   // (through the pinned mirror)
-  FT_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
+  GFBE_CHECK(c, hipMemcpyAsync(t->stage_h, t->d.count, sizeof(int) * t->d.W, hipMemcpyDeviceToHost, ctx_stream(c)));   // (through the pinned mirror)
+  GFBE_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
   std::memcpy(n, t->stage_h, sizeof(int) * t->d.W);
   return GFBE_OK;
 }
@@ -821,17 +796,17 @@ gfbe_status gfbe_ftab_download(gfbe_ctx *c, gfbe_ftab *t, int32_t w, int32_t *id
   if (st != GFBE_OK) return st;
   if (w < 0 || w >= t->d.W) return GFBE_BAD_INPUT;
   int n = 0;
-  FT_CHECK(c, hipMemcpyAsync(&n, t->d.count + w, sizeof(int), hipMemcpyDeviceToHost, ctx_stream(c)));
-  FT_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
+  GFBE_CHECK(c, hipMemcpyAsync(&n, t->d.count + w, sizeof(int), hipMemcpyDeviceToHost, ctx_stream(c)));
+  GFBE_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
   const size_t base = (size_t)w * t->d.F;
   const int b = t->cur;
   hipStream_t s = ctx_stream(c);
-#define DN(h, dptr, cnt) if (h && n) FT_CHECK(c, hipMemcpyAsync(h, dptr, sizeof(*h) * (cnt), hipMemcpyDeviceToHost, s))
+#define DN(h, dptr, cnt) if (h && n) GFBE_CHECK(c, hipMemcpyAsync(h, dptr, sizeof(*h) * (cnt), hipMemcpyDeviceToHost, s))
   DN(id, t->d.id[b] + base, (size_t)n); DN(start, t->d.start[b] + base, (size_t)n); DN(nobs, t->d.nobs[b] + base, (size_t)n);
   DN(eflag, t->d.eflag[b] + base, (size_t)n); DN(sflag, t->d.sflag[b] + base, (size_t)n); DN(depth, t->d.depth[b] + base, (size_t)n);
   DN(obs8, t->d.obs[b] + base * NOBS * OW, (size_t)n * NOBS * OW); DN(obs_td, t->d.td[b] + base * NOBS, (size_t)n * NOBS);
 #undef DN
-  FT_CHECK(c, hipStreamSynchronize(s));
+  GFBE_CHECK(c, hipStreamSynchronize(s));
   return GFBE_OK;
 }
 

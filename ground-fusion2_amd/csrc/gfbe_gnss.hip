@@ -6,7 +6,7 @@
 #include <string>
 #include <vector>
 
-#include "gfbe_device.h"
+#include "gfbe_handle.h"
 #include "gfbe_gnss.h"
 
 using namespace gfd;
@@ -47,12 +47,6 @@ __global__ __launch_bounds__(128) void k_gnss(GnssArgs a, const gfbe_gnss_obs *o
   }
 }
 
-#define GN_CHECK(c, call)                                                                                      \
-  do {                                                                                                         \
-    hipError_t e_ = (call);                                                                                    \
-    if (e_ != hipSuccess) { ctx_set_error(c, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); st = GFBE_DEVICE_ERROR; goto done; } \
-  } while (0)
-
 }  // namespace
 
 extern "C" gfbe_status gfbe_gnss_eval(gfbe_ctx *c, int32_t n_obs, const gfbe_gnss_obs *obs, const double *iono, const gfbe_state *state,
@@ -80,19 +74,19 @@ extern "C" gfbe_status gfbe_gnss_eval(gfbe_ctx *c, int32_t n_obs, const gfbe_gns
   a.n_obs = n_obs; a.has_iono = iono != nullptr; a.ddt_weight = ddt_weight;
   for (int i = 0; i < 8; i++) a.iono[i] = iono ? iono[i] : 0.0;
   for (int i = 0; i < W; i++) a.dt[i] = frame_dt[i];
-  GN_CHECK(c, hipMalloc((void **)&d, total));
-  if (n_obs) GN_CHECK(c, hipMemcpyAsync(d + o_obs, obs, sizeof(gfbe_gnss_obs) * (size_t)n_obs, hipMemcpyHostToDevice, s));
-  GN_CHECK(c, hipMemcpyAsync(d + o_st, state, sizeof(gfbe_state), hipMemcpyHostToDevice, s));
-  GN_CHECK(c, hipMemcpyAsync(d + o_g, gnss, sizeof(gfbe_gnss_state), hipMemcpyHostToDevice, s));
+  GFBE_CHECK_DONE(c, hipMalloc((void **)&d, total));
+  if (n_obs) GFBE_CHECK_DONE(c, hipMemcpyAsync(d + o_obs, obs, sizeof(gfbe_gnss_obs) * (size_t)n_obs, hipMemcpyHostToDevice, s));
+  GFBE_CHECK_DONE(c, hipMemcpyAsync(d + o_st, state, sizeof(gfbe_state), hipMemcpyHostToDevice, s));
+  GFBE_CHECK_DONE(c, hipMemcpyAsync(d + o_g, gnss, sizeof(gfbe_gnss_state), hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_gnss, dim3((nt + 127) / 128), dim3(128), 0, s, a, (const gfbe_gnss_obs *)(d + o_obs), (const gfbe_state *)(d + o_st),
                      (const gfbe_gnss_state *)(d + o_g), r_obs ? (double *)(d + o_r) : nullptr, J_obs ? (double *)(d + o_J) : nullptr,
                      (double *)(d + o_clk), (double *)(d + o_c));
-  GN_CHECK(c, hipGetLastError());
-  if (r_obs && n_obs) GN_CHECK(c, hipMemcpyAsync(r_obs, d + o_r, sizeof(double) * 2 * (size_t)n_obs, hipMemcpyDeviceToHost, s));
-  if (J_obs && n_obs) GN_CHECK(c, hipMemcpyAsync(J_obs, d + o_J, sizeof(double) * 36 * (size_t)n_obs, hipMemcpyDeviceToHost, s));
-  GN_CHECK(c, hipMemcpyAsync(hclk.data(), d + o_clk, sizeof(double) * 5 * W, hipMemcpyDeviceToHost, s));
-  GN_CHECK(c, hipMemcpyAsync(hc.data(), d + o_c, sizeof(double) * nt, hipMemcpyDeviceToHost, s));
-  GN_CHECK(c, hipStreamSynchronize(s));
+  GFBE_CHECK_DONE(c, hipGetLastError());
+  if (r_obs && n_obs) GFBE_CHECK_DONE(c, hipMemcpyAsync(r_obs, d + o_r, sizeof(double) * 2 * (size_t)n_obs, hipMemcpyDeviceToHost, s));
+  if (J_obs && n_obs) GFBE_CHECK_DONE(c, hipMemcpyAsync(J_obs, d + o_J, sizeof(double) * 36 * (size_t)n_obs, hipMemcpyDeviceToHost, s));
+  GFBE_CHECK_DONE(c, hipMemcpyAsync(hclk.data(), d + o_clk, sizeof(double) * 5 * W, hipMemcpyDeviceToHost, s));
+  GFBE_CHECK_DONE(c, hipMemcpyAsync(hc.data(), d + o_c, sizeof(double) * nt, hipMemcpyDeviceToHost, s));
+  GFBE_CHECK_DONE(c, hipStreamSynchronize(s));
   if (r_dt_ddt) for (int q = 0; q < 4 * W; q++) r_dt_ddt[q] = hclk[q];
   if (r_smooth) for (int q = 0; q < W; q++) r_smooth[q] = hclk[4 * W + q];
   if (cost) { double t = 0.0; for (int k = 0; k < nt; k++) t += hc[k]; *cost = t; }

@@ -6,6 +6,7 @@
 // Reference being replaced: Estimator::optimization()
 //   Ground-Fusion++/vins_estimator/src/estimator/estimator.cpp:2951-3698
 #include "gfbe_device.h"
+#include "gfbe_handle.h"
 #include "gfbe_upload.h"
 #include <algorithm>
 #include <atomic>

@@ -24,7 +24,7 @@
 #include "gfbe_device.h"
 #include "gfbe_klt.h"
 #include "gfbe_klt_priv.h"
-#include "gfbe_tabstage.h"
+#include "gfbe_handle.h"
 
 using namespace gfd;
 
@@ -229,23 +229,6 @@ __global__ __launch_bounds__(KLT_DECIDE_THREADS) void k_klt_decide(KltDecideArgs
   }
 }
 
-#define KLT_CHECK(c, call)                                                                                     \
-  do {                                                                                                         \
-    hipError_t e_ = (call);                                                                                    \
-    if (e_ != hipSuccess) { ctx_set_error(c, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); return GFBE_DEVICE_ERROR; } \
-  } while (0)
-
-gfbe_status klt_bad(gfbe_ctx *c, const char *who, const char *what) {
-  ctx_set_error(c, (std::string(who) + ": " + what).c_str());
-  return GFBE_BAD_INPUT;
-}
-gfbe_status klt_ready(gfbe_ctx *c, gfbe_klt *m, const char *who) {
-  if (!c) return GFBE_BAD_INPUT;
-  if (ctx_device(c) < 0) { ctx_set_error(c, (std::string(who) + ": HIP device context required (no CPU fallback)").c_str()); return GFBE_NO_DEVICE; }
-  if (!m) return GFBE_BAD_INPUT;
-  if (m->owner != c) return klt_bad(c, who, "the handle belongs to another context");
-  return GFBE_OK;
-}
 const char *klt_options_error(const gfbe_klt_options *o) {
   if (o->struct_size != (int32_t)sizeof(gfbe_klt_options)) return "gfbe_klt_options.struct_size does not match this library (ABI mismatch)";
   if (o->max_level < 0 || o->max_level > GFBE_KLT_MAX_LEVEL) return "max_level outside 0 .. GFBE_KLT_MAX_LEVEL";
@@ -282,12 +265,7 @@ void gfbe_klt_default_options(gfbe_klt_options *o) {
 
 void gfbe_klt_destroy(gfbe_ctx *c, gfbe_klt *m) {
   if (!m) return;
-  if (c && ctx_device(c) >= 0) (void)hipStreamSynchronize(ctx_stream(c));
-  for (void *p : m->allocs) (void)hipFree(p);
-  if (m->raw_h) (void)hipHostFree(m->raw_h);
-  if (m->ev_raw) (void)hipEventDestroy(m->ev_raw);
-  if (m->stage_d) (void)hipFree(m->stage_d);
-  if (m->stage_h) (void)hipHostFree(m->stage_h);
+  m->release(c);
   delete m;
 }
 
@@ -296,13 +274,13 @@ gfbe_status gfbe_klt_create(gfbe_ctx *c, int32_t n_cameras, int32_t rows, int32_
   *out = nullptr;
   gfbe_klt_options o;
   if (opt) o = *opt; else gfbe_klt_default_options(&o);
-  if (const char *bad = klt_options_error(&o)) return klt_bad(c, "gfbe_klt_create", bad);
-  if (rows <= KLT_WIN || cols <= KLT_WIN || rows > (1 << 14) || cols > (1 << 14)) return klt_bad(c, "gfbe_klt_create", "rows / cols outside 22 .. 16384 (the window is 21 x 21)");
+  if (const char *bad = klt_options_error(&o)) return handle_bad(c, "gfbe_klt_create", bad);
+  if (rows <= KLT_WIN || cols <= KLT_WIN || rows > (1 << 14) || cols > (1 << 14)) return handle_bad(c, "gfbe_klt_create", "rows / cols outside 22 .. 16384 (the window is 21 x 21)");
   if (n_cameras < 1 || n_cameras > (1 << 16) || point_capacity < 1 || point_capacity > (1 << 20) || (long long)n_cameras * point_capacity > (1ll << 28))
-    return klt_bad(c, "gfbe_klt_create", "n_cameras outside 1 .. 2^16, point_capacity outside 1 .. 2^20 or more than 2^28 points in all");
+    return handle_bad(c, "gfbe_klt_create", "n_cameras outside 1 .. 2^16, point_capacity outside 1 .. 2^20 or more than 2^28 points in all");
   if (ctx_device(c) < 0) { ctx_set_error(c, "gfbe_klt_create: HIP device context required (no CPU fallback)"); return GFBE_NO_DEVICE; }
   gfbe_klt *m = new gfbe_klt();
-  struct Guard { gfbe_ctx *c; gfbe_klt *m; bool armed = true; ~Guard() { if (armed) gfbe_klt_destroy(c, m); } } guard{c, m};
+  CreateGuard<gfbe_klt> guard{c, m, gfbe_klt_destroy};
   m->owner = c; m->opt = o; m->n_cam = n_cameras; m->rows = rows; m->cols = cols; m->cap = point_capacity;
   KltGeom &g = m->g;
   std::memset(&g, 0, sizeof g);
@@ -314,41 +292,32 @@ gfbe_status gfbe_klt_create(gfbe_ctx *c, int32_t n_cameras, int32_t rows, int32_
   }
   g.img_cam = io; g.der_cam = 2 * io;
   hipStream_t st = ctx_stream(c);
-  auto alloc = [&](auto **p, size_t n) {
-    void *q = nullptr;
-    if (hipMalloc(&q, n * sizeof(**p)) != hipSuccess) return false;
-    m->allocs.push_back(q);
-    *p = (std::remove_reference_t<decltype(**p)> *)q;
-    return hipMemsetAsync(q, 0, n * sizeof(**p), st) == hipSuccess;
-  };
   const size_t C = (size_t)n_cameras, N = C * (size_t)point_capacity, R = C * (size_t)rows * (size_t)cols;
-  bool ok = alloc(&m->raw_d, R);
+  bool ok = m->alloc(&m->raw_d, R);
   for (int s = 0; s < 2 && ok; s++)
-    ok = alloc(&m->img[s], C * (size_t)g.img_cam) && alloc(&m->der[s], C * (size_t)g.der_cam) && alloc(&m->pts[s], 2 * N) && alloc(&m->ids[s], N) && alloc(&m->cnt[s], N) &&
-         alloc(&m->seg_count[s], C);
-  ok = ok && alloc(&m->seg_begin, C) && alloc(&m->w_cur, 2 * N) && alloc(&m->w_rev, 2 * N) && alloc(&m->w_err, N) && alloc(&m->w_st, N) &&
-       alloc(&m->w_rst, N) && alloc(&m->w_dec, N) && alloc(&m->gate, C);
+    ok = m->alloc(&m->img[s], C * (size_t)g.img_cam) && m->alloc(&m->der[s], C * (size_t)g.der_cam) && m->alloc(&m->pts[s], 2 * N) && m->alloc(&m->ids[s], N) && m->alloc(&m->cnt[s], N) &&
+         m->alloc(&m->seg_count[s], C);
+  ok = ok && m->alloc(&m->seg_begin, C) && m->alloc(&m->w_cur, 2 * N) && m->alloc(&m->w_rev, 2 * N) && m->alloc(&m->w_err, N) && m->alloc(&m->w_st, N) &&
+       m->alloc(&m->w_rst, N) && m->alloc(&m->w_dec, N) && m->alloc(&m->gate, C);
   if (!ok) { ctx_set_error(c, "gfbe_klt_create: device allocation failed"); return GFBE_DEVICE_ERROR; }
-  KLT_CHECK(c, hipHostMalloc((void **)&m->raw_h, R));
-  KLT_CHECK(c, hipEventCreateWithFlags(&m->ev_raw, hipEventDisableTiming));
-  { Staged warm(c, m, 1 << 16); if (!warm.ok) { ctx_set_error(c, "gfbe_klt_create: staging allocation failed"); return GFBE_DEVICE_ERROR; } }
+  if (!m->alloc_pinned(&m->raw_h, R) || !m->create(&m->ev_raw) || !m->make_staging(c, "gfbe_klt_create", 1 << 16, false)) return GFBE_DEVICE_ERROR;
   m->begin_h.assign(C, 0); m->count_h.assign(C, 0);
-  KLT_CHECK(c, hipStreamSynchronize(st));
+  GFBE_CHECK(c, hipStreamSynchronize(st));
   guard.armed = false;
   *out = m;
   return GFBE_OK;
 }
 
 gfbe_status gfbe_klt_push_image(gfbe_ctx *c, gfbe_klt *m, const uint8_t *images) {
-  gfbe_status rc = klt_ready(c, m, "gfbe_klt_push_image");
+  gfbe_status rc = handle_ready(c, m, "gfbe_klt_push_image");
   if (rc != GFBE_OK) return rc;
-  if (!images) return klt_bad(c, "gfbe_klt_push_image", "images NULL");
+  if (!images) return handle_bad(c, "gfbe_klt_push_image", "images NULL");
   hipStream_t st = ctx_stream(c);
   const size_t R = (size_t)m->n_cam * (size_t)m->rows * (size_t)m->cols;
-  if (m->raw_busy) KLT_CHECK(c, hipEventSynchronize(m->ev_raw));      // (the mirror's last copy has left it)
+  if (m->raw_busy) GFBE_CHECK(c, hipEventSynchronize(m->ev_raw));      // (the mirror's last copy has left it)
   std::memcpy(m->raw_h, images, R);
-  KLT_CHECK(c, hipMemcpyAsync(m->raw_d, m->raw_h, R, hipMemcpyHostToDevice, st));
-  KLT_CHECK(c, hipEventRecord(m->ev_raw, st));
+  GFBE_CHECK(c, hipMemcpyAsync(m->raw_d, m->raw_h, R, hipMemcpyHostToDevice, st));
+  GFBE_CHECK(c, hipEventRecord(m->ev_raw, st));
   m->raw_busy = true;
   m->cur_set ^= 1;
   m->n_pushed++;
@@ -360,18 +329,18 @@ gfbe_status gfbe_klt_push_image(gfbe_ctx *c, gfbe_klt *m, const uint8_t *images)
   for (int l = 0; l < g.n_levels; l++)
     hipLaunchKernelGGL(k_klt_step, dim3(klt_grid((long long)(g.w[l] + 2 * KLT_WIN) * (g.h[l] + 2 * KLT_WIN), KLT_THREADS), 1, m->n_cam), dim3(KLT_THREADS), 0, st, g, l,
                        (int)(l + 1 < g.n_levels), img, der);
-  KLT_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   return GFBE_OK;
 }
 
 gfbe_status gfbe_klt_set_points(gfbe_ctx *c, gfbe_klt *m, const int32_t *offset, const float *pts, const int32_t *ids, const int32_t *track_cnt) {
-  gfbe_status rc = klt_ready(c, m, "gfbe_klt_set_points");
+  gfbe_status rc = handle_ready(c, m, "gfbe_klt_set_points");
   if (rc != GFBE_OK) return rc;
   const int bad = klt_check_points(m->n_cam, offset, m->cap, pts);
-  if (bad == KLT_C_COUNT) return klt_bad(c, "gfbe_klt_set_points", "offsets that do not ascend from 0, a camera with more points than point_capacity, or pts NULL");
-  if (bad == KLT_C_FINITE) return klt_bad(c, "gfbe_klt_set_points", "a non-finite point");
+  if (bad == KLT_C_COUNT) return handle_bad(c, "gfbe_klt_set_points", "offsets that do not ascend from 0, a camera with more points than point_capacity, or pts NULL");
+  if (bad == KLT_C_FINITE) return handle_bad(c, "gfbe_klt_set_points", "a non-finite point");
   const size_t C = (size_t)m->n_cam, N = (size_t)offset[m->n_cam];
-  if (N > 0 && (!ids || !track_cnt)) return klt_bad(c, "gfbe_klt_set_points", "ids / track_cnt NULL");
+  if (N > 0 && (!ids || !track_cnt)) return handle_bad(c, "gfbe_klt_set_points", "ids / track_cnt NULL");
   std::vector<int> cnt(C);
   for (size_t k = 0; k < C; k++) cnt[k] = offset[k + 1] - offset[k];
   hipStream_t st = ctx_stream(c);
@@ -383,12 +352,12 @@ gfbe_status gfbe_klt_set_points(gfbe_ctx *c, gfbe_klt *m, const int32_t *offset,
     sg.flush();
     const int hf = m->half;
     if (N > 0) {
-      KLT_CHECK(c, hipMemcpyAsync(m->pts[hf], dp, sizeof(float) * 2 * N, hipMemcpyDeviceToDevice, st));
-      KLT_CHECK(c, hipMemcpyAsync(m->ids[hf], di, sizeof(int) * N, hipMemcpyDeviceToDevice, st));
-      KLT_CHECK(c, hipMemcpyAsync(m->cnt[hf], dc, sizeof(int) * N, hipMemcpyDeviceToDevice, st));
+      GFBE_CHECK(c, hipMemcpyAsync(m->pts[hf], dp, sizeof(float) * 2 * N, hipMemcpyDeviceToDevice, st));
+      GFBE_CHECK(c, hipMemcpyAsync(m->ids[hf], di, sizeof(int) * N, hipMemcpyDeviceToDevice, st));
+      GFBE_CHECK(c, hipMemcpyAsync(m->cnt[hf], dc, sizeof(int) * N, hipMemcpyDeviceToDevice, st));
     }
-    KLT_CHECK(c, hipMemcpyAsync(m->seg_begin, dof, sizeof(int) * C, hipMemcpyDeviceToDevice, st));
-    KLT_CHECK(c, hipMemcpyAsync(m->seg_count[hf], dn, sizeof(int) * C, hipMemcpyDeviceToDevice, st));
+    GFBE_CHECK(c, hipMemcpyAsync(m->seg_begin, dof, sizeof(int) * C, hipMemcpyDeviceToDevice, st));
+    GFBE_CHECK(c, hipMemcpyAsync(m->seg_count[hf], dn, sizeof(int) * C, hipMemcpyDeviceToDevice, st));
     sg.finish();
   }
   for (size_t k = 0; k < C; k++) { m->begin_h[k] = offset[k]; m->count_h[k] = cnt[k]; }
@@ -397,9 +366,9 @@ gfbe_status gfbe_klt_set_points(gfbe_ctx *c, gfbe_klt *m, const int32_t *offset,
 
 gfbe_status gfbe_klt_track(gfbe_ctx *c, gfbe_klt *m, const uint8_t *has_prediction, const float *predict_pts, int32_t *offset_out, float *prev_pts, float *cur_pts,
                            int32_t *ids, int32_t *track_cnt, int32_t *counters) {
-  gfbe_status rc = klt_ready(c, m, "gfbe_klt_track");
+  gfbe_status rc = handle_ready(c, m, "gfbe_klt_track");
   if (rc != GFBE_OK) return rc;
-  if (m->n_pushed < 2) return klt_bad(c, "gfbe_klt_track", "two images must have been pushed");
+  if (m->n_pushed < 2) return handle_bad(c, "gfbe_klt_track", "two images must have been pushed");
   const size_t C = (size_t)m->n_cam;
   // the held rows: camera k at begin_h[k] .. + count_h[k]; `span` covers them all
   size_t span = 0;
@@ -416,7 +385,7 @@ gfbe_status gfbe_klt_track(gfbe_ctx *c, gfbe_klt *m, const uint8_t *has_predicti
         any_pred = true; gate[k] = 2;
         for (size_t i = 0; i < 2 * n; i++) {
           const float v = predict_pts[2 * row + i];
-          if (!std::isfinite(v)) return klt_bad(c, "gfbe_klt_track", "a non-finite point in predict_pts");
+          if (!std::isfinite(v)) return handle_bad(c, "gfbe_klt_track", "a non-finite point in predict_pts");
           pred[2 * (size_t)m->begin_h[k] + i] = v;
         }
       }
@@ -436,11 +405,11 @@ gfbe_status gfbe_klt_track(gfbe_ctx *c, gfbe_klt *m, const uint8_t *has_predicti
     float *o_prev = sg.up((const float *)nullptr, 2 * span), *o_cur = sg.up((const float *)nullptr, 2 * span);
     if (!sg.ok) { ctx_set_error(c, "gfbe_klt_track: staging allocation failed"); return GFBE_DEVICE_ERROR; }
     sg.flush();
-    KLT_CHECK(c, hipMemcpyAsync(m->gate, dgate, sizeof(int) * C, hipMemcpyDeviceToDevice, st));
+    GFBE_CHECK(c, hipMemcpyAsync(m->gate, dgate, sizeof(int) * C, hipMemcpyDeviceToDevice, st));
     KltFlowArgs A = klt_flow_args(m, 0, 1, 1);
     A.seg_begin = m->seg_begin; A.seg_count = m->seg_count[hf]; A.prev = m->pts[hf]; A.next = m->w_cur; A.status = m->w_st; A.err = m->w_err; A.gate = m->gate;
     if (any_pred && span > 0) {                                                  // :121-131
-      KLT_CHECK(c, hipMemcpyAsync(m->w_cur, dpred, sizeof(float) * 2 * span, hipMemcpyDeviceToDevice, st));
+      GFBE_CHECK(c, hipMemcpyAsync(m->w_cur, dpred, sizeof(float) * 2 * span, hipMemcpyDeviceToDevice, st));
       A.gate_want = 2;
       klt_launch_flow(c, m, A, max_count);
       hipLaunchKernelGGL(k_klt_fallback, dim3(m->n_cam), dim3(KLT_THREADS), 0, st, (const int *)m->seg_begin, (const int *)m->seg_count[hf], (const uint8_t *)m->w_st,
@@ -449,7 +418,7 @@ gfbe_status gfbe_klt_track(gfbe_ctx *c, gfbe_klt *m, const uint8_t *has_predicti
     A.max_level = std::min((int)m->opt.max_level, m->g.n_levels - 1); A.use_initial = 0; A.gate_want = 1;      // :132, :135
     klt_launch_flow(c, m, A, max_count);
     if (m->opt.flow_back && span > 0) {                                          // :141
-      KLT_CHECK(c, hipMemcpyAsync(m->w_rev, m->pts[hf], sizeof(float) * 2 * span, hipMemcpyDeviceToDevice, st));
+      GFBE_CHECK(c, hipMemcpyAsync(m->w_rev, m->pts[hf], sizeof(float) * 2 * span, hipMemcpyDeviceToDevice, st));
       KltFlowArgs B = klt_flow_args(m, 1, 1, 1);
       B.seg_begin = m->seg_begin; B.seg_count = m->seg_count[hf]; B.prev = m->w_cur; B.next = m->w_rev; B.status = m->w_rst; B.err = m->w_err;
       klt_launch_flow(c, m, B, max_count);
@@ -465,7 +434,7 @@ gfbe_status gfbe_klt_track(gfbe_ctx *c, gfbe_klt *m, const uint8_t *has_predicti
     // the result range comes back in one copy; the rows are compacted over the cameras straight from the pinned mirror
     sg.dlo = (size_t)((const char *)o_cnts - sg.bd); sg.dhi = (size_t)((const char *)(o_cur + 2 * span) - sg.bd);
     sg.finish();      // the one wait
-    KLT_CHECK(c, hipGetLastError());
+    GFBE_CHECK(c, hipGetLastError());
     auto host = [&](const auto *d) { return (decltype(d))(sg.bh + ((const char *)d - sg.bd)); };
     const float *h_prev = host(o_prev), *h_cur = host(o_cur);
     const int *h_ids = host(o_ids), *h_cnt = host(o_cnt);
@@ -489,17 +458,17 @@ gfbe_status gfbe_klt_track(gfbe_ctx *c, gfbe_klt *m, const uint8_t *has_predicti
 
 gfbe_status gfbe_klt_flow(gfbe_ctx *c, gfbe_klt *m, int32_t direction, int32_t max_level, int32_t use_initial_flow, const int32_t *offset, const float *pts, float *next_pts,
                           uint8_t *status, float *err) {
-  gfbe_status rc = klt_ready(c, m, "gfbe_klt_flow");
+  gfbe_status rc = handle_ready(c, m, "gfbe_klt_flow");
   if (rc != GFBE_OK) return rc;
-  if (m->n_pushed < 2) return klt_bad(c, "gfbe_klt_flow", "two images must have been pushed");
-  if ((direction != 0 && direction != 1) || max_level < 0 || max_level > GFBE_KLT_MAX_LEVEL) return klt_bad(c, "gfbe_klt_flow", "direction outside 0 .. 1 or max_level outside 0 .. GFBE_KLT_MAX_LEVEL");
+  if (m->n_pushed < 2) return handle_bad(c, "gfbe_klt_flow", "two images must have been pushed");
+  if ((direction != 0 && direction != 1) || max_level < 0 || max_level > GFBE_KLT_MAX_LEVEL) return handle_bad(c, "gfbe_klt_flow", "direction outside 0 .. 1 or max_level outside 0 .. GFBE_KLT_MAX_LEVEL");
   int bad = klt_check_points(m->n_cam, offset, m->cap, pts);
   const size_t C = (size_t)m->n_cam, N = bad ? 0 : (size_t)offset[m->n_cam];
   if (!bad && N > 0 && !next_pts) bad = KLT_C_COUNT;
   if (!bad && use_initial_flow)
     for (size_t i = 0; i < 2 * N; i++) if (!std::isfinite(next_pts[i])) { bad = KLT_C_FINITE; break; }
-  if (bad == KLT_C_COUNT) return klt_bad(c, "gfbe_klt_flow", "offsets that do not ascend from 0, a camera with more points than point_capacity, or a NULL array");
-  if (bad == KLT_C_FINITE) return klt_bad(c, "gfbe_klt_flow", "a non-finite point");
+  if (bad == KLT_C_COUNT) return handle_bad(c, "gfbe_klt_flow", "offsets that do not ascend from 0, a camera with more points than point_capacity, or a NULL array");
+  if (bad == KLT_C_FINITE) return handle_bad(c, "gfbe_klt_flow", "a non-finite point");
   std::vector<int> cnt(C);
   int max_count = 0;
   for (size_t k = 0; k < C; k++) { cnt[k] = offset[k + 1] - offset[k]; max_count = std::max(max_count, cnt[k]); }
@@ -520,23 +489,23 @@ gfbe_status gfbe_klt_flow(gfbe_ctx *c, gfbe_klt *m, int32_t direction, int32_t m
     sg.down(err, (const float *)de, N);
     sg.finish();
   }
-  KLT_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   return GFBE_OK;
 }
 
 gfbe_status gfbe_klt_download_level(gfbe_ctx *c, gfbe_klt *m, int32_t which, int32_t camera, int32_t level, uint8_t *image_out, int16_t *deriv_out, int32_t *dims_out) {
-  gfbe_status rc = klt_ready(c, m, "gfbe_klt_download_level");
+  gfbe_status rc = handle_ready(c, m, "gfbe_klt_download_level");
   if (rc != GFBE_OK) return rc;
   if ((which != 0 && which != 1) || camera < 0 || camera >= m->n_cam || level < 0 || level >= m->g.n_levels)
-    return klt_bad(c, "gfbe_klt_download_level", "which outside 0 .. 1, camera outside the handle's, or a level that was not built");
-  if (m->n_pushed < (which ? 1 : 2)) return klt_bad(c, "gfbe_klt_download_level", "that image set has not been pushed");
+    return handle_bad(c, "gfbe_klt_download_level", "which outside 0 .. 1, camera outside the handle's, or a level that was not built");
+  if (m->n_pushed < (which ? 1 : 2)) return handle_bad(c, "gfbe_klt_download_level", "that image set has not been pushed");
   const KltGeom &g = m->g;
   const int s = which ? m->cur_set : m->cur_set ^ 1;
   const size_t px = (size_t)(g.w[level] + 2 * KLT_WIN) * (size_t)(g.h[level] + 2 * KLT_WIN);
   hipStream_t st = ctx_stream(c);
-  if (image_out) KLT_CHECK(c, hipMemcpyAsync(image_out, m->img[s] + (size_t)camera * (size_t)g.img_cam + (size_t)g.img_off[level], px, hipMemcpyDeviceToHost, st));
-  if (deriv_out) KLT_CHECK(c, hipMemcpyAsync(deriv_out, m->der[s] + (size_t)camera * (size_t)g.der_cam + (size_t)g.der_off[level], 2 * px * sizeof(int16_t), hipMemcpyDeviceToHost, st));
-  KLT_CHECK(c, hipStreamSynchronize(st));
+  if (image_out) GFBE_CHECK(c, hipMemcpyAsync(image_out, m->img[s] + (size_t)camera * (size_t)g.img_cam + (size_t)g.img_off[level], px, hipMemcpyDeviceToHost, st));
+  if (deriv_out) GFBE_CHECK(c, hipMemcpyAsync(deriv_out, m->der[s] + (size_t)camera * (size_t)g.der_cam + (size_t)g.der_off[level], 2 * px * sizeof(int16_t), hipMemcpyDeviceToHost, st));
+  GFBE_CHECK(c, hipStreamSynchronize(st));
   if (dims_out) { dims_out[0] = g.w[level]; dims_out[1] = g.h[level]; dims_out[2] = g.w[level] + 2 * KLT_WIN; dims_out[3] = g.n_levels; }
   return GFBE_OK;
 }

@@ -7,7 +7,7 @@
 #include <vector>
 
 #include "../../include/gfbe_klt.h"
-#include "gfbe_device.h"
+#include "gfbe_handle.h"
 #include "gfbe_klt.h"
 
 namespace gfd {
@@ -24,8 +24,7 @@ __host__ __device__ inline KltLevel klt_view(const KltGeom &g, const uint8_t *im
 }
 }  // namespace gfd
 
-struct gfbe_klt : gfbe_tab_staging {
-  gfbe_ctx *owner = nullptr;
+struct gfbe_klt : gfbe_handle {
   gfbe_klt_options opt;
   int n_cam = 0, rows = 0, cols = 0, cap = 0;
   gfd::KltGeom g;
@@ -46,6 +45,5 @@ struct gfbe_klt : gfbe_tab_staging {
   float *w_cur = nullptr, *w_rev = nullptr, *w_err = nullptr;
   uint8_t *w_st = nullptr, *w_rst = nullptr, *w_dec = nullptr;      // forward / reverse status, the decision of a point
   int *gate = nullptr;
-  std::vector<void *> allocs;
   std::vector<int> begin_h, count_h;          // exact host mirrors
 };

@@ -21,7 +21,7 @@
 
 #include "gfbe_device.h"
 #include "gfbe_ldb.h"
-#include "gfbe_tabstage.h"
+#include "gfbe_handle.h"
 
 using namespace gfd;
 
@@ -39,8 +39,7 @@ struct LdbTreeDev {
 };
 }  // namespace
 
-struct gfbe_ldb : gfbe_tab_staging {
-  gfbe_ctx *owner = nullptr;
+struct gfbe_ldb : gfbe_handle {
   gfbe_ldb_options opt;
   int kcap = 0;
   long long dcap = 0;
@@ -56,7 +55,6 @@ struct gfbe_ldb : gfbe_tab_staging {
   int *word_of = nullptr, *q_word = nullptr; double *q_val = nullptr;      // [max_keyframe_descriptors]
   double *raw = nullptr; int *has = nullptr;                               // [kcap]
   int *meta = nullptr;
-  std::vector<void *> allocs;
   // exact host mirrors
   std::vector<long long> kf_begin; std::vector<int> kf_n;
   long long n_desc = 0;
@@ -298,19 +296,6 @@ __global__ __launch_bounds__(LDB_BOW_THREADS) void k_ldb_compact(int n_window, c
   if (t == 0) *n_matched = total;
 }
 
-#define LDB_CHECK(c, call)                                                                                     \
-  do {                                                                                                         \
-    hipError_t e_ = (call);                                                                                    \
-    if (e_ != hipSuccess) { ctx_set_error(c, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); return GFBE_DEVICE_ERROR; } \
-  } while (0)
-
-gfbe_status ldb_ready(gfbe_ctx *c, gfbe_ldb *m, const char *who) {
-  if (!c) return GFBE_BAD_INPUT;
-  if (ctx_device(c) < 0) { ctx_set_error(c, (std::string(who) + ": HIP device context required (no CPU fallback)").c_str()); return GFBE_NO_DEVICE; }
-  if (!m) return GFBE_BAD_INPUT;
-  if (m->owner != c) { ctx_set_error(c, (std::string(who) + ": the handle belongs to another context").c_str()); return GFBE_BAD_INPUT; }
-  return GFBE_OK;
-}
 const char *ldb_options_error(const gfbe_ldb_options *o) {
   if (o->struct_size != (int32_t)sizeof(gfbe_ldb_options)) return "gfbe_ldb_options.struct_size does not match this library (ABI mismatch)";
   if (o->max_results < 1 || o->max_results > LDB_MAX_RESULTS) return "max_results outside 1 .. 16";
@@ -346,13 +331,7 @@ void gfbe_ldb_default_options(gfbe_ldb_options *o) {
 
 void gfbe_ldb_destroy(gfbe_ctx *c, gfbe_ldb *m) {
   if (!m) return;
-  if (c && ctx_device(c) >= 0) (void)hipStreamSynchronize(ctx_stream(c));
-  for (void *p : m->allocs) (void)hipFree(p);
-  if (m->stage_d) (void)hipFree(m->stage_d);
-  if (m->stage_h) (void)hipHostFree(m->stage_h);
-  if (m->ring_d) (void)hipFree(m->ring_d);
-  if (m->ring_h) (void)hipHostFree(m->ring_h);
-  for (hipEvent_t e : m->ring_ev) if (e) (void)hipEventDestroy(e);
+  m->release(c);
   delete m;
 }
 
@@ -372,42 +351,32 @@ gfbe_status gfbe_ldb_create(gfbe_ctx *c, const gfbe_ldb_vocab *voc, int32_t keyf
   if (const int bad = ldb_plan_vocab(vin, ctx_device(c) < 0 ? nullptr : &T)) { ctx_set_error(c, (std::string("gfbe_ldb_create: vocabulary: ") + ldb_vocab_error(bad)).c_str()); return GFBE_BAD_INPUT; }
   if (ctx_device(c) < 0) { ctx_set_error(c, "gfbe_ldb_create: HIP device context required (no CPU fallback)"); return GFBE_NO_DEVICE; }
   gfbe_ldb *m = new gfbe_ldb();
-  struct Guard { gfbe_ctx *c; gfbe_ldb *m; bool armed = true; ~Guard() { if (armed) gfbe_ldb_destroy(c, m); } } guard{c, m};
+  CreateGuard<gfbe_ldb> guard{c, m, gfbe_ldb_destroy};
   m->owner = c; m->opt = o; m->kcap = keyframe_capacity; m->dcap = descriptor_capacity;
   const size_t N = (size_t)voc->n_nodes + 1, K = (size_t)keyframe_capacity, D = (size_t)descriptor_capacity, Q = (size_t)o.max_keyframe_descriptors;
   hipStream_t st = ctx_stream(c);
-  auto alloc = [&](auto **p, size_t n) {
-    void *q = nullptr;
-    if (hipMalloc(&q, n * sizeof(**p)) != hipSuccess) return false;
-    m->allocs.push_back(q);
-    *p = (std::remove_reference_t<decltype(**p)> *)q;
-    return hipMemsetAsync(q, 0, n * sizeof(**p), st) == hipSuccess;
-  };
-  bool ok = alloc(&m->t_desc, 4 * N) && alloc(&m->t_child_begin, N) && alloc(&m->t_child_count, N) && alloc(&m->t_child, N) && alloc(&m->t_word, N) &&
-            alloc(&m->t_word_weight, (size_t)T.n_words) && alloc(&m->bow_word, D) && alloc(&m->bow_val, D) && alloc(&m->desc, 4 * D) && alloc(&m->pts, 2 * D) &&
-            alloc(&m->ptsn, 2 * D) && alloc(&m->ent, 4 * K) && alloc(&m->word_of, Q) && alloc(&m->q_word, Q) && alloc(&m->q_val, Q) && alloc(&m->raw, K) && alloc(&m->has, K) &&
-            alloc(&m->meta, (size_t)LM_META);
+  bool ok = m->alloc(&m->t_desc, 4 * N) && m->alloc(&m->t_child_begin, N) && m->alloc(&m->t_child_count, N) && m->alloc(&m->t_child, N) && m->alloc(&m->t_word, N) &&
+            m->alloc(&m->t_word_weight, (size_t)T.n_words) && m->alloc(&m->bow_word, D) && m->alloc(&m->bow_val, D) && m->alloc(&m->desc, 4 * D) && m->alloc(&m->pts, 2 * D) &&
+            m->alloc(&m->ptsn, 2 * D) && m->alloc(&m->ent, 4 * K) && m->alloc(&m->word_of, Q) && m->alloc(&m->q_word, Q) && m->alloc(&m->q_val, Q) && m->alloc(&m->raw, K) && m->alloc(&m->has, K) &&
+            m->alloc(&m->meta, (size_t)LM_META);
   if (!ok) { ctx_set_error(c, "gfbe_ldb_create: device allocation failed"); return GFBE_DEVICE_ERROR; }
   std::vector<double> word_weight((size_t)T.n_words, 0.0);
   for (size_t id = 1; id < N; id++) if (T.word[id] >= 0) word_weight[(size_t)T.word[id]] = T.weight[id];
-  LDB_CHECK(c, hipMemcpyAsync(m->t_desc, T.desc.data(), sizeof(uint64_t) * 4 * N, hipMemcpyHostToDevice, st));
-  LDB_CHECK(c, hipMemcpyAsync(m->t_child_begin, T.child_begin.data(), sizeof(int) * N, hipMemcpyHostToDevice, st));
-  LDB_CHECK(c, hipMemcpyAsync(m->t_child_count, T.child_count.data(), sizeof(int) * N, hipMemcpyHostToDevice, st));
-  LDB_CHECK(c, hipMemcpyAsync(m->t_child, T.child.data(), sizeof(int) * (N - 1), hipMemcpyHostToDevice, st));
-  LDB_CHECK(c, hipMemcpyAsync(m->t_word, T.word.data(), sizeof(int) * N, hipMemcpyHostToDevice, st));
-  LDB_CHECK(c, hipMemcpyAsync(m->t_word_weight, word_weight.data(), sizeof(double) * (size_t)T.n_words, hipMemcpyHostToDevice, st));
-  { Staged warm(c, m, 1 << 16); if (!warm.ok) { ctx_set_error(c, "gfbe_ldb_create: staging allocation failed"); return GFBE_DEVICE_ERROR; } }
-  LDB_CHECK(c, hipMalloc((void **)&m->ring_d, (size_t)gfbe_ldb::RING * gfbe_ldb::RING_SLOT));
-  LDB_CHECK(c, hipHostMalloc((void **)&m->ring_h, (size_t)gfbe_ldb::RING * gfbe_ldb::RING_SLOT));
-  for (int k = 0; k < gfbe_ldb::RING; k++) LDB_CHECK(c, hipEventCreateWithFlags(&m->ring_ev[k], hipEventDisableTiming));
-  LDB_CHECK(c, hipStreamSynchronize(st));      // (the host vectors of the tree leave scope)
+  GFBE_CHECK(c, hipMemcpyAsync(m->t_desc, T.desc.data(), sizeof(uint64_t) * 4 * N, hipMemcpyHostToDevice, st));
+  GFBE_CHECK(c, hipMemcpyAsync(m->t_child_begin, T.child_begin.data(), sizeof(int) * N, hipMemcpyHostToDevice, st));
+  GFBE_CHECK(c, hipMemcpyAsync(m->t_child_count, T.child_count.data(), sizeof(int) * N, hipMemcpyHostToDevice, st));
+  GFBE_CHECK(c, hipMemcpyAsync(m->t_child, T.child.data(), sizeof(int) * (N - 1), hipMemcpyHostToDevice, st));
+  GFBE_CHECK(c, hipMemcpyAsync(m->t_word, T.word.data(), sizeof(int) * N, hipMemcpyHostToDevice, st));
+  GFBE_CHECK(c, hipMemcpyAsync(m->t_word_weight, word_weight.data(), sizeof(double) * (size_t)T.n_words, hipMemcpyHostToDevice, st));
+  if (!m->make_staging(c, "gfbe_ldb_create", 1 << 16, true)) return GFBE_DEVICE_ERROR;
+  GFBE_CHECK(c, hipStreamSynchronize(st));      // (the host vectors of the tree leave scope)
   guard.armed = false;
   *out = m;
   return GFBE_OK;
 }
 
 gfbe_status gfbe_ldb_transform(gfbe_ctx *c, gfbe_ldb *m, int32_t n, const uint64_t *desc, int32_t *word_out, int32_t *n_bow, int32_t *bow_word, double *bow_value) {
-  gfbe_status rc = ldb_ready(c, m, "gfbe_ldb_transform");
+  gfbe_status rc = handle_ready(c, m, "gfbe_ldb_transform");
   if (rc != GFBE_OK) return rc;
   if (n < 0 || n > m->opt.max_keyframe_descriptors || (n > 0 && !desc)) { ctx_set_error(c, "gfbe_ldb_transform: n outside 0 .. max_keyframe_descriptors or desc NULL"); return GFBE_BAD_INPUT; }
   const size_t N = (size_t)n;
@@ -424,18 +393,18 @@ gfbe_status gfbe_ldb_transform(gfbe_ctx *c, gfbe_ldb *m, int32_t n, const uint64
     sg.down(word_out, (const int32_t *)m->word_of, N);
     sg.finish();
   }
-  LDB_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   if (n_bow) *n_bow = hres.n_bow;
   hipStream_t st = ctx_stream(c);
-  if (hres.n_bow > 0 && bow_word) LDB_CHECK(c, hipMemcpyAsync(bow_word, m->q_word, sizeof(int) * (size_t)hres.n_bow, hipMemcpyDeviceToHost, st));
-  if (hres.n_bow > 0 && bow_value) LDB_CHECK(c, hipMemcpyAsync(bow_value, m->q_val, sizeof(double) * (size_t)hres.n_bow, hipMemcpyDeviceToHost, st));
-  LDB_CHECK(c, hipStreamSynchronize(st));
+  if (hres.n_bow > 0 && bow_word) GFBE_CHECK(c, hipMemcpyAsync(bow_word, m->q_word, sizeof(int) * (size_t)hres.n_bow, hipMemcpyDeviceToHost, st));
+  if (hres.n_bow > 0 && bow_value) GFBE_CHECK(c, hipMemcpyAsync(bow_value, m->q_val, sizeof(double) * (size_t)hres.n_bow, hipMemcpyDeviceToHost, st));
+  GFBE_CHECK(c, hipStreamSynchronize(st));
   return GFBE_OK;
 }
 
 gfbe_status gfbe_ldb_add_keyframe(gfbe_ctx *c, gfbe_ldb *m, int32_t n, const uint64_t *desc, const float *pts, const float *pts_norm, int32_t detect_loop, int32_t *index_out,
                                   int32_t *loop_index, int32_t *n_results, int32_t *result_id, double *result_score) {
-  gfbe_status rc = ldb_ready(c, m, "gfbe_ldb_add_keyframe");
+  gfbe_status rc = handle_ready(c, m, "gfbe_ldb_add_keyframe");
   if (rc != GFBE_OK) return rc;
   if (n < 0 || n > m->opt.max_keyframe_descriptors || (n > 0 && (!desc || !pts || !pts_norm))) {
     ctx_set_error(c, "gfbe_ldb_add_keyframe: n outside 0 .. max_keyframe_descriptors or a NULL input array");
@@ -447,7 +416,7 @@ gfbe_status gfbe_ldb_add_keyframe(gfbe_ctx *c, gfbe_ldb *m, int32_t n, const uin
   const int frame_index = (int)m->kf_n.size();
   if (!ldb_fits(frame_index, m->kcap, m->n_desc, m->dcap, n)) {      // refused whole and counted; nobody waits
     hipLaunchKernelGGL(k_ldb_refuse, dim3(1), dim3(1), 0, st, m->meta);
-    LDB_CHECK(c, hipGetLastError());
+    GFBE_CHECK(c, hipGetLastError());
     if (index_out) *index_out = -1;
     return GFBE_OK;
   }
@@ -478,7 +447,7 @@ gfbe_status gfbe_ldb_add_keyframe(gfbe_ctx *c, gfbe_ldb *m, int32_t n, const uin
     sg.finish();      // detecting: the one wait, for the results; otherwise the slot's event
   }
   m->kf_begin.push_back(m->n_desc); m->kf_n.push_back(n); m->n_desc += n;
-  LDB_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   if (index_out) *index_out = frame_index;
   if (detect_loop) {
     if (loop_index) *loop_index = hres.loop_index;
@@ -490,7 +459,7 @@ gfbe_status gfbe_ldb_add_keyframe(gfbe_ctx *c, gfbe_ldb *m, int32_t n, const uin
 
 gfbe_status gfbe_ldb_match(gfbe_ctx *c, gfbe_ldb *m, int32_t old_index, int32_t n_window, const uint64_t *window_desc, uint8_t *status, int32_t *best_index, int32_t *best_dist,
                            int32_t *n_matched, int32_t *matched_src, float *matched_pt, float *matched_pt_norm) {
-  gfbe_status rc = ldb_ready(c, m, "gfbe_ldb_match");
+  gfbe_status rc = handle_ready(c, m, "gfbe_ldb_match");
   if (rc != GFBE_OK) return rc;
   if (old_index < 0 || old_index >= (int)m->kf_n.size()) { ctx_set_error(c, "gfbe_ldb_match: old_index is not a held keyframe"); return GFBE_BAD_INPUT; }
   if (n_window < 0 || n_window > LDB_MAX_WINDOW || (n_window > 0 && !window_desc)) { ctx_set_error(c, "gfbe_ldb_match: n_window outside 0 .. 2^20 or window_desc NULL"); return GFBE_BAD_INPUT; }
@@ -527,39 +496,39 @@ gfbe_status gfbe_ldb_match(gfbe_ctx *c, gfbe_ldb *m, int32_t old_index, int32_t 
     if (matched_pt) std::memcpy(matched_pt, pt_h.data(), sizeof(float) * 2 * (size_t)hn);
     if (matched_pt_norm) std::memcpy(matched_pt_norm, ptn_h.data(), sizeof(float) * 2 * (size_t)hn);
   }
-  LDB_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   if (n_matched) *n_matched = hn;
   return GFBE_OK;
 }
 
 gfbe_status gfbe_ldb_size(gfbe_ctx *c, gfbe_ldb *m, int32_t *counts) {
-  gfbe_status rc = ldb_ready(c, m, "gfbe_ldb_size");
+  gfbe_status rc = handle_ready(c, m, "gfbe_ldb_size");
   if (rc != GFBE_OK) return rc;
   int h[LM_META];
-  LDB_CHECK(c, hipMemcpyAsync(h, m->meta, sizeof h, hipMemcpyDeviceToHost, ctx_stream(c)));
-  LDB_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
+  GFBE_CHECK(c, hipMemcpyAsync(h, m->meta, sizeof h, hipMemcpyDeviceToHost, ctx_stream(c)));
+  GFBE_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
   if (counts) for (int a = 0; a < GFBE_LDB_N_COUNTS; a++) counts[a] = h[a];
   return GFBE_OK;
 }
 
 gfbe_status gfbe_ldb_download_entry(gfbe_ctx *c, gfbe_ldb *m, int32_t e, int32_t *n_bow, int32_t *bow_word, double *bow_value, int32_t *n_desc, uint64_t *desc, float *pts,
                                     float *pts_norm) {
-  gfbe_status rc = ldb_ready(c, m, "gfbe_ldb_download_entry");
+  gfbe_status rc = handle_ready(c, m, "gfbe_ldb_download_entry");
   if (rc != GFBE_OK) return rc;
   if (e < 0 || e >= (int)m->kf_n.size()) { ctx_set_error(c, "gfbe_ldb_download_entry: no such entry"); return GFBE_BAD_INPUT; }
   hipStream_t st = ctx_stream(c);
   long long row[4];
-  LDB_CHECK(c, hipMemcpyAsync(row, m->ent + 4 * (size_t)e, sizeof row, hipMemcpyDeviceToHost, st));
-  LDB_CHECK(c, hipStreamSynchronize(st));
+  GFBE_CHECK(c, hipMemcpyAsync(row, m->ent + 4 * (size_t)e, sizeof row, hipMemcpyDeviceToHost, st));
+  GFBE_CHECK(c, hipStreamSynchronize(st));
   const size_t nb = (size_t)row[1], nd = (size_t)row[3];
   if (n_bow) *n_bow = (int32_t)nb;
   if (n_desc) *n_desc = (int32_t)nd;
-  if (nb && bow_word) LDB_CHECK(c, hipMemcpyAsync(bow_word, m->bow_word + row[0], sizeof(int) * nb, hipMemcpyDeviceToHost, st));
-  if (nb && bow_value) LDB_CHECK(c, hipMemcpyAsync(bow_value, m->bow_val + row[0], sizeof(double) * nb, hipMemcpyDeviceToHost, st));
-  if (nd && desc) LDB_CHECK(c, hipMemcpyAsync(desc, m->desc + 4 * row[2], sizeof(uint64_t) * 4 * nd, hipMemcpyDeviceToHost, st));
-  if (nd && pts) LDB_CHECK(c, hipMemcpyAsync(pts, m->pts + 2 * row[2], sizeof(float) * 2 * nd, hipMemcpyDeviceToHost, st));
-  if (nd && pts_norm) LDB_CHECK(c, hipMemcpyAsync(pts_norm, m->ptsn + 2 * row[2], sizeof(float) * 2 * nd, hipMemcpyDeviceToHost, st));
-  LDB_CHECK(c, hipStreamSynchronize(st));
+  if (nb && bow_word) GFBE_CHECK(c, hipMemcpyAsync(bow_word, m->bow_word + row[0], sizeof(int) * nb, hipMemcpyDeviceToHost, st));
+  if (nb && bow_value) GFBE_CHECK(c, hipMemcpyAsync(bow_value, m->bow_val + row[0], sizeof(double) * nb, hipMemcpyDeviceToHost, st));
+  if (nd && desc) GFBE_CHECK(c, hipMemcpyAsync(desc, m->desc + 4 * row[2], sizeof(uint64_t) * 4 * nd, hipMemcpyDeviceToHost, st));
+  if (nd && pts) GFBE_CHECK(c, hipMemcpyAsync(pts, m->pts + 2 * row[2], sizeof(float) * 2 * nd, hipMemcpyDeviceToHost, st));
+  if (nd && pts_norm) GFBE_CHECK(c, hipMemcpyAsync(pts_norm, m->ptsn + 2 * row[2], sizeof(float) * 2 * nd, hipMemcpyDeviceToHost, st));
+  GFBE_CHECK(c, hipStreamSynchronize(st));
   return GFBE_OK;
 }
 

@@ -322,22 +322,22 @@ extern "C" gfbe_status gfbe_line_eval(gfbe_ctx *c, int32_t n, const double *pose
   const size_t np = (size_t)7 * n, no = (size_t)4 * n, nr = (size_t)2 * n, nj = (size_t)14 * n, nk = (size_t)8 * n;
   double *dpose, *dex, *dorth, *dobs, *dr, *djp, *dje, *djo, *dc;
   std::vector<double> hc(n);
-  LINE_CHECK(c, hipMalloc((void **)&d, sizeof(double) * (np + 7 + 2 * no + nr + 2 * nj + nk + n)));
+  GFBE_CHECK_DONE(c, hipMalloc((void **)&d, sizeof(double) * (np + 7 + 2 * no + nr + 2 * nj + nk + n)));
   dpose = d; dex = dpose + np; dorth = dex + 7; dobs = dorth + no; dr = dobs + no; djp = dr + nr; dje = djp + nj; djo = dje + nj; dc = djo + nk;
-  LINE_CHECK(c, hipMemcpyAsync(dpose, pose, sizeof(double) * np, hipMemcpyHostToDevice, s));
-  LINE_CHECK(c, hipMemcpyAsync(dex, ex_cam, sizeof(double) * 7, hipMemcpyHostToDevice, s));
-  LINE_CHECK(c, hipMemcpyAsync(dorth, orth, sizeof(double) * no, hipMemcpyHostToDevice, s));
-  LINE_CHECK(c, hipMemcpyAsync(dobs, obs, sizeof(double) * no, hipMemcpyHostToDevice, s));
+  GFBE_CHECK_DONE(c, hipMemcpyAsync(dpose, pose, sizeof(double) * np, hipMemcpyHostToDevice, s));
+  GFBE_CHECK_DONE(c, hipMemcpyAsync(dex, ex_cam, sizeof(double) * 7, hipMemcpyHostToDevice, s));
+  GFBE_CHECK_DONE(c, hipMemcpyAsync(dorth, orth, sizeof(double) * no, hipMemcpyHostToDevice, s));
+  GFBE_CHECK_DONE(c, hipMemcpyAsync(dobs, obs, sizeof(double) * no, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_line_eval, dim3((n + 255) / 256), dim3(256), 0, s, n, dpose, dex, dorth, dobs, sqrt_info, robustify ? 1 : 0,
                      r ? dr : nullptr, J_pose ? djp : nullptr, J_ex ? dje : nullptr, J_orth ? djo : nullptr, dc);
-  LINE_CHECK(c, hipGetLastError());
-  LINE_CHECK(c, hipMemcpyAsync(hc.data(), dc, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-  LINE_CHECK(c, hipStreamSynchronize(s));
+  GFBE_CHECK_DONE(c, hipGetLastError());
+  GFBE_CHECK_DONE(c, hipMemcpyAsync(hc.data(), dc, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+  GFBE_CHECK_DONE(c, hipStreamSynchronize(s));
   // (outputs are written only once the whole evaluation has succeeded)
-  if (r) LINE_CHECK(c, hipMemcpy(r, dr, sizeof(double) * nr, hipMemcpyDeviceToHost));
-  if (J_pose) LINE_CHECK(c, hipMemcpy(J_pose, djp, sizeof(double) * nj, hipMemcpyDeviceToHost));
-  if (J_ex) LINE_CHECK(c, hipMemcpy(J_ex, dje, sizeof(double) * nj, hipMemcpyDeviceToHost));
-  if (J_orth) LINE_CHECK(c, hipMemcpy(J_orth, djo, sizeof(double) * nk, hipMemcpyDeviceToHost));
+  if (r) GFBE_CHECK_DONE(c, hipMemcpy(r, dr, sizeof(double) * nr, hipMemcpyDeviceToHost));
+  if (J_pose) GFBE_CHECK_DONE(c, hipMemcpy(J_pose, djp, sizeof(double) * nj, hipMemcpyDeviceToHost));
+  if (J_ex) GFBE_CHECK_DONE(c, hipMemcpy(J_ex, dje, sizeof(double) * nj, hipMemcpyDeviceToHost));
+  if (J_orth) GFBE_CHECK_DONE(c, hipMemcpy(J_orth, djo, sizeof(double) * nk, hipMemcpyDeviceToHost));
   if (cost) { double tot = 0.0; for (int k = 0; k < n; k++) tot += hc[k]; *cost = tot; }
 done:
   if (d) (void)hipFree(d);
@@ -369,17 +369,17 @@ extern "C" gfbe_status gfbe_line_refine(gfbe_ctx *c, int32_t n_windows, const gf
     P.sum = a.take<gfbe_summary>(n_windows); P.keep = a.take<unsigned char>(std::max(n_lines, 1));
     return a.off;
   };
-  LINE_CHECK(c, upload_line_windows(s, n_windows, win, B, layout(nullptr), U));
+  GFBE_CHECK_DONE(c, upload_line_windows(s, n_windows, win, B, layout(nullptr), U));
   (void)layout(U.extra);
   P.L = U.L; P.sqrt_info = sqrt_info; P.cauchy = cauchy_scale; P.max_it = std::min<int>(max_num_iterations, 15);
   hipLaunchKernelGGL(k_line_refine<false>, dim3(n_windows), dim3(LR_THREADS), 0, s, P);
-  LINE_CHECK(c, hipGetLastError());
+  GFBE_CHECK_DONE(c, hipGetLastError());
   if (n_lines) {
-    LINE_CHECK(c, hipMemcpyAsync(h_out.data(), P.plk_out, b_out, hipMemcpyDeviceToHost, s));
-    LINE_CHECK(c, hipMemcpyAsync(h_keep.data(), P.keep, (size_t)n_lines, hipMemcpyDeviceToHost, s));
+    GFBE_CHECK_DONE(c, hipMemcpyAsync(h_out.data(), P.plk_out, b_out, hipMemcpyDeviceToHost, s));
+    GFBE_CHECK_DONE(c, hipMemcpyAsync(h_keep.data(), P.keep, (size_t)n_lines, hipMemcpyDeviceToHost, s));
   }
-  LINE_CHECK(c, hipMemcpyAsync(h_sum.data(), P.sum, b_sum, hipMemcpyDeviceToHost, s));
-  LINE_CHECK(c, hipStreamSynchronize(s));
+  GFBE_CHECK_DONE(c, hipMemcpyAsync(h_sum.data(), P.sum, b_sum, hipMemcpyDeviceToHost, s));
+  GFBE_CHECK_DONE(c, hipStreamSynchronize(s));
   {
     int worst = GFBE_OK;
     for (int w = 0; w < n_windows; w++) worst = std::max(worst, (int)h_sum[w].status);

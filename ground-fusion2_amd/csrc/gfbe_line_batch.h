@@ -10,15 +10,8 @@
 #include <string>
 #include <vector>
 
-#include "gfbe_device.h"
+#include "gfbe_handle.h"
 #include "gfbe_line.h"
-
-// a failed HIP call: its text into the context, GFBE_DEVICE_ERROR into the function's `st`, on to its `done:`
-#define LINE_CHECK(c, call)                                                                                    \
-  do {                                                                                                         \
-    hipError_t e_ = (call);                                                                                    \
-    if (e_ != hipSuccess) { ctx_set_error(c, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); st = GFBE_DEVICE_ERROR; goto done; } \
-  } while (0)
 
 namespace gfd {
 

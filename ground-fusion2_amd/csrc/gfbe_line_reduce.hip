@@ -318,34 +318,34 @@ gfbe_status reduce_run(gfbe_ctx *c, ReduceBatch P, int W, const std::vector<int>
     P.oV = a.take<double>(N * 10); P.ofailed = a.take<unsigned char>(N + 1);
     return a.off;
   };
-  LINE_CHECK(c, lay_out(s, buf, layout));
+  GFBE_CHECK_DONE(c, lay_out(s, buf, layout));
   if (keep) {
     keep->rec_valid = false; keep->cand_valid = false;
-    LINE_CHECK(c, lay_out(s, keep->rec_buf, keep_layout));
-    LINE_CHECK(c, hipMemcpyAsync(k_off, rec_off.data(), sizeof(int) * (W + 1), hipMemcpyHostToDevice, s));
+    GFBE_CHECK_DONE(c, lay_out(s, keep->rec_buf, keep_layout));
+    GFBE_CHECK_DONE(c, hipMemcpyAsync(k_off, rec_off.data(), sizeof(int) * (W + 1), hipMemcpyHostToDevice, s));
   }
   P.n_windows = W; P.slab_lines = (int)slab_lines;
   if (h_pose) {
-    LINE_CHECK(c, hipMemcpyAsync((void *)P.L.pose, h_pose, 8 * 77 * (size_t)W, hipMemcpyHostToDevice, s));
-    LINE_CHECK(c, hipMemcpyAsync((void *)P.L.ex, h_ex, 8 * 7 * (size_t)W, hipMemcpyHostToDevice, s));
+    GFBE_CHECK_DONE(c, hipMemcpyAsync((void *)P.L.pose, h_pose, 8 * 77 * (size_t)W, hipMemcpyHostToDevice, s));
+    GFBE_CHECK_DONE(c, hipMemcpyAsync((void *)P.L.ex, h_ex, 8 * 7 * (size_t)W, hipMemcpyHostToDevice, s));
   }
-  LINE_CHECK(c, hipMemcpyAsync(d_rec, rec_off.data(), sizeof(int) * (W + 1), hipMemcpyHostToDevice, s));
+  GFBE_CHECK_DONE(c, hipMemcpyAsync(d_rec, rec_off.data(), sizeof(int) * (W + 1), hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_line_reduce<TAB>, dim3(grid), dim3(RC_THREADS), 0, s, P);
-  LINE_CHECK(c, hipGetLastError());
-  if (out->H) LINE_CHECK(c, download(hH, P.H, n5k, s));
-  if (out->U) LINE_CHECK(c, download(hU, P.U, n5k, s));
-  if (out->g) LINE_CHECK(c, download(hg, P.g, n72, s));
-  if (out->bp) LINE_CHECK(c, download(hbp, P.bp, n72, s));
-  if (out->cost) LINE_CHECK(c, download(hcost, P.cost, (size_t)W, s));
-  if (out->ms_kernel) LINE_CHECK(c, download(hms, P.ms, 2 * (size_t)W, s));
-  LINE_CHECK(c, download(hne, P.n_elig, (size_t)W, s));
-  LINE_CHECK(c, download(hnf, P.n_failed, (size_t)W, s));
-  if (out->Vinv) LINE_CHECK(c, download(hV, P.oVinv, N * 16, s));
-  if (out->bl) LINE_CHECK(c, download(hb, P.obl, N * 4, s));
-  if (out->W) LINE_CHECK(c, download(hW, P.oW, N * RC_WROW, s));
-  if (out->failed) LINE_CHECK(c, download(hf, P.ofailed, N, s));
-  if (out->V) LINE_CHECK(c, download(hVl, P.oV, N * 10, s));
-  LINE_CHECK(c, hipStreamSynchronize(s));
+  GFBE_CHECK_DONE(c, hipGetLastError());
+  if (out->H) GFBE_CHECK_DONE(c, download(hH, P.H, n5k, s));
+  if (out->U) GFBE_CHECK_DONE(c, download(hU, P.U, n5k, s));
+  if (out->g) GFBE_CHECK_DONE(c, download(hg, P.g, n72, s));
+  if (out->bp) GFBE_CHECK_DONE(c, download(hbp, P.bp, n72, s));
+  if (out->cost) GFBE_CHECK_DONE(c, download(hcost, P.cost, (size_t)W, s));
+  if (out->ms_kernel) GFBE_CHECK_DONE(c, download(hms, P.ms, 2 * (size_t)W, s));
+  GFBE_CHECK_DONE(c, download(hne, P.n_elig, (size_t)W, s));
+  GFBE_CHECK_DONE(c, download(hnf, P.n_failed, (size_t)W, s));
+  if (out->Vinv) GFBE_CHECK_DONE(c, download(hV, P.oVinv, N * 16, s));
+  if (out->bl) GFBE_CHECK_DONE(c, download(hb, P.obl, N * 4, s));
+  if (out->W) GFBE_CHECK_DONE(c, download(hW, P.oW, N * RC_WROW, s));
+  if (out->failed) GFBE_CHECK_DONE(c, download(hf, P.ofailed, N, s));
+  if (out->V) GFBE_CHECK_DONE(c, download(hVl, P.oV, N * 10, s));
+  GFBE_CHECK_DONE(c, hipStreamSynchronize(s));
   // (outputs are written only once the whole call has succeeded)
   if (out->H) std::memcpy(out->H, hH.data(), 8 * n5k);
   if (out->U) std::memcpy(out->U, hU.data(), 8 * n5k);
@@ -396,7 +396,7 @@ extern "C" gfbe_status gfbe_line_reduce(gfbe_ctx *c, int32_t n_windows, const gf
   gfbe_status st = GFBE_OK;
   LineUpload U;
   ReduceBatch P{};
-  LINE_CHECK(c, upload_line_windows(s, n_windows, win, B, 0, U));
+  GFBE_CHECK_DONE(c, upload_line_windows(s, n_windows, win, B, 0, U));
   P.L = U.L; P.sqrt_info = sqrt_info; P.huber = huber_width; P.mu = mu; P.mode = mode;
   st = reduce_run<false>(c, P, n_windows, nlines, &full, nullptr, nullptr, nullptr);     // (synchronises the stream: the packed host buffers stay alive until then)
 done:
@@ -417,8 +417,8 @@ extern "C" gfbe_status gfbe_ltab_reduce(gfbe_ctx *c, gfbe_ltab *t, int32_t mode,
   std::vector<int> nlines(W);
   ReduceBatch P{};
   // the tables' sizes (the record slots and the scratch slab) come down first: the one wait of the call besides the results'
-  LINE_CHECK(c, hipMemcpyAsync(nlines.data(), t->d.count, sizeof(int) * W, hipMemcpyDeviceToHost, s));
-  LINE_CHECK(c, hipStreamSynchronize(s));
+  GFBE_CHECK_DONE(c, hipMemcpyAsync(nlines.data(), t->d.count, sizeof(int) * W, hipMemcpyDeviceToHost, s));
+  GFBE_CHECK_DONE(c, hipStreamSynchronize(s));
   P.L = ltab_line_list(*t, nullptr, nullptr);      // (reduce_run copies the poses up)
   P.sqrt_info = sqrt_info; P.huber = huber_width; P.mu = mu; P.mode = mode;
   st = reduce_run<true>(c, P, W, nlines, &full, pose7, ex_cam, &t->reduce_buf,

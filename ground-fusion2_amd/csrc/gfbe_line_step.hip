@@ -223,35 +223,35 @@ gfbe_status step_run(gfbe_ctx *c, StepBatch P, int W, const std::vector<int> &re
     P.invalid = a.take<unsigned char>(nw); P.n_elig = a.take<int>(nw);
     return a.off;
   };
-  LINE_CHECK(c, lay_out(s, buf, layout));
+  GFBE_CHECK_DONE(c, lay_out(s, buf, layout));
   P.n_windows = W; P.yp = d_yp; P.vp = d_vp; P.rest = d_rest; P.radius = d_radius;
-  LINE_CHECK(c, hipMemcpyAsync(d_yp, yp, 8 * nw * LS_NP, hipMemcpyHostToDevice, s));
-  LINE_CHECK(c, hipMemcpyAsync(d_vp, vp, 8 * nw * LS_NP, hipMemcpyHostToDevice, s));
-  LINE_CHECK(c, hipMemcpyAsync(d_rest, rest, 8 * nw * 8, hipMemcpyHostToDevice, s));
-  LINE_CHECK(c, hipMemcpyAsync(d_radius, radius, 8 * nw, hipMemcpyHostToDevice, s));
+  GFBE_CHECK_DONE(c, hipMemcpyAsync(d_yp, yp, 8 * nw * LS_NP, hipMemcpyHostToDevice, s));
+  GFBE_CHECK_DONE(c, hipMemcpyAsync(d_vp, vp, 8 * nw * LS_NP, hipMemcpyHostToDevice, s));
+  GFBE_CHECK_DONE(c, hipMemcpyAsync(d_rest, rest, 8 * nw * 8, hipMemcpyHostToDevice, s));
+  GFBE_CHECK_DONE(c, hipMemcpyAsync(d_radius, radius, 8 * nw, hipMemcpyHostToDevice, s));
   if (h_pose) {
     P.L.pose = d_pose; P.L.ex = d_ex;
-    LINE_CHECK(c, hipMemcpyAsync(d_pose, h_pose, 8 * 77 * nw, hipMemcpyHostToDevice, s));
-    LINE_CHECK(c, hipMemcpyAsync(d_ex, h_ex, 8 * 7 * nw, hipMemcpyHostToDevice, s));
+    GFBE_CHECK_DONE(c, hipMemcpyAsync(d_pose, h_pose, 8 * 77 * nw, hipMemcpyHostToDevice, s));
+    GFBE_CHECK_DONE(c, hipMemcpyAsync(d_ex, h_ex, 8 * 7 * nw, hipMemcpyHostToDevice, s));
   }
   if (d_rec_off) P.rec_off = d_rec_off;
-  else { P.rec_off = d_off; LINE_CHECK(c, hipMemcpyAsync(d_off, rec_off.data(), sizeof(int) * (nw + 1), hipMemcpyHostToDevice, s)); }
+  else { P.rec_off = d_off; GFBE_CHECK_DONE(c, hipMemcpyAsync(d_off, rec_off.data(), sizeof(int) * (nw + 1), hipMemcpyHostToDevice, s)); }
   if (laid) *laid = P;
   hipLaunchKernelGGL(k_line_step<TAB>, dim3(grid), dim3(LS_THREADS), 0, s, P);
-  LINE_CHECK(c, hipGetLastError());
-  if (out->gram) LINE_CHECK(c, download(hgram, P.gram, nw * 8, s));
-  if (out->total) LINE_CHECK(c, download(htotal, P.total, nw * 8, s));
-  if (out->coef) LINE_CHECK(c, download(hcoef, P.coef, nw * 4, s));
-  if (out->invalid) LINE_CHECK(c, download(hinv, P.invalid, nw, s));
-  if (out->y_l) LINE_CHECK(c, download(hyl, P.yl, N * 4, s));
-  if (out->v_l) LINE_CHECK(c, download(hvl, P.vl, N * 4, s));
-  if (out->orth_cand) LINE_CHECK(c, download(hxc, P.xc, N * 4, s));
-  if (out->plucker_cand) LINE_CHECK(c, download(hplk, P.plkc, N * 6, s));
-  if (out->pose_cand) LINE_CHECK(c, download(hpose, P.pose_c, nw * 77, s));
-  if (out->ex_cand) LINE_CHECK(c, download(hex, P.ex_c, nw * 7, s));
-  if (out->cost_cand) LINE_CHECK(c, download(hcost, P.cost, nw, s));
-  if (out->ms_kernel) LINE_CHECK(c, download(hms, P.ms, nw, s));
-  LINE_CHECK(c, hipStreamSynchronize(s));
+  GFBE_CHECK_DONE(c, hipGetLastError());
+  if (out->gram) GFBE_CHECK_DONE(c, download(hgram, P.gram, nw * 8, s));
+  if (out->total) GFBE_CHECK_DONE(c, download(htotal, P.total, nw * 8, s));
+  if (out->coef) GFBE_CHECK_DONE(c, download(hcoef, P.coef, nw * 4, s));
+  if (out->invalid) GFBE_CHECK_DONE(c, download(hinv, P.invalid, nw, s));
+  if (out->y_l) GFBE_CHECK_DONE(c, download(hyl, P.yl, N * 4, s));
+  if (out->v_l) GFBE_CHECK_DONE(c, download(hvl, P.vl, N * 4, s));
+  if (out->orth_cand) GFBE_CHECK_DONE(c, download(hxc, P.xc, N * 4, s));
+  if (out->plucker_cand) GFBE_CHECK_DONE(c, download(hplk, P.plkc, N * 6, s));
+  if (out->pose_cand) GFBE_CHECK_DONE(c, download(hpose, P.pose_c, nw * 77, s));
+  if (out->ex_cand) GFBE_CHECK_DONE(c, download(hex, P.ex_c, nw * 7, s));
+  if (out->cost_cand) GFBE_CHECK_DONE(c, download(hcost, P.cost, nw, s));
+  if (out->ms_kernel) GFBE_CHECK_DONE(c, download(hms, P.ms, nw, s));
+  GFBE_CHECK_DONE(c, hipStreamSynchronize(s));
   // (outputs are written only once the whole call has succeeded)
   if (out->gram) std::memcpy(out->gram, hgram.data(), 8 * nw * 8);
   if (out->total) std::memcpy(out->total, htotal.data(), 8 * nw * 8);
@@ -316,15 +316,15 @@ extern "C" gfbe_status gfbe_line_step(gfbe_ctx *c, int32_t n_windows, const gfbe
     P.failed = a.take<unsigned char>(N + 1);
     return a.off;
   };
-  LINE_CHECK(c, upload_line_windows(s, n_windows, win, B, layout(nullptr), U));
+  GFBE_CHECK_DONE(c, upload_line_windows(s, n_windows, win, B, layout(nullptr), U));
   (void)layout(U.extra);
   P.L = U.L; P.sqrt_info = sqrt_info; P.huber = huber_width;
   if (N) {
-    LINE_CHECK(c, hipMemcpyAsync((void *)P.Vinv, rec->Vinv, 8 * N * 16, hipMemcpyHostToDevice, s));
-    LINE_CHECK(c, hipMemcpyAsync((void *)P.bl, rec->bl, 8 * N * 4, hipMemcpyHostToDevice, s));
-    LINE_CHECK(c, hipMemcpyAsync((void *)P.W, rec->W, 8 * N * LS_WROW, hipMemcpyHostToDevice, s));
-    LINE_CHECK(c, hipMemcpyAsync((void *)P.V, rec->V, 8 * N * 10, hipMemcpyHostToDevice, s));
-    LINE_CHECK(c, hipMemcpyAsync((void *)P.failed, rec->failed, N, hipMemcpyHostToDevice, s));
+    GFBE_CHECK_DONE(c, hipMemcpyAsync((void *)P.Vinv, rec->Vinv, 8 * N * 16, hipMemcpyHostToDevice, s));
+    GFBE_CHECK_DONE(c, hipMemcpyAsync((void *)P.bl, rec->bl, 8 * N * 4, hipMemcpyHostToDevice, s));
+    GFBE_CHECK_DONE(c, hipMemcpyAsync((void *)P.W, rec->W, 8 * N * LS_WROW, hipMemcpyHostToDevice, s));
+    GFBE_CHECK_DONE(c, hipMemcpyAsync((void *)P.V, rec->V, 8 * N * 10, hipMemcpyHostToDevice, s));
+    GFBE_CHECK_DONE(c, hipMemcpyAsync((void *)P.failed, rec->failed, N, hipMemcpyHostToDevice, s));
   }
   st = step_run<false>(c, P, n_windows, rec_off, B.entering, y_p, v_p, rest, radius, nullptr, nullptr, nullptr, out, nullptr);   // (synchronises the stream)
 done:

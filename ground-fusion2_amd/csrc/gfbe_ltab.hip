@@ -22,7 +22,7 @@
 #include "gfbe_device.h"
 #include "gfbe_line.h"
 #include "gfbe_line_batch.h"
-#include "gfbe_tabstage.h"
+#include "gfbe_handle.h"
 
 using namespace gfd;
 
@@ -234,26 +234,7 @@ __global__ __launch_bounds__(256) void k_ltab_line_count(LtabDev T, int cur, int
   if (threadIdx.x == 0) count_out[w] = s_cnt;
 }
 
-#define LT_CHECK(c, call)                                                                                      \
-  do {                                                                                                         \
-    hipError_t e_ = (call);                                                                                    \
-    if (e_ != hipSuccess) { ctx_set_error(c, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); return GFBE_DEVICE_ERROR; } \
-  } while (0)
-
-template <typename T>
-gfbe_status lt_alloc(gfbe_ctx *c, gfbe_ltab *t, T **p, size_t n) {
-  void *q = nullptr;
-  LT_CHECK(c, hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
-  t->allocs.push_back(q);
-  LT_CHECK(c, hipMemsetAsync(q, 0, std::max<size_t>(n, 1) * sizeof(T), ctx_stream(c)));
-  *p = (T *)q;
-  return GFBE_OK;
-}
-gfbe_status lt_ready(gfbe_ctx *c, gfbe_ltab *t) {
-  if (!c || !t) return GFBE_BAD_INPUT;
-  if (ctx_device(c) < 0) return GFBE_NO_DEVICE;
-  return GFBE_OK;
-}
+gfbe_status lt_ready(gfbe_ctx *c, gfbe_ltab *t) { return t ? handle_device(c, t, "gfbe_ltab") : GFBE_BAD_INPUT; }
 // the survivor scan and the copy into the other half; the halves swap
 void lt_erase_launch(gfbe_ctx *c, gfbe_ltab *t, int op, const int *iarg, const double *da, const double *db) {
   const int W = t->d.W;
@@ -274,7 +255,7 @@ gfbe_status lt_erase(gfbe_ctx *c, gfbe_ltab *t, int op, const double *a, const d
     s.flush();
     lt_erase_launch(c, t, op, di, da, db);
   }
-  LT_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   return GFBE_OK;
 }
 
@@ -289,23 +270,20 @@ gfbe_status gfbe_ltab_create(gfbe_ctx *c, int32_t n_tables, int32_t cap, gfbe_lt
   if (ctx_device(c) < 0) { ctx_set_error(c, "gfbe_ltab_create: HIP device context required (no CPU fallback)"); return GFBE_NO_DEVICE; }
   gfbe_ltab *t = new gfbe_ltab();
   // (a failed allocation leaves nothing behind: the table built so far is destroyed and *out stays null)
-  struct Guard { gfbe_ctx *c; gfbe_ltab *t; bool armed = true; ~Guard() { if (armed) gfbe_ltab_destroy(c, t); } } guard{c, t};
+  CreateGuard<gfbe_ltab> guard{c, t, gfbe_ltab_destroy};
+  t->owner = c;
   LtabDev &d = t->d;
   d.W = n_tables; d.F = cap;
   const size_t N = (size_t)n_tables * cap;
-  gfbe_status st;
-#define LA(p, n) if ((st = lt_alloc(c, t, &p, n)) != GFBE_OK) return st
+#define LA(p, n) if (!t->alloc(&p, n)) return GFBE_DEVICE_ERROR
   LA(d.count, n_tables); LA(d.err, n_tables); LA(d.cnt_scratch, n_tables); LA(d.keep, N); LA(d.dst, N);
   LA(d.row, N * line_refine_row_doubles()); LA(d.plk_out, N * 6); LA(d.rkeep, N);
   for (int b = 0; b < 2; b++) {
     LA(d.id[b], N); LA(d.start[b], N); LA(d.nobs[b], N); LA(d.tri[b], N); LA(d.plk[b], N * 6); LA(d.obs[b], N * NOBS * OW);
   }
 #undef LA
-  { Staged warm(c, t, (size_t)n_tables * (sizeof(gfbe_summary) + 1024)); if (!warm.ok) { ctx_set_error(c, "gfbe_ltab_create: staging allocation failed"); return GFBE_DEVICE_ERROR; } }
-  LT_CHECK(c, hipMalloc((void **)&t->ring_d, (size_t)gfbe_ltab::RING * gfbe_ltab::RING_SLOT));
-  LT_CHECK(c, hipHostMalloc((void **)&t->ring_h, (size_t)gfbe_ltab::RING * gfbe_ltab::RING_SLOT));
-  for (int k = 0; k < gfbe_ltab::RING; k++) LT_CHECK(c, hipEventCreateWithFlags(&t->ring_ev[k], hipEventDisableTiming));
-  LT_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
+  if (!t->make_staging(c, "gfbe_ltab_create", (size_t)n_tables * (sizeof(gfbe_summary) + 1024), true)) return GFBE_DEVICE_ERROR;
+  GFBE_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
   guard.armed = false;
   *out = t;
   return GFBE_OK;
@@ -313,15 +291,9 @@ gfbe_status gfbe_ltab_create(gfbe_ctx *c, int32_t n_tables, int32_t cap, gfbe_lt
 
 void gfbe_ltab_destroy(gfbe_ctx *c, gfbe_ltab *t) {
   if (!t) return;
-  if (c && ctx_device(c) >= 0) (void)hipStreamSynchronize(ctx_stream(c));
-  for (void *p : t->allocs) (void)hipFree(p);
+  t->release(c);
   for (const DevBuf *b : {&t->reduce_buf, &t->rec_buf, &t->step_buf})
     if (b->d) (void)hipFree(b->d);
-  if (t->stage_d) (void)hipFree(t->stage_d);
-  if (t->stage_h) (void)hipHostFree(t->stage_h);
-  if (t->ring_d) (void)hipFree(t->ring_d);
-  if (t->ring_h) (void)hipHostFree(t->ring_h);
-  for (hipEvent_t e : t->ring_ev) if (e) (void)hipEventDestroy(e);
   delete t;
 }
 
@@ -355,7 +327,7 @@ gfbe_status gfbe_ltab_add_frame(gfbe_ctx *c, gfbe_ltab *t, const int32_t *frame_
     (void)hipMemcpyAsync(derr, t->d.err, sizeof(int) * W, hipMemcpyDeviceToDevice, ctx_stream(c));
     s.down(counters, dcnt, 2 * (size_t)W); s.down(err.data(), derr, W);
   }
-  LT_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   for (int w = 0; w < W; w++)
     if (err[w]) { ctx_set_error(c, err[w] & 1 ? "line table capacity exceeded" : "a line received more than WINDOW_SIZE + 1 observations"); return GFBE_BAD_INPUT; }
   return GFBE_OK;
@@ -374,7 +346,7 @@ gfbe_status gfbe_ltab_triangulate(gfbe_ctx *c, gfbe_ltab *t, const double *poses
     s.flush();
     hipLaunchKernelGGL(k_ltab_triangulate, dim3((t->d.F + 255) / 256, W), dim3(256), 0, ctx_stream(c), t->d, t->cur, dp, de);
   }
-  LT_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   return GFBE_OK;
 }
 
@@ -407,7 +379,7 @@ gfbe_status gfbe_ltab_refine(gfbe_ctx *c, gfbe_ltab *t, const double *pose7, con
     lt_erase_launch(c, t, OP_REFINE, nullptr, nullptr, nullptr);
     s.down(h_sum.data(), dsum, W);
   }
-  LT_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   int worst = GFBE_OK;
   for (int w = 0; w < W; w++) worst = std::max(worst, (int)h_sum[w].status);
   std::memcpy(summary, h_sum.data(), sizeof(gfbe_summary) * (size_t)W);
@@ -418,8 +390,8 @@ gfbe_status gfbe_ltab_size(gfbe_ctx *c, gfbe_ltab *t, int32_t *n) {
   gfbe_status st = lt_ready(c, t);
   if (st != GFBE_OK) return st;
   if (!n) return GFBE_BAD_INPUT;
-  LT_CHECK(c, hipMemcpyAsync(t->stage_h, t->d.count, sizeof(int) * t->d.W, hipMemcpyDeviceToHost, ctx_stream(c)));   // (through the pinned mirror)
-  LT_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
+  GFBE_CHECK(c, hipMemcpyAsync(t->stage_h, t->d.count, sizeof(int) * t->d.W, hipMemcpyDeviceToHost, ctx_stream(c)));   // (through the pinned mirror)
+  GFBE_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
   std::memcpy(n, t->stage_h, sizeof(int) * t->d.W);
   return GFBE_OK;
 }
@@ -436,7 +408,7 @@ gfbe_status gfbe_ltab_line_count(gfbe_ctx *c, gfbe_ltab *t, int32_t *count) {
     hipLaunchKernelGGL(k_ltab_line_count, dim3(W), dim3(256), 0, ctx_stream(c), t->d, t->cur, dcnt);
     s.down(count, dcnt, W);
   }
-  LT_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   return GFBE_OK;
 }
 
@@ -446,17 +418,17 @@ gfbe_status gfbe_ltab_download(gfbe_ctx *c, gfbe_ltab *t, int32_t w, int32_t *id
   if (st != GFBE_OK) return st;
   if (w < 0 || w >= t->d.W) return GFBE_BAD_INPUT;
   hipStream_t s = ctx_stream(c);
-  LT_CHECK(c, hipMemcpyAsync(t->stage_h, t->d.count + w, sizeof(int), hipMemcpyDeviceToHost, s));
-  LT_CHECK(c, hipStreamSynchronize(s));
+  GFBE_CHECK(c, hipMemcpyAsync(t->stage_h, t->d.count + w, sizeof(int), hipMemcpyDeviceToHost, s));
+  GFBE_CHECK(c, hipStreamSynchronize(s));
   const int n = *(const int *)t->stage_h;
   const size_t base = (size_t)w * t->d.F;
   const int b = t->cur;
-#define DN(h, dptr, cnt) if (h && n) LT_CHECK(c, hipMemcpyAsync(h, dptr, sizeof(*h) * (cnt), hipMemcpyDeviceToHost, s))
+#define DN(h, dptr, cnt) if (h && n) GFBE_CHECK(c, hipMemcpyAsync(h, dptr, sizeof(*h) * (cnt), hipMemcpyDeviceToHost, s))
   DN(id, t->d.id[b] + base, (size_t)n); DN(start, t->d.start[b] + base, (size_t)n); DN(nobs, t->d.nobs[b] + base, (size_t)n);
   DN(tri, t->d.tri[b] + base, (size_t)n); DN(plk, t->d.plk[b] + base * 6, (size_t)n * 6);
   DN(obs4, t->d.obs[b] + base * NOBS * OW, (size_t)n * NOBS * OW);
 #undef DN
-  LT_CHECK(c, hipStreamSynchronize(s));
+  GFBE_CHECK(c, hipStreamSynchronize(s));
   return GFBE_OK;
 }
 
@@ -489,14 +461,14 @@ gfbe_status gfbe_ltab_upload(gfbe_ctx *c, gfbe_ltab *t, int32_t w, int32_t n, co
     }
     s.flush();
     hipStream_t q = ctx_stream(c);
-#define UP(dptr, src, cnt) if (n) LT_CHECK(c, hipMemcpyAsync(dptr, src, sizeof(*src) * (cnt), hipMemcpyDeviceToDevice, q))
+#define UP(dptr, src, cnt) if (n) GFBE_CHECK(c, hipMemcpyAsync(dptr, src, sizeof(*src) * (cnt), hipMemcpyDeviceToDevice, q))
     UP(t->d.id[b] + base, did, (size_t)n); UP(t->d.start[b] + base, dst, (size_t)n); UP(t->d.nobs[b] + base, dno, (size_t)n);
     UP(t->d.tri[b] + base, dtri, (size_t)n); UP(t->d.plk[b] + base * 6, dplk, (size_t)n * 6);
     UP(t->d.obs[b] + base * NOBS * OW, dobs, (size_t)n * NOBS * OW);
 #undef UP
-    LT_CHECK(c, hipMemcpyAsync(t->d.count + w, dn, sizeof(int), hipMemcpyDeviceToDevice, q));
+    GFBE_CHECK(c, hipMemcpyAsync(t->d.count + w, dn, sizeof(int), hipMemcpyDeviceToDevice, q));
   }
-  LT_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   return GFBE_OK;
 }
 

@@ -26,15 +26,14 @@
 #include "gfbe_device.h"
 #include "gfbe_klt_priv.h"
 #include "gfbe_obs.h"
-#include "gfbe_tabstage.h"
+#include "gfbe_handle.h"
 
 using namespace gfd;
 
 static_assert(OBS_MAX_POINTS == GFBE_DET_MAX_POINTS, "the header's bound");
 static_assert(OBS_OW == FT_OW, "a row of the frame is a row of the tables");
 
-struct gfbe_obs {
-  gfbe_ctx *owner = nullptr;
+struct gfbe_obs : gfbe_handle {
   gfbe_klt *trk = nullptr;
   gfbe_obs_options opt;
   ObsCam *cams = nullptr;                      // [n_cam]
@@ -53,7 +52,6 @@ struct gfbe_obs {
   int phalf = 0;
   bool has_time = false;
   std::vector<double> prev_time;
-  std::vector<void *> allocs;
 };
 
 namespace {
@@ -241,23 +239,6 @@ __global__ __launch_bounds__(OBS_THREADS) void k_obs_predict(FtabDev T, int cur,
   A.predict[2 * ((size_t)out + i)] = u; A.predict[2 * ((size_t)out + i) + 1] = v;
 }
 
-#define OBS_CHECK(c, call)                                                                                     \
-  do {                                                                                                         \
-    hipError_t e_ = (call);                                                                                    \
-    if (e_ != hipSuccess) { ctx_set_error(c, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); return GFBE_DEVICE_ERROR; } \
-  } while (0)
-
-gfbe_status obs_bad(gfbe_ctx *c, const char *who, const char *what) {
-  ctx_set_error(c, (std::string(who) + ": " + what).c_str());
-  return GFBE_BAD_INPUT;
-}
-gfbe_status obs_ready(gfbe_ctx *c, gfbe_obs *m, const char *who) {
-  if (!c) return GFBE_BAD_INPUT;
-  if (ctx_device(c) < 0) { ctx_set_error(c, (std::string(who) + ": HIP device context required (no CPU fallback)").c_str()); return GFBE_NO_DEVICE; }
-  if (!m) return GFBE_BAD_INPUT;
-  if (m->owner != c) return obs_bad(c, who, "the handle belongs to another context");
-  return GFBE_OK;
-}
 bool obs_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 const char *obs_options_error(const gfbe_obs_options *o) {
   if (o->struct_size != (int32_t)sizeof(gfbe_obs_options)) return "gfbe_obs_options.struct_size does not match this library (ABI mismatch)";
@@ -285,10 +266,7 @@ void gfbe_obs_default_options(gfbe_obs_options *o) {
 
 void gfbe_obs_destroy(gfbe_ctx *c, gfbe_obs *m) {
   if (!m) return;
-  if (c && ctx_device(c) >= 0) (void)hipStreamSynchronize(ctx_stream(c));
-  for (void *p : m->allocs) (void)hipFree(p);
-  if (m->depth_h) (void)hipHostFree(m->depth_h);
-  if (m->ev_depth) (void)hipEventDestroy(m->ev_depth);
+  m->release(c);
   delete m;
 }
 
@@ -297,66 +275,58 @@ gfbe_status gfbe_obs_create(gfbe_ctx *c, gfbe_klt *k, const double *cameras, con
   *out = nullptr;
   gfbe_obs_options o;
   if (opt) o = *opt; else gfbe_obs_default_options(&o);
-  if (const char *bad = obs_options_error(&o)) return obs_bad(c, "gfbe_obs_create", bad);
+  if (const char *bad = obs_options_error(&o)) return handle_bad(c, "gfbe_obs_create", bad);
   if (ctx_device(c) < 0) { ctx_set_error(c, "gfbe_obs_create: HIP device context required (no CPU fallback)"); return GFBE_NO_DEVICE; }
-  if (!k) return obs_bad(c, "gfbe_obs_create", "tracker NULL");
-  if (k->owner != c) return obs_bad(c, "gfbe_obs_create", "the tracker belongs to another context");
-  if (k->cap > OBS_MAX_POINTS) return obs_bad(c, "gfbe_obs_create", "the tracker's point_capacity is above GFBE_DET_MAX_POINTS");
-  if (!cameras) return obs_bad(c, "gfbe_obs_create", "cameras NULL");
+  if (!k) return handle_bad(c, "gfbe_obs_create", "tracker NULL");
+  if (k->owner != c) return handle_bad(c, "gfbe_obs_create", "the tracker belongs to another context");
+  if (k->cap > OBS_MAX_POINTS) return handle_bad(c, "gfbe_obs_create", "the tracker's point_capacity is above GFBE_DET_MAX_POINTS");
+  if (!cameras) return handle_bad(c, "gfbe_obs_create", "cameras NULL");
   const size_t C = (size_t)k->n_cam, N = C * (size_t)k->cap;
   std::vector<ObsCam> cams(C);
   for (size_t q = 0; q < C; q++) {
-    if (!obs_camera_ok(cameras + 8 * q)) return obs_bad(c, "gfbe_obs_create", "a camera parameter is not finite, or fx / fy is 0");
+    if (!obs_camera_ok(cameras + 8 * q)) return handle_bad(c, "gfbe_obs_create", "a camera parameter is not finite, or fx / fy is 0");
     cams[q] = obs_camera(cameras + 8 * q);
   }
   gfbe_obs *m = new gfbe_obs();
-  struct Guard { gfbe_ctx *c; gfbe_obs *m; bool armed = true; ~Guard() { if (armed) gfbe_obs_destroy(c, m); } } guard{c, m};
+  CreateGuard<gfbe_obs> guard{c, m, gfbe_obs_destroy};
   m->owner = c; m->trk = k; m->opt = o;
   m->prev_time.assign(C, 0.0);
   hipStream_t st = ctx_stream(c);
-  auto alloc = [&](auto **p, size_t n) {
-    void *q = nullptr;
-    if (hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(**p)) != hipSuccess) return false;
-    m->allocs.push_back(q);
-    *p = (std::remove_reference_t<decltype(**p)> *)q;
-    return hipMemsetAsync(q, 0, std::max<size_t>(n, 1) * sizeof(**p), st) == hipSuccess;
-  };
   const size_t px = C * (size_t)k->rows * (size_t)k->cols;
-  bool ok = alloc(&m->cams, C) && alloc(&m->f_off, C + 1) && alloc(&m->f_id, N) && alloc(&m->f_obs, OBS_OW * N);
-  for (int b = 0; b < 2; b++) ok = ok && alloc(&m->p_ids[b], N) && alloc(&m->p_n[b], C) && alloc(&m->p_un[b], 2 * N);
-  if (o.depth_cam) ok = ok && alloc(&m->depth_d, px) && hipHostMalloc((void **)&m->depth_h, px * sizeof(uint16_t)) == hipSuccess &&
-                        hipEventCreateWithFlags(&m->ev_depth, hipEventDisableTiming) == hipSuccess;
+  bool ok = m->alloc(&m->cams, C) && m->alloc(&m->f_off, C + 1) && m->alloc(&m->f_id, N) && m->alloc(&m->f_obs, OBS_OW * N);
+  for (int b = 0; b < 2; b++) ok = ok && m->alloc(&m->p_ids[b], N) && m->alloc(&m->p_n[b], C) && m->alloc(&m->p_un[b], 2 * N);
+  if (o.depth_cam) ok = ok && m->alloc(&m->depth_d, px) && m->alloc_pinned(&m->depth_h, px) && m->create(&m->ev_depth);
   if (!ok) { ctx_set_error(c, "gfbe_obs_create: device allocation failed"); return GFBE_DEVICE_ERROR; }
-  OBS_CHECK(c, hipMemcpyAsync(m->cams, cams.data(), sizeof(ObsCam) * C, hipMemcpyHostToDevice, st));
-  OBS_CHECK(c, hipStreamSynchronize(st));      // (cams leaves scope)
+  GFBE_CHECK(c, hipMemcpyAsync(m->cams, cams.data(), sizeof(ObsCam) * C, hipMemcpyHostToDevice, st));
+  GFBE_CHECK(c, hipStreamSynchronize(st));      // (cams leaves scope)
   guard.armed = false;
   *out = m;
   return GFBE_OK;
 }
 
 gfbe_status gfbe_obs_reset(gfbe_ctx *c, gfbe_obs *m) {
-  gfbe_status rc = obs_ready(c, m, "gfbe_obs_reset");
+  gfbe_status rc = handle_ready(c, m, "gfbe_obs_reset");
   if (rc != GFBE_OK) return rc;
   const size_t C = (size_t)m->trk->n_cam;
-  for (int b = 0; b < 2; b++) OBS_CHECK(c, hipMemsetAsync(m->p_n[b], 0, sizeof(int) * C, ctx_stream(c)));
+  for (int b = 0; b < 2; b++) GFBE_CHECK(c, hipMemsetAsync(m->p_n[b], 0, sizeof(int) * C, ctx_stream(c)));
   m->has_time = false; m->frame_state = 0; m->frame_dup = false;
   return GFBE_OK;
 }
 
 gfbe_status gfbe_obs_observe(gfbe_ctx *c, gfbe_obs *m, const double *cur_time, const uint16_t *depth, int32_t *offset_out, int32_t *feature_id, double *obs8,
                              int32_t *counters) {
-  gfbe_status rc = obs_ready(c, m, "gfbe_obs_observe");
+  gfbe_status rc = handle_ready(c, m, "gfbe_obs_observe");
   if (rc != GFBE_OK) return rc;
   gfbe_klt *k = m->trk;
-  if (k->n_pushed < 1) return obs_bad(c, "gfbe_obs_observe", "no image has been pushed");
-  if (!cur_time) return obs_bad(c, "gfbe_obs_observe", "cur_time NULL");
+  if (k->n_pushed < 1) return handle_bad(c, "gfbe_obs_observe", "no image has been pushed");
+  if (!cur_time) return handle_bad(c, "gfbe_obs_observe", "cur_time NULL");
   const size_t C = (size_t)k->n_cam;
   std::vector<double> dt(C, 0.0);
   for (size_t q = 0; q < C; q++) {
-    if (!std::isfinite(cur_time[q]) || (m->has_time && !(cur_time[q] > m->prev_time[q]))) return obs_bad(c, "gfbe_obs_observe", "a time is not finite or not greater than the camera's previous time");
+    if (!std::isfinite(cur_time[q]) || (m->has_time && !(cur_time[q] > m->prev_time[q]))) return handle_bad(c, "gfbe_obs_observe", "a time is not finite or not greater than the camera's previous time");
     dt[q] = cur_time[q] - m->prev_time[q];
   }
-  if (m->opt.depth_cam && !depth) return obs_bad(c, "gfbe_obs_observe", "depth_cam == 1 needs the depth images");
+  if (m->opt.depth_cam && !depth) return handle_bad(c, "gfbe_obs_observe", "depth_cam == 1 needs the depth images");
   std::vector<int> off;
   int most = 0;
   obs_offsets(k, &off, &most);
@@ -372,10 +342,10 @@ gfbe_status gfbe_obs_observe(gfbe_ctx *c, gfbe_obs *m, const double *cur_time, c
     sg.flush();
     if (m->opt.depth_cam) {
       const size_t px = C * (size_t)k->rows * (size_t)k->cols;
-      if (m->depth_busy) OBS_CHECK(c, hipEventSynchronize(m->ev_depth));      // (the mirror's last copy has left it)
+      if (m->depth_busy) GFBE_CHECK(c, hipEventSynchronize(m->ev_depth));      // (the mirror's last copy has left it)
       std::memcpy(m->depth_h, depth, px * sizeof(uint16_t));
-      OBS_CHECK(c, hipMemcpyAsync(m->depth_d, m->depth_h, px * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-      OBS_CHECK(c, hipEventRecord(m->ev_depth, st));
+      GFBE_CHECK(c, hipMemcpyAsync(m->depth_d, m->depth_h, px * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+      GFBE_CHECK(c, hipEventRecord(m->ev_depth, st));
       m->depth_busy = true;
     }
     const int ph = m->phalf, nh = ph ^ 1, hf = k->half;
@@ -392,7 +362,7 @@ gfbe_status gfbe_obs_observe(gfbe_ctx *c, gfbe_obs *m, const double *cur_time, c
       sg.down(obs8, (const double *)m->f_obs, OBS_OW * n);
     }
     sg.finish();      // the one wait
-    OBS_CHECK(c, hipGetLastError());
+    GFBE_CHECK(c, hipGetLastError());
     m->phalf = nh;
   }
   m->has_time = true;
@@ -406,29 +376,29 @@ gfbe_status gfbe_obs_observe(gfbe_ctx *c, gfbe_obs *m, const double *cur_time, c
 
 gfbe_status gfbe_obs_add_frame(gfbe_ctx *c, gfbe_obs *m, gfbe_ftab *t, const int32_t *frame_count, const double *td, int32_t *keyframe, int32_t *counters,
                                double *avg_parallax) {
-  gfbe_status rc = obs_ready(c, m, "gfbe_obs_add_frame");
+  gfbe_status rc = handle_ready(c, m, "gfbe_obs_add_frame");
   if (rc != GFBE_OK) return rc;
-  if (!t || !frame_count || !td) return obs_bad(c, "gfbe_obs_add_frame", "ftab, frame_count or td NULL");
-  if (t->d.W != m->trk->n_cam) return obs_bad(c, "gfbe_obs_add_frame", "the table count is not the tracker's camera count");
-  if (m->frame_state == 0) return obs_bad(c, "gfbe_obs_add_frame", "no frame is held: observe first");
-  if (m->frame_state == 2) return obs_bad(c, "gfbe_obs_add_frame", "the frame was already added");
-  if (m->frame_dup) return obs_bad(c, "gfbe_obs_add_frame", "the frame holds two points of a camera with the same id");
+  if (!t || !frame_count || !td) return handle_bad(c, "gfbe_obs_add_frame", "ftab, frame_count or td NULL");
+  if (t->d.W != m->trk->n_cam) return handle_bad(c, "gfbe_obs_add_frame", "the table count is not the tracker's camera count");
+  if (m->frame_state == 0) return handle_bad(c, "gfbe_obs_add_frame", "no frame is held: observe first");
+  if (m->frame_state == 2) return handle_bad(c, "gfbe_obs_add_frame", "the frame was already added");
+  if (m->frame_dup) return handle_bad(c, "gfbe_obs_add_frame", "the frame holds two points of a camera with the same id");
   rc = ftab_add_frame_device(c, t, frame_count, td, m->frame_rows, m->frame_max, m->f_off, m->f_id, m->f_obs, keyframe, counters, avg_parallax);
   if (rc == GFBE_OK || rc == GFBE_BAD_INPUT) m->frame_state = 2;      // (the kernels ran: BAD_INPUT here is a table's capacity)
   return rc;
 }
 
 gfbe_status gfbe_obs_remove_outliers(gfbe_ctx *c, gfbe_obs *m, const int32_t *offset, const int32_t *ids, int32_t *held_out) {
-  gfbe_status rc = obs_ready(c, m, "gfbe_obs_remove_outliers");
+  gfbe_status rc = handle_ready(c, m, "gfbe_obs_remove_outliers");
   if (rc != GFBE_OK) return rc;
   gfbe_klt *k = m->trk;
-  if (k->n_pushed < 1) return obs_bad(c, "gfbe_obs_remove_outliers", "no image has been pushed");
+  if (k->n_pushed < 1) return handle_bad(c, "gfbe_obs_remove_outliers", "no image has been pushed");
   const size_t C = (size_t)k->n_cam;
-  if (!offset || offset[0] != 0) return obs_bad(c, "gfbe_obs_remove_outliers", "offsets that do not ascend from 0");
+  if (!offset || offset[0] != 0) return handle_bad(c, "gfbe_obs_remove_outliers", "offsets that do not ascend from 0");
   for (size_t q = 0; q < C; q++)
-    if (offset[q + 1] < offset[q]) return obs_bad(c, "gfbe_obs_remove_outliers", "offsets that do not ascend from 0");
+    if (offset[q + 1] < offset[q]) return handle_bad(c, "gfbe_obs_remove_outliers", "offsets that do not ascend from 0");
   const size_t L = (size_t)offset[C];
-  if (L > 0 && !ids) return obs_bad(c, "gfbe_obs_remove_outliers", "ids NULL");
+  if (L > 0 && !ids) return handle_bad(c, "gfbe_obs_remove_outliers", "ids NULL");
   std::vector<int32_t> held(C, 0);
   {
     Staged sg(c, k, L * 4 + C * 8 + 8192);
@@ -444,7 +414,7 @@ gfbe_status gfbe_obs_remove_outliers(gfbe_ctx *c, gfbe_obs *m, const int32_t *of
     hipLaunchKernelGGL(k_obs_remove, dim3(k->n_cam), dim3(OBS_THREADS), 0, ctx_stream(c), A);
     sg.down(held.data(), (const int32_t *)o_held, C);
     sg.finish();      // the one wait: the tracker's host mirrors stay exact
-    OBS_CHECK(c, hipGetLastError());
+    GFBE_CHECK(c, hipGetLastError());
     k->half = nh;
   }
   for (size_t q = 0; q < C; q++) k->count_h[q] = std::min(held[q], k->count_h[q]);      // (the rows of camera q stay at begin_h[q], as after a track)
@@ -454,12 +424,12 @@ gfbe_status gfbe_obs_remove_outliers(gfbe_ctx *c, gfbe_obs *m, const int32_t *of
 
 gfbe_status gfbe_obs_predict(gfbe_ctx *c, gfbe_obs *m, gfbe_ftab *t, const int32_t *frame_count, const double *poses, const double *tic_ric, const double *next_pose,
                              float *predict_pts, int32_t *n_predicted) {
-  gfbe_status rc = obs_ready(c, m, "gfbe_obs_predict");
+  gfbe_status rc = handle_ready(c, m, "gfbe_obs_predict");
   if (rc != GFBE_OK) return rc;
   gfbe_klt *k = m->trk;
-  if (k->n_pushed < 1) return obs_bad(c, "gfbe_obs_predict", "no image has been pushed");
-  if (!t || !frame_count || !poses || !tic_ric || !next_pose) return obs_bad(c, "gfbe_obs_predict", "ftab, frame_count, poses, tic_ric or next_pose NULL");
-  if (t->d.W != k->n_cam) return obs_bad(c, "gfbe_obs_predict", "the table count is not the tracker's camera count");
+  if (k->n_pushed < 1) return handle_bad(c, "gfbe_obs_predict", "no image has been pushed");
+  if (!t || !frame_count || !poses || !tic_ric || !next_pose) return handle_bad(c, "gfbe_obs_predict", "ftab, frame_count, poses, tic_ric or next_pose NULL");
+  if (t->d.W != k->n_cam) return handle_bad(c, "gfbe_obs_predict", "the table count is not the tracker's camera count");
   rc = ftab_ready(c, t);
   if (rc != GFBE_OK) return rc;
   const size_t C = (size_t)k->n_cam;
@@ -475,7 +445,7 @@ gfbe_status gfbe_obs_predict(gfbe_ctx *c, gfbe_obs *m, gfbe_ftab *t, const int32
     float *o_pred = sg.up((const float *)nullptr, 2 * n);
     if (!sg.ok) { ctx_set_error(c, "gfbe_obs_predict: staging allocation failed"); return GFBE_DEVICE_ERROR; }
     sg.flush();
-    OBS_CHECK(c, hipMemsetAsync(o_np, 0, sizeof(int) * C, ctx_stream(c)));
+    GFBE_CHECK(c, hipMemsetAsync(o_np, 0, sizeof(int) * C, ctx_stream(c)));
     if (most > 0) {
       const int hf = k->half;
       ObsPredictArgs A;
@@ -488,26 +458,26 @@ gfbe_status gfbe_obs_predict(gfbe_ctx *c, gfbe_obs *m, gfbe_ftab *t, const int32
     sg.down(n_predicted, (const int32_t *)o_np, C);
     sg.down(predict_pts, (const float *)o_pred, 2 * n);
     sg.finish();      // the one wait
-    OBS_CHECK(c, hipGetLastError());
+    GFBE_CHECK(c, hipGetLastError());
   }
   return GFBE_OK;
 }
 
 gfbe_status gfbe_obs_download_prev(gfbe_ctx *c, gfbe_obs *m, int32_t camera, int32_t *n_out, int32_t *ids, float *un_pts) {
-  gfbe_status rc = obs_ready(c, m, "gfbe_obs_download_prev");
+  gfbe_status rc = handle_ready(c, m, "gfbe_obs_download_prev");
   if (rc != GFBE_OK) return rc;
   gfbe_klt *k = m->trk;
-  if (camera < 0 || camera >= k->n_cam) return obs_bad(c, "gfbe_obs_download_prev", "camera outside the handle's");
-  if (!n_out) return obs_bad(c, "gfbe_obs_download_prev", "n_out NULL");
+  if (camera < 0 || camera >= k->n_cam) return handle_bad(c, "gfbe_obs_download_prev", "camera outside the handle's");
+  if (!n_out) return handle_bad(c, "gfbe_obs_download_prev", "n_out NULL");
   hipStream_t st = ctx_stream(c);
   int n = 0;
-  OBS_CHECK(c, hipMemcpyAsync(&n, m->p_n[m->phalf] + camera, sizeof(int), hipMemcpyDeviceToHost, st));
-  OBS_CHECK(c, hipStreamSynchronize(st));
+  GFBE_CHECK(c, hipMemcpyAsync(&n, m->p_n[m->phalf] + camera, sizeof(int), hipMemcpyDeviceToHost, st));
+  GFBE_CHECK(c, hipStreamSynchronize(st));
   n = std::max(0, std::min(n, k->cap));
   const size_t list = (size_t)camera * (size_t)k->cap;
-  if (ids && n) OBS_CHECK(c, hipMemcpyAsync(ids, m->p_ids[m->phalf] + list, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
-  if (un_pts && n) OBS_CHECK(c, hipMemcpyAsync(un_pts, m->p_un[m->phalf] + 2 * list, sizeof(float) * 2 * (size_t)n, hipMemcpyDeviceToHost, st));
-  OBS_CHECK(c, hipStreamSynchronize(st));
+  if (ids && n) GFBE_CHECK(c, hipMemcpyAsync(ids, m->p_ids[m->phalf] + list, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+  if (un_pts && n) GFBE_CHECK(c, hipMemcpyAsync(un_pts, m->p_un[m->phalf] + 2 * list, sizeof(float) * 2 * (size_t)n, hipMemcpyDeviceToHost, st));
+  GFBE_CHECK(c, hipStreamSynchronize(st));
   *n_out = n;
   return GFBE_OK;
 }

@@ -11,7 +11,7 @@
 #include <string>
 #include <vector>
 
-#include "gfbe_device.h"
+#include "gfbe_handle.h"
 #include "gfbe_factors.h"
 
 using namespace gfd;
@@ -47,12 +47,6 @@ __global__ __launch_bounds__(256) void k_anchor(int n, const double *pose, const
   cost_part[k] = c;
 }
 
-#define OP_CHECK(c, call)                                                                                      \
-  do {                                                                                                         \
-    hipError_t e_ = (call);                                                                                    \
-    if (e_ != hipSuccess) { ctx_set_error(c, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); st = GFBE_DEVICE_ERROR; goto done; } \
-  } while (0)
-
 }  // namespace
 
 extern "C" gfbe_status gfbe_plane_eval(gfbe_ctx *c, int32_t n, const double *pose, const double *ex_wheel, const double *plane_R,
@@ -71,14 +65,14 @@ extern "C" gfbe_status gfbe_plane_eval(gfbe_ctx *c, int32_t n, const double *pos
   for (int i = 0; i < 4; i++) pc.q[i] = plane_R[i];
   for (int i = 0; i < 3; i++) pc.ninv[i] = noise_inv[i];
   pc.z = plane_Z;
-  OP_CHECK(c, hipMalloc((void **)&d, sizeof(double) * (np + nr + nj + nc)));
-  OP_CHECK(c, hipMemcpyAsync(d, pose, sizeof(double) * np, hipMemcpyHostToDevice, s));
+  GFBE_CHECK_DONE(c, hipMalloc((void **)&d, sizeof(double) * (np + nr + nj + nc)));
+  GFBE_CHECK_DONE(c, hipMemcpyAsync(d, pose, sizeof(double) * np, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_plane, dim3((n + 255) / 256), dim3(256), 0, s, n, d, pc, r ? d + np : nullptr, J ? d + np + nr : nullptr, d + np + nr + nj);
-  OP_CHECK(c, hipGetLastError());
-  if (r) OP_CHECK(c, hipMemcpyAsync(r, d + np, sizeof(double) * nr, hipMemcpyDeviceToHost, s));
-  if (J) OP_CHECK(c, hipMemcpyAsync(J, d + np + nr, sizeof(double) * nj, hipMemcpyDeviceToHost, s));
-  OP_CHECK(c, hipMemcpyAsync(hc.data(), d + np + nr + nj, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-  OP_CHECK(c, hipStreamSynchronize(s));
+  GFBE_CHECK_DONE(c, hipGetLastError());
+  if (r) GFBE_CHECK_DONE(c, hipMemcpyAsync(r, d + np, sizeof(double) * nr, hipMemcpyDeviceToHost, s));
+  if (J) GFBE_CHECK_DONE(c, hipMemcpyAsync(J, d + np + nr, sizeof(double) * nj, hipMemcpyDeviceToHost, s));
+  GFBE_CHECK_DONE(c, hipMemcpyAsync(hc.data(), d + np + nr + nj, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+  GFBE_CHECK_DONE(c, hipStreamSynchronize(s));
   if (cost) { double t = 0.0; for (int k = 0; k < n; k++) t += hc[k]; *cost = t; }
 done:
   if (d) (void)hipFree(d);
@@ -96,16 +90,16 @@ extern "C" gfbe_status gfbe_anchor_eval(gfbe_ctx *c, int32_t n, const double *po
   double *d = nullptr;
   const size_t np = (size_t)7 * n, nr = (size_t)6 * n, nj = (size_t)36 * n;
   std::vector<double> hc(n);
-  OP_CHECK(c, hipMalloc((void **)&d, sizeof(double) * (2 * np + nr + nj + n)));
-  OP_CHECK(c, hipMemcpyAsync(d, pose, sizeof(double) * np, hipMemcpyHostToDevice, s));
-  OP_CHECK(c, hipMemcpyAsync(d + np, anchor, sizeof(double) * np, hipMemcpyHostToDevice, s));
+  GFBE_CHECK_DONE(c, hipMalloc((void **)&d, sizeof(double) * (2 * np + nr + nj + n)));
+  GFBE_CHECK_DONE(c, hipMemcpyAsync(d, pose, sizeof(double) * np, hipMemcpyHostToDevice, s));
+  GFBE_CHECK_DONE(c, hipMemcpyAsync(d + np, anchor, sizeof(double) * np, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_anchor, dim3((n + 255) / 256), dim3(256), 0, s, n, d, d + np, sqrt_info, r ? d + 2 * np : nullptr,
                      J ? d + 2 * np + nr : nullptr, d + 2 * np + nr + nj);
-  OP_CHECK(c, hipGetLastError());
-  if (r) OP_CHECK(c, hipMemcpyAsync(r, d + 2 * np, sizeof(double) * nr, hipMemcpyDeviceToHost, s));
-  if (J) OP_CHECK(c, hipMemcpyAsync(J, d + 2 * np + nr, sizeof(double) * nj, hipMemcpyDeviceToHost, s));
-  OP_CHECK(c, hipMemcpyAsync(hc.data(), d + 2 * np + nr + nj, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-  OP_CHECK(c, hipStreamSynchronize(s));
+  GFBE_CHECK_DONE(c, hipGetLastError());
+  if (r) GFBE_CHECK_DONE(c, hipMemcpyAsync(r, d + 2 * np, sizeof(double) * nr, hipMemcpyDeviceToHost, s));
+  if (J) GFBE_CHECK_DONE(c, hipMemcpyAsync(J, d + 2 * np + nr, sizeof(double) * nj, hipMemcpyDeviceToHost, s));
+  GFBE_CHECK_DONE(c, hipMemcpyAsync(hc.data(), d + 2 * np + nr + nj, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+  GFBE_CHECK_DONE(c, hipStreamSynchronize(s));
   if (cost) { double t = 0.0; for (int k = 0; k < n; k++) t += hc[k]; *cost = t; }
 done:
   if (d) (void)hipFree(d);

@@ -25,7 +25,7 @@
 
 #include "gfbe_device.h"
 #include "gfbe_scan.h"
-#include "gfbe_tabstage.h"
+#include "gfbe_handle.h"
 #include "gfbe_vmap.h"
 #include "gfbe_vmap_impl.h"
 
@@ -36,8 +36,7 @@ enum { SM_N = 0, SM_NKP, SM_SKIP, SM_SKIPKP, SM_NOLD, SC_META = 8 };
 constexpr int SC_THREADS = 256, SC_SCAN_THREADS = 1024;
 }  // namespace
 
-struct gfbe_scan : gfbe_tab_staging {
-  gfbe_ctx *owner = nullptr;
+struct gfbe_scan : gfbe_handle {
   int cap = 0, slots = 0;
   int *src[2] = {};                       // [cap] index in the uploaded cloud
   double *pts[2] = {}, *alpha[2] = {}, *ts[2] = {};      // [cap][3], [cap], [cap]
@@ -50,7 +49,6 @@ struct gfbe_scan : gfbe_tab_staging {
   int *part = nullptr;                    // [2][cap / SC_THREADS + 1] survivors / dropped points per workgroup, then their offsets
   double *world = nullptr;                // [cap][3]
   int *meta = nullptr;                    // [SC_META]
-  std::vector<void *> allocs;
   int n_up = 0;                           // the count of the last upload: the host's upper bound of the point count
   bool has_ts = false, kp_valid = false, counts_known = true;
   int n_pts = 0, n_kp = 0;                // the host's copy of the counts (counts_known)
@@ -150,19 +148,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_sc_compact(const int *meta, int 
   for (int a = 0; a < 3; a++) O.pts[3 * (size_t)dst + a] = I.pts[3 * (size_t)i + a];
 }
 
-#define SC_CHECK(c, call)                                                                                      \
-  do {                                                                                                         \
-    hipError_t e_ = (call);                                                                                    \
-    if (e_ != hipSuccess) { ctx_set_error(c, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); return GFBE_DEVICE_ERROR; } \
-  } while (0)
-
-gfbe_status sc_ready(gfbe_ctx *c, gfbe_scan *s, const char *who) {
-  if (!c) return GFBE_BAD_INPUT;
-  if (ctx_device(c) < 0) return GFBE_NO_DEVICE;
-  if (!s) return GFBE_BAD_INPUT;
-  if (s->owner != c) { ctx_set_error(c, (std::string(who) + ": the scan handle belongs to another context").c_str()); return GFBE_BAD_INPUT; }
-  return GFBE_OK;
-}
+gfbe_status sc_ready(gfbe_ctx *c, gfbe_scan *s, const char *who) { return handle_ready(c, s, who, "scan handle"); }
 ScCols sc_cols(const gfbe_scan *s, int half) { return ScCols{s->src[half], s->pts[half], s->alpha[half], s->ts[half]}; }
 bool sc_pose_ok(const double *p) {
   for (int a = 0; a < 7; a++) if (!std::isfinite(p[a])) return false;
@@ -172,8 +158,8 @@ bool sc_pose_ok(const double *p) {
 gfbe_status sc_counts(gfbe_ctx *c, gfbe_scan *s) {
   if (s->counts_known) return GFBE_OK;
   int h[SC_META];
-  SC_CHECK(c, hipMemcpyAsync(h, s->meta, sizeof h, hipMemcpyDeviceToHost, ctx_stream(c)));
-  SC_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
+  GFBE_CHECK(c, hipMemcpyAsync(h, s->meta, sizeof h, hipMemcpyDeviceToHost, ctx_stream(c)));
+  GFBE_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
   s->n_pts = h[SM_N]; s->n_kp = h[SM_NKP]; s->counts_known = true;
   return GFBE_OK;
 }
@@ -203,13 +189,7 @@ extern "C" {
 
 void gfbe_scan_destroy(gfbe_ctx *c, gfbe_scan *s) {
   if (!s) return;
-  if (c && ctx_device(c) >= 0) (void)hipStreamSynchronize(ctx_stream(c));
-  for (void *p : s->allocs) (void)hipFree(p);
-  if (s->stage_d) (void)hipFree(s->stage_d);
-  if (s->stage_h) (void)hipHostFree(s->stage_h);
-  if (s->ring_d) (void)hipFree(s->ring_d);
-  if (s->ring_h) (void)hipHostFree(s->ring_h);
-  for (hipEvent_t e : s->ring_ev) if (e) (void)hipEventDestroy(e);
+  s->release(c);
   delete s;
 }
 
@@ -219,29 +199,19 @@ gfbe_status gfbe_scan_create(gfbe_ctx *c, int32_t point_capacity, gfbe_scan **ou
   if (point_capacity < 1 || point_capacity > (1 << 21)) { ctx_set_error(c, "gfbe_scan_create: point_capacity outside 1 .. 2^21"); return GFBE_BAD_INPUT; }
   if (ctx_device(c) < 0) { ctx_set_error(c, "gfbe_scan_create: HIP device context required (no CPU fallback)"); return GFBE_NO_DEVICE; }
   gfbe_scan *s = new gfbe_scan();
-  struct Guard { gfbe_ctx *c; gfbe_scan *s; bool armed = true; ~Guard() { if (armed) gfbe_scan_destroy(c, s); } } guard{c, s};
+  CreateGuard<gfbe_scan> guard{c, s, gfbe_scan_destroy};
   s->owner = c; s->cap = point_capacity;
   int slots = 64;
   while (slots < 2 * point_capacity) slots <<= 1;
   s->slots = slots;
   const size_t N = (size_t)point_capacity, G = (N + SC_THREADS - 1) / SC_THREADS;
-  auto alloc = [&](auto **p, size_t n) {
-    void *q = nullptr;
-    if (hipMalloc(&q, n * sizeof(**p)) != hipSuccess) return false;
-    s->allocs.push_back(q);
-    *p = (std::remove_reference_t<decltype(**p)> *)q;
-    return hipMemsetAsync(q, 0, n * sizeof(**p), ctx_stream(c)) == hipSuccess;
-  };
   bool ok = true;
-  for (int b = 0; b < 2; b++) ok = ok && alloc(&s->src[b], N) && alloc(&s->pts[b], 3 * N) && alloc(&s->alpha[b], N) && alloc(&s->ts[b], N);
-  ok = ok && alloc(&s->kp_src, N) && alloc(&s->kp_pts, 3 * N) && alloc(&s->kp_alpha, N) && alloc(&s->kp_ts, N) && alloc(&s->keys, (size_t)slots) &&
-       alloc(&s->minidx, (size_t)slots) && alloc(&s->slot_of, N) && alloc(&s->part, 2 * G + 2) && alloc(&s->world, 3 * N) && alloc(&s->meta, (size_t)SC_META);
+  for (int b = 0; b < 2; b++) ok = ok && s->alloc(&s->src[b], N) && s->alloc(&s->pts[b], 3 * N) && s->alloc(&s->alpha[b], N) && s->alloc(&s->ts[b], N);
+  ok = ok && s->alloc(&s->kp_src, N) && s->alloc(&s->kp_pts, 3 * N) && s->alloc(&s->kp_alpha, N) && s->alloc(&s->kp_ts, N) && s->alloc(&s->keys, (size_t)slots) &&
+       s->alloc(&s->minidx, (size_t)slots) && s->alloc(&s->slot_of, N) && s->alloc(&s->part, 2 * G + 2) && s->alloc(&s->world, 3 * N) && s->alloc(&s->meta, (size_t)SC_META);
   if (!ok) { ctx_set_error(c, "gfbe_scan_create: device allocation failed"); return GFBE_DEVICE_ERROR; }
-  { Staged warm(c, s, 1 << 16); if (!warm.ok) { ctx_set_error(c, "gfbe_scan_create: staging allocation failed"); return GFBE_DEVICE_ERROR; } }
-  SC_CHECK(c, hipMalloc((void **)&s->ring_d, (size_t)gfbe_scan::RING * gfbe_scan::RING_SLOT));
-  SC_CHECK(c, hipHostMalloc((void **)&s->ring_h, (size_t)gfbe_scan::RING * gfbe_scan::RING_SLOT));
-  for (int k = 0; k < gfbe_scan::RING; k++) SC_CHECK(c, hipEventCreateWithFlags(&s->ring_ev[k], hipEventDisableTiming));
-  SC_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
+  if (!s->make_staging(c, "gfbe_scan_create", 1 << 16, true)) return GFBE_DEVICE_ERROR;
+  GFBE_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
   guard.armed = false;
   *out = s;
   return GFBE_OK;
@@ -265,7 +235,7 @@ gfbe_status gfbe_scan_upload(gfbe_ctx *c, gfbe_scan *s, int32_t n, const double 
   }
   s->n_up = n; s->has_ts = timestamp != nullptr; s->kp_valid = false;
   s->n_pts = n; s->n_kp = 0; s->counts_known = true;
-  SC_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   return GFBE_OK;
 }
 
@@ -276,7 +246,7 @@ gfbe_status gfbe_scan_subsample(gfbe_ctx *c, gfbe_scan *s, double size_voxel) {
   s->kp_valid = false; s->counts_known = false;
   sc_enqueue_sample(c, s, s->pts[s->cur], size_voxel, false, sc_cols(s, 1 - s->cur));
   s->cur = 1 - s->cur;
-  SC_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   return GFBE_OK;
 }
 
@@ -299,7 +269,7 @@ gfbe_status gfbe_scan_undistort(gfbe_ctx *c, gfbe_scan *s, int32_t n_states, con
     const int G = (s->n_up + SC_THREADS - 1) / SC_THREADS;
     if (G > 0) hipLaunchKernelGGL(k_sc_undistort, dim3(G), dim3(SC_THREADS), 0, ctx_stream(c), (const int *)s->meta, (int)n_states, dt, dp, s->pts[s->cur], (const double *)s->ts[s->cur]);
   }
-  SC_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   return GFBE_OK;
 }
 
@@ -323,7 +293,7 @@ gfbe_status gfbe_scan_keypoints(gfbe_ctx *c, gfbe_scan *s, int32_t ct, const dou
     sg.down(h, (const int *)s->meta, (size_t)SC_META);
     sg.finish();      // the host wait: the counts
   }
-  SC_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   s->n_pts = h[SM_N]; s->n_kp = h[SM_NKP]; s->counts_known = true; s->kp_valid = true;
   if (n_keypoints) *n_keypoints = h[SM_NKP];
   return GFBE_OK;
@@ -333,8 +303,8 @@ gfbe_status gfbe_scan_size(gfbe_ctx *c, gfbe_scan *s, int32_t *n_points, int32_t
   gfbe_status st = sc_ready(c, s, "gfbe_scan_size");
   if (st != GFBE_OK) return st;
   int h[SC_META];
-  SC_CHECK(c, hipMemcpyAsync(h, s->meta, sizeof h, hipMemcpyDeviceToHost, ctx_stream(c)));
-  SC_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
+  GFBE_CHECK(c, hipMemcpyAsync(h, s->meta, sizeof h, hipMemcpyDeviceToHost, ctx_stream(c)));
+  GFBE_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
   s->n_pts = h[SM_N]; s->n_kp = h[SM_NKP]; s->counts_known = true;
   if (n_points) *n_points = h[SM_N];
   if (n_keypoints) *n_keypoints = s->kp_valid ? h[SM_NKP] : 0;
@@ -351,11 +321,11 @@ gfbe_status gfbe_scan_download(gfbe_ctx *c, gfbe_scan *s, int32_t which, int32_t
   if (n == 0) return GFBE_OK;
   const ScCols C = which ? ScCols{s->kp_src, s->kp_pts, s->kp_alpha, s->kp_ts} : sc_cols(s, s->cur);
   hipStream_t q = ctx_stream(c);
-  if (src) SC_CHECK(c, hipMemcpyAsync(src, C.src, sizeof(int) * n, hipMemcpyDeviceToHost, q));
-  if (pts) SC_CHECK(c, hipMemcpyAsync(pts, C.pts, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, q));
-  if (alpha) SC_CHECK(c, hipMemcpyAsync(alpha, C.alpha, sizeof(double) * n, hipMemcpyDeviceToHost, q));
-  if (timestamp) SC_CHECK(c, hipMemcpyAsync(timestamp, C.ts, sizeof(double) * n, hipMemcpyDeviceToHost, q));
-  SC_CHECK(c, hipStreamSynchronize(q));
+  if (src) GFBE_CHECK(c, hipMemcpyAsync(src, C.src, sizeof(int) * n, hipMemcpyDeviceToHost, q));
+  if (pts) GFBE_CHECK(c, hipMemcpyAsync(pts, C.pts, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, q));
+  if (alpha) GFBE_CHECK(c, hipMemcpyAsync(alpha, C.alpha, sizeof(double) * n, hipMemcpyDeviceToHost, q));
+  if (timestamp) GFBE_CHECK(c, hipMemcpyAsync(timestamp, C.ts, sizeof(double) * n, hipMemcpyDeviceToHost, q));
+  GFBE_CHECK(c, hipStreamSynchronize(q));
   return GFBE_OK;
 }
 

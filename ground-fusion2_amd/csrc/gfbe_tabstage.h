@@ -1,4 +1,5 @@
-// gfbe_tabstage.h — argument staging of the device-resident tables (gfbe_ftab.hip, gfbe_ltab.hip).
+// gfbe_tabstage.h — argument staging of the device handles' operations: the tables (gfbe_ftab, gfbe_ltab), the maps (gfbe_vmap, gfbe_scan,
+// gfbe_dmap), the loop database (gfbe_ldb) and the tracker (gfbe_klt), whose chunk the detector and the observer borrow.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +9,21 @@
 #include <vector>
 
 #include "gfbe_device.h"
+
+// argument staging of a device handle's operations (the part of gfbe_handle, gfbe_handle.h, that gfd::Staged below works on)
+struct gfbe_tab_staging {
+  // one device chunk + its pinned host mirror, grown on demand and kept (a hipMalloc / hipFree pair per argument cost more than the
+  // kernels: 0.4 ms per call measured)
+  char *stage_d = nullptr, *stage_h = nullptr;
+  size_t stage_cap = 0;
+  // the operations that return nothing (triangulate, setDepth, the erasing ones) do not wait for the device: their arguments go
+  // through a ring of small staging slots, a slot is reused when the event recorded behind its operation has passed
+  enum { RING = 8, RING_SLOT = 64 << 10 };
+  char *ring_d = nullptr, *ring_h = nullptr;
+  hipEvent_t ring_ev[RING] = {};
+  bool ring_used[RING] = {};
+  int ring_next = 0;
+};
 
 namespace gfd {
 

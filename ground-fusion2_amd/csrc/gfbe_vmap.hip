@@ -34,7 +34,7 @@
 #include "gfbe_device.h"
 #include "gfbe_line_batch.h"      // grow()
 #include "gfbe_lio_pose.h"
-#include "gfbe_tabstage.h"
+#include "gfbe_handle.h"
 #include "gfbe_vmap.h"
 #include "gfbe_vmap_impl.h"
 
@@ -323,18 +323,8 @@ __global__ __launch_bounds__(256) void k_vm_local(VmDev V, const double *nrm, do
   }
 }
 
-#define VM_CHECK(c, call)                                                                                      \
-  do {                                                                                                         \
-    hipError_t e_ = (call);                                                                                    \
-    if (e_ != hipSuccess) { ctx_set_error(c, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); return GFBE_DEVICE_ERROR; } \
-  } while (0)
-
 VmDev vm_dev(const gfbe_vmap *m, int half) { return VmDev{m->keys[half], m->cnt[half], m->pts[half], m->slots - 1, m->P, m->cap, m->meta}; }
-gfbe_status vm_ready(gfbe_ctx *c, gfbe_vmap *m) {
-  if (!c) return GFBE_BAD_INPUT;
-  if (ctx_device(c) < 0) return GFBE_NO_DEVICE;
-  return m ? GFBE_OK : GFBE_BAD_INPUT;
-}
+gfbe_status vm_ready(gfbe_ctx *c, gfbe_vmap *m) { return handle_device(c, m, "gfbe_vmap"); }
 bool vm_options_ok(const gfbe_vmap_options *o) {
   return o->struct_size == (int32_t)sizeof(gfbe_vmap_options) && o->size_voxel_map > 0.0 && std::isfinite(o->size_voxel_map) &&
          o->max_num_points_in_voxel >= 1 && o->max_num_points_in_voxel <= VM_MAXP && o->min_distance_points >= 0.0 && o->max_distance > 0.0 &&
@@ -344,22 +334,13 @@ bool vm_options_ok(const gfbe_vmap_options *o) {
          std::fabs(o->weight_alpha) + std::fabs(o->weight_neighborhood) > 0.0 && o->max_num_residuals >= 1 && o->max_num_residuals <= (1 << 22);
 }
 template <typename T>
-gfbe_status vm_alloc(gfbe_ctx *c, gfbe_vmap *m, T **p, size_t n, int fill) {
-  void *q = nullptr;
-  VM_CHECK(c, hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
-  m->allocs.push_back(q);
-  VM_CHECK(c, hipMemsetAsync(q, fill, std::max<size_t>(n, 1) * sizeof(T), ctx_stream(c)));
-  *p = (T *)q;
-  return GFBE_OK;
-}
-template <typename T>
 T *vm_carve(char *&p, size_t n) { T *r = (T *)p; p += (std::max<size_t>(n, 1) * sizeof(T) + 255) & ~(size_t)255; return r; }
 
 // the per-keypoint scratch of one association and the options it reads (raw, alpha, pb, pe, skip are the caller's)
 gfbe_status vm_assoc_args(gfbe_ctx *c, gfbe_vmap *m, int ct, int n, int frame_init, AssocArgs *out) {
   const gfbe_vmap_options &o = m->opt;
   const size_t N = (size_t)std::max(n, 1);
-  VM_CHECK(c, grow(ctx_stream(c), m->kp_buf, 3 * ((N * 4 + 255) & ~(size_t)255) + ((N * 4 * o.max_number_neighbors + 255) & ~(size_t)255) + 2 * ((N * 8 + 255) & ~(size_t)255) + 2 * ((N * 24 + 255) & ~(size_t)255) +
+  GFBE_CHECK(c, grow(ctx_stream(c), m->kp_buf, 3 * ((N * 4 + 255) & ~(size_t)255) + ((N * 4 * o.max_number_neighbors + 255) & ~(size_t)255) + 2 * ((N * 8 + 255) & ~(size_t)255) + 2 * ((N * 24 + 255) & ~(size_t)255) +
                                      ((N * 8 * o.num_closest_neighbors + 255) & ~(size_t)255)));
   char *p = m->kp_buf.d;
   AssocArgs A;
@@ -390,15 +371,9 @@ void gfbe_vmap_default_options(gfbe_vmap_options *o) {
 
 void gfbe_vmap_destroy(gfbe_ctx *c, gfbe_vmap *m) {
   if (!m) return;
-  if (c && ctx_device(c) >= 0) (void)hipStreamSynchronize(ctx_stream(c));
-  for (void *p : m->allocs) (void)hipFree(p);
+  m->release(c);
   for (const DevBuf *b : {&m->add_buf, &m->kp_buf, &m->sort_buf})
     if (b->d) (void)hipFree(b->d);
-  if (m->stage_d) (void)hipFree(m->stage_d);
-  if (m->stage_h) (void)hipHostFree(m->stage_h);
-  if (m->ring_d) (void)hipFree(m->ring_d);
-  if (m->ring_h) (void)hipHostFree(m->ring_h);
-  for (hipEvent_t e : m->ring_ev) if (e) (void)hipEventDestroy(e);
   delete m;
 }
 
@@ -412,23 +387,19 @@ gfbe_status gfbe_vmap_create(gfbe_ctx *c, int32_t voxel_capacity, const gfbe_vma
   if (voxel_capacity < 1 || voxel_capacity > (1 << 21)) return GFBE_BAD_INPUT;
   if (ctx_device(c) < 0) { ctx_set_error(c, "gfbe_vmap_create: HIP device context required (no CPU fallback)"); return GFBE_NO_DEVICE; }
   gfbe_vmap *m = new gfbe_vmap();
-  struct Guard { gfbe_ctx *c; gfbe_vmap *m; bool armed = true; ~Guard() { if (armed) gfbe_vmap_destroy(c, m); } } guard{c, m};
-  m->opt = o; m->cap = voxel_capacity; m->P = o.max_num_points_in_voxel;
+  CreateGuard<gfbe_vmap> guard{c, m, gfbe_vmap_destroy};
+  m->owner = c; m->opt = o; m->cap = voxel_capacity; m->P = o.max_num_points_in_voxel;
   int slots = 64;
   while (slots < 2 * voxel_capacity) slots <<= 1;
   m->slots = slots;
-  gfbe_status st;
-#define VA(p, n, fill) if ((st = vm_alloc(c, m, &p, n, fill)) != GFBE_OK) return st
+#define VA(p, n, fill) if (!m->alloc(&p, n, fill)) return GFBE_DEVICE_ERROR
   for (int b = 0; b < 2; b++) { VA(m->keys[b], (size_t)slots, 0xFF); VA(m->cnt[b], (size_t)slots, 0); VA(m->pts[b], (size_t)slots * m->P * 3, 0); }
   VA(m->meta, VM_META, 0); VA(m->part, 2 * (size_t)(slots / 256 + 1), 0);
   const size_t R = (size_t)o.max_num_residuals;
   VA(m->res_src, R, 0); VA(m->res_pts, 3 * R, 0); VA(m->res_nrm, 3 * R, 0); VA(m->res_off, R, 0); VA(m->res_al, R, 0); VA(m->res_w, R, 0);
 #undef VA
-  { Staged warm(c, m, 1 << 16); if (!warm.ok) { ctx_set_error(c, "gfbe_vmap_create: staging allocation failed"); return GFBE_DEVICE_ERROR; } }
-  VM_CHECK(c, hipMalloc((void **)&m->ring_d, (size_t)gfbe_vmap::RING * gfbe_vmap::RING_SLOT));
-  VM_CHECK(c, hipHostMalloc((void **)&m->ring_h, (size_t)gfbe_vmap::RING * gfbe_vmap::RING_SLOT));
-  for (int k = 0; k < gfbe_vmap::RING; k++) VM_CHECK(c, hipEventCreateWithFlags(&m->ring_ev[k], hipEventDisableTiming));
-  VM_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
+  if (!m->make_staging(c, "gfbe_vmap_create", 1 << 16, true)) return GFBE_DEVICE_ERROR;
+  GFBE_CHECK(c, hipStreamSynchronize(ctx_stream(c)));
   guard.armed = false;
   *out = m;
   return GFBE_OK;
@@ -442,7 +413,7 @@ static gfbe_status vm_add_device(gfbe_ctx *c, gfbe_vmap *m, int n, const double 
   const VmDev V = vm_dev(m, m->cur);
   const unsigned g = (unsigned)((N + 255) / 256);
   hipLaunchKernelGGL(k_vm_keys, dim3(g), dim3(256), 0, s, n, din, m->opt.size_voxel_map, key, idx);
-  VM_CHECK(c, rocprim::radix_sort_pairs(m->sort_buf.d, tmp_bytes, key, skey, idx, sidx, N, 0, 49, s));      // (stable: input order inside a voxel)
+  GFBE_CHECK(c, rocprim::radix_sort_pairs(m->sort_buf.d, tmp_bytes, key, skey, idx, sidx, N, 0, 49, s));      // (stable: input order inside a voxel)
   hipLaunchKernelGGL(k_vm_probe, dim3(g), dim3(256), 0, s, V, n, skey, min_num_points, isnew, skip);
   hipLaunchKernelGGL(k_vm_admit, dim3(1), dim3(VM_THREADS), 0, s, V, n, isnew, skip);
   hipLaunchKernelGGL(k_vm_insert, dim3(g), dim3(256), 0, s, V, n, skey, sidx, din, m->opt.size_voxel_map, m->opt.min_distance_points, min_num_points, added);
@@ -454,14 +425,14 @@ struct AddScratch { unsigned long long *key, *skey; int *idx, *sidx, *isnew, *sk
 static gfbe_status vm_add_scratch(gfbe_ctx *c, gfbe_vmap *m, int n, bool world, AddScratch *a) {
   hipStream_t s = ctx_stream(c);
   const size_t N = (size_t)n;
-  VM_CHECK(c, grow(s, m->add_buf, 2 * ((N * 8 + 255) & ~(size_t)255) + 5 * ((N * 4 + 255) & ~(size_t)255) + (world ? ((N * 24 + 255) & ~(size_t)255) : 0)));
+  GFBE_CHECK(c, grow(s, m->add_buf, 2 * ((N * 8 + 255) & ~(size_t)255) + 5 * ((N * 4 + 255) & ~(size_t)255) + (world ? ((N * 24 + 255) & ~(size_t)255) : 0)));
   char *p = m->add_buf.d;
   a->key = vm_carve<unsigned long long>(p, N); a->skey = vm_carve<unsigned long long>(p, N);
   a->idx = vm_carve<int>(p, N); a->sidx = vm_carve<int>(p, N); a->isnew = vm_carve<int>(p, N); a->skip = vm_carve<int>(p, N); a->added = vm_carve<int>(p, N);
   a->world = world ? vm_carve<double>(p, 3 * N) : nullptr;
   a->tmp_bytes = 0;
-  VM_CHECK(c, rocprim::radix_sort_pairs(nullptr, a->tmp_bytes, a->key, a->skey, a->idx, a->sidx, N, 0, 49, s));
-  VM_CHECK(c, grow(s, m->sort_buf, std::max<size_t>(a->tmp_bytes, 256)));
+  GFBE_CHECK(c, rocprim::radix_sort_pairs(nullptr, a->tmp_bytes, a->key, a->skey, a->idx, a->sidx, N, 0, 49, s));
+  GFBE_CHECK(c, grow(s, m->sort_buf, std::max<size_t>(a->tmp_bytes, 256)));
   return GFBE_OK;
 }
 
@@ -481,7 +452,7 @@ gfbe_status gfbe_vmap_add_points(gfbe_ctx *c, gfbe_vmap *m, int32_t n, const dou
     sg.flush();
     if ((st = vm_add_device(c, m, n, din, min_num_points, a.key, a.skey, a.idx, a.sidx, a.isnew, a.skip, a.added, a.tmp_bytes)) != GFBE_OK) return st;
   }
-  VM_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   return GFBE_OK;
 }
 
@@ -494,7 +465,7 @@ static gfbe_status vm_add_scan_device(gfbe_ctx *c, gfbe_vmap *m, int ct, int n, 
   gfbe_status st;
   hipLaunchKernelGGL(k_vm_world, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, n, ct ? 1 : 0, draw, dal, dpb, dpe, a.world);
   if ((st = vm_add_device(c, m, n, a.world, min_num_points, a.key, a.skey, a.idx, a.sidx, a.isnew, a.skip, a.added, a.tmp_bytes)) != GFBE_OK) return st;
-  if (pts_world_out) VM_CHECK(c, hipMemcpyAsync(pts_world_out, a.world, sizeof(double) * 3 * N, hipMemcpyDeviceToHost, s));
+  if (pts_world_out) GFBE_CHECK(c, hipMemcpyAsync(pts_world_out, a.world, sizeof(double) * 3 * N, hipMemcpyDeviceToHost, s));
   return GFBE_OK;
 }
 
@@ -516,7 +487,7 @@ gfbe_status gfbe_vmap_add_scan(gfbe_ctx *c, gfbe_vmap *m, int32_t ct, int32_t n,
     sg.flush();
     if ((st = vm_add_scan_device(c, m, ct, n, draw, dal, dpb, dpe, min_num_points, a, pts_world_out)) != GFBE_OK) return st;
   }
-  VM_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   return GFBE_OK;
 }
 
@@ -539,7 +510,7 @@ gfbe_status gfbe_vmap_add_scan_handle(gfbe_ctx *c, gfbe_vmap *m, int32_t ct, gfb
     sg.flush();
     if ((st = vm_add_scan_device(c, m, ct, sv.n, sv.pts, sv.alpha, dpb, dpe, min_num_points, a, nullptr)) != GFBE_OK) return st;
   }
-  VM_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   return GFBE_OK;
 }
 
@@ -557,10 +528,10 @@ gfbe_status gfbe_vmap_erase_far(gfbe_ctx *c, gfbe_vmap *m, const double *locatio
     const int nb = (m->slots + 255) / 256;
     hipLaunchKernelGGL(k_vm_rehash, dim3(nb), dim3(256), 0, s, vm_dev(m, m->cur), vm_dev(m, 1 - m->cur), dloc, m->opt.max_distance * m->opt.max_distance, m->part);
     hipLaunchKernelGGL(k_vm_recount, dim3(1), dim3(VM_THREADS), 0, s, vm_dev(m, m->cur), nb, m->part);
-    VM_CHECK(c, hipMemsetAsync(m->keys[m->cur], 0xFF, sizeof(unsigned long long) * (size_t)m->slots, s));
+    GFBE_CHECK(c, hipMemsetAsync(m->keys[m->cur], 0xFF, sizeof(unsigned long long) * (size_t)m->slots, s));
     m->cur = 1 - m->cur;
   }
-  VM_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   return GFBE_OK;
 }
 
@@ -568,8 +539,8 @@ gfbe_status gfbe_vmap_size(gfbe_ctx *c, gfbe_vmap *m, int32_t *n_voxels, int32_t
   gfbe_status st = vm_ready(c, m);
   if (st != GFBE_OK) return st;
   hipStream_t s = ctx_stream(c);
-  VM_CHECK(c, hipMemcpyAsync(m->stage_h, m->meta, sizeof(int) * VM_META, hipMemcpyDeviceToHost, s));
-  VM_CHECK(c, hipStreamSynchronize(s));
+  GFBE_CHECK(c, hipMemcpyAsync(m->stage_h, m->meta, sizeof(int) * VM_META, hipMemcpyDeviceToHost, s));
+  GFBE_CHECK(c, hipStreamSynchronize(s));
   const int *h = (const int *)m->stage_h;
   if (n_voxels) *n_voxels = h[M_VOX];
   if (n_points) *n_points = h[M_PTS];
@@ -585,9 +556,9 @@ gfbe_status gfbe_vmap_download(gfbe_ctx *c, gfbe_vmap *m, int16_t *keys, int32_t
   const size_t S = (size_t)m->slots;
   std::vector<unsigned long long> hk(S);
   std::vector<int> hc(S);
-  VM_CHECK(c, hipMemcpyAsync(hk.data(), m->keys[m->cur], 8 * S, hipMemcpyDeviceToHost, s));
-  VM_CHECK(c, hipMemcpyAsync(hc.data(), m->cnt[m->cur], 4 * S, hipMemcpyDeviceToHost, s));
-  VM_CHECK(c, hipStreamSynchronize(s));
+  GFBE_CHECK(c, hipMemcpyAsync(hk.data(), m->keys[m->cur], 8 * S, hipMemcpyDeviceToHost, s));
+  GFBE_CHECK(c, hipMemcpyAsync(hc.data(), m->cnt[m->cur], 4 * S, hipMemcpyDeviceToHost, s));
+  GFBE_CHECK(c, hipStreamSynchronize(s));
   std::vector<int> slot;
   for (size_t i = 0; i < S; i++) if (hk[i] != VM_EMPTY) slot.push_back((int)i);
   std::sort(slot.begin(), slot.end(), [&](int a, int b) { return hk[a] < hk[b]; });
@@ -609,7 +580,7 @@ gfbe_status gfbe_vmap_download(gfbe_ctx *c, gfbe_vmap *m, int16_t *keys, int32_t
     hipLaunchKernelGGL(k_vm_gather, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, s, vm_dev(m, m->cur), (int)nv, dslot, doff, dout);
     sg.down(points, dout, 3 * np);
   }
-  VM_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   return GFBE_OK;
 }
 
@@ -637,11 +608,11 @@ gfbe_status gfbe_vmap_upload(gfbe_ctx *c, gfbe_vmap *m, int32_t n_voxels, const 
     double *dp = sg.up(points, 3 * np);
     if (!sg.ok) { ctx_set_error(c, "gfbe_vmap_upload: staging allocation failed"); return GFBE_DEVICE_ERROR; }
     sg.flush();
-    VM_CHECK(c, hipMemsetAsync(m->keys[m->cur], 0xFF, sizeof(unsigned long long) * (size_t)m->slots, s));
-    VM_CHECK(c, hipMemsetAsync(m->meta, 0, sizeof(int) * 2, s));      // voxel and point count (the sticky counters stay)
+    GFBE_CHECK(c, hipMemsetAsync(m->keys[m->cur], 0xFF, sizeof(unsigned long long) * (size_t)m->slots, s));
+    GFBE_CHECK(c, hipMemsetAsync(m->meta, 0, sizeof(int) * 2, s));      // voxel and point count (the sticky counters stay)
     if (nv) hipLaunchKernelGGL(k_vm_scatter, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, s, vm_dev(m, m->cur), (int)nv, dk, doff, dp);
   }
-  VM_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   return GFBE_OK;
 }
 
@@ -672,17 +643,17 @@ gfbe_status gfbe_vmap_associate(gfbe_ctx *c, gfbe_vmap *m, int32_t ct, int32_t n
     sg.down(hmeta, (const int *)m->meta, VM_META);
     if (n > 0) { sg.down(neighbor_count, (const int *)A.kp_cnt, (size_t)n); sg.down(a2D, (const double *)A.kp_a2d, (size_t)n); sg.down(neighbor_visit, (const int *)A.kp_vis, (size_t)n * o.max_number_neighbors); }
   }
-  VM_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   if (hmeta[M_OVER]) { ctx_set_error(c, "voxel map capacity exceeded"); return GFBE_BAD_INPUT; }
   const size_t R = (size_t)hmeta[M_NRES];
   m->n_res = (int)R; m->assoc_ct = A.ct; m->assoc_gen = m->gen; m->assoc_valid = true;
   if (n_res) *n_res = (int32_t)R;
   if (n_nan) *n_nan = hmeta[M_NAN];
   if (R) {
-#define DN(h, d, cnt) if (h) VM_CHECK(c, hipMemcpyAsync(h, d, sizeof(*h) * (cnt), hipMemcpyDeviceToHost, s))
+#define DN(h, d, cnt) if (h) GFBE_CHECK(c, hipMemcpyAsync(h, d, sizeof(*h) * (cnt), hipMemcpyDeviceToHost, s))
     DN(src, m->res_src, R); DN(pts, m->res_pts, 3 * R); DN(normals, m->res_nrm, 3 * R); DN(offsets, m->res_off, R); DN(alpha_out, m->res_al, R); DN(weights, m->res_w, R);
 #undef DN
-    VM_CHECK(c, hipStreamSynchronize(s));
+    GFBE_CHECK(c, hipStreamSynchronize(s));
   }
   return GFBE_OK;
 }
@@ -715,7 +686,7 @@ gfbe_status gfbe_vmap_localizability(gfbe_ctx *c, gfbe_vmap *m, double *sv, int3
     hipLaunchKernelGGL(k_vm_local, dim3(1), dim3(256), 0, ctx_stream(c), vm_dev(m, m->cur), m->res_nrm, dout);
     sg.down(out, (const double *)dout, 4);
   }
-  VM_CHECK(c, hipGetLastError());
+  GFBE_CHECK(c, hipGetLastError());
   if (sv) for (int a = 0; a < 3; a++) sv[a] = out[a];
   if (degenerate) *degenerate = out[3] != 0.0;
   return GFBE_OK;

@@ -5,10 +5,10 @@
 #include <vector>
 
 #include "gfbe.h"
-#include "gfbe_device.h"      // gfbe_tab_staging, gfd::DevBuf
+#include "gfbe_handle.h"      // gfbe_handle, gfd::DevBuf
 #include "gfbe_vmap.h"        // vmap_hash, VM_EMPTY
 
-struct gfbe_vmap : gfbe_tab_staging {
+struct gfbe_vmap : gfbe_handle {
   gfbe_vmap_options opt;
   int cap = 0, slots = 0, P = 0;
   unsigned long long *keys[2] = {};     // [slots]
@@ -17,7 +17,6 @@ struct gfbe_vmap : gfbe_tab_staging {
   int cur = 0;
   int *meta = nullptr;                  // [VM_META]
   int *part = nullptr;                  // [2][slots / 256] per-workgroup survivor counts of erase_far
-  std::vector<void *> allocs;
   gfd::DevBuf add_buf, kp_buf, sort_buf;
   // the association held on the handle: [max_num_residuals] each
   int *res_src = nullptr;

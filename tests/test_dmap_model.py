@@ -262,3 +262,30 @@ def test_c_abi_without_a_device():
     with pytest.raises(RuntimeError):
         abi.DenseMap(lib, "gfbe_", ctx, 64, 4)
     lib.gfbe_destroy(ctx)
+
+
+def test_no_device_calls_name_themselves():
+    """Every gfbe_dmap_* call on a context without a device leaves its own name and the "no CPU fallback" text in gfbe_last_error."""
+    gf.build_native()
+    lib = C.CDLL(gf.lib_path())
+    for s in gf.backend.EXPORTS:
+        if s.startswith("gfbe_dmap_") and s not in ("gfbe_dmap_destroy", "gfbe_dmap_default_options"):
+            getattr(lib, s).restype = abi.c_i
+    lib.gfbe_create.restype = abi.c_i
+    lib.gfbe_last_error.restype = C.c_char_p
+    ctx = C.c_void_p()
+    assert lib.gfbe_create(C.byref(ctx), -1, None) == abi.OK
+    pose, n = np.array([0, 0, 0, 0, 0, 0, 1.0]), abi.c_i(-7)
+    counts = (abi.c_i * 8)(*[-7] * 8)
+    calls = dict(
+        add_keyframe=lambda: lib.gfbe_dmap_add_keyframe(ctx, None, pose.ctypes.data_as(PD), 0, None, None),
+        rebuild=lambda: lib.gfbe_dmap_rebuild(ctx, None, 0, None),
+        filter=lambda: lib.gfbe_dmap_filter(ctx, None, None, C.byref(n), None, None),
+        size=lambda: lib.gfbe_dmap_size(ctx, None, counts),
+        download_cloud=lambda: lib.gfbe_dmap_download_cloud(ctx, None, None, None, None, None),
+        download_keyframe=lambda: lib.gfbe_dmap_download_keyframe(ctx, None, 0, C.byref(n), None, None))
+    for name, f in calls.items():
+        assert f() == abi.NO_DEVICE, name
+        msg = lib.gfbe_last_error(ctx) or b""
+        assert msg.startswith(b"gfbe_dmap_" + name.encode() + b":") and b"no CPU fallback" in msg, (name, msg)
+    lib.gfbe_destroy(ctx)

@@ -219,3 +219,31 @@ def test_c_abi_without_a_device():
     with pytest.raises(RuntimeError):
         abi.Scan(lib, "gfbe_", ctx, 64)
     lib.gfbe_destroy(ctx)
+
+
+def test_no_device_calls_name_themselves():
+    """Every gfbe_scan_* call on a context without a device leaves its own name and the "no CPU fallback" text in gfbe_last_error."""
+    gf.build_native()
+    lib = C.CDLL(gf.lib_path())
+    for s in gf.backend.EXPORTS:
+        if s.startswith("gfbe_scan_") and s != "gfbe_scan_destroy":
+            getattr(lib, s).restype = abi.c_i
+    lib.gfbe_create.restype = abi.c_i
+    lib.gfbe_last_error.restype = C.c_char_p
+    lib.gfbe_scan_subsample.argtypes = [C.c_void_p, C.c_void_p, C.c_double]
+    lib.gfbe_scan_keypoints.argtypes = [C.c_void_p, C.c_void_p, abi.c_i, PD, PD, C.c_double, C.POINTER(abi.c_i)]
+    ctx = C.c_void_p()
+    assert lib.gfbe_create(C.byref(ctx), -1, None) == abi.OK
+    pose, n = np.array([0, 0, 0, 0, 0, 0, 1.0]), abi.c_i(0)
+    calls = dict(
+        upload=lambda: lib.gfbe_scan_upload(ctx, None, 0, None, None, None, None),
+        subsample=lambda: lib.gfbe_scan_subsample(ctx, None, 0.2),
+        undistort=lambda: lib.gfbe_scan_undistort(ctx, None, 1, _p(pose), _p(pose)),
+        keypoints=lambda: lib.gfbe_scan_keypoints(ctx, None, 0, _p(pose), _p(pose), 0.2, C.byref(n)),
+        size=lambda: lib.gfbe_scan_size(ctx, None, None, None, None),
+        download=lambda: lib.gfbe_scan_download(ctx, None, 0, None, None, None, None))
+    for name, f in calls.items():
+        assert f() == abi.NO_DEVICE, name
+        msg = lib.gfbe_last_error(ctx) or b""
+        assert msg.startswith(b"gfbe_scan_" + name.encode() + b":") and b"no CPU fallback" in msg, (name, msg)
+    lib.gfbe_destroy(ctx)
