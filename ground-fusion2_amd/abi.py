@@ -2105,3 +2105,121 @@ class Observer(Handle):
         n, ids, un = c_i(-1), np.zeros(cap, np.int32), np.zeros((cap, 2), np.float32)
         self._check(self._f("download_prev")(self.ctx, self.h, int(camera), C.byref(n), _pi(ids), un.ctypes.data_as(PF)), "download_prev")
         return dict(ids=ids[:n.value].copy(), un_pts=un[:n.value].copy())
+
+
+# ---------------------------------------------------------------------------------------------
+# the keyframe descriptors between the tracker and the loop database (gfbe_kfd_* of include/gfbe_kfd.h; the model is tests/kfd_np.py,
+# there is no oracle row)
+# ---------------------------------------------------------------------------------------------
+KFD_PREFIX = "gfbe_kfd_"
+KFD_COUNTERS = ("corners", "kept", "listed", "overflow")
+
+
+class KfdOptions(C.Structure):
+    _fields_ = [("struct_size", c_i), ("ring_slots", c_i), ("fast_threshold", c_i), ("keypoint_capacity", c_i), ("window_capacity", c_i), ("reserved", c_i)]
+
+
+def kfd_default_options(lib, **kw):
+    return options_struct(lib, KFD_PREFIX, "", KfdOptions, kw)
+
+
+class KeyframeDescriber(Handle):
+    """The blurred image, FAST corners, BRIEF descriptors and keypoints_norm of a keyframe for n_cameras cameras of rows x cols uint8
+    images, and their hand-over to a LoopDatabase on the same library and context; see include/gfbe_kfd.h. pattern [4, 256] int32 =
+    x1 y1 x2 y2 of the pairs, cameras [n_cameras, 8] = fx fy cx cy k1 k2 p1 p2. options: fields of gfbe_kfd_options. The *_raw methods
+    return the status first; the others raise."""
+
+    def __init__(self, lib, ctx, n_cameras, rows, cols, pattern, cameras, **options):
+        Handle.__init__(self, lib, KFD_PREFIX, ctx)
+        self.n_cameras, self.rows, self.cols = int(n_cameras), int(rows), int(cols)
+        self.opt = self._options(KfdOptions, options)
+        pat, cams = _i32(pattern).reshape(4, 256), _f64(cameras).reshape(-1, 8)
+        assert len(cams) == self.n_cameras, cams.shape
+        self._check(self._f("create")(self.ctx, self.n_cameras, self.rows, self.cols, _pi(pat), _pd(cams), C.byref(self.opt), C.byref(self.h)), "create")
+
+    def push_image_raw(self, slot, images):
+        im = _u8(images)
+        assert im.size == self.n_cameras * self.rows * self.cols, im.shape
+        return self._f("push_image")(self.ctx, self.h, int(slot), im.ctypes.data_as(PU8))
+
+    def push_image(self, slot, images):
+        """images [n_cameras, rows, cols] uint8 into ring slot `slot` (K6), with the slot's blurred image."""
+        self._check(self.push_image_raw(slot, images), "push_image")
+
+    def capture_raw(self, tracker, slot):
+        return self._f("capture")(self.ctx, self.h, tracker.h, int(slot))
+
+    def capture(self, tracker, slot):
+        """The current images of `tracker` (a Tracker of the same n_cameras, rows and cols) into ring slot `slot`; no wait."""
+        self._check(self.capture_raw(tracker, slot), "capture")
+
+    def extract_raw(self, slot, outputs=True, fill=-7):
+        """K2 .. K5 on a slot. Returns (status, per-camera list of dict(pts [n, 2], score [n], pts_norm [n, 2], desc [n, 4] uint64,
+        counters)); outputs False: only the counters come back (the lists None). The flat outputs start as `fill`."""
+        C_, room = self.n_cameras, self.n_cameras * self.opt.keypoint_capacity if outputs else 0
+        off, counters = np.full(C_ + 1, fill, np.int32), np.full((C_, 4), fill, np.int32)
+        pts, ptsn = np.full((room, 2), fill, np.float32), np.full((room, 2), fill, np.float32)
+        score, desc = np.full(room, fill, np.int32), np.full((room, 4), fill % (1 << 64), np.uint64)
+        rc = self._f("extract")(self.ctx, self.h, int(slot), _pi(off), pts.ctypes.data_as(PF) if outputs else None, _pi(score) if outputs else None,
+                                ptsn.ctypes.data_as(PF) if outputs else None, desc.ctypes.data_as(PU64) if outputs else None, _pi(counters))
+        if rc != OK:
+            return rc, dict(offset=off, pts=pts, score=score, pts_norm=ptsn, desc=desc, counters=counters)
+        if not outputs:
+            return rc, [dict(pts=None, score=None, pts_norm=None, desc=None, counters=dict(zip(KFD_COUNTERS, counters[k].tolist()))) for k in range(C_)]
+        return rc, [dict(pts=pts[a:b].copy(), score=score[a:b].copy(), pts_norm=ptsn[a:b].copy(), desc=desc[a:b].copy(), counters=dict(zip(KFD_COUNTERS, counters[k].tolist())))
+                    for k, (a, b) in enumerate(zip(off[:-1], off[1:]))]
+
+    def extract(self, slot, outputs=True):
+        rc, out = self.extract_raw(slot, outputs)
+        self._check(rc, "extract")
+        return out
+
+    def describe_raw(self, slot, pts_uv, fill=-7):
+        """K4 on per-camera window points pts_uv [n, 2]. Returns (status, per-camera list of dict(desc [n, 4], points, zeroed))."""
+        off = _offsets([len(np.asarray(p).reshape(-1, 2)) for p in pts_uv])
+        n = int(off[-1])
+        p = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 2) for x in pts_uv]) if len(pts_uv) else np.zeros((0, 2)), np.float32)
+        desc, counters = np.full((n, 4), fill % (1 << 64), np.uint64), np.full((self.n_cameras, 2), fill, np.int32)
+        rc = self._f("describe")(self.ctx, self.h, int(slot), _pi(off), p.ctypes.data_as(PF), desc.ctypes.data_as(PU64), _pi(counters))
+        if rc != OK:
+            return rc, dict(desc=desc, counters=counters)
+        return rc, [dict(desc=desc[a:b].copy(), points=int(counters[k, 0]), zeroed=int(counters[k, 1])) for k, (a, b) in enumerate(zip(off[:-1], off[1:]))]
+
+    def describe(self, slot, pts_uv):
+        rc, out = self.describe_raw(slot, pts_uv)
+        self._check(rc, "describe")
+        return out
+
+    def add_keyframe_raw(self, camera, db, detect_loop=True):
+        """LoopDatabase.add_keyframe_raw on `camera`'s lists of the last extract, from the device."""
+        idx, loop, nr = c_i(-7), c_i(-7), c_i(-7)
+        rid, rs = np.full(LDB_MAX_RESULTS, -7, np.int32), np.zeros(LDB_MAX_RESULTS)
+        rc = self._f("add_keyframe")(self.ctx, self.h, int(camera), db.h, int(bool(detect_loop)), C.byref(idx), C.byref(loop), C.byref(nr), _pi(rid), _pd(rs))
+        n = max(nr.value, 0)
+        return rc, dict(index=idx.value, loop_index=loop.value, result_id=rid[:n].copy(), result_score=rs[:n].copy())
+
+    def add_keyframe(self, camera, db, detect_loop=True):
+        rc, out = self.add_keyframe_raw(camera, db, detect_loop)
+        self._check(rc, "add_keyframe")
+        return out
+
+    def match_raw(self, camera, db, old_index, n_window):
+        """LoopDatabase.match_raw with `camera`'s n_window window descriptors of the last describe, from the device."""
+        n = int(n_window)
+        st, bi, bd, nm = np.zeros(n, np.uint8), np.zeros(n, np.int32), np.zeros(n, np.int32), c_i(-7)
+        src, pt, ptn = np.zeros(n, np.int32), np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32)
+        rc = self._f("match")(self.ctx, self.h, int(camera), db.h, int(old_index), st.ctypes.data_as(PU8), _pi(bi), _pi(bd), C.byref(nm), _pi(src), pt.ctypes.data_as(PF),
+                              ptn.ctypes.data_as(PF))
+        m = max(nm.value, 0)
+        return rc, dict(status=st, best_index=bi, best_dist=bd, n_matched=nm.value, matched_src=src[:m], matched_pt=pt[:m], matched_pt_norm=ptn[:m])
+
+    def match(self, camera, db, old_index, n_window):
+        rc, out = self.match_raw(camera, db, old_index, n_window)
+        self._check(rc, "match")
+        return out
+
+    def planes(self, slot, camera, score=True):
+        """dict(blurred [rows, cols] uint8, score [rows, cols] uint8 after suppression) of a camera of a slot (score: after an extract)."""
+        bl, sc = np.zeros((self.rows, self.cols), np.uint8), np.zeros((self.rows, self.cols), np.uint8)
+        self._check(self._f("download")(self.ctx, self.h, int(slot), int(camera), bl.ctypes.data_as(PU8), sc.ctypes.data_as(PU8) if score else None), "download")
+        return dict(blurred=bl, score=sc if score else None)

@@ -26,6 +26,7 @@ LC6_EXPORTS = ["gfbe_lc6_" + name for name in signatures.LC6]      # include/gfb
 KLT_EXPORTS = ["gfbe_klt_" + name for name in signatures.KLT]      # include/gfbe_klt.h: likewise
 DET_EXPORTS = ["gfbe_det_" + name for name in signatures.DET]      # include/gfbe_det.h: likewise
 OBS_EXPORTS = ["gfbe_obs_" + name for name in signatures.OBS]      # include/gfbe_obs.h: likewise
+KFD_EXPORTS = ["gfbe_kfd_" + name for name in signatures.KFD]      # include/gfbe_kfd.h: likewise
 
 
 class BackendError(RuntimeError):
@@ -54,7 +55,7 @@ def build_native(force=False, verbose=False, out=None, extra_flags=None, fp_cont
     so = out or os.path.join(_CSRC, "libgfbe.so")
     srcs = sources()
     hdrs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".h", ".hpp"))]
-    hdrs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("gfbe.h", "gfbe_lc6.h", "gfbe_klt.h", "gfbe_det.h", "gfbe_obs.h")]
+    hdrs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("gfbe.h", "gfbe_lc6.h", "gfbe_klt.h", "gfbe_det.h", "gfbe_obs.h", "gfbe_kfd.h")]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = os.environ.get("GFBE_EXTRA_FLAGS", "").split() if extra_flags is None else list(extra_flags)
     cflags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=" + fp_contract, "-munsafe-fp-atomics",
@@ -113,6 +114,7 @@ class Backend(abi.CApi):
         if not os.path.exists(_SO):
             raise BackendError("HIP extension %s is missing: run __graft_entry__.build() (no CPU fallback)" % _SO)
         self.lib = abi.bind(abi.bind(abi.bind(abi.bind(abi.bind(C.CDLL(_SO), "gfbe_"), abi.LC6_PREFIX), abi.KLT_PREFIX), abi.DET_PREFIX), abi.OBS_PREFIX)
+        abi.bind(self.lib, abi.KFD_PREFIX)
         self.opt = options or abi.default_options()
         self.ctx = C.c_void_p()
         rc = self.lib.gfbe_create(C.byref(self.ctx), int(device), C.byref(self.opt))
@@ -226,6 +228,12 @@ class Backend(abi.CApi):
         id-ordered frame of trackImage, its hand-over to FeatureTables, removeOutliers and the prediction, include/gfbe_obs.h).
         cameras [n_cameras, 8] = fx fy cx cy k1 k2 p1 p2. Close it before its tracker. options: fields of gfbe_obs_options."""
         return abi.Observer(self.lib, self.ctx, tracker, cameras, **options)
+
+    def describer(self, n_cameras, rows, cols, pattern, cameras, **options):
+        """The keyframe descriptors (abi.KeyframeDescriber: the blurred image, FAST corners, BRIEF descriptors and keypoints_norm of a
+        keyframe for n_cameras cameras and their hand-over to a LoopDatabase, include/gfbe_kfd.h). pattern [4, 256] = x1 y1 x2 y2 of
+        the BRIEF pairs, cameras [n_cameras, 8] = fx fy cx cy k1 k2 p1 p2. options: fields of gfbe_kfd_options."""
+        return abi.KeyframeDescriber(self.lib, self.ctx, n_cameras, rows, cols, pattern, cameras, **options)
 
     def loop_database(self, voc, keyframe_capacity=1024, descriptor_capacity=1 << 20, **options):
         """The loop database of the loop-closure thread held on the device (abi.LoopDatabase: detectLoop's vocabulary query and decision,

@@ -497,6 +497,12 @@ void launch_ftab_pack(const FtabDev &T, int cur, int w0, int n, const BatchDev &
 gfbe_status ftab_ready(gfbe_ctx *c, gfbe_ftab *t);
 gfbe_status ftab_add_frame_device(gfbe_ctx *c, gfbe_ftab *t, const int32_t *frame_count, const double *td, int M, int mmax, const int *offset, const int *feature_id,
                                   const double *obs8, int32_t *keyframe, int32_t *counters, double *avg_parallax);
+// what gfbe_kfd.hip (include/gfbe_kfd.h) must see of the loop database: the launch halves of gfbe_ldb_add_keyframe and gfbe_ldb_match for
+// a keyframe's lists (desc [n][4], pts / pts_norm [n][2]) and window descriptors that lie on the device; `who` names the caller in errors
+gfbe_status ldb_add_keyframe_device(gfbe_ctx *c, gfbe_ldb *m, const char *who, int n, const uint64_t *desc, const float *pts, const float *pts_norm, int detect_loop,
+                                    int32_t *index_out, int32_t *loop_index, int32_t *n_results, int32_t *result_id, double *result_score);
+gfbe_status ldb_match_device(gfbe_ctx *c, gfbe_ldb *m, const char *who, int old_index, int n_window, const uint64_t *window_desc, uint8_t *status, int32_t *best_index,
+                             int32_t *best_dist, int32_t *n_matched, int32_t *matched_src, float *matched_pt, float *matched_pt_norm);
 
 
 // ---- device-resident line tables (gfbe_ltab.hip) and the table-fed line refinement (k_line_refine<true>, gfbe_line.hip)

@@ -315,7 +315,115 @@ void ldb_enqueue_transform(gfbe_ctx *c, gfbe_ldb *m, int n, const uint64_t *d_de
   hipLaunchKernelGGL(k_ldb_bow, dim3(1), dim3(LDB_BOW_THREADS), 0, st, n, (const int *)m->word_of, (const double *)m->t_word_weight, m->q_word, m->q_val, m->meta, res);
 }
 
+// rule 5's refusal: a keyframe that does not fit is refused whole and counted; nobody waits. True: the call is over with *rc.
+bool ldb_add_refused(gfbe_ctx *c, gfbe_ldb *m, int n, int32_t *index_out, int32_t *loop_index, int32_t *n_results, gfbe_status *rc) {
+  if (loop_index) *loop_index = -1;
+  if (n_results) *n_results = 0;
+  if (ldb_fits((long long)m->kf_n.size(), m->kcap, m->n_desc, m->dcap, n)) return false;
+  hipLaunchKernelGGL(k_ldb_refuse, dim3(1), dim3(1), 0, ctx_stream(c), m->meta);
+  *rc = hip_ok(c, hipGetLastError(), "hipGetLastError()") ? GFBE_OK : GFBE_DEVICE_ERROR;
+  if (index_out) *index_out = -1;
+  return true;
+}
+
+// The launch half of an add: rules 1 to 5 on n descriptors and keypoints that lie on the device (dd [n][4], dp / dpn [n][2]: in `sg`
+// after gfbe_ldb_add_keyframe's upload half, or a producer's own lists, gfbe_kfd_add_keyframe). `sg` is the database's staging,
+// opened by the caller and not yet flushed; the keyframe fits (ldb_add_refused).
+gfbe_status ldb_add_launch(gfbe_ctx *c, gfbe_ldb *m, const char *who, int n, const uint64_t *dd, const float *dp, const float *dpn, int detect_loop, Staged &sg,
+                           int32_t *index_out, int32_t *loop_index, int32_t *n_results, int32_t *result_id, double *result_score) {
+  hipStream_t st = ctx_stream(c);
+  const int frame_index = (int)m->kf_n.size();
+  LdbResult hres;
+  std::memset(&hres, 0, sizeof hres);
+  LdbResult *dres = sg.up((const LdbResult *)nullptr, 1);
+  if (!sg.ok) { ctx_set_error(c, (std::string(who) + ": staging allocation failed").c_str()); return GFBE_DEVICE_ERROR; }
+  sg.flush();
+  ldb_enqueue_transform(c, m, n, dd, nullptr);
+  if (detect_loop) {
+    // the query sees the database before this keyframe is added (db.query, then db.add: pose_graph.cpp:447-452)
+    hipLaunchKernelGGL(k_ldb_query, dim3(std::max(1, std::min(LDB_QUERY_BLOCKS, ldb_grid(frame_index, LDB_THREADS / 64)))), dim3(LDB_THREADS), 0, st, (const int *)m->meta,
+                       frame_index - m->opt.query_gap, (const int *)m->q_word, (const double *)m->q_val, (const long long *)m->ent, (const int *)m->bow_word,
+                       (const double *)m->bow_val, m->raw, m->has);
+    hipLaunchKernelGGL(k_ldb_select, dim3(1), dim3(LDB_BOW_THREADS), 0, st, (const int *)m->meta, (const double *)m->raw, (const int *)m->has,
+                       LdbDecide{m->opt.max_results, m->opt.min_loop_frame, m->opt.score_first, m->opt.score_other}, dres);
+    sg.down(&hres, (const LdbResult *)dres, 1);
+  }
+  if (n > 0)
+    hipLaunchKernelGGL(k_ldb_store, dim3(ldb_grid(n, LDB_THREADS)), dim3(LDB_THREADS), 0, st, (const int *)m->meta, (int)n, dd, dp, dpn, (const int *)m->q_word,
+                       (const double *)m->q_val, m->desc, m->pts, m->ptsn, m->bow_word, m->bow_val);
+  hipLaunchKernelGGL(k_ldb_commit, dim3(1), dim3(1), 0, st, m->meta, (int)n, m->ent);
+  sg.finish();      // detecting: the one wait, for the results; otherwise the slot's event
+  m->kf_begin.push_back(m->n_desc); m->kf_n.push_back(n); m->n_desc += n;
+  GFBE_CHECK(c, hipGetLastError());
+  if (index_out) *index_out = frame_index;
+  if (detect_loop) {
+    if (loop_index) *loop_index = hres.loop_index;
+    if (n_results) *n_results = hres.n_results;
+    for (int a = 0; a < hres.n_results; a++) { if (result_id) result_id[a] = hres.id[a]; if (result_score) result_score[a] = hres.score[a]; }
+  }
+  return GFBE_OK;
+}
+
+// The launch half of a match: rule 6 of n_window descriptors on the device (dw [n_window][4]) against held keyframe old_index; `sg` as above.
+gfbe_status ldb_match_launch(gfbe_ctx *c, gfbe_ldb *m, const char *who, int old_index, int n_window, const uint64_t *dw, Staged &sg, uint8_t *status, int32_t *best_index,
+                             int32_t *best_dist, int32_t *n_matched, int32_t *matched_src, float *matched_pt, float *matched_pt_norm) {
+  const size_t W = (size_t)n_window;
+  int hn = 0;
+  int *d_bi = sg.up((const int *)nullptr, W), *d_bd = sg.up((const int *)nullptr, W), *d_flag = sg.up((const int *)nullptr, W), *d_src = sg.up((const int *)nullptr, W);
+  int *d_n = sg.up((const int *)nullptr, 1);
+  uint8_t *d_st = sg.up((const uint8_t *)nullptr, W);
+  float *d_pt = sg.up((const float *)nullptr, 2 * W), *d_ptn = sg.up((const float *)nullptr, 2 * W);
+  if (!sg.ok) { ctx_set_error(c, (std::string(who) + ": staging allocation failed").c_str()); return GFBE_DEVICE_ERROR; }
+  sg.flush();
+  hipStream_t st = ctx_stream(c);
+  const long long ob = m->kf_begin[(size_t)old_index];
+  if (n_window > 0)
+    hipLaunchKernelGGL(k_ldb_match, dim3(ldb_grid(n_window, LDB_THREADS / 64)), dim3(LDB_THREADS), 0, st, (int)n_window, dw, ob, m->kf_n[(size_t)old_index],
+                       (const uint64_t *)m->desc, (int)m->opt.match_start, (int)m->opt.match_max, d_bi, d_bd, d_flag, d_st);
+  hipLaunchKernelGGL(k_ldb_compact, dim3(1), dim3(LDB_BOW_THREADS), 0, st, (int)n_window, (const int *)d_flag, (const int *)d_bi, ob, (const float *)m->pts,
+                     (const float *)m->ptsn, d_n, d_src, d_pt, d_ptn);
+  // the compacted outputs are copied whole (n_window rows): only the first n_matched are defined, the rest the caller never reads
+  std::vector<int32_t> src_h(matched_src ? W : 0);
+  std::vector<float> pt_h(matched_pt ? 2 * W : 0), ptn_h(matched_pt_norm ? 2 * W : 0);
+  sg.down(&hn, (const int *)d_n, 1);
+  sg.down(status, (const uint8_t *)d_st, W);
+  sg.down(best_index, (const int32_t *)d_bi, W);
+  sg.down(best_dist, (const int32_t *)d_bd, W);
+  sg.down(src_h.data(), (const int32_t *)d_src, src_h.size());
+  sg.down(pt_h.data(), (const float *)d_pt, pt_h.size());
+  sg.down(ptn_h.data(), (const float *)d_ptn, ptn_h.size());
+  sg.finish();      // the one wait
+  if (matched_src) std::memcpy(matched_src, src_h.data(), sizeof(int32_t) * (size_t)hn);
+  if (matched_pt) std::memcpy(matched_pt, pt_h.data(), sizeof(float) * 2 * (size_t)hn);
+  if (matched_pt_norm) std::memcpy(matched_pt_norm, ptn_h.data(), sizeof(float) * 2 * (size_t)hn);
+  GFBE_CHECK(c, hipGetLastError());
+  if (n_matched) *n_matched = hn;
+  return GFBE_OK;
+}
+
 }  // namespace
+
+// ---- what gfbe_kfd.hip (include/gfbe_kfd.h) sees of the database: the two calls on lists that lie on the device (gfbe_device.h)
+namespace gfd {
+gfbe_status ldb_add_keyframe_device(gfbe_ctx *c, gfbe_ldb *m, const char *who, int n, const uint64_t *dd, const float *dp, const float *dpn, int detect_loop, int32_t *index_out,
+                                    int32_t *loop_index, int32_t *n_results, int32_t *result_id, double *result_score) {
+  gfbe_status rc = handle_ready(c, m, who, "loop database");
+  if (rc != GFBE_OK) return rc;
+  if (n < 0 || n > m->opt.max_keyframe_descriptors) return handle_bad(c, who, "n outside 0 .. max_keyframe_descriptors of the loop database");
+  if (ldb_add_refused(c, m, n, index_out, loop_index, n_results, &rc)) return rc;
+  Staged sg(c, m, 4096, /*defer=*/!detect_loop);
+  return ldb_add_launch(c, m, who, n, dd, dp, dpn, detect_loop, sg, index_out, loop_index, n_results, result_id, result_score);
+}
+gfbe_status ldb_match_device(gfbe_ctx *c, gfbe_ldb *m, const char *who, int old_index, int n_window, const uint64_t *dw, uint8_t *status, int32_t *best_index, int32_t *best_dist,
+                             int32_t *n_matched, int32_t *matched_src, float *matched_pt, float *matched_pt_norm) {
+  gfbe_status rc = handle_ready(c, m, who, "loop database");
+  if (rc != GFBE_OK) return rc;
+  if (old_index < 0 || old_index >= (int)m->kf_n.size()) return handle_bad(c, who, "old_index is not a held keyframe");
+  if (n_window < 0 || n_window > LDB_MAX_WINDOW) return handle_bad(c, who, "n_window outside 0 .. 2^20");
+  Staged sg(c, m, (size_t)n_window * 40 + 8192);
+  return ldb_match_launch(c, m, who, old_index, n_window, dw, sg, status, best_index, best_dist, n_matched, matched_src, matched_pt, matched_pt_norm);
+}
+}  // namespace gfd
 
 extern "C" {
 
@@ -410,51 +518,13 @@ gfbe_status gfbe_ldb_add_keyframe(gfbe_ctx *c, gfbe_ldb *m, int32_t n, const uin
     ctx_set_error(c, "gfbe_ldb_add_keyframe: n outside 0 .. max_keyframe_descriptors or a NULL input array");
     return GFBE_BAD_INPUT;
   }
-  hipStream_t st = ctx_stream(c);
-  if (loop_index) *loop_index = -1;
-  if (n_results) *n_results = 0;
-  const int frame_index = (int)m->kf_n.size();
-  if (!ldb_fits(frame_index, m->kcap, m->n_desc, m->dcap, n)) {      // refused whole and counted; nobody waits
-    hipLaunchKernelGGL(k_ldb_refuse, dim3(1), dim3(1), 0, st, m->meta);
-    GFBE_CHECK(c, hipGetLastError());
-    if (index_out) *index_out = -1;
-    return GFBE_OK;
-  }
+  if (ldb_add_refused(c, m, n, index_out, loop_index, n_results, &rc)) return rc;
+  // the upload half: the keyframe goes into the staging chunk (detecting) or a slot of the ring
   const size_t N = (size_t)n;
-  LdbResult hres;
-  std::memset(&hres, 0, sizeof hres);
-  {
-    Staged sg(c, m, N * 48 + 4096, /*defer=*/!detect_loop);
-    const uint64_t *dd = sg.up(desc, 4 * N);
-    const float *dp = sg.up(pts, 2 * N), *dpn = sg.up(pts_norm, 2 * N);
-    LdbResult *dres = sg.up((const LdbResult *)nullptr, 1);
-    if (!sg.ok) { ctx_set_error(c, "gfbe_ldb_add_keyframe: staging allocation failed"); return GFBE_DEVICE_ERROR; }
-    sg.flush();
-    ldb_enqueue_transform(c, m, n, dd, nullptr);
-    if (detect_loop) {
-      // the query sees the database before this keyframe is added (db.query, then db.add: pose_graph.cpp:447-452)
-      hipLaunchKernelGGL(k_ldb_query, dim3(std::max(1, std::min(LDB_QUERY_BLOCKS, ldb_grid(frame_index, LDB_THREADS / 64)))), dim3(LDB_THREADS), 0, st, (const int *)m->meta,
-                         frame_index - m->opt.query_gap, (const int *)m->q_word, (const double *)m->q_val, (const long long *)m->ent, (const int *)m->bow_word,
-                         (const double *)m->bow_val, m->raw, m->has);
-      hipLaunchKernelGGL(k_ldb_select, dim3(1), dim3(LDB_BOW_THREADS), 0, st, (const int *)m->meta, (const double *)m->raw, (const int *)m->has,
-                         LdbDecide{m->opt.max_results, m->opt.min_loop_frame, m->opt.score_first, m->opt.score_other}, dres);
-      sg.down(&hres, (const LdbResult *)dres, 1);
-    }
-    if (n > 0)
-      hipLaunchKernelGGL(k_ldb_store, dim3(ldb_grid(n, LDB_THREADS)), dim3(LDB_THREADS), 0, st, (const int *)m->meta, (int)n, dd, dp, dpn, (const int *)m->q_word,
-                         (const double *)m->q_val, m->desc, m->pts, m->ptsn, m->bow_word, m->bow_val);
-    hipLaunchKernelGGL(k_ldb_commit, dim3(1), dim3(1), 0, st, m->meta, (int)n, m->ent);
-    sg.finish();      // detecting: the one wait, for the results; otherwise the slot's event
-  }
-  m->kf_begin.push_back(m->n_desc); m->kf_n.push_back(n); m->n_desc += n;
-  GFBE_CHECK(c, hipGetLastError());
-  if (index_out) *index_out = frame_index;
-  if (detect_loop) {
-    if (loop_index) *loop_index = hres.loop_index;
-    if (n_results) *n_results = hres.n_results;
-    for (int a = 0; a < hres.n_results; a++) { if (result_id) result_id[a] = hres.id[a]; if (result_score) result_score[a] = hres.score[a]; }
-  }
-  return GFBE_OK;
+  Staged sg(c, m, N * 48 + 4096, /*defer=*/!detect_loop);
+  const uint64_t *dd = sg.up(desc, 4 * N);
+  const float *dp = sg.up(pts, 2 * N), *dpn = sg.up(pts_norm, 2 * N);
+  return ldb_add_launch(c, m, "gfbe_ldb_add_keyframe", n, dd, dp, dpn, detect_loop, sg, index_out, loop_index, n_results, result_id, result_score);
 }
 
 gfbe_status gfbe_ldb_match(gfbe_ctx *c, gfbe_ldb *m, int32_t old_index, int32_t n_window, const uint64_t *window_desc, uint8_t *status, int32_t *best_index, int32_t *best_dist,
@@ -464,41 +534,9 @@ gfbe_status gfbe_ldb_match(gfbe_ctx *c, gfbe_ldb *m, int32_t old_index, int32_t 
   if (old_index < 0 || old_index >= (int)m->kf_n.size()) { ctx_set_error(c, "gfbe_ldb_match: old_index is not a held keyframe"); return GFBE_BAD_INPUT; }
   if (n_window < 0 || n_window > LDB_MAX_WINDOW || (n_window > 0 && !window_desc)) { ctx_set_error(c, "gfbe_ldb_match: n_window outside 0 .. 2^20 or window_desc NULL"); return GFBE_BAD_INPUT; }
   const size_t W = (size_t)n_window;
-  int hn = 0;
-  {
-    Staged sg(c, m, W * 72 + 8192);
-    const uint64_t *dw = sg.up(window_desc, 4 * W);
-    int *d_bi = sg.up((const int *)nullptr, W), *d_bd = sg.up((const int *)nullptr, W), *d_flag = sg.up((const int *)nullptr, W), *d_src = sg.up((const int *)nullptr, W);
-    int *d_n = sg.up((const int *)nullptr, 1);
-    uint8_t *d_st = sg.up((const uint8_t *)nullptr, W);
-    float *d_pt = sg.up((const float *)nullptr, 2 * W), *d_ptn = sg.up((const float *)nullptr, 2 * W);
-    if (!sg.ok) { ctx_set_error(c, "gfbe_ldb_match: staging allocation failed"); return GFBE_DEVICE_ERROR; }
-    sg.flush();
-    hipStream_t st = ctx_stream(c);
-    const long long ob = m->kf_begin[(size_t)old_index];
-    if (n_window > 0)
-      hipLaunchKernelGGL(k_ldb_match, dim3(ldb_grid(n_window, LDB_THREADS / 64)), dim3(LDB_THREADS), 0, st, (int)n_window, dw, ob, m->kf_n[(size_t)old_index],
-                         (const uint64_t *)m->desc, (int)m->opt.match_start, (int)m->opt.match_max, d_bi, d_bd, d_flag, d_st);
-    hipLaunchKernelGGL(k_ldb_compact, dim3(1), dim3(LDB_BOW_THREADS), 0, st, (int)n_window, (const int *)d_flag, (const int *)d_bi, ob, (const float *)m->pts,
-                       (const float *)m->ptsn, d_n, d_src, d_pt, d_ptn);
-    // the compacted outputs are copied whole (n_window rows): only the first n_matched are defined, the rest the caller never reads
-    std::vector<int32_t> src_h(matched_src ? W : 0);
-    std::vector<float> pt_h(matched_pt ? 2 * W : 0), ptn_h(matched_pt_norm ? 2 * W : 0);
-    sg.down(&hn, (const int *)d_n, 1);
-    sg.down(status, (const uint8_t *)d_st, W);
-    sg.down(best_index, (const int32_t *)d_bi, W);
-    sg.down(best_dist, (const int32_t *)d_bd, W);
-    sg.down(src_h.data(), (const int32_t *)d_src, src_h.size());
-    sg.down(pt_h.data(), (const float *)d_pt, pt_h.size());
-    sg.down(ptn_h.data(), (const float *)d_ptn, ptn_h.size());
-    sg.finish();      // the one wait
-    if (matched_src) std::memcpy(matched_src, src_h.data(), sizeof(int32_t) * (size_t)hn);
-    if (matched_pt) std::memcpy(matched_pt, pt_h.data(), sizeof(float) * 2 * (size_t)hn);
-    if (matched_pt_norm) std::memcpy(matched_pt_norm, ptn_h.data(), sizeof(float) * 2 * (size_t)hn);
-  }
-  GFBE_CHECK(c, hipGetLastError());
-  if (n_matched) *n_matched = hn;
-  return GFBE_OK;
+  Staged sg(c, m, W * 72 + 8192);
+  const uint64_t *dw = sg.up(window_desc, 4 * W);
+  return ldb_match_launch(c, m, "gfbe_ldb_match", old_index, n_window, dw, sg, status, best_index, best_dist, n_matched, matched_src, matched_pt, matched_pt_norm);
 }
 
 gfbe_status gfbe_ldb_size(gfbe_ctx *c, gfbe_ldb *m, int32_t *counts) {

@@ -2,9 +2,9 @@
 
 GFBE holds the exports of include/gfbe.h, RCCL those of include/gfbe_rccl.h, LC6 those of include/gfbe_lc6.h (they live in the
 product library under the prefix gfbe_lc6_), KLT those of include/gfbe_klt.h (prefix gfbe_klt_, likewise), DET those of
-include/gfbe_det.h (prefix gfbe_det_, likewise), OBS those of include/gfbe_obs.h (prefix gfbe_obs_, likewise), GFO what the CPU oracle
-(prefix gfo_) shares with the product. tests/test_abi.py checks GFBE and RCCL against the prototypes of their headers,
-tests/test_lc6_host.py LC6, tests/test_klt_model.py KLT, tests/test_det_model.py DET, tests/test_obs_model.py OBS. abi.bind(lib, prefix) applies a
+include/gfbe_det.h (prefix gfbe_det_, likewise), OBS those of include/gfbe_obs.h (prefix gfbe_obs_, likewise), KFD those of
+include/gfbe_kfd.h (prefix gfbe_kfd_, likewise), GFO what the CPU oracle (prefix gfo_) shares with the product. tests/test_abi.py checks GFBE and RCCL against the prototypes of their headers,
+tests/test_lc6_host.py LC6, tests/test_klt_model.py KLT, tests/test_det_model.py DET, tests/test_obs_model.py OBS, tests/test_kfd_model.py KFD. abi.bind(lib, prefix) applies a
 table to a loaded library; nothing else in the package assigns restype / argtypes.
 
 Spelling: opaque handles (gfbe_ctx *, gfbe_ftab *, gfbe_batch *, ...) and void * are V, their out-parameters PV; gfbe_status is
@@ -12,7 +12,7 @@ an int32; struct pointers are pointers to the ctypes mirrors of abi.py.
 """
 import ctypes as C
 
-from .abi import (DetOptions, DmapOptions, FeatureList, FtabOptions, GnssObs, GnssState, ImuPreint, KltOptions, Lc4Options, Lc6Options, LdbOptions, LdbVocab, LineReducedV,
+from .abi import (DetOptions, DmapOptions, FeatureList, FtabOptions, GnssObs, GnssState, ImuPreint, KfdOptions, KltOptions, Lc4Options, Lc6Options, LdbOptions, LdbVocab, LineReducedV,
                   LineStepped, LineWindow, ObsOptions, Options, Prior, State, Summary, VmapOptions, VregOptions, VregSummary, WheelPreint, Window)
 
 P = C.POINTER
@@ -206,6 +206,19 @@ OBS = {             # prefix gfbe_obs_ (the frame observations between the track
     "download_prev": (i, [V, V, i, PI, PI, PF]),
 }
 
+KFD = {             # prefix gfbe_kfd_ (the keyframe descriptors between the tracker and the loop database; symbols of the product library)
+    "default_options": (None, [P(KfdOptions)]),
+    "create": (i, [V, i, i, i, PI, PD, P(KfdOptions), PV]),
+    "destroy": (None, [V, V]),
+    "push_image": (i, [V, V, i, PU8]),
+    "capture": (i, [V, V, V, i]),
+    "extract": (i, [V, V, i, PI, PF, PI, PF, PU64, PI]),
+    "describe": (i, [V, V, i, PI, PF, PU64, PI]),
+    "add_keyframe": (i, [V, V, i, V, i, PI, PI, PI, PI, PD]),
+    "match": (i, [V, V, i, V, i, PU8, PI, PI, PI, PI, PF, PF]),
+    "download": (i, [V, V, i, i, PU8, PU8]),
+}
+
 
 def _oracle(name):
     """The oracle's flavour of a shared entry point: the compute calls take `const gfbe_options *` where the product takes its
@@ -219,7 +232,8 @@ def _oracle(name):
 
 
 GFO = {name: _oracle(name) for name in GFBE}
-TABLES = {"gfbe_": GFBE, "gfo_": GFO, "gfbe_rccl_": RCCL, "gfbe_lc6_": LC6, "gfbe_klt_": KLT, "gfbe_det_": DET, "gfbe_obs_": OBS}
+TABLES = {"gfbe_": GFBE, "gfo_": GFO, "gfbe_rccl_": RCCL, "gfbe_lc6_": LC6, "gfbe_klt_": KLT, "gfbe_det_": DET, "gfbe_obs_": OBS,
+          "gfbe_kfd_": KFD}
 
 
 def declare(lib, prefix, table):
