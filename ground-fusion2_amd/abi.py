@@ -2223,3 +2223,98 @@ class KeyframeDescriber(Handle):
         bl, sc = np.zeros((self.rows, self.cols), np.uint8), np.zeros((self.rows, self.cols), np.uint8)
         self._check(self._f("download")(self.ctx, self.h, int(slot), int(camera), bl.ctypes.data_as(PU8), sc.ctypes.data_as(PU8) if score else None), "download")
         return dict(blurred=bl, score=sc if score else None)
+
+
+# ---------------------------------------------------------------------------------------------
+# the loop verification between the loop database's matches and a loop edge (gfbe_pnp_* of include/gfbe_pnp.h; the model is
+# tests/pnp_np.py, there is no oracle row)
+# ---------------------------------------------------------------------------------------------
+PNP_PREFIX = "gfbe_pnp_"
+
+
+class PnpOptions(C.Structure):
+    _fields_ = [("struct_size", c_i), ("max_problems", c_i), ("max_points", c_i), ("iterations", c_i), ("refine_iterations", c_i), ("min_loop_num", c_i),
+                ("seed", C.c_uint64), ("reproj_threshold", c_d), ("max_yaw_deg", c_d), ("max_translation", c_d)]
+
+
+def pnp_default_options(lib, **kw):
+    return options_struct(lib, PNP_PREFIX, "", PnpOptions, kw)
+
+
+class LoopVerifier(Handle):
+    """PnPRANSAC and the loop_info half of KeyFrame::findConnection for a batch of problems, and the whole chain from window descriptors
+    on a LoopDatabase (and a KeyframeDescriber) of the same library and context; see include/gfbe_pnp.h. options: fields of
+    gfbe_pnp_options. The *_raw methods return the status first; the others raise."""
+
+    def __init__(self, lib, ctx, **options):
+        Handle.__init__(self, lib, PNP_PREFIX, ctx)
+        self.opt = self._options(PnpOptions, options)
+        self._check(self._f("create")(self.ctx, C.byref(self.opt), C.byref(self.h)), "create")
+
+    @staticmethod
+    def _results(B, fill):
+        return dict(n_inliers=np.full(B, fill, np.int32), has_loop=np.full(B, fill, np.int32), loop_info=np.full((B, 8), float(fill)), pnp_pose=np.full((B, 12), float(fill)),
+                    best=np.full((B, 2), fill, np.int32), refine_flag=np.full(B, fill, np.int32))
+
+    @staticmethod
+    def _result_args(r):
+        return [_pi(r["n_inliers"]), _pi(r["has_loop"]), _pd(r["loop_info"]), _pd(r["pnp_pose"]), _pi(r["best"]), _pi(r["refine_flag"])]
+
+    def verify_raw(self, offset, point_3d, pt_norm, pose_cur, tic_qic, diagnostics=False, fill=-7):
+        """V1 .. V8 of len(offset) - 1 problems. Returns (status, dict(status [n] uint8, n_inliers, has_loop, refine_flag [B], loop_info
+        [B, 8], pnp_pose [B, 12], best [B, 2]; diagnostics: sample_idx [B, H, 3], n_solutions [B, H], hyp_pose [B, H, 4, 12], hyp_count
+        [B, H, 4])). The outputs start as `fill`."""
+        off, p3, pn = _i32(offset), _f32(point_3d).reshape(-1, 3), _f32(pt_norm).reshape(-1, 2)
+        pc, tq = _f64(pose_cur).reshape(-1, 12), _f64(tic_qic).reshape(-1, 12)
+        B, H = len(off) - 1, self.opt.iterations
+        assert len(p3) == len(pn) and len(pc) == len(tq) == B
+        r = self._results(B, fill)
+        r["status"] = np.full(len(p3), fill % 256, np.uint8)
+        d = [None] * 4
+        if diagnostics:
+            r.update(sample_idx=np.full((B, H, 3), fill, np.int32), n_solutions=np.full((B, H), fill, np.int32), hyp_pose=np.full((B, H, 4, 12), float(fill)),
+                     hyp_count=np.full((B, H, 4), fill, np.int32))
+            d = [_pi(r["sample_idx"]), _pi(r["n_solutions"]), _pd(r["hyp_pose"]), _pi(r["hyp_count"])]
+        rc = self._f("verify")(self.ctx, self.h, B, _pi(off), p3.ctypes.data_as(PF), pn.ctypes.data_as(PF), _pd(pc), _pd(tq), r["status"].ctypes.data_as(PU8),
+                               *(self._result_args(r) + d))
+        return rc, r
+
+    def verify(self, offset, point_3d, pt_norm, pose_cur, tic_qic, diagnostics=False):
+        rc, out = self.verify_raw(offset, point_3d, pt_norm, pose_cur, tic_qic, diagnostics)
+        self._check(rc, "verify")
+        return out
+
+    def _connect(self, name, head, n_window, point_3d, pose_cur, tic_qic, fill):
+        n = int(n_window)
+        p3, pc, tq = _f32(point_3d).reshape(-1, 3), _f64(pose_cur).reshape(12), _f64(tic_qic).reshape(12)
+        assert len(p3) == n, (p3.shape, n)
+        nm, src, pt, ptn, stp = c_i(fill), np.full(n, fill, np.int32), np.full((n, 2), fill, np.float32), np.full((n, 2), fill, np.float32), np.full(n, fill % 256, np.uint8)
+        r = self._results(1, fill)
+        rc = self._f(name)(self.ctx, self.h, *(head + [p3.ctypes.data_as(PF), _pd(pc), _pd(tq), C.byref(nm), _pi(src), pt.ctypes.data_as(PF), ptn.ctypes.data_as(PF),
+                                                       stp.ctypes.data_as(PU8)] + self._result_args(r)))
+        m = max(nm.value, 0) if rc == OK else 0
+        out = dict(n_matched=nm.value, matched_src=src[:m], matched_pt=pt[:m], matched_pt_norm=ptn[:m], status_pnp=stp[:m])
+        out.update({k: v[0] for k, v in r.items()})
+        out["raw"] = dict(matched_src=src, matched_pt=pt, matched_pt_norm=ptn, status_pnp=stp)
+        return rc, out
+
+    def find_connection_raw(self, db, old_index, window_desc, point_3d, pose_cur, tic_qic, fill=-7):
+        """gfbe_ldb_match's rule 6 and reduceVector on window_desc [n_window, 4] against held keyframe old_index of `db`, the gather of
+        point_3d [n_window, 3] by matched_src and V1 .. V8, with one wait. Returns (status, dict(n_matched, matched_src, matched_pt,
+        matched_pt_norm, status_pnp, n_inliers, has_loop, loop_info [8], pnp_pose [12], best [2], refine_flag))."""
+        w = _u64(window_desc)
+        return self._connect("find_connection", [db.h, int(old_index), len(w), w.ctypes.data_as(PU64)], len(w), point_3d, pose_cur, tic_qic, fill)
+
+    def find_connection(self, db, old_index, window_desc, point_3d, pose_cur, tic_qic):
+        rc, out = self.find_connection_raw(db, old_index, window_desc, point_3d, pose_cur, tic_qic)
+        self._check(rc, "find_connection")
+        return out
+
+    def find_connection_kfd_raw(self, describer, camera, db, old_index, n_window, point_3d, pose_cur, tic_qic, fill=-7):
+        """find_connection_raw on `camera`'s n_window window descriptors of `describer`'s last describe, from the device."""
+        return self._connect("find_connection_kfd", [describer.h, int(camera), db.h, int(old_index)], n_window, point_3d, pose_cur, tic_qic, fill)
+
+    def find_connection_kfd(self, describer, camera, db, old_index, n_window, point_3d, pose_cur, tic_qic):
+        rc, out = self.find_connection_kfd_raw(describer, camera, db, old_index, n_window, point_3d, pose_cur, tic_qic)
+        self._check(rc, "find_connection_kfd")
+        return out

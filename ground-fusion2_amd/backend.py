@@ -27,6 +27,7 @@ KLT_EXPORTS = ["gfbe_klt_" + name for name in signatures.KLT]      # include/gfb
 DET_EXPORTS = ["gfbe_det_" + name for name in signatures.DET]      # include/gfbe_det.h: likewise
 OBS_EXPORTS = ["gfbe_obs_" + name for name in signatures.OBS]      # include/gfbe_obs.h: likewise
 KFD_EXPORTS = ["gfbe_kfd_" + name for name in signatures.KFD]      # include/gfbe_kfd.h: likewise
+PNP_EXPORTS = ["gfbe_pnp_" + name for name in signatures.PNP]      # include/gfbe_pnp.h: likewise
 
 
 class BackendError(RuntimeError):
@@ -55,7 +56,7 @@ def build_native(force=False, verbose=False, out=None, extra_flags=None, fp_cont
     so = out or os.path.join(_CSRC, "libgfbe.so")
     srcs = sources()
     hdrs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".h", ".hpp"))]
-    hdrs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("gfbe.h", "gfbe_lc6.h", "gfbe_klt.h", "gfbe_det.h", "gfbe_obs.h", "gfbe_kfd.h")]
+    hdrs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("gfbe.h", "gfbe_lc6.h", "gfbe_klt.h", "gfbe_det.h", "gfbe_obs.h", "gfbe_kfd.h", "gfbe_pnp.h")]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = os.environ.get("GFBE_EXTRA_FLAGS", "").split() if extra_flags is None else list(extra_flags)
     cflags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=" + fp_contract, "-munsafe-fp-atomics",
@@ -115,6 +116,7 @@ class Backend(abi.CApi):
             raise BackendError("HIP extension %s is missing: run __graft_entry__.build() (no CPU fallback)" % _SO)
         self.lib = abi.bind(abi.bind(abi.bind(abi.bind(abi.bind(C.CDLL(_SO), "gfbe_"), abi.LC6_PREFIX), abi.KLT_PREFIX), abi.DET_PREFIX), abi.OBS_PREFIX)
         abi.bind(self.lib, abi.KFD_PREFIX)
+        abi.bind(self.lib, abi.PNP_PREFIX)
         self.opt = options or abi.default_options()
         self.ctx = C.c_void_p()
         rc = self.lib.gfbe_create(C.byref(self.ctx), int(device), C.byref(self.opt))
@@ -234,6 +236,12 @@ class Backend(abi.CApi):
         keyframe for n_cameras cameras and their hand-over to a LoopDatabase, include/gfbe_kfd.h). pattern [4, 256] = x1 y1 x2 y2 of
         the BRIEF pairs, cameras [n_cameras, 8] = fx fy cx cy k1 k2 p1 p2. options: fields of gfbe_kfd_options."""
         return abi.KeyframeDescriber(self.lib, self.ctx, n_cameras, rows, cols, pattern, cameras, **options)
+
+    def loop_verifier(self, **options):
+        """The loop verification (abi.LoopVerifier: P3P RANSAC on matched pairs, the refit on the inliers, loop_info and its acceptance
+        test for a batch of problems, and findConnection's chain from window descriptors to the decision behind one wait,
+        include/gfbe_pnp.h). options: fields of gfbe_pnp_options."""
+        return abi.LoopVerifier(self.lib, self.ctx, **options)
 
     def loop_database(self, voc, keyframe_capacity=1024, descriptor_capacity=1 << 20, **options):
         """The loop database of the loop-closure thread held on the device (abi.LoopDatabase: detectLoop's vocabulary query and decision,

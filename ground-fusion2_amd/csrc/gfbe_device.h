@@ -14,6 +14,8 @@
 
 #include "../../include/gfbe.h"
 
+struct gfbe_kfd;      // (include/gfbe_kfd.h; named by kfd_window_desc below)
+
 #ifndef GFBE_LIN_SMALL_THREADS
 #define GFBE_LIN_SMALL_THREADS 256     // (four waves, one per SIMD: each has the whole register file — arch + acc — for the scalar algebra of an inertial /
                                        //  wheel factor; eight waves = 256 registers each spilled 508 bytes per lane: 1.244 against 1.212 ms host to host)
@@ -503,7 +505,13 @@ gfbe_status ldb_add_keyframe_device(gfbe_ctx *c, gfbe_ldb *m, const char *who, i
                                     int32_t *index_out, int32_t *loop_index, int32_t *n_results, int32_t *result_id, double *result_score);
 gfbe_status ldb_match_device(gfbe_ctx *c, gfbe_ldb *m, const char *who, int old_index, int n_window, const uint64_t *window_desc, uint8_t *status, int32_t *best_index,
                              int32_t *best_dist, int32_t *n_matched, int32_t *matched_src, float *matched_pt, float *matched_pt_norm);
-
+// what gfbe_pnp.hip (include/gfbe_pnp.h) must see of it: the checks of a match (ldb_match_check) and its two kernels enqueued into
+// caller-given device buffers of n_window rows without a wait (ldb_match_enqueue; gfbe_ldb_match's own launch half calls it)
+gfbe_status ldb_match_check(gfbe_ctx *c, gfbe_ldb *m, const char *who, int old_index, int n_window);
+void ldb_match_enqueue(gfbe_ctx *c, gfbe_ldb *m, int old_index, int n_window, const uint64_t *window_desc, int *best_index, int *best_dist, int *flag, uint8_t *status,
+                       int *n_matched, int *matched_src, float *matched_pt, float *matched_pt_norm);
+// ... and of a describer (gfbe_kfd.hip): camera's window descriptors of its last describe, *n of them at *desc on the device
+gfbe_status kfd_window_desc(gfbe_ctx *c, gfbe_kfd *m, const char *who, int camera, int *n, const uint64_t **desc);
 
 // ---- device-resident line tables (gfbe_ltab.hip) and the table-fed line refinement (k_line_refine<true>, gfbe_line.hip)
 enum { LT_NOBS = GFBE_WINDOW_SIZE + 1 };

@@ -214,6 +214,20 @@ void kfd_launch_blur(gfbe_ctx *c, gfbe_kfd *m, int slot) {
 
 }  // namespace
 
+// ---- what gfbe_pnp.hip (include/gfbe_pnp.h) sees of a describer (gfbe_handle.h)
+namespace gfd {
+gfbe_status kfd_window_desc(gfbe_ctx *c, gfbe_kfd *m, const char *who, int camera, int *n, const uint64_t **desc) {
+  gfbe_status rc = handle_ready(c, m, who, "describer");
+  if (rc != GFBE_OK) return rc;
+  if (camera < 0 || camera >= m->n_cam) return handle_bad(c, who, "camera outside the describer's");
+  if (!m->described) return handle_bad(c, who, "no window descriptors are held: describe first");
+  const int b = m->w_off[(size_t)camera];
+  *n = m->w_off[(size_t)camera + 1] - b;
+  *desc = m->w_desc + 4 * (size_t)b;
+  return GFBE_OK;
+}
+}  // namespace gfd
+
 extern "C" {
 
 void gfbe_kfd_default_options(gfbe_kfd_options *o) {

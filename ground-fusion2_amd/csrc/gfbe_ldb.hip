@@ -375,13 +375,7 @@ gfbe_status ldb_match_launch(gfbe_ctx *c, gfbe_ldb *m, const char *who, int old_
   float *d_pt = sg.up((const float *)nullptr, 2 * W), *d_ptn = sg.up((const float *)nullptr, 2 * W);
   if (!sg.ok) { ctx_set_error(c, (std::string(who) + ": staging allocation failed").c_str()); return GFBE_DEVICE_ERROR; }
   sg.flush();
-  hipStream_t st = ctx_stream(c);
-  const long long ob = m->kf_begin[(size_t)old_index];
-  if (n_window > 0)
-    hipLaunchKernelGGL(k_ldb_match, dim3(ldb_grid(n_window, LDB_THREADS / 64)), dim3(LDB_THREADS), 0, st, (int)n_window, dw, ob, m->kf_n[(size_t)old_index],
-                       (const uint64_t *)m->desc, (int)m->opt.match_start, (int)m->opt.match_max, d_bi, d_bd, d_flag, d_st);
-  hipLaunchKernelGGL(k_ldb_compact, dim3(1), dim3(LDB_BOW_THREADS), 0, st, (int)n_window, (const int *)d_flag, (const int *)d_bi, ob, (const float *)m->pts,
-                     (const float *)m->ptsn, d_n, d_src, d_pt, d_ptn);
+  ldb_match_enqueue(c, m, old_index, n_window, dw, d_bi, d_bd, d_flag, d_st, d_n, d_src, d_pt, d_ptn);
   // the compacted outputs are copied whole (n_window rows): only the first n_matched are defined, the rest the caller never reads
   std::vector<int32_t> src_h(matched_src ? W : 0);
   std::vector<float> pt_h(matched_pt ? 2 * W : 0), ptn_h(matched_pt_norm ? 2 * W : 0);
@@ -416,12 +410,29 @@ gfbe_status ldb_add_keyframe_device(gfbe_ctx *c, gfbe_ldb *m, const char *who, i
 }
 gfbe_status ldb_match_device(gfbe_ctx *c, gfbe_ldb *m, const char *who, int old_index, int n_window, const uint64_t *dw, uint8_t *status, int32_t *best_index, int32_t *best_dist,
                              int32_t *n_matched, int32_t *matched_src, float *matched_pt, float *matched_pt_norm) {
+  const gfbe_status rc = ldb_match_check(c, m, who, old_index, n_window);
+  if (rc != GFBE_OK) return rc;
+  Staged sg(c, m, (size_t)n_window * 40 + 8192);
+  return ldb_match_launch(c, m, who, old_index, n_window, dw, sg, status, best_index, best_dist, n_matched, matched_src, matched_pt, matched_pt_norm);
+}
+// ---- ... and gfbe_pnp.hip (include/gfbe_pnp.h): the checks of a match, and rule 6 + reduceVector enqueued on the context's stream into
+// device buffers of n_window rows (at least one); nobody waits here
+gfbe_status ldb_match_check(gfbe_ctx *c, gfbe_ldb *m, const char *who, int old_index, int n_window) {
   gfbe_status rc = handle_ready(c, m, who, "loop database");
   if (rc != GFBE_OK) return rc;
   if (old_index < 0 || old_index >= (int)m->kf_n.size()) return handle_bad(c, who, "old_index is not a held keyframe");
   if (n_window < 0 || n_window > LDB_MAX_WINDOW) return handle_bad(c, who, "n_window outside 0 .. 2^20");
-  Staged sg(c, m, (size_t)n_window * 40 + 8192);
-  return ldb_match_launch(c, m, who, old_index, n_window, dw, sg, status, best_index, best_dist, n_matched, matched_src, matched_pt, matched_pt_norm);
+  return GFBE_OK;
+}
+void ldb_match_enqueue(gfbe_ctx *c, gfbe_ldb *m, int old_index, int n_window, const uint64_t *dw, int *d_bi, int *d_bd, int *d_flag, uint8_t *d_st, int *d_n, int *d_src,
+                       float *d_pt, float *d_ptn) {
+  hipStream_t st = ctx_stream(c);
+  const long long ob = m->kf_begin[(size_t)old_index];
+  if (n_window > 0)
+    hipLaunchKernelGGL(k_ldb_match, dim3(ldb_grid(n_window, LDB_THREADS / 64)), dim3(LDB_THREADS), 0, st, (int)n_window, dw, ob, m->kf_n[(size_t)old_index],
+                       (const uint64_t *)m->desc, (int)m->opt.match_start, (int)m->opt.match_max, d_bi, d_bd, d_flag, d_st);
+  hipLaunchKernelGGL(k_ldb_compact, dim3(1), dim3(LDB_BOW_THREADS), 0, st, (int)n_window, (const int *)d_flag, (const int *)d_bi, ob, (const float *)m->pts,
+                     (const float *)m->ptsn, d_n, d_src, d_pt, d_ptn);
 }
 }  // namespace gfd
 

@@ -3,8 +3,8 @@
 GFBE holds the exports of include/gfbe.h, RCCL those of include/gfbe_rccl.h, LC6 those of include/gfbe_lc6.h (they live in the
 product library under the prefix gfbe_lc6_), KLT those of include/gfbe_klt.h (prefix gfbe_klt_, likewise), DET those of
 include/gfbe_det.h (prefix gfbe_det_, likewise), OBS those of include/gfbe_obs.h (prefix gfbe_obs_, likewise), KFD those of
-include/gfbe_kfd.h (prefix gfbe_kfd_, likewise), GFO what the CPU oracle (prefix gfo_) shares with the product. tests/test_abi.py checks GFBE and RCCL against the prototypes of their headers,
-tests/test_lc6_host.py LC6, tests/test_klt_model.py KLT, tests/test_det_model.py DET, tests/test_obs_model.py OBS, tests/test_kfd_model.py KFD. abi.bind(lib, prefix) applies a
+include/gfbe_kfd.h (prefix gfbe_kfd_, likewise), PNP those of include/gfbe_pnp.h (prefix gfbe_pnp_, likewise), GFO what the CPU oracle (prefix gfo_) shares with the product. tests/test_abi.py checks GFBE and RCCL against the prototypes of their headers,
+tests/test_lc6_host.py LC6, tests/test_klt_model.py KLT, tests/test_det_model.py DET, tests/test_obs_model.py OBS, tests/test_kfd_model.py KFD, tests/test_pnp_model.py PNP. abi.bind(lib, prefix) applies a
 table to a loaded library; nothing else in the package assigns restype / argtypes.
 
 Spelling: opaque handles (gfbe_ctx *, gfbe_ftab *, gfbe_batch *, ...) and void * are V, their out-parameters PV; gfbe_status is
@@ -13,7 +13,7 @@ an int32; struct pointers are pointers to the ctypes mirrors of abi.py.
 import ctypes as C
 
 from .abi import (DetOptions, DmapOptions, FeatureList, FtabOptions, GnssObs, GnssState, ImuPreint, KfdOptions, KltOptions, Lc4Options, Lc6Options, LdbOptions, LdbVocab, LineReducedV,
-                  LineStepped, LineWindow, ObsOptions, Options, Prior, State, Summary, VmapOptions, VregOptions, VregSummary, WheelPreint, Window)
+                  LineStepped, LineWindow, ObsOptions, Options, PnpOptions, Prior, State, Summary, VmapOptions, VregOptions, VregSummary, WheelPreint, Window)
 
 P = C.POINTER
 i, i64, d, V, PV, STR = C.c_int32, C.c_int64, C.c_double, C.c_void_p, P(C.c_void_p), C.c_char_p
@@ -219,6 +219,17 @@ KFD = {             # prefix gfbe_kfd_ (the keyframe descriptors between the tra
     "download": (i, [V, V, i, i, PU8, PU8]),
 }
 
+_PNP_RESULTS = [PI, PI, PD, PD, PI, PI]      # n_inliers, has_loop, loop_info, pnp_pose, best, refine_flag
+_PNP_MATCHED = [PI, PI, PF, PF, PU8]         # n_matched, matched_src, matched_pt, matched_pt_norm, status_pnp
+PNP = {             # prefix gfbe_pnp_ (the loop verification between the loop database's matches and a loop edge; symbols of the product library)
+    "default_options": (None, [P(PnpOptions)]),
+    "create": (i, [V, P(PnpOptions), PV]),
+    "destroy": (None, [V, V]),
+    "verify": (i, [V, V, i, PI, PF, PF, PD, PD, PU8] + _PNP_RESULTS + [PI, PI, PD, PI]),
+    "find_connection": (i, [V, V, V, i, i, PU64, PF, PD, PD] + _PNP_MATCHED + _PNP_RESULTS),
+    "find_connection_kfd": (i, [V, V, V, i, V, i, PF, PD, PD] + _PNP_MATCHED + _PNP_RESULTS),
+}
+
 
 def _oracle(name):
     """The oracle's flavour of a shared entry point: the compute calls take `const gfbe_options *` where the product takes its
@@ -233,7 +244,7 @@ def _oracle(name):
 
 GFO = {name: _oracle(name) for name in GFBE}
 TABLES = {"gfbe_": GFBE, "gfo_": GFO, "gfbe_rccl_": RCCL, "gfbe_lc6_": LC6, "gfbe_klt_": KLT, "gfbe_det_": DET, "gfbe_obs_": OBS,
-          "gfbe_kfd_": KFD}
+          "gfbe_kfd_": KFD, "gfbe_pnp_": PNP}
 
 
 def declare(lib, prefix, table):

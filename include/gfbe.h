@@ -653,7 +653,7 @@ gfbe_status gfbe_dmap_download_keyframe(gfbe_ctx *ctx, gfbe_dmap *map, int32_t k
  *       detectLoop: BoW vector, query, add, the decision             pose_graph.cpp:432-512          gfbe_ldb_add_keyframe, detect_loop = 1
  *       addKeyFrameIntoVoc: add without a query                      :514-527                        gfbe_ldb_add_keyframe, detect_loop = 0
  *       searchByBRIEFDes / searchInAera / HammingDis, reduceVector   keyframe.cpp:194-244, 571-576, 374-380   gfbe_ldb_match
- *     PnPRANSAC (cv::solvePnPRansac) and the loop_info arithmetic behind it stay with the caller.
+ *     PnPRANSAC (cv::solvePnPRansac) and the loop_info arithmetic behind it are gfbe_pnp_* of the companion header gfbe_pnp.h.
  *     A descriptor is uint64_t [4], the four blocks loadBin hands to boost::dynamic_bitset (TemplatedVocabulary.h:1541); pts /
  *     pts_norm are float [n][2] (keypoints[i].pt, keypoints_norm[i].pt). Conventions of gfbe_dmap: operations run in order on
  *     the context's stream, the counts live in device memory, without a GPU every entry point returns GFBE_NO_DEVICE, a bad

@@ -38,8 +38,8 @@
  *    two pushes behind the tracker's current image: the handle owns a ring of ring_slots image sets. A slot is filled by a device copy
  *    of a tracker's current level-0 images (capture) or by a host upload (push_image); filling writes the slot's image and its blurred
  *    image whole, and voids the slot's score plane until the next extract of that slot.
- * Not covered: PnPRANSAC / findConnection, colour input, the 80 x 60 thumbnail, the dead goodFeaturesToTrack branch of :166-176
- * (gfbe_det_corners has it), camera models other than PINHOLE.
+ * Not covered: colour input, the 80 x 60 thumbnail, the dead goodFeaturesToTrack branch of :166-176 (gfbe_det_corners has it), camera
+ * models other than PINHOLE. PnPRANSAC / findConnection are gfbe_pnp_* of gfbe_pnp.h (gfbe_pnp_find_connection_kfd on this handle).
  *
  *   create          pattern int32 [4][256] = x1, y1, x2, y2 of the pairs (the caller's brief_pattern.yml), every offset in -64 .. 64;
  *                   cameras double [n_cameras][8].
