@@ -2318,3 +2318,70 @@ class LoopVerifier(Handle):
         rc, out = self.find_connection_kfd_raw(describer, camera, db, old_index, n_window, point_3d, pose_cur, tic_qic)
         self._check(rc, "find_connection_kfd")
         return out
+
+
+# ---------------------------------------------------------------------------------------------
+# the image equalisation in front of the tracker and the keyframe descriptors (gfbe_eq_* of include/gfbe_eq.h; the model is
+# tests/eq_np.py, there is no oracle row)
+# ---------------------------------------------------------------------------------------------
+EQ_PREFIX = "gfbe_eq_"
+
+
+class EqOptions(C.Structure):
+    _fields_ = [("struct_size", c_i), ("tiles_x", c_i), ("tiles_y", c_i), ("reserved", c_i), ("clip_limit", c_d)]
+
+
+def eq_default_options(lib, **kw):
+    return options_struct(lib, EQ_PREFIX, "", EqOptions, kw)
+
+
+class Equalizer(Handle):
+    """CLAHE of n_cameras uint8 images of rows x cols on the device: on its own (apply), or in front of a Tracker's push_image
+    (push_klt) and of a KeyframeDescriber's push_image (push_kfd) on the same library and context; see include/gfbe_eq.h. options:
+    fields of gfbe_eq_options. The *_raw methods return the status first; the others raise."""
+
+    def __init__(self, lib, ctx, n_cameras, rows, cols, **options):
+        Handle.__init__(self, lib, EQ_PREFIX, ctx)
+        self.n_cameras, self.rows, self.cols = int(n_cameras), int(rows), int(cols)
+        self.opt = self._options(EqOptions, options)
+        self._check(self._f("create")(self.ctx, self.n_cameras, self.rows, self.cols, C.byref(self.opt), C.byref(self.h)), "create")
+
+    def _images(self, images):
+        im = _u8(images)
+        assert im.size == self.n_cameras * self.rows * self.cols, im.shape
+        return im
+
+    def apply_raw(self, images, out=None):
+        """(status, equalised images [n_cameras, rows, cols]); out: the array to write (it may be `images` itself)."""
+        im = self._images(images)
+        res = np.zeros((self.n_cameras, self.rows, self.cols), np.uint8) if out is None else out
+        return self._f("apply")(self.ctx, self.h, im.ctypes.data_as(PU8), res.ctypes.data_as(PU8)), res
+
+    def apply(self, images, out=None):
+        rc, res = self.apply_raw(images, out)
+        self._check(rc, "apply")
+        return res
+
+    def push_klt_raw(self, tracker, images):
+        return self._f("push_klt")(self.ctx, self.h, tracker.h, self._images(images).ctypes.data_as(PU8))
+
+    def push_klt(self, tracker, images):
+        """Tracker.push_image of the equalised images (does not wait for the device)."""
+        self._check(self.push_klt_raw(tracker, images), "push_klt")
+
+    def push_kfd_raw(self, describer, slot, images):
+        return self._f("push_kfd")(self.ctx, self.h, describer.h, int(slot), self._images(images).ctypes.data_as(PU8))
+
+    def push_kfd(self, describer, slot, images):
+        """KeyframeDescriber.push_image of the equalised images into ring slot `slot`."""
+        self._check(self.push_kfd_raw(describer, slot, images), "push_kfd")
+
+    def lut_raw(self, fill=7):
+        lut = np.full((self.n_cameras, self.opt.tiles_y, self.opt.tiles_x, 256), fill, np.uint8)
+        return self._f("download_lut")(self.ctx, self.h, lut.ctypes.data_as(PU8)), lut
+
+    def lut(self):
+        """The LUTs [n_cameras, tiles_y, tiles_x, 256] of the last apply / push."""
+        rc, lut = self.lut_raw()
+        self._check(rc, "download_lut")
+        return lut

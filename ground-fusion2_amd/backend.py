@@ -28,6 +28,7 @@ DET_EXPORTS = ["gfbe_det_" + name for name in signatures.DET]      # include/gfb
 OBS_EXPORTS = ["gfbe_obs_" + name for name in signatures.OBS]      # include/gfbe_obs.h: likewise
 KFD_EXPORTS = ["gfbe_kfd_" + name for name in signatures.KFD]      # include/gfbe_kfd.h: likewise
 PNP_EXPORTS = ["gfbe_pnp_" + name for name in signatures.PNP]      # include/gfbe_pnp.h: likewise
+EQ_EXPORTS = ["gfbe_eq_" + name for name in signatures.EQ]         # include/gfbe_eq.h: likewise
 
 
 class BackendError(RuntimeError):
@@ -57,6 +58,7 @@ def build_native(force=False, verbose=False, out=None, extra_flags=None, fp_cont
     srcs = sources()
     hdrs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".h", ".hpp"))]
     hdrs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("gfbe.h", "gfbe_lc6.h", "gfbe_klt.h", "gfbe_det.h", "gfbe_obs.h", "gfbe_kfd.h", "gfbe_pnp.h")]
+    hdrs.append(os.path.join(os.path.dirname(_HERE), "include", "gfbe_eq.h"))
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = os.environ.get("GFBE_EXTRA_FLAGS", "").split() if extra_flags is None else list(extra_flags)
     cflags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=" + fp_contract, "-munsafe-fp-atomics",
@@ -117,6 +119,7 @@ class Backend(abi.CApi):
         self.lib = abi.bind(abi.bind(abi.bind(abi.bind(abi.bind(C.CDLL(_SO), "gfbe_"), abi.LC6_PREFIX), abi.KLT_PREFIX), abi.DET_PREFIX), abi.OBS_PREFIX)
         abi.bind(self.lib, abi.KFD_PREFIX)
         abi.bind(self.lib, abi.PNP_PREFIX)
+        abi.bind(self.lib, abi.EQ_PREFIX)
         self.opt = options or abi.default_options()
         self.ctx = C.c_void_p()
         rc = self.lib.gfbe_create(C.byref(self.ctx), int(device), C.byref(self.opt))
@@ -236,6 +239,11 @@ class Backend(abi.CApi):
         keyframe for n_cameras cameras and their hand-over to a LoopDatabase, include/gfbe_kfd.h). pattern [4, 256] = x1 y1 x2 y2 of
         the BRIEF pairs, cameras [n_cameras, 8] = fx fy cx cy k1 k2 p1 p2. options: fields of gfbe_kfd_options."""
         return abi.KeyframeDescriber(self.lib, self.ctx, n_cameras, rows, cols, pattern, cameras, **options)
+
+    def equalizer(self, n_cameras, rows, cols, **options):
+        """The image equalisation (abi.Equalizer: CLAHE of n_cameras uint8 images on the device, on its own or in front of a Tracker's
+        push_image and a KeyframeDescriber's push_image, include/gfbe_eq.h). options: fields of gfbe_eq_options."""
+        return abi.Equalizer(self.lib, self.ctx, n_cameras, rows, cols, **options)
 
     def loop_verifier(self, **options):
         """The loop verification (abi.LoopVerifier: P3P RANSAC on matched pairs, the refit on the inliers, loop_info and its acceptance

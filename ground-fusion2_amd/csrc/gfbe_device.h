@@ -512,6 +512,12 @@ void ldb_match_enqueue(gfbe_ctx *c, gfbe_ldb *m, int old_index, int n_window, co
                        int *n_matched, int *matched_src, float *matched_pt, float *matched_pt_norm);
 // ... and of a describer (gfbe_kfd.hip): camera's window descriptors of its last describe, *n of them at *desc on the device
 gfbe_status kfd_window_desc(gfbe_ctx *c, gfbe_kfd *m, const char *who, int camera, int *n, const uint64_t **desc);
+// what gfbe_eq.hip (include/gfbe_eq.h) must see of it: gfbe_kfd_push_image in its parts. The checks of a push for `who`, with the
+// describer's n_cameras, rows and cols against the caller's; the upload through the pinned mirror into the slot (*img_d: the slot's
+// images on the device); the blur that fills the slot.
+gfbe_status kfd_push_check(gfbe_ctx *c, gfbe_kfd *m, const char *who, int slot, int n_cam, int rows, int cols);
+gfbe_status kfd_push_upload(gfbe_ctx *c, gfbe_kfd *m, int slot, const uint8_t *images, uint8_t **img_d);
+gfbe_status kfd_push_enqueue(gfbe_ctx *c, gfbe_kfd *m, int slot);
 
 // ---- device-resident line tables (gfbe_ltab.hip) and the table-fed line refinement (k_line_refine<true>, gfbe_line.hip)
 enum { LT_NOBS = GFBE_WINDOW_SIZE + 1 };

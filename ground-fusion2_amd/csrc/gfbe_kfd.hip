@@ -226,6 +226,31 @@ gfbe_status kfd_window_desc(gfbe_ctx *c, gfbe_kfd *m, const char *who, int camer
   *desc = m->w_desc + 4 * (size_t)b;
   return GFBE_OK;
 }
+
+// ---- gfbe_kfd_push_image in its parts, for gfbe_eq.hip (include/gfbe_eq.h) as well: it equalises the slot's images before the blur
+gfbe_status kfd_push_check(gfbe_ctx *c, gfbe_kfd *m, const char *who, int slot, int n_cam, int rows, int cols) {
+  gfbe_status rc = handle_ready(c, m, who, "describer");
+  if (rc != GFBE_OK) return rc;
+  if ((rc = kfd_slot(c, m, who, slot, false)) != GFBE_OK) return rc;
+  if (m->n_cam != n_cam || m->rows != rows || m->cols != cols) return handle_bad(c, who, "the describer's n_cameras, rows or cols are not the handle's");
+  return GFBE_OK;
+}
+gfbe_status kfd_push_upload(gfbe_ctx *c, gfbe_kfd *m, int slot, const uint8_t *images, uint8_t **img_d) {
+  hipStream_t st = ctx_stream(c);
+  const size_t P = m->plane_bytes();
+  if (m->raw_busy) GFBE_CHECK(c, hipEventSynchronize(m->ev_raw));      // (the mirror's last copy has left it)
+  std::memcpy(m->raw_h, images, P);
+  GFBE_CHECK(c, hipMemcpyAsync(m->img + (size_t)slot * P, m->raw_h, P, hipMemcpyHostToDevice, st));
+  GFBE_CHECK(c, hipEventRecord(m->ev_raw, st));
+  m->raw_busy = true;
+  if (img_d) *img_d = m->img + (size_t)slot * P;
+  return GFBE_OK;
+}
+gfbe_status kfd_push_enqueue(gfbe_ctx *c, gfbe_kfd *m, int slot) {
+  kfd_launch_blur(c, m, slot);
+  GFBE_CHECK(c, hipGetLastError());
+  return GFBE_OK;
+}
 }  // namespace gfd
 
 extern "C" {
@@ -288,16 +313,8 @@ gfbe_status gfbe_kfd_push_image(gfbe_ctx *c, gfbe_kfd *m, int32_t slot, const ui
   if (rc != GFBE_OK) return rc;
   if ((rc = kfd_slot(c, m, "gfbe_kfd_push_image", slot, false)) != GFBE_OK) return rc;
   if (!images) return handle_bad(c, "gfbe_kfd_push_image", "images NULL");
-  hipStream_t st = ctx_stream(c);
-  const size_t P = m->plane_bytes();
-  if (m->raw_busy) GFBE_CHECK(c, hipEventSynchronize(m->ev_raw));      // (the mirror's last copy has left it)
-  std::memcpy(m->raw_h, images, P);
-  GFBE_CHECK(c, hipMemcpyAsync(m->img + (size_t)slot * P, m->raw_h, P, hipMemcpyHostToDevice, st));
-  GFBE_CHECK(c, hipEventRecord(m->ev_raw, st));
-  m->raw_busy = true;
-  kfd_launch_blur(c, m, slot);
-  GFBE_CHECK(c, hipGetLastError());
-  return GFBE_OK;
+  if ((rc = kfd_push_upload(c, m, slot, images, nullptr)) != GFBE_OK) return rc;
+  return kfd_push_enqueue(c, m, slot);
 }
 
 gfbe_status gfbe_kfd_capture(gfbe_ctx *c, gfbe_kfd *m, gfbe_klt *k, int32_t slot) {

@@ -253,6 +253,36 @@ void klt_launch_flow(gfbe_ctx *c, const gfbe_klt *m, const KltFlowArgs &A, int m
 
 }  // namespace
 
+// ---- the two halves of a push, for gfbe_eq.hip (include/gfbe_eq.h) as well: it equalises raw_d between them
+namespace gfd {
+gfbe_status klt_push_upload(gfbe_ctx *c, gfbe_klt *m, const uint8_t *images) {
+  hipStream_t st = ctx_stream(c);
+  const size_t R = (size_t)m->n_cam * (size_t)m->rows * (size_t)m->cols;
+  if (m->raw_busy) GFBE_CHECK(c, hipEventSynchronize(m->ev_raw));      // (the mirror's last copy has left it)
+  std::memcpy(m->raw_h, images, R);
+  GFBE_CHECK(c, hipMemcpyAsync(m->raw_d, m->raw_h, R, hipMemcpyHostToDevice, st));
+  GFBE_CHECK(c, hipEventRecord(m->ev_raw, st));
+  m->raw_busy = true;
+  return GFBE_OK;
+}
+
+gfbe_status klt_push_enqueue(gfbe_ctx *c, gfbe_klt *m) {
+  hipStream_t st = ctx_stream(c);
+  m->cur_set ^= 1;
+  m->n_pushed++;
+  const KltGeom &g = m->g;
+  uint8_t *img = m->img[m->cur_set];
+  int16_t *der = m->der[m->cur_set];
+  hipLaunchKernelGGL(k_klt_level0, dim3(klt_grid((long long)(g.w[0] + 2 * KLT_WIN) * (g.h[0] + 2 * KLT_WIN), KLT_THREADS), 1, m->n_cam), dim3(KLT_THREADS), 0, st, g,
+                     (const uint8_t *)m->raw_d, img);
+  for (int l = 0; l < g.n_levels; l++)
+    hipLaunchKernelGGL(k_klt_step, dim3(klt_grid((long long)(g.w[l] + 2 * KLT_WIN) * (g.h[l] + 2 * KLT_WIN), KLT_THREADS), 1, m->n_cam), dim3(KLT_THREADS), 0, st, g, l,
+                       (int)(l + 1 < g.n_levels), img, der);
+  GFBE_CHECK(c, hipGetLastError());
+  return GFBE_OK;
+}
+}  // namespace gfd
+
 extern "C" {
 
 void gfbe_klt_default_options(gfbe_klt_options *o) {
@@ -312,25 +342,8 @@ gfbe_status gfbe_klt_push_image(gfbe_ctx *c, gfbe_klt *m, const uint8_t *images)
   gfbe_status rc = handle_ready(c, m, "gfbe_klt_push_image");
   if (rc != GFBE_OK) return rc;
   if (!images) return handle_bad(c, "gfbe_klt_push_image", "images NULL");
-  hipStream_t st = ctx_stream(c);
-  const size_t R = (size_t)m->n_cam * (size_t)m->rows * (size_t)m->cols;
-  if (m->raw_busy) GFBE_CHECK(c, hipEventSynchronize(m->ev_raw));      // (the mirror's last copy has left it)
-  std::memcpy(m->raw_h, images, R);
-  GFBE_CHECK(c, hipMemcpyAsync(m->raw_d, m->raw_h, R, hipMemcpyHostToDevice, st));
-  GFBE_CHECK(c, hipEventRecord(m->ev_raw, st));
-  m->raw_busy = true;
-  m->cur_set ^= 1;
-  m->n_pushed++;
-  const KltGeom &g = m->g;
-  uint8_t *img = m->img[m->cur_set];
-  int16_t *der = m->der[m->cur_set];
-  hipLaunchKernelGGL(k_klt_level0, dim3(klt_grid((long long)(g.w[0] + 2 * KLT_WIN) * (g.h[0] + 2 * KLT_WIN), KLT_THREADS), 1, m->n_cam), dim3(KLT_THREADS), 0, st, g,
-                     (const uint8_t *)m->raw_d, img);
-  for (int l = 0; l < g.n_levels; l++)
-    hipLaunchKernelGGL(k_klt_step, dim3(klt_grid((long long)(g.w[l] + 2 * KLT_WIN) * (g.h[l] + 2 * KLT_WIN), KLT_THREADS), 1, m->n_cam), dim3(KLT_THREADS), 0, st, g, l,
-                       (int)(l + 1 < g.n_levels), img, der);
-  GFBE_CHECK(c, hipGetLastError());
-  return GFBE_OK;
+  if ((rc = klt_push_upload(c, m, images)) != GFBE_OK) return rc;
+  return klt_push_enqueue(c, m);
 }
 
 gfbe_status gfbe_klt_set_points(gfbe_ctx *c, gfbe_klt *m, const int32_t *offset, const float *pts, const int32_t *ids, const int32_t *track_cnt) {

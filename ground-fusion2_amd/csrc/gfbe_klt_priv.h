@@ -47,3 +47,10 @@ struct gfbe_klt : gfbe_handle {
   int *gate = nullptr;
   std::vector<int> begin_h, count_h;          // exact host mirrors
 };
+
+namespace gfd {
+// the two halves of gfbe_klt_push_image on a checked handle (gfbe_klt.hip): images through the pinned mirror into raw_d, then the
+// pyramid build of raw_d into the other set. gfbe_eq.hip (include/gfbe_eq.h) equalises raw_d between them.
+gfbe_status klt_push_upload(gfbe_ctx *c, gfbe_klt *m, const uint8_t *images);
+gfbe_status klt_push_enqueue(gfbe_ctx *c, gfbe_klt *m);
+}  // namespace gfd

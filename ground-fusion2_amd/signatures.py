@@ -15,6 +15,8 @@ import ctypes as C
 from .abi import (DetOptions, DmapOptions, FeatureList, FtabOptions, GnssObs, GnssState, ImuPreint, KfdOptions, KltOptions, Lc4Options, Lc6Options, LdbOptions, LdbVocab, LineReducedV,
                   LineStepped, LineWindow, ObsOptions, Options, PnpOptions, Prior, State, Summary, VmapOptions, VregOptions, VregSummary, WheelPreint, Window)
 
+from .abi import EqOptions
+
 P = C.POINTER
 i, i64, d, V, PV, STR = C.c_int32, C.c_int64, C.c_double, C.c_void_p, P(C.c_void_p), C.c_char_p
 PD, PF, PI, PI16, PI64, PU8, PU16, PU64, PC = P(d), P(C.c_float), P(i), P(C.c_int16), P(i64), P(C.c_uint8), P(C.c_uint16), P(C.c_uint64), P(C.c_char)
@@ -230,6 +232,17 @@ PNP = {             # prefix gfbe_pnp_ (the loop verification between the loop d
     "find_connection_kfd": (i, [V, V, V, i, V, i, PF, PD, PD] + _PNP_MATCHED + _PNP_RESULTS),
 }
 
+EQ = {              # prefix gfbe_eq_ (the image equalisation in front of the tracker and the keyframe descriptors; symbols of the product library;
+    # include/gfbe_eq.h, checked against it by tests/test_eq_model.py)
+    "default_options": (None, [P(EqOptions)]),
+    "create": (i, [V, i, i, i, P(EqOptions), PV]),
+    "destroy": (None, [V, V]),
+    "apply": (i, [V, V, PU8, PU8]),
+    "push_klt": (i, [V, V, V, PU8]),
+    "push_kfd": (i, [V, V, V, i, PU8]),
+    "download_lut": (i, [V, V, PU8]),
+}
+
 
 def _oracle(name):
     """The oracle's flavour of a shared entry point: the compute calls take `const gfbe_options *` where the product takes its
@@ -245,6 +258,7 @@ def _oracle(name):
 GFO = {name: _oracle(name) for name in GFBE}
 TABLES = {"gfbe_": GFBE, "gfo_": GFO, "gfbe_rccl_": RCCL, "gfbe_lc6_": LC6, "gfbe_klt_": KLT, "gfbe_det_": DET, "gfbe_obs_": OBS,
           "gfbe_kfd_": KFD, "gfbe_pnp_": PNP}
+TABLES["gfbe_eq_"] = EQ
 
 
 def declare(lib, prefix, table):

@@ -43,7 +43,8 @@
  *
  *   create          pattern int32 [4][256] = x1, y1, x2, y2 of the pairs (the caller's brief_pattern.yml), every offset in -64 .. 64;
  *                   cameras double [n_cameras][8].
- *   push_image      images uint8 [n_cameras][rows][cols] into slot; does not wait beyond the pinned mirror's previous copy.
+ *   push_image      images uint8 [n_cameras][rows][cols] into slot; does not wait beyond the pinned mirror's previous copy. With
+ *                   `equalize: 1` the CLAHE in front of it is gfbe_eq_push_kfd of gfbe_eq.h.
  *   capture         the tracker's current level-0 images into slot, device to device; no wait. The tracker's n_cameras, rows and cols
  *                   must match and an image must have been pushed.
  *   extract         K2, K3, K5 and K4 on the kept corners of slot, for every camera; one host wait, for the counters, and a second one

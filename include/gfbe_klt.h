@@ -50,7 +50,8 @@
  * The handle holds, for n_cameras cameras, two image sets (previous, current), each with the padded pyramid and its derivative
  * pyramid, and the current point list (up to point_capacity points a camera).
  *   push_image   the current set becomes the previous one; images [n_cameras][rows][cols] are uploaded and R1, R2 run for every
- *                level. Returns without waiting for the device (the images are copied before it returns).
+ *                level. Returns without waiting for the device (the images are copied before it returns). With `equalize: 1` the
+ *                CLAHE in front of it is gfbe_eq_push_klt of gfbe_eq.h.
  *   set_points   the points of the CURRENT image as the caller's setMask / goodFeaturesToTrack / addPoints left them: offset
  *                [n_cameras + 1] (offset[0] = 0), pts [n][2], ids [n], track_cnt [n]. They are prev_pts of the next track.
  *   track        R5 for every camera, one host wait. has_prediction [n_cameras] (NULL: none), predict_pts [n][2] in the order of the
