@@ -391,6 +391,11 @@ void launch_pair_schur_marg(const BatchDev &d, hipStream_t s);   // small batche
 void launch_lin_small(const BatchDev &d, int mode, hipStream_t s, int fuse = 0);   // fuse (mode 1): bit 1 candidate tiles first, bit 2 k_accept last
 void launch_dense_factors(const BatchDev &d, int mode, int debug_out, hipStream_t s, int spec = 0);
 void launch_schur(const BatchDev &d, int marg, hipStream_t s, int with_visblock = 0);   // with_visblock: k_schur_visblock_small
+// the solve pass of a batch takes k_schur's lean form (k_schur_lean): a throughput batch with constant extrinsic / td whose landmark
+// arrays a 32-bit BYTE offset spans (8 tot_lm < 2^32: its loads are [row base + 32-bit offset of the slot]); any other the general form
+inline bool schur_lean_form(int schur_groups, int vis_full, long long tot_lm) {
+  return schur_groups == SCHUR_GROUPS && !vis_full && 8 * tot_lm < (1ll << 32);
+}
 void launch_linschur(const BatchDev &d, int spec, int gate_mu, hipStream_t s);            // BatchDev::linschur: k_vis<0, false> + k_schur in one launch
 void launch_visblock(const BatchDev &d, hipStream_t s);
 void launch_lio_window(const BatchDev &d, int mode, hipStream_t s, int spec = 0);

@@ -105,6 +105,28 @@ __device__ __forceinline__ void lm_row_dot2(const double *fs, const double *dv, 
 }
 enum { LM_FS = 15 };      // doubles per frame of the staged steps above
 
+// ---- loads and stores as [wave-uniform base + 32-bit lane offset] (k_visasm's asm_H_tp, the lean form of k_schur)
+// a pointer every lane of the wave holds the same value of, moved to scalar registers (a base formed from a LOADED value — the set index
+// WinCtl::lb behind lin_view — is a vector value to the compiler, whatever its lanes hold)
+template <class T> __device__ __forceinline__ T *uniform_ptr(T *p) {
+  const unsigned long long v = (unsigned long long)p;
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+  return (T *)(((unsigned long long)hi << 32) | lo);
+}
+// (global address space spelled out: a pointer rebuilt from two scalar halves is a generic one to the compiler — FLAT loads)
+typedef __attribute__((address_space(1))) char asm_glb_char;
+typedef __attribute__((address_space(1))) double asm_glb_double;
+typedef __attribute__((address_space(1))) int asm_glb_int;
+// entry `idx` of a double array whose base is wave-uniform: the BYTE offset formed in 32 bits, so that the load is [scalar base + 32-bit
+// vector offset] instead of a 64-bit address per lane (idx < 2^29)
+// (the byte offset behind an empty assembly statement: the combiner otherwise turns zext(select(c, x, 0)) into a 64-bit select and the
+//  [scalar base + 32-bit offset] form is lost again)
+__device__ __forceinline__ double ld_u32(const double *base, unsigned idx) { unsigned bo = idx << 3; asm("" : "+v"(bo)); return *(const asm_glb_double *)((const asm_glb_char *)base + bo); }
+__device__ __forceinline__ void st_u32(double *base, unsigned idx, double v) { unsigned bo = idx << 3; asm("" : "+v"(bo)); *(asm_glb_double *)((asm_glb_char *)base + bo) = v; }
+// the same with a BYTE offset the caller formed once for many loads (and hid from the combiner itself, if it has to)
+__device__ __forceinline__ double ld_b32(const double *base, unsigned bo) { return *(const asm_glb_double *)((const asm_glb_char *)base + bo); }
+__device__ __forceinline__ int ld_b32(const int *base, unsigned bo) { return *(const asm_glb_int *)((const asm_glb_char *)base + bo); }
+
 __device__ __forceinline__ void tri_decode(int e, int &a, int &b) {
   a = (int)((sqrtf(8.0f * e + 1.0f) - 1.0f) * 0.5f);
   while ((a + 1) * (a + 2) / 2 <= e) a++;

@@ -1793,7 +1793,9 @@ __device__ __forceinline__ int schur_group_first(int g, int ng) { return ng >= N
 //   * the staging does not form the rows of an observation step the tile never ran (k >= m0, the track length of its first landmark):
 //     there it writes zeros, and only into columns a chunk of this tile reads; the columns in front of the start block are cleared
 //     when the start frame changes, those behind the last pose once per workgroup
-// (the LDS of schur_body: one object for both of its forms, which k_schur holds side by side)
+//   * its addresses are [the wave's row base, formed on the scalar unit + one 32-bit byte offset of the lane's slot per tile], the start
+//     frame of a tile comes from scalar registers, and it is a kernel of its own, k_schur_lean (profiles/schur_addr_ab.txt)
+// (the LDS of schur_body: one object for both of its forms, k_schur and k_schur_lean)
 struct SchurLds {
   double hs[LM_TILE * HS_LD + 8];      // the panel (+ the overrun of the last row's last block)
   double s_rt[NF][12];                 // yrows: R_f | t_f = P_f - P_0 of the linearisation point (FrameConst of the pair table)
@@ -1869,7 +1871,7 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
   int *const s_sf = lds_.s_sf;
   double (*const s_rt)[12] = lds_.s_rt;
   const bool yrows = LEAN || (!marg && !d.vis_full);      // the rows are in the compressed form of k_vis<0, false> (gfbe_devutil.h)
-  if (t <= NF) s_sf[t] = ds.sf_tile_begin[t];
+  if (!LEAN && t <= NF) s_sf[t] = ds.sf_tile_begin[t];      // (LEAN: the group's boundaries in scalar registers, sfb below)
   if (yrows && t < NF * 12) s_rt[t / 12][t % 12] = d.pc[(((size_t)w * 3 + c.cur) * NPAIR + (t / 12) * (NF + 1)) * PC_DOUBLES + LM_RT_OFF + t % 12];
   const int lm_off_c = ds.lm_off;
   __syncthreads();
@@ -1881,7 +1883,49 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
   // (s_waitcnt vmcnt(23+) instead of vmcnt(0)); rows a thread does not need are loaded from a neighbouring valid row and ignored.
 #define SCHUR_PV 20
 #define SCHUR_PV_LEAN 12
+  // LEAN: of a tile's addresses only the slot is the lane's. The row index is the wave's (wv: t >> 6 is a lane's value to the compiler),
+  // the array bases (uniform_ptr: lin_view picks the set by a loaded value), tot_lm and the start frame are the workgroup's — the start
+  // frame from the group's <= 4 inner boundaries, read once into scalar registers (the LDS table costs a dependent round trip per
+  // boundary in front of every prefetch). A wave forms its row bases on the scalar unit and every load of a tile is [scalar base + ONE
+  // 32-bit byte offset 8 slot] (the offset behind an empty assembly statement once per tile, not per load: ld_u32 would copy it twelve
+  // times): schur_lean_form (gfbe_device.h) keeps 8 tot_lm below 2^32. Same addresses, same loads per thread and tile as before.
+  const double *const u_hC = uniform_ptr(d.lm_hC), *const u_sw = uniform_ptr(spec_sw ? d.lm_Hll : d.lm_sw), *const u_sl = uniform_ptr(d.lm_sl);
+  const int *const u_info = uniform_ptr(d.lm_info);
+  int sfb[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) sfb[j] = __builtin_amdgcn_readfirstlane(s_first + 1 + j < s_end ? ds.sf_tile_begin[min(s_first + 1 + j, (int)NF)] : 0x7fffffff);
+  // the wave's three row blocks u: array, last observation step it may name (clamped per tile to the start frame's last) and row stride —
+  // wave 0: lm_hC rows 0..2 | g_l three times (stride 0) | lm_hP step 9, waves 1..3: lm_hP steps wv - 1, wv + 2, wv + 5. Chosen here,
+  // so that the prefetch is straight-line code: behind a branch the loads lose sight of the offset's 32 bits and add 64-bit addresses
+  const double *rb_[3];
+  int kc_[3];
+#pragma unroll
+  for (int u = 0; u < 3; u++) {
+    rb_[u] = uniform_ptr(wv == 0 ? (u == 0 ? d.lm_hC : (u == 1 ? d.lm_gl : d.lm_hP)) : d.lm_hP);
+    kc_[u] = __builtin_amdgcn_readfirstlane(wv == 0 ? (u == 2 ? 9 : 0) : wv - 1 + 3 * u);
+  }
+  const size_t st1_ = wv == 0 ? 0 : TL;
+#define SCHUR_PREFETCH_LEAN(PV, PHLL, PSL, PINFO, PS, TILE)                                                            \
+  {                                                                                                                      \
+    const int tile_ = min((TILE), te - 1);                                                                               \
+    unsigned bo_ = (unsigned)(lm_off_c + tile_ * LM_TILE + l) << 3;      /* 8 slot: the lane's one term */               \
+    asm("" : "+v"(bo_));                                                                                                 \
+    PS = s_first;                                   /* + the boundaries at or below the tile (sign bits: scalar arithmetic) */ \
+    _Pragma("unroll") for (int j_ = 0; j_ < 4; j_++) PS += (int)((unsigned)(sfb[j_] - 1 - tile_) >> 31);                 \
+    const int klast_ = max(NF - 2 - PS, 0);       /* last observing pose index of the tile's start frame */              \
+    PINFO = ld_b32(u_info, bo_ >> 1);                                                                                    \
+    PHLL = ld_b32(u_sw, bo_);                        /* sqrt(w_l), left by the linearisation */                          \
+    /* the twelve doubles a thread stages, nothing else — x (lm_hC rows 3..5) once, then wave 0: D | g_l (+ two ignored) | d of the */ \
+    /* tenth pose, waves 1..3: d of their three poses                                                                              */ \
+    _Pragma("unroll") for (int q_ = 0; q_ < 3; q_++) PV[q_] = ld_b32(u_hC + (size_t)(3 + q_) * TL, bo_);                 \
+    _Pragma("unroll") for (int u_ = 0; u_ < 3; u_++) {                                                                   \
+      const double *const b_ = rb_[u_] + (size_t)(6 * min(kc_[u_], klast_)) * TL;                                        \
+      _Pragma("unroll") for (int q_ = 0; q_ < 3; q_++) PV[3 + 3 * u_ + q_] = ld_b32(b_ + q_ * (u_ == 1 ? st1_ : TL), bo_); \
+    }                                                                                                                    \
+    if (spec_sw) PSL = ld_b32(u_sl, bo_);           /* (speculative batches: Hll and s_l, sqrt(w_l) formed at the staging) */    \
+  }
 #define SCHUR_PREFETCH(PV, PHLL, PSL, PINFO, PS, TILE)                                                                 \
+  if (LEAN) SCHUR_PREFETCH_LEAN(PV, PHLL, PSL, PINFO, PS, TILE) else                                                     \
   {                                                                                                                      \
     const int tile_ = min((TILE), te - 1);                                                                               \
     const int slot_ = lm_off_c + tile_ * LM_TILE + l;                                                                    \
@@ -1891,19 +1935,6 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
     PHLL = (marg || spec_sw ? d.lm_Hll : d.lm_sw)[slot_];      /* solve: sqrt(w_l), left by the linearisation */         \
     if (spec_sw) PSL = d.lm_sl[slot_];              /* (speculative batches: Hll and s_l, sqrt(w_l) formed at the staging) */    \
     const double *gl_ = d.lm_gl + slot_;                                                                                 \
-    /* LEAN (compressed rows, constant extrinsic / td): the twelve doubles a thread stages, nothing else — x (lm_hC rows 3..5) once, */ \
-    /* then part 0: D | g_l (+ two ignored) | d of the tenth pose, parts 1..3: d of their three poses                              */ \
-    if (LEAN) {                                                                                                          \
-      _Pragma("unroll") for (int idx_ = 0; idx_ < SCHUR_PV_LEAN; idx_++) {                                                 \
-        const int u_ = max(idx_ - 3, 0) / 3, q_ = max(idx_ - 3, 0) - 3 * u_;                                             \
-        const int kk_ = min(part - 1 + 3 * u_, klast_), k9_ = min(9, klast_);                                            \
-        const double *src_ = idx_ < 3 ? d.lm_hC + (size_t)(3 + idx_) * TL + slot_                                       \
-                           : (part == 0 ? (u_ == 0 ? d.lm_hC + (size_t)q_ * TL + slot_                                  \
-                                                   : (u_ == 1 ? gl_ : d.lm_hP + ((size_t)k9_ * 6 + q_) * TL + slot_))   \
-                                        : d.lm_hP + ((size_t)kk_ * 6 + q_) * TL + slot_);                                \
-        PV[idx_] = *src_;                                                                                                \
-      }                                                                                                                  \
-    } else                                                                                                               \
     _Pragma("unroll") for (int idx_ = 0; idx_ < SCHUR_PV; idx_++) {                                                      \
       const int u_ = idx_ / 6, q_ = idx_ - 6 * u_;                                                                       \
       const int kk_ = min(part - 1 + 3 * u_, klast_), k9_ = min(9, klast_);                                              \
@@ -1976,7 +2007,7 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
         sw = sqrt(PSL * PSL / (hs2_ + spec_mu * clamp_diag(hs2_)));                                                      \
       }                                                                                                                  \
       double *row = hs + l * HS_LD + coff;                                                                               \
-      if (part == 0) {                                                                                                   \
+      if ((LEAN ? wv : part) == 0) {                                                                                     \
         /* (LEAN: the columns in front of the start block change only with the start frame, those behind the poses never) */ \
         if (fresh_) for (int q = compact ? 6 * s_first : 16 * I0; q < 6 * s; q++) row[q] = 0.0;                          \
         double blk0[6];                                                                                                  \
@@ -2064,8 +2095,14 @@ __device__ __forceinline__ void schur_body(const BatchDev &d, const int marg, co
 __global__ __launch_bounds__(256, GFBE_SCHUR_WGS) void k_schur(BatchDev d0, int marg) {
   const BatchDev d = marg ? d0 : lin_view(d0, d0.ctl[blockIdx.x].lb);
   // group-major dispatch: the heavy first group of every window first
-  if (!marg && d.schur_groups == SCHUR_GROUPS && !d.vis_full) schur_body<true>(d, 0, blockIdx.x, blockIdx.y);
-  else schur_body<false>(d, marg, blockIdx.x, blockIdx.y);
+  schur_body<false>(d, marg, blockIdx.x, blockIdx.y);
+}
+// The lean form as a kernel of its own (launch_schur picks it by schur_lean_form): held side by side in one kernel, the general form's
+// twenty-value register set and branches shared the allocation — 98 scalar registers spilled to vector lanes and read back inside the
+// lean tile loop, 128 VGPRs. Same launch bounds, same LDS object.
+__global__ __launch_bounds__(256, GFBE_SCHUR_WGS) void k_schur_lean(BatchDev d0) {
+  const BatchDev d = lin_view(d0, d0.ctl[blockIdx.x].lb);
+  schur_body<true>(d, 0, blockIdx.x, blockIdx.y);
 }
 // =============================================================================================
 // k_linschur (round 6): the linearisation of the visual factors AND the landmark elimination of
@@ -2528,22 +2565,7 @@ hipError_t asm_tables_build(int **full, int **compact, int *n_compact, hipStream
   return e;
 }
 
-// entry `idx` of a double array whose base is wave-uniform: the BYTE offset formed in 32 bits, so that the load is [scalar base + 32-bit
-// vector offset] instead of a 64-bit address per lane (idx < 2^29)
-// a pointer every lane of the wave holds the same value of, moved to scalar registers (a base formed from a LOADED value — the set index
-// WinCtl::lb behind lin_view — is a vector value to the compiler, whatever its lanes hold)
-template <class T> __device__ __forceinline__ T *uniform_ptr(T *p) {
-  const unsigned long long v = (unsigned long long)p;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return (T *)(((unsigned long long)hi << 32) | lo);
-}
-// (global address space spelled out: a pointer rebuilt from two scalar halves is a generic one to the compiler — FLAT loads)
-typedef __attribute__((address_space(1))) char asm_glb_char;
-typedef __attribute__((address_space(1))) double asm_glb_double;
-// (the byte offset behind an empty assembly statement: the combiner otherwise turns zext(select(c, x, 0)) into a 64-bit select and the
-//  [scalar base + 32-bit offset] form is lost again)
-__device__ __forceinline__ double ld_u32(const double *base, unsigned idx) { unsigned bo = idx << 3; asm("" : "+v"(bo)); return *(const asm_glb_double *)((const asm_glb_char *)base + bo); }
-__device__ __forceinline__ void st_u32(double *base, unsigned idx, double v) { unsigned bo = idx << 3; asm("" : "+v"(bo)); *(asm_glb_double *)((asm_glb_char *)base + bo) = v; }
+// (uniform_ptr, ld_u32 / st_u32 — a load as [scalar base + 32-bit vector offset] — live in gfbe_devutil.h)
 __device__ __forceinline__ double gather_g_dense(const BatchDev &d, const AsmTab &tb, const double *Z, int w, int a) {
   const int fa = dim_frame(a);
   const double *p[2] = {Z, Z};
@@ -4338,6 +4360,7 @@ void launch_dense_factors(const BatchDev &d, int mode, int debug_out, hipStream_
 void launch_schur(const BatchDev &d, int marg, hipStream_t s, int with_visblock) {
   if (d.max_tiles == 0) return;
   if (with_visblock && !marg && d.vis_Hs) hipLaunchKernelGGL(k_schur_visblock_small, dim3(d.B, d.schur_groups + (d.vis_full ? (int)VS_BLOCKS : (int)NF)), dim3(VB_GROUP), 0, s, d);
+  else if (!marg && schur_lean_form(d.schur_groups, d.vis_full, d.tot_lm)) hipLaunchKernelGGL(k_schur_lean, dim3(d.B, d.schur_groups), dim3(256), 0, s, d);
   else hipLaunchKernelGGL(k_schur, dim3(d.B, marg ? 1 : d.schur_groups), dim3(256), 0, s, d, marg);
 }
 void launch_linschur(const BatchDev &d, int spec, int gate_mu, hipStream_t s) {
