@@ -631,7 +631,8 @@ class FeatureTables(Handle):
     def _ragged(rows, dtype, width=None):
         off = np.zeros(len(rows) + 1, np.int32)
         off[1:] = np.cumsum([len(r) for r in rows])
-        flat = np.concatenate([np.asarray(r, dtype).reshape(len(r), -1) if width else np.asarray(r, dtype).ravel() for r in rows]) \
+        # (reshape(-1, width): a table without rows in the frame is [0, width])
+        flat = np.concatenate([np.asarray(r, dtype).reshape(-1, width) if width else np.asarray(r, dtype).ravel() for r in rows]) \
             if off[-1] else np.zeros((0, width) if width else 0, dtype)
         return off, np.ascontiguousarray(flat)
 
@@ -2385,3 +2386,97 @@ class Equalizer(Handle):
         rc, lut = self.lut_raw()
         self._check(rc, "download_lut")
         return lut
+
+
+# ---------------------------------------------------------------------------------------------
+# the sensor gate on the feature tables: stationarity, wheel anomaly, the wheel prediction (gfbe_gate_* of include/gfbe_gate.h; the
+# model is tests/gate_np.py, there is no oracle row)
+# ---------------------------------------------------------------------------------------------
+GATE_PREFIX = "gfbe_gate_"
+GATE_WHEEL_ANOMALY, GATE_WHEEL_STATIONARY, GATE_PREINT_STATIONARY, GATE_VAR_STATIONARY = 1, 2, 4, 8
+GATE_IMU_EXCITED, GATE_VISUAL_STATIONARY, GATE_IMU_STATIONARY, GATE_SYSTEM_STATIONARY = 16, 32, 64, 128
+
+
+class GateOptions(C.Structure):
+    _fields_ = [("struct_size", c_i), ("max_samples", c_i), ("max_frames", c_i), ("use_wheel", c_i), ("wdetect", c_i), ("depth_mode", c_i), ("min_pair_count", c_i),
+                ("reserved", c_i), ("dis_threshold", c_d), ("wheel_still_norm", c_d), ("preint_still_norm", c_d), ("var_still", c_d), ("var_excited", c_d),
+                ("still_parallax_px", c_d), ("init_parallax_px", c_d), ("parallax_focal", c_d), ("depth_min", c_d), ("depth_max", c_d)]
+
+
+def gate_default_options(lib, **kw):
+    return options_struct(lib, GATE_PREFIX, "", GateOptions, kw)
+
+
+def gate_ragged(rows, width):
+    """(offset [B + 1] int32, the rows of B lists [n, width] packed)"""
+    rows = [np.asarray(r, np.float64).reshape(-1, width) for r in rows]
+    off = np.zeros(len(rows) + 1, np.int32)
+    off[1:] = np.cumsum([len(r) for r in rows])
+    return off, np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, width)))
+
+
+class SensorGate(Handle):
+    """The reference's per-frame sensor-state detectors and the wheel prediction of the newest frame for n_robots robots, robot b on
+    table b of a FeatureTables of the same library and context; see include/gfbe_gate.h. options: fields of gfbe_gate_options. The
+    *_raw methods return the status first; the others raise."""
+
+    def __init__(self, lib, ctx, n_robots, **options):
+        Handle.__init__(self, lib, GATE_PREFIX, ctx)
+        self.B = int(n_robots)
+        self.opt = self._options(GateOptions, options)
+        self._check(self._f("create")(self.ctx, self.B, C.byref(self.opt), C.byref(self.h)), "create")
+
+    def _stats(self, fill):
+        B = self.B
+        return dict(pair_count=np.full((B, 10), fill, np.int32), pair_sum=np.full((B, 10), float(fill)), l_still=np.full(B, fill, np.int32), l_init=np.full(B, fill, np.int32))
+
+    def frame_raw(self, tables, frame_count, imu, imu_first, wheel, wheel_first, pose, vel_ba, g_norm, stationary_prev, frames, fill=-7):
+        """G1 .. G7. imu / wheel: per robot [n, 7] rows (wheel, wheel_first: None with use_wheel == 0); frames: per robot [M, 4]; imu_first,
+        wheel_first [B, 6]; pose [B, 12]; vel_ba [B, 6]. Returns (status, dict(flags, l_still, l_init [B], pair_count, pair_sum [B, 10],
+        dP_imu, dP_wheel [B, 3], dis, var [B], pose_out [B, 12], vel_out [B, 3])). The outputs start as `fill`."""
+        B = self.B
+        io, iv = gate_ragged(imu, 7)
+        fo, fv = gate_ragged(frames, 4)
+        wo, wv, wf = (None, None, None) if wheel is None else gate_ragged(wheel, 7) + (_f64(wheel_first).reshape(B, 6),)
+        fc, sp, i1, ps, vb = _i32(frame_count), _i32(stationary_prev), _f64(imu_first).reshape(B, 6), _f64(pose).reshape(B, 12), _f64(vel_ba).reshape(B, 6)
+        assert len(fc) == len(sp) == len(io) - 1 == len(fo) - 1 == B
+        r = self._stats(fill)
+        r.update(flags=np.full(B, fill, np.int32), dP_imu=np.full((B, 3), float(fill)), dP_wheel=np.full((B, 3), float(fill)), dis=np.full(B, float(fill)),
+                 var=np.full(B, float(fill)), pose_out=np.full((B, 12), float(fill)), vel_out=np.full((B, 3), float(fill)))
+        opt = lambda a, f: f(a) if a is not None else None
+        rc = self._f("frame")(self.ctx, self.h, tables.h, _pi(fc), _pi(io), _pd(iv), _pd(i1), opt(wo, _pi), opt(wv, _pd), opt(wf, _pd), _pd(ps), _pd(vb), float(g_norm), _pi(sp),
+                              _pi(fo), _pd(fv), _pi(r["flags"]), _pi(r["l_still"]), _pi(r["l_init"]), _pi(r["pair_count"]), _pd(r["pair_sum"]), _pd(r["dP_imu"]),
+                              _pd(r["dP_wheel"]), _pd(r["dis"]), _pd(r["var"]), _pd(r["pose_out"]), _pd(r["vel_out"]))
+        return rc, r
+
+    def frame(self, tables, frame_count, imu, imu_first, wheel, wheel_first, pose, vel_ba, g_norm, stationary_prev, frames):
+        rc, out = self.frame_raw(tables, frame_count, imu, imu_first, wheel, wheel_first, pose, vel_ba, g_norm, stationary_prev, frames)
+        self._check(rc, "frame")
+        return out
+
+    def pair_stats_raw(self, tables, mode, fill=-7):
+        """G5, G6 alone: (status, dict(pair_count, pair_sum [B, 10], l_still, l_init [B]))."""
+        r = self._stats(fill)
+        return self._f("pair_stats")(self.ctx, self.h, tables.h, int(mode), _pi(r["pair_count"]), _pd(r["pair_sum"]), _pi(r["l_still"]), _pi(r["l_init"])), r
+
+    def pair_stats(self, tables, mode):
+        rc, out = self.pair_stats_raw(tables, mode)
+        self._check(rc, "pair_stats")
+        return out
+
+    def corresponding_raw(self, tables, mode, l, r, room, fill=-7):
+        """G8 with room[b] pairs of room for table b: (status, count [B], a, b [sum(room), 3], offset [B + 1])."""
+        lv, rv = _i32(l), _i32(r)
+        off = np.zeros(self.B + 1, np.int32)
+        off[1:] = np.cumsum(_i32(room))
+        a, b, cnt = np.full((int(off[-1]), 3), float(fill)), np.full((int(off[-1]), 3), float(fill)), np.full(self.B, fill, np.int32)
+        return self._f("corresponding")(self.ctx, self.h, tables.h, int(mode), _pi(lv), _pi(rv), _pi(off), _pd(a), _pd(b), _pi(cnt)), cnt, a, b, off
+
+    def corresponding(self, tables, mode, l, r):
+        """The pairs of (l[b], r[b]) per table in list order: a list of (a [n, 3], b [n, 3]). Sizes with a first call without room."""
+        rc, cnt, _, _, _ = self.corresponding_raw(tables, mode, l, r, np.zeros(self.B, np.int32))
+        if rc != OK and (rc != BAD_INPUT or (cnt < 0).any()):
+            self._check(rc, "corresponding")
+        rc, cnt, a, b, off = self.corresponding_raw(tables, mode, l, r, cnt)
+        self._check(rc, "corresponding")
+        return [(a[off[q]:off[q] + cnt[q]].copy(), b[off[q]:off[q] + cnt[q]].copy()) for q in range(self.B)]

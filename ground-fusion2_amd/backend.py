@@ -29,6 +29,7 @@ OBS_EXPORTS = ["gfbe_obs_" + name for name in signatures.OBS]      # include/gfb
 KFD_EXPORTS = ["gfbe_kfd_" + name for name in signatures.KFD]      # include/gfbe_kfd.h: likewise
 PNP_EXPORTS = ["gfbe_pnp_" + name for name in signatures.PNP]      # include/gfbe_pnp.h: likewise
 EQ_EXPORTS = ["gfbe_eq_" + name for name in signatures.EQ]         # include/gfbe_eq.h: likewise
+GATE_EXPORTS = ["gfbe_gate_" + name for name in signatures.GATE]   # include/gfbe_gate.h: likewise
 
 
 class BackendError(RuntimeError):
@@ -59,6 +60,7 @@ def build_native(force=False, verbose=False, out=None, extra_flags=None, fp_cont
     hdrs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".h", ".hpp"))]
     hdrs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("gfbe.h", "gfbe_lc6.h", "gfbe_klt.h", "gfbe_det.h", "gfbe_obs.h", "gfbe_kfd.h", "gfbe_pnp.h")]
     hdrs.append(os.path.join(os.path.dirname(_HERE), "include", "gfbe_eq.h"))
+    hdrs.append(os.path.join(os.path.dirname(_HERE), "include", "gfbe_gate.h"))
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = os.environ.get("GFBE_EXTRA_FLAGS", "").split() if extra_flags is None else list(extra_flags)
     cflags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=" + fp_contract, "-munsafe-fp-atomics",
@@ -120,6 +122,7 @@ class Backend(abi.CApi):
         abi.bind(self.lib, abi.KFD_PREFIX)
         abi.bind(self.lib, abi.PNP_PREFIX)
         abi.bind(self.lib, abi.EQ_PREFIX)
+        abi.bind(self.lib, abi.GATE_PREFIX)
         self.opt = options or abi.default_options()
         self.ctx = C.c_void_p()
         rc = self.lib.gfbe_create(C.byref(self.ctx), int(device), C.byref(self.opt))
@@ -244,6 +247,12 @@ class Backend(abi.CApi):
         """The image equalisation (abi.Equalizer: CLAHE of n_cameras uint8 images on the device, on its own or in front of a Tracker's
         push_image and a KeyframeDescriber's push_image, include/gfbe_eq.h). options: fields of gfbe_eq_options."""
         return abi.Equalizer(self.lib, self.ctx, n_cameras, rows, cols, **options)
+
+    def sensor_gate(self, n_robots, **options):
+        """The sensor gate (abi.SensorGate: the reference's per-frame stationarity and wheel-anomaly detectors and the wheel prediction of
+        the newest frame for n_robots robots on the FeatureTables of the same library and context, include/gfbe_gate.h). options: fields
+        of gfbe_gate_options."""
+        return abi.SensorGate(self.lib, self.ctx, n_robots, **options)
 
     def loop_verifier(self, **options):
         """The loop verification (abi.LoopVerifier: P3P RANSAC on matched pairs, the refit on the inliers, loop_info and its acceptance

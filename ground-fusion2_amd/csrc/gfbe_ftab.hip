@@ -551,7 +551,7 @@ void ft_launch_add(gfbe_ctx *c, gfbe_ftab *t, int M, int mmax, const int *dfc, c
 }
 gfbe_status ft_add_result(gfbe_ctx *c, gfbe_ftab *t, const std::vector<int> &err) {
   for (int w = 0; w < t->d.W; w++)
-    if (err[w]) { ctx_set_error(c, err[w] & 1 ? "feature table capacity exceeded" : "a feature received more than WINDOW_SIZE + 1 observations"); return GFBE_BAD_INPUT; }
+    if (err[w]) { t->err_seen = true; ctx_set_error(c, err[w] & 1 ? "feature table capacity exceeded" : "a feature received more than WINDOW_SIZE + 1 observations"); return GFBE_BAD_INPUT; }
   return ft_finish(c, t);
 }
 }  // namespace

@@ -1,5 +1,5 @@
 // gfbe_handle.h — the host side every device handle shares (gfbe_ftab, gfbe_ltab, gfbe_vmap, gfbe_scan, gfbe_dmap, gfbe_ldb, gfbe_klt,
-// gfbe_det, gfbe_obs, gfbe_kfd, gfbe_pnp, gfbe_eq): the check of a HIP call, the base that owns what a handle holds on the device, the guard of a create, and the
+// gfbe_det, gfbe_obs, gfbe_kfd, gfbe_pnp, gfbe_eq, gfbe_gate): the check of a HIP call, the base that owns what a handle holds on the device, the guard of a create, and the
 // entry checks of a call. Host code only, for the translation units that see the HIP runtime; the headers the HIP-free shims of the
 // tests include stay clear of it.
 #pragma once
@@ -111,6 +111,7 @@ struct gfbe_ftab : gfbe_handle {
   // operation waits for that one (read_pending)
   hipEvent_t ev_ops = nullptr, ev_read = nullptr;
   bool read_pending = false;
+  bool err_seen = false;      // a table's sticky error flag (d.err) came back set from an add_frame: what gfbe_gate_* refuses without a copy
 };
 
 struct gfbe_ltab : gfbe_handle {

@@ -15,7 +15,7 @@ import ctypes as C
 from .abi import (DetOptions, DmapOptions, FeatureList, FtabOptions, GnssObs, GnssState, ImuPreint, KfdOptions, KltOptions, Lc4Options, Lc6Options, LdbOptions, LdbVocab, LineReducedV,
                   LineStepped, LineWindow, ObsOptions, Options, PnpOptions, Prior, State, Summary, VmapOptions, VregOptions, VregSummary, WheelPreint, Window)
 
-from .abi import EqOptions
+from .abi import EqOptions, GateOptions
 
 P = C.POINTER
 i, i64, d, V, PV, STR = C.c_int32, C.c_int64, C.c_double, C.c_void_p, P(C.c_void_p), C.c_char_p
@@ -243,6 +243,16 @@ EQ = {              # prefix gfbe_eq_ (the image equalisation in front of the tr
     "download_lut": (i, [V, V, PU8]),
 }
 
+GATE = {            # prefix gfbe_gate_ (the sensor gate on the feature tables: stationarity, wheel anomaly, the wheel prediction; symbols of the product library;
+    # include/gfbe_gate.h, checked against it by tests/test_gate_model.py)
+    "default_options": (None, [P(GateOptions)]),
+    "create": (i, [V, i, P(GateOptions), PV]),
+    "destroy": (None, [V, V]),
+    "frame": (i, [V, V, V, PI, PI, PD, PD, PI, PD, PD, PD, PD, d, PI, PI, PD, PI, PI, PI, PI, PD, PD, PD, PD, PD, PD, PD]),
+    "pair_stats": (i, [V, V, V, i, PI, PD, PI, PI]),
+    "corresponding": (i, [V, V, V, i, PI, PI, PI, PD, PD, PI]),
+}
+
 
 def _oracle(name):
     """The oracle's flavour of a shared entry point: the compute calls take `const gfbe_options *` where the product takes its
@@ -259,6 +269,7 @@ GFO = {name: _oracle(name) for name in GFBE}
 TABLES = {"gfbe_": GFBE, "gfo_": GFO, "gfbe_rccl_": RCCL, "gfbe_lc6_": LC6, "gfbe_klt_": KLT, "gfbe_det_": DET, "gfbe_obs_": OBS,
           "gfbe_kfd_": KFD, "gfbe_pnp_": PNP}
 TABLES["gfbe_eq_"] = EQ
+TABLES["gfbe_gate_"] = GATE
 
 
 def declare(lib, prefix, table):
